@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the interaction score test on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 One "step" = the whole hot path (null fits over the rho grid, Khatri-Rao contraction, score statistic,
 eigenvalues, Davies) over one batch of `--batch` synthetic variants of BASELINE config 3 (20 000 cells,
@@ -65,6 +65,24 @@ def executed_flops(n, cols, r_list, r_star, k0, c, fast_rotation, kin=None):
         rot = 2.0 * n * cols + 2.0 * cols * R if fast_rotation else 2.0 * n * R
         contraction = 2.0 * n * r_star * k0
     return rot + contraction + n * k0 * (k0 + 1) + 2.0 * n * k0 * (c + 2) + r_star * k0 * (k0 + 1)
+
+
+DUMP_LIMIT_BYTES = 64 * 10 ** 6 - 64 * 1024     # 64 MB, less room for the .npy headers
+
+
+def dump_outputs(dest, arrays):
+    """--dump-outputs: every array as dest/<name>.npy in float64.  Arrays of one length per variant; when together they
+    would pass DUMP_LIMIT_BYTES, the same fixed, seeded sample of the variants is kept from each, and its positions go to
+    dest/index.npy."""
+    os.makedirs(dest, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    count = len(next(iter(arrays.values())))
+    keep = DUMP_LIMIT_BYTES // (8 * (len(arrays) + 1))
+    if 8 * count * len(arrays) > DUMP_LIMIT_BYTES:
+        index = np.sort(np.random.default_rng(0).choice(count, size=keep, replace=False))
+        arrays = {"index": index.astype(np.float64), **{k: v[index] for k, v in arrays.items()}}
+    for k, v in arrays.items():
+        np.save(os.path.join(dest, k + ".npy"), np.ascontiguousarray(v))
 
 
 def _free_port():
@@ -316,7 +334,12 @@ def main():
     ap.add_argument("--genes-variants", type=int, default=0,
                     help="variants of the config-4 leg, all ranks together (0 = the config's whole fixed panel when "
                          "--full-panel is on, i.e. BASELINE config 4 itself at --genes 64; else the weak-scaling panel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (pv, rho1, Q of its batch; "
+                         "N > 1: every rank's batch, rank by rank) as DIR/<name>.npy in float64")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1 (it writes the last timed step's outputs)")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -558,11 +581,16 @@ def main():
                                          ctypes.byref(tot)))
     _lib.check(lib.crm_kernel_timer_stop(ctx))
     pv_dense = pv.copy()
+    last_step = slice(((steps - 1) % weak_blocks) * batch, ((steps - 1) % weak_blocks + 1) * batch)
+    dumped = {"pv": pv[last_step].copy(), "rho1": rho1[last_step].copy(), "Q": Q[last_step].copy()}
     if dist is not None:
         # the path's one data-path collective: gather the shard results on every rank (RCCL over xGMI)
         full = gather_variant_results({"pv": pv, "rho1": rho1, "Q": Q}, p_need * world, comm.group)
         assert full["pv"].shape == (p_need * world,)
         torch.cuda.synchronize()
+        dumped = {k: full[k].reshape(world, p_need)[:, last_step].ravel() for k in dumped}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dumped)
     total_variants = steps * batch * world
     value = total_variants / elapsed
 

@@ -9,6 +9,12 @@ if ROOT not in sys.path:
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
+# One HIP runtime per process.  torch bundles its own libamdhip64 (soname libamdhip64.so.7); libcrm_hip.so binds to an
+# already loaded runtime of that soname, and loads the system one otherwise.  Tests of this session use torch in-process
+# (gloo groups, device checks), and a second runtime that initialises the GPU leaves the library's without a device.
+# Loading torch before any test loads the library keeps both on one runtime -- the order bench.py and tests/workers use.
+import torch  # noqa: E402,F401
+
 # the scans show the reference's tqdm bar by default; the suite keeps its logs clean (tests of the bar pass progress=True)
 os.environ.setdefault("CELLREGMAP_AMD_PROGRESS", "0")
 

@@ -176,6 +176,33 @@ def test_the_committed_traffic_profile_is_of_this_library():
     assert form == {"contraction_sync": True, "tail_launch": True, "library": version, "kinship_route": True, "tile_band": 8}
 
 
+def test_bench_dump_outputs_stays_within_its_size_limit(tmp_path):
+    """bench.py --dump-outputs: one float64 .npy per array, whole while they are small; past the limit the same seeded
+    sample of the variants from every array, its positions in index.npy, the same from run to run."""
+    import sys
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    small = {"pv": np.linspace(0, 1, 4096), "rho1": np.zeros(4096, np.float32)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    for k, v in small.items():
+        got = np.load(tmp_path / "small" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    assert not (tmp_path / "small" / "index.npy").exists()
+    n = bench.DUMP_LIMIT_BYTES // 16 + 1          # two arrays that together pass the limit
+    big = {"pv": np.arange(n, dtype=float), "Q": -np.arange(n, dtype=float)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["Q.npy", "index.npy", "pv.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 * 10 ** 6
+    index = np.load(tmp_path / "a" / "index.npy")
+    assert np.array_equal(np.load(tmp_path / "a" / "pv.npy"), index) and np.array_equal(np.load(tmp_path / "a" / "Q.npy"), -index)
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
 def test_kinship_groups_of_expanded_factors():
     """``_engine._kinship_groups`` (what the Python host announces through crm_background_set_kinship_groups): exact donor
     structure or nothing.  Indicator factors (one 1 per row: every sampled column looks alike) and cells in shuffled order

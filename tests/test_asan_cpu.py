@@ -72,6 +72,11 @@ def test_deflation_plan_matches_the_prototype():
 
 
 def test_host_side_under_address_sanitizer(tmp_path):
+    if os.path.exists("/dev/kfd"):
+        import pytest
+
+        pytest.skip("needs a machine without a GPU: it drives the no-GPU error paths, and ROCm's AddressSanitizer "
+                    "runtime intercepts the HIP runtime's device allocations where a GPU is present")
     from cellregmap_amd import build
 
     lib = build.build_asan(verbose=False)
@@ -98,6 +103,8 @@ assert lib.crm_scan_interaction(None, None, 0, 0, None, None, *([None] * 11)) !=
 assert lib.crm_background_complete(None, None) != 0 and lib.crm_background_seal(None) != 0
 print("asan drive ok")
 """)
-    env = dict(os.environ, LD_PRELOAD=rt, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1")
+    # the ASan runtime must come first; whatever the environment already preloads stays after it
+    preload = ":".join(p for p in (rt, os.environ.get("LD_PRELOAD", "")) if p)
+    env = dict(os.environ, LD_PRELOAD=preload, ASAN_OPTIONS="detect_leaks=0:abort_on_error=1")
     r = subprocess.run([sys.executable, str(script)], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0 and "asan drive ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

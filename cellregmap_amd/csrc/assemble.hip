@@ -38,7 +38,7 @@ __global__ __launch_bounds__(256) void gram_ext_kernel(AssembleArgs a, double* _
                   RPT = ROWS / 4;
     extern __shared__ double Ss[];  // [ROWS][SLD]
     __shared__ int tile_ij[NTILES];
-    __shared__ const double* tail_ptr[CRM_MAX_COV_XWIDE + 2];
+    __shared__ const double* tail_ptr[ROWS];   // (rows past k0: KT - k0 <= ROWS)
     const int b = blockIdx.x;
     const NullFitOut fit = a.fit[b];
     const AssembleRho R = a.rho[fit.rho_index];
@@ -57,12 +57,13 @@ __global__ __launch_bounds__(256) void gram_ext_kernel(AssembleArgs a, double* _
         while (rem >= NTL - ti) { rem -= NTL - ti; ti++; }
         tile_ij[e] = ti | ((ti + rem) << 8);
     }
-    if (tid < c + 2) {
+    for (int t = tid; t < KT - k0; t += 256) {
         const double* p;
-        if (tid < c) p = R.tW + (long)tid * R.ldW;
-        else if (tid == c) p = R.T + (long)b * R.ldT;
-        else p = R.ty;
-        tail_ptr[tid] = p;
+        if (t < c) p = R.tW + (long)t * R.ldW;
+        else if (t == c) p = R.T + (long)b * R.ldT;
+        else if (t == c + 1) p = R.ty;
+        else p = a.wb_R + (long)(t - c - 2) * a.wb_ldR;   // (unrelated-donor form: the E1 rows)
+        tail_ptr[t] = p;
     }
     __syncthreads();
     // tiles of this wavefront: the entries first, first + 4, ... of this workgroup's list (MAXT or MAXT - 1 of them)
@@ -239,6 +240,7 @@ __global__ __launch_bounds__(256) void gram_ext_dma_kernel(AssembleArgs a, doubl
         if (row >= KT) row = 0;
         if (row < k0) return Arows + (long)row * a_stride;
         const int t = row - k0;
+        if (t > c + 1) return a.wb_R + (long)(t - c - 2) * a.wb_ldR;   // (unrelated-donor form: the E1 rows)
         return t < c ? R.tW + (long)t * R.ldW : (t == c ? R.T + (long)b * R.ldT : R.ty);
     };
     auto row_off = [](int row) { return row < HALF ? row * QLD : (row - HALF) * QLD + 64; };
@@ -368,6 +370,83 @@ __global__ __launch_bounds__(256) void gram_ext_dma_kernel(AssembleArgs a, doubl
                 }
             }
         }
+    }
+}
+
+// Unrelated-donor form (scan.hip: kin_wb).  The Gram Gw of the KT + k1 rows [X ; W ; gx ; y ; E1] was taken over the
+// donors k2 positions with the weights of N = v1 I + v0 sum_p s_p(rho) phi_p phi_p' alone, so that
+//     M_uv = u'N^-1 v = (u'v - Gw_uv) / v1 ;
+// K0 = N + v0 rho E1 E1' then gives, with the k1 x k1 capacitance C = I + v0 rho M_EE (positive definite, >= I),
+//     u'K0^-1 v = M_uv - v0 rho M_uE C^-1 M_Ev .
+// finalize_kernel reads K0^-1 as (plain - Ge) / v1, so Ge = Gw + v1 v0 rho M_uE C^-1 M_Ev on the leading KT x KT block.
+// A variant without a kinship term to speak of (sorted_pos < 0: its X rows of Gw are zero, scan.hip: no_kinship_term)
+// drops the X part of the correction the same way.  v0 rho = 0 (rho* = 0, or no kinship variance) leaves Gw as it is.
+// One workgroup per variant; LDS: M_uE [KT][k1], C [k1][k1], C^-1 M_Ev [k1][KT].
+__global__ __launch_bounds__(256) void woodbury_kernel(AssembleArgs a, const double* __restrict__ Gw, int KT,
+                                                       double* __restrict__ Gext) {
+    extern __shared__ double wsm[];
+    const int k1 = a.wb_k1, KW = KT + k1, k0 = a.k0, c = a.c;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const NullFitOut fit = a.fit[b];
+    const double g = fit.v0 * a.rho[fit.rho_index].rho;
+    const double inv = 1.0 / fit.v1;
+    const double* __restrict__ G = Gw + (long)b * KW * KW;
+    double* __restrict__ out = Gext + (long)b * KT * KT;
+    if (!(g > 0.0)) {
+        for (int e = tid; e < KT * KT; e += 256) out[e] = G[(long)(e / KT) * KW + e % KT];
+        return;
+    }
+    double* ME = wsm;               // [KT][k1]
+    double* Cm = ME + KT * k1;      // [k1][k1]
+    double* Z = Cm + k1 * k1;       // [k1][KT]
+    const long pos = a.sorted_pos[b];
+    for (int e = tid; e < KT * k1; e += 256) {
+        const int u = e / k1, f = e - u * k1;
+        double plain;
+        if (u < k0) plain = pos >= 0 ? a.wb_E1X[(long)f * a.wb_ldE1X + pos * k0 + u] : 0.0;
+        else if (u < k0 + c) plain = a.wb_E1yW[(long)f * a.wb_ldE1yW + 1 + (u - k0)];
+        else if (u == k0 + c) plain = a.wb_E1g[(long)f * a.wb_ldE1g + b];
+        else plain = a.wb_E1yW[(long)f * a.wb_ldE1yW];
+        ME[e] = (u < k0 && pos < 0) ? 0.0 : (plain - G[(long)u * KW + KT + f]) * inv;
+    }
+    for (int e = tid; e < k1 * k1; e += 256) {
+        const int i = e / k1, j = e - i * k1;
+        Cm[e] = (i == j ? 1.0 : 0.0) + g * (a.wb_EE[e] - G[(long)(KT + i) * KW + KT + j]) * inv;
+    }
+    __syncthreads();
+    // Cholesky C = L L' in place (lower triangle), column by column
+    for (int j = 0; j < k1; j++) {
+        if (tid == 0) Cm[j * k1 + j] = sqrt(Cm[j * k1 + j]);
+        __syncthreads();
+        const double l = Cm[j * k1 + j];
+        for (int i = j + 1 + tid; i < k1; i += 256) Cm[i * k1 + j] /= l;
+        __syncthreads();
+        for (int e = tid; e < (k1 - j - 1) * (k1 - j - 1); e += 256) {
+            const int i = j + 1 + e / (k1 - j - 1), q = j + 1 + e % (k1 - j - 1);
+            if (q <= i) Cm[i * k1 + q] -= Cm[i * k1 + j] * Cm[q * k1 + j];
+        }
+        __syncthreads();
+    }
+    // Z = C^-1 M_E. : one column per thread
+    for (int u = tid; u < KT; u += 256) {
+        for (int i = 0; i < k1; i++) {
+            double s = ME[u * k1 + i];
+            for (int q = 0; q < i; q++) s -= Cm[i * k1 + q] * Z[q * KT + u];
+            Z[i * KT + u] = s / Cm[i * k1 + i];
+        }
+        for (int i = k1 - 1; i >= 0; i--) {
+            double s = Z[i * KT + u];
+            for (int q = i + 1; q < k1; q++) s -= Cm[q * k1 + i] * Z[q * KT + u];
+            Z[i * KT + u] = s / Cm[i * k1 + i];
+        }
+    }
+    __syncthreads();
+    const double scale = fit.v1 * g;
+    for (int e = tid; e < KT * KT; e += 256) {
+        const int u = e / KT, v = e - u * KT;
+        double s = 0.0;
+        for (int f = 0; f < k1; f++) s += ME[u * k1 + f] * Z[f * KT + v];
+        out[e] = G[(long)u * KW + v] + scale * s;
     }
 }
 
@@ -576,6 +655,8 @@ __global__ __launch_bounds__(128) void finalize_kernel(AssembleArgs a, const dou
 
 }  // namespace
 
+size_t woodbury_lds_bytes(int KT, int k1) { return sizeof(double) * ((size_t)2 * KT * k1 + (size_t)k1 * k1); }
+
 size_t assemble_rows_scratch_doubles(int variants, int k0, int c) {
     const size_t P = (size_t)c + 1;
     const size_t lds = sizeof(double) * (P * P + 3 * P + k0 + 2 * (size_t)k0 * P);
@@ -584,7 +665,17 @@ size_t assemble_rows_scratch_doubles(int variants, int k0, int c) {
 
 int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double* Gext, double* fin_rows) {
     if (variants <= 0) return CRM_OK;
-    const int KT = a.k0 + a.c + 2;
+    const int KT0 = a.k0 + a.c + 2;
+    // (unrelated-donor form: the Gram takes the k1 E1 rows as well, the correction folds them back into KT0 x KT0)
+    const int KT = KT0 + (a.wb_k1 > 0 ? a.wb_k1 : 0);
+    double* const Gfin = Gext;
+    if (a.wb_k1 > 0) {
+        if (KT > CRM_MAX_GRAM_ROWS || woodbury_lds_bytes(KT0, a.wb_k1) > 150 * 1024 || !a.wb_Gw) {
+            set_error("assemble: unrelated-donor form with %d + %d rows outside its supported range", KT0, a.wb_k1);
+            return CRM_ERR_INTERNAL;
+        }
+        Gext = a.wb_Gw;
+    }
     const int P = a.c + 1;
     const size_t fin_small = sizeof(double) * ((size_t)P * P + 3 * P + a.k0);
     size_t fin_lds = fin_small + sizeof(double) * 2 * (size_t)a.k0 * P;
@@ -604,6 +695,7 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
         dma = R.ldW % 2 == 0 && R.ldT % 2 == 0 && ((reinterpret_cast<uintptr_t>(R.ty) | reinterpret_cast<uintptr_t>(R.tW) |
                                                     reinterpret_cast<uintptr_t>(R.T)) & 15) == 0;
     }
+    if (a.wb_k1 > 0) dma = dma && a.wb_ldR % 2 == 0 && (reinterpret_cast<uintptr_t>(a.wb_R) & 15) == 0;
 #define CRM_GRAM_DMA(NTL)                                                                                     \
     do {                                                                                                      \
         const size_t lds = sizeof(double) * (2 * (16 * NTL / 2) * 130 + 2 * CH);                              \
@@ -636,6 +728,7 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
     } else if (ts <= 2) CRM_GRAM(2);
     else if (ts <= 4) CRM_GRAM(4);
     else if (ts <= 6) CRM_GRAM(6);
+    else if (ts <= 7) CRM_GRAM(7);   // (unrelated-donor form at config 3: 50 + 3 + 50 rows)
     else if (ts <= 9) CRM_GRAM(9);
     else if (ts <= 12) CRM_GRAM_GROUPS(12, 2);
     else if (ts <= 15) CRM_GRAM_GROUPS(15, 4);
@@ -643,10 +736,18 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
 #undef CRM_GRAM
 #undef CRM_GRAM_GROUPS
     CRM_HIP(hipGetLastError());
+    if (a.wb_k1 > 0) {
+        const size_t lds = woodbury_lds_bytes(KT0, a.wb_k1);
+        if (lds > 60 * 1024)
+            CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&woodbury_kernel),
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(woodbury_kernel, dim3(variants), dim3(256), lds, st, a, a.wb_Gw, KT0, Gfin);
+        CRM_HIP(hipGetLastError());
+    }
     if (fin_lds > 60 * 1024)
         CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&finalize_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_lds));
-    hipLaunchKernelGGL(finalize_kernel, dim3(variants), dim3(128), fin_lds, st, a, Gext, KT, rows_global ? fin_rows : nullptr);
+    hipLaunchKernelGGL(finalize_kernel, dim3(variants), dim3(128), fin_lds, st, a, Gfin, KT0, rows_global ? fin_rows : nullptr);
     CRM_HIP(hipGetLastError());
     return CRM_OK;
 }

@@ -100,6 +100,7 @@ struct crm_ctx {
     long tail_launches = 0;   // blocks whose last columns took the 160-column-tile launch (crm_test_tail_launches)
     long spectrum_tail_launches = 0;   // blocks whose last few columns of the spectrum went through the skinny one-pass kernel
     long donor_pair_blocks = 0;   // blocks whose per-donor sums came from the symmetric pair features (crm_test_donor_pair_blocks)
+    long unrelated_donor_blocks = 0;   // blocks served by the unrelated-donor form (crm_test_unrelated_donor_blocks)
     long tests_without_pair = 0;  // (phenotype, variant) tests whose fit has no kinship term to speak of: no A~ formed for them
     // crm_scan_interaction_permuted: what the scan of a block computes BEFORE the permutation hooks enter -- the eleven
     // rotations T(rho) = G'Q0(rho), the null fits and rho* (cellregmap/_cellregmap.py:345-357 sit above the hooks at
@@ -133,10 +134,11 @@ struct crm_ctx {
     crm::DevBuf ws_xwide;  // scratch of the 63..128-column null-fit kernel (nullfit_xwide.hip)
     crm::DevBuf ws_Tcut;   // rotations: the few small products taken out of the batched launch (cut along the contraction axis)
     crm::DevBuf ws_Gk, ws_S, ws_S2;   // kinship-structure route: the block in donor order, the per-donor sums (step 6 / step 3)
+    crm::DevBuf ws_WB;                // unrelated-donor form: Phi'gx of the block, Phi'[y, W] and E1'[y, W] of the genes, scratch
     crm::DevBuf ws_Pd;                // ... the per-donor products against the symmetric pair features (step 6, donor pairs)
     crm::DevBuf ws_Anone;             // a row of zeros: A~ of the tests whose fit has no kinship term (AssembleArgs::A_none)
     std::vector<crm::DevBuf*> all_bufs() {
-        return {&sync_counters, &ws_xwide, &ws_Tcut, &ws_S, &ws_S2, &ws_Gk, &ws_Pd, &ws_Anone, &ws_AH, &ws_XG, &ws_TH, &ws_T, &ws_A, &ws_Gb, &ws_Gx, &ws_Gs, &ws_G2, &ws_GG, &ws_Gt, &ws_Z, &ws_small, &ws_probs, &ws_F, &ws_Gext};
+        return {&sync_counters, &ws_xwide, &ws_Tcut, &ws_S, &ws_S2, &ws_Gk, &ws_Pd, &ws_WB, &ws_Anone, &ws_AH, &ws_XG, &ws_TH, &ws_T, &ws_A, &ws_Gb, &ws_Gx, &ws_Gs, &ws_G2, &ws_GG, &ws_Gt, &ws_Z, &ws_small, &ws_probs, &ws_F, &ws_Gext};
     }
 };
 

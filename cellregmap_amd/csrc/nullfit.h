@@ -164,6 +164,7 @@ struct AssembleRho {
     long ldW, ldT;
     int r;
     int pad_;
+    double rho;       // the grid point (unrelated-donor form: the weight v0 rho of the E1 term)
 };
 
 struct AssembleArgs {
@@ -185,12 +186,25 @@ struct AssembleArgs {
                                         // (launch_ortho_block; null where the block was not orthogonalised)
     double* Q;   // [variants]
     double* F;   // [variants x k0 x k0]
+    // Unrelated-donor form (scan.hip: kin_wb, assemble.hip: woodbury_kernel), wb_k1 > 0: the Gram runs over donors k2
+    // positions with k1 more rows R = Phi'E1 behind the k0 + c + 2 of the spectral form, and the E1 term is added back by
+    // a k1 x k1 capacitance solve before the finalize.  Plain E1 products: E1'X (rows of the folded S), E1'[y, W] (gene),
+    // E1'gx (block), E1'E1.
+    int wb_k1;
+    const double* wb_R; long wb_ldR;         // [k1 x ldR]
+    const double* wb_E1X; long wb_ldE1X;     // [k1 x ld]: column pos k0 + i
+    const double* wb_E1yW; long wb_ldE1yW;   // [k1 x ld]: column 0 y, 1.. W
+    const double* wb_E1g; long wb_ldE1g;     // [k1 x ld]: column b
+    const double* wb_EE;                     // [k1 x k1]
+    double* wb_Gw;                           // workspace [variants x (k0 + c + 2 + k1)^2]
 };
 
 // Gext: workspace [variants x (k0+c+2)^2]; fin_rows: assemble_rows_scratch_doubles(...) doubles (0: not needed -- the
 // per-variant rows D'K^-1X and their solves fit LDS)
 int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double* Gext, double* fin_rows = nullptr);
 size_t assemble_rows_scratch_doubles(int variants, int k0, int c);
+// LDS of the unrelated-donor correction (assemble.hip: woodbury_kernel) for KT = k0 + c + 2 rows and k1 E1 columns
+size_t woodbury_lds_bytes(int KT, int k1);
 
 // ---- eigenvalues + Davies / Liu (davies.hip) -----------------------------------------------------
 // lambda: ascending eigenvalues of the lower triangle of F (count x k x k); pvalue per SKAT rule.

@@ -71,6 +71,18 @@ struct crm_background {
     bool kin_fold = false;
     long kin_kdim = 0;                          // k1 + kin_groups * k2, padded to whole stages of the contraction
     crm::DevBuf MixK[crm::CRM_MAX_RHO];        // [kin_kdim x ldq]
+    // Unrelated donors (folded form with hKd hKd' diagonal, kappa_d on the diagonal): the kinship part of Sigma(rho) is
+    // blockdiag_d (1 - rho) kappa_d us_d us_d', with G_d = us_d'us_d = U_d Lambda_d U_d' per donor.  Phi_d = us_d U_d
+    // Lambda_d^-1/2 is an orthonormal basis of that block, so K0 = v1 I + v0 (rho E1E1' + sum_p s_p(rho) phi_p phi_p')
+    // with s_p(rho) = (1 - rho) kappa_d lambda_dj over the donors k2 positions p = d k2 + j, and the E1 term goes by
+    // Woodbury (a k1 x k1 capacitance per variant): no product with MixK(rho*) at all.
+    bool kin_wb = false;
+    long wb_P = 0, wb_ldp = 0;                  // positions donors k2, padded to 128
+    int wb_k2pad = 0;                           // k2 padded to whole stages of the contraction
+    crm::DevBuf wb_U;                           // [donors][k2pad x 128]: U_d Lambda_d^-1/2, zero padded
+    crm::DevBuf wb_R;                           // [k1 x wb_ldp]: R[a, d k2 + j] = (Phi_d' E1_d)[j, a]
+    crm::DevBuf wb_EE;                          // [k1 x k1]: E1'E1
+    crm::DevBuf wb_S0[crm::CRM_MAX_RHO];        // [wb_ldp]: s_p(rho)
     // shared donor tables, most recently used first (at most DT_CACHE entries)
     static constexpr int DT_CACHE = 2;
     std::vector<crm_donor_tables*> dt_cache;

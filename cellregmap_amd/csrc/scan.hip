@@ -56,6 +56,136 @@ __global__ void verify_panel_kernel(const double* __restrict__ G, long ld, long 
     }
 }
 
+// Symmetric eigen-decomposition A = V diag(w) V' of a small k x k matrix (row-major, destroyed) by cyclic Jacobi:
+// rotations until every off-diagonal entry is below eps times the root of its two diagonal entries (the relative
+// accuracy of the eigenvalues of a positive semidefinite Gram matrix).  V: k x k row-major, columns the eigenvectors.
+static void jacobi_eigh(int k, std::vector<double>& A, std::vector<double>& V, std::vector<double>& w) {
+    V.assign((size_t)k * k, 0.0);
+    for (int i = 0; i < k; i++) V[(size_t)i * k + i] = 1.0;
+    for (int sweep = 0; sweep < 60; sweep++) {
+        bool rotated = false;
+        for (int p = 0; p < k - 1; p++)
+            for (int q = p + 1; q < k; q++) {
+                const double apq = A[(size_t)p * k + q], app = A[(size_t)p * k + p], aqq = A[(size_t)q * k + q];
+                if (!(std::fabs(apq) > 2.220446049250313e-16 * std::sqrt(std::fabs(app * aqq))) || apq == 0.0) continue;
+                rotated = true;
+                const double theta = (aqq - app) / (2.0 * apq);
+                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+                const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
+                for (int r = 0; r < k; r++) {   // columns p, q
+                    const double arp = A[(size_t)r * k + p], arq = A[(size_t)r * k + q];
+                    A[(size_t)r * k + p] = cs * arp - sn * arq;
+                    A[(size_t)r * k + q] = sn * arp + cs * arq;
+                }
+                for (int r = 0; r < k; r++) {   // rows p, q
+                    const double apr = A[(size_t)p * k + r], aqr = A[(size_t)q * k + r];
+                    A[(size_t)p * k + r] = cs * apr - sn * aqr;
+                    A[(size_t)q * k + r] = sn * apr + cs * aqr;
+                }
+                A[(size_t)p * k + q] = A[(size_t)q * k + p] = 0.0;
+                for (int r = 0; r < k; r++) {
+                    const double vrp = V[(size_t)r * k + p], vrq = V[(size_t)r * k + q];
+                    V[(size_t)r * k + p] = cs * vrp - sn * vrq;
+                    V[(size_t)r * k + q] = sn * vrp + cs * vrq;
+                }
+            }
+        if (!rotated) break;
+    }
+    w.resize(k);
+    for (int i = 0; i < k; i++) w[i] = A[(size_t)i * k + i];
+}
+
+// Unrelated donors (objects.h: kin_wb): is the donor-level kinship hKd hKd' diagonal to rounding?  Then the per-donor
+// eigen-decompositions of G_d = us_d'us_d and the rows R = Phi'E1, uploaded once per background.  Any off-diagonal entry
+// above 8 m eps sqrt(kappa_d kappa_d') keeps the MixK route; so do k2 > 128, k1 > 64 and donor counts whose test or
+// tables would be large.
+static int seal_unrelated_donors(crm_background* bg, const double* hKd, long m) {
+    bg->kin_wb = false;
+    const long groups = bg->kin_groups;
+    const int k1 = bg->kin_k1, k2 = bg->kin_k2, KK = k1 + k2;
+    if (form("kin_diag", 1) == 0 || k2 > 128 || k1 > 64 || (double)groups * groups * m > 4e9) return CRM_OK;
+    std::vector<double> kappa(groups, 0.0);
+    for (long d = 0; d < groups; d++)
+        for (long q = 0; q < m; q++) kappa[d] += hKd[d * m + q] * hKd[d * m + q];
+    const double tol = 8.0 * (double)m * 2.220446049250313e-16;
+    for (long d = 0; d < groups; d++)
+        for (long e = d + 1; e < groups; e++) {
+            double s = 0.0;
+            for (long q = 0; q < m; q++) s += hKd[d * m + q] * hKd[e * m + q];
+            if (!(std::fabs(s) <= tol * std::sqrt(kappa[d] * kappa[e]))) return CRM_OK;
+        }
+    crm_ctx* ctx = bg->ctx;
+    hipStream_t st = ctx->stream;
+    // [us | E1]'[us | E1] per donor over its own cells: G_d, us_d'E1_d and the donor's share of E1'E1
+    const long ldc = round_up(KK, 128);
+    if (sizeof(double) * (double)groups * KK * ldc > (double)(1ull << 30)) return CRM_OK;
+    ScopedBuf dC, probs_dev;
+    CRM_TRY(dC.ensure(sizeof(double) * (size_t)groups * KK * ldc));
+    std::vector<GemmProblem> pr((size_t)groups);
+    long maxlen = GEMM_BK;
+    for (long d = 0; d < groups; d++) {
+        GemmProblem p{};
+        p.X = bg->kin_Y.as<double>() + bg->kin_row0[d] * bg->kin_ldy; p.ldx = bg->kin_ldy;
+        p.Y = p.X; p.ldy = bg->kin_ldy;
+        p.C = dC.as<double>() + (size_t)d * KK * ldc; p.ldc = ldc;
+        p.M = KK; p.N = KK; p.cells = bg->kin_len[d];
+        maxlen = std::max(maxlen, bg->kin_len[d]);
+        pr[d] = p;
+    }
+    CRM_TRY(probs_dev.ensure(sizeof(GemmProblem) * pr.size()));
+    CRM_HIP(hipMemcpyAsync(probs_dev.ptr, pr.data(), sizeof(GemmProblem) * pr.size(), hipMemcpyHostToDevice, st));
+    CRM_TRY(launch_gemm_tn(ctx, probs_dev.as<GemmProblem>(), (int)groups, KK, KK, maxlen, false, 0, 1, 0));
+    std::vector<double> C((size_t)groups * KK * ldc);
+    CRM_HIP(hipMemcpyAsync(C.data(), dC.ptr, sizeof(double) * C.size(), hipMemcpyDeviceToHost, st));
+    CRM_HIP(hipStreamSynchronize(st));
+    const int k2pad = (int)round_up(k2, GEMM_BK);
+    const long P = groups * k2, ldp = round_up(P, 128);
+    std::vector<double> hU((size_t)groups * k2pad * 128, 0.0), hR((size_t)k1 * ldp, 0.0), hEE((size_t)k1 * k1, 0.0),
+        lam((size_t)P, 0.0);
+    std::vector<double> A((size_t)k2 * k2), V, w;
+    for (long d = 0; d < groups; d++) {
+        const double* Cd = C.data() + (size_t)d * KK * ldc;
+        for (int i = 0; i < k2; i++)
+            for (int j = 0; j < k2; j++) A[(size_t)i * k2 + j] = 0.5 * (Cd[i * ldc + j] + Cd[j * ldc + i]);
+        jacobi_eigh(k2, A, V, w);
+        double wmax = 0.0;
+        for (int j = 0; j < k2; j++) wmax = std::max(wmax, w[j]);
+        double* Ud = hU.data() + (size_t)d * k2pad * 128;
+        for (int j = 0; j < k2; j++) {
+            // (directions of us_d below rounding -- k2 > the donor's cells -- carry no variance: dropped)
+            if (!(w[j] > (double)k2 * 2.220446049250313e-16 * wmax)) continue;
+            const double sc = 1.0 / std::sqrt(w[j]);
+            lam[d * k2 + j] = w[j];
+            for (int q = 0; q < k2; q++) Ud[(size_t)q * 128 + j] = V[(size_t)q * k2 + j] * sc;
+            for (int a = 0; a < k1; a++) {
+                double s = 0.0;
+                for (int q = 0; q < k2; q++) s += Ud[(size_t)q * 128 + j] * Cd[q * ldc + k2 + a];
+                hR[(size_t)a * ldp + d * k2 + j] = s;
+            }
+        }
+        for (int a = 0; a < k1; a++)
+            for (int e = 0; e < k1; e++) hEE[(size_t)a * k1 + e] += Cd[(k2 + a) * ldc + k2 + e];
+    }
+    CRM_TRY(bg->wb_U.ensure(sizeof(double) * hU.size()));
+    CRM_TRY(bg->wb_R.ensure(sizeof(double) * hR.size()));
+    CRM_TRY(bg->wb_EE.ensure(sizeof(double) * hEE.size()));
+    CRM_HIP(hipMemcpyAsync(bg->wb_U.ptr, hU.data(), sizeof(double) * hU.size(), hipMemcpyHostToDevice, st));
+    CRM_HIP(hipMemcpyAsync(bg->wb_R.ptr, hR.data(), sizeof(double) * hR.size(), hipMemcpyHostToDevice, st));
+    CRM_HIP(hipMemcpyAsync(bg->wb_EE.ptr, hEE.data(), sizeof(double) * hEE.size(), hipMemcpyHostToDevice, st));
+    std::vector<std::vector<double>> s0(bg->nrho, std::vector<double>((size_t)ldp, 0.0));
+    for (int i = 0; i < bg->nrho; i++) {
+        for (long p = 0; p < P; p++) s0[i][p] = (1.0 - bg->rho[i]) * kappa[p / k2] * lam[p];
+        CRM_TRY(bg->wb_S0[i].ensure(sizeof(double) * (size_t)ldp));
+        CRM_HIP(hipMemcpyAsync(bg->wb_S0[i].ptr, s0[i].data(), sizeof(double) * (size_t)ldp, hipMemcpyHostToDevice, st));
+    }
+    CRM_HIP(hipStreamSynchronize(st));
+    bg->wb_P = P;
+    bg->wb_ldp = ldp;
+    bg->wb_k2pad = k2pad;
+    bg->kin_wb = true;
+    return CRM_OK;
+}
+
 __global__ void gather_rows_kernel(const double* __restrict__ G, long ld, const long* __restrict__ rep,
                                    double* __restrict__ Gd) {
     const long d = blockIdx.x;
@@ -164,7 +294,9 @@ int crm_background_set_kinship_groups(crm_background* bg, const int* group, long
         ~Undo() {
             if (b->kin) return;
             b->kin_fold = false;
-            for (DevBuf* x : {&b->kin_map, &b->kin_Y, &b->kin_hKd}) x->release();
+            b->kin_wb = false;
+            for (DevBuf* x : {&b->kin_map, &b->kin_Y, &b->kin_hKd, &b->wb_U, &b->wb_R, &b->wb_EE}) x->release();
+            for (int i = 0; i < b->nrho; i++) b->wb_S0[i].release();
             for (int i = 0; i < b->nrho; i++) b->MixK[i].release();
         }
     } undo{bg};
@@ -265,6 +397,7 @@ int crm_background_set_kinship_groups(crm_background* bg, const int* group, long
         CRM_HIP(hipStreamSynchronize(st));
         bg->kin_kdim = kdim;
         bg->kin_fold = true;
+        CRM_TRY(seal_unrelated_donors(bg, hKd, m));
     }
     bg->kin = true;
     return CRM_OK;
@@ -1409,7 +1542,8 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
     int ks_h = 1;
     // (rows of the operand of the rotations' Mix products: the half factor's columns, or -- folded kinship structure,
     // objects.h: kin_fold -- k1 + donors k2)
-    const long th_slab = std::max<long>(bg->ldh, bg->kin && bg->kin_fold ? bg->kin_kdim : 0) * ldb;
+    // (unrelated-donor form: the per-donor rotations read up to a stage past the last donor's rows -- zeros)
+    const long th_slab = std::max<long>(bg->ldh, bg->kin && bg->kin_fold ? bg->kin_kdim + (bg->kin_wb ? GEMM_BK : 0) : 0) * ldb;
     if (bg->fast_T) {
         const long tiles_h = (long)((bg->cols + GEMM_BM - 1) / GEMM_BM) * ((BLK + 127) / 128);
         while (tiles_h * ks_h < 1024 && ks_h < 16 && np / GEMM_BK / (ks_h + 1) >= 16) ks_h++;
@@ -1429,7 +1563,8 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
                  o_if = carve(sizeof(int) * BLK), o_liu = carve(sizeof(double) * BLK),
                  o_part = carve(stats_ws), o_queue = carve(sizeof(unsigned) * CRM_MAX_RHO),
                  o_coef = carve(sizeof(double) * (size_t)c * ldb), o_thr = carve(sizeof(double) * BLK),
-                 o_drop = carve(sizeof(int) * BLK), o_near = carve(sizeof(int) * BLK);
+                 o_drop = carve(sizeof(int) * BLK), o_near = carve(sizeof(int) * BLK),
+                 o_posw = carve(sizeof(int) * BLK * ng);
     CRM_TRY(ctx->ws_small.ensure(off));
     char* sm = ctx->ws_small.as<char>();
     double* d_gg = (double*)(sm + o_gg);
@@ -1450,7 +1585,8 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
     double* d_thr = (double*)(sm + o_thr);           // the reference's rank rule as a bound on |gx|^2
     int* d_drop = (int*)(sm + o_drop);               // 1: the variant's direction is dropped from [W, g]
     int* d_near = (int*)(sm + o_near);               // collapsed path: 1 = repeat this variant on the dense path
-    const int kin_probs = bg->kin ? bg->kin_groups + bg->kin_k2 + 16 : 0;
+    int* d_posw = (int*)(sm + o_posw);               // unrelated-donor form, several phenotypes: block position or -1
+    const int kin_probs = bg->kin ? bg->kin_groups * (bg->kin_wb ? 2 : 1) + bg->kin_k2 + 16 : 0;
     CRM_TRY(ctx->ws_probs.ensure(sizeof(GemmProblem) * (2 * CRM_MAX_RHO + 4 + kin_probs + ng)));
     GemmProblem* d_probs = ctx->ws_probs.as<GemmProblem>();
 
@@ -1474,7 +1610,8 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
     const int KK = bg->kin ? bg->kin_k1 + bg->kin_k2 : 0;   // rows of S per donor: [us | E1]
     // folded form (objects.h: kin_fold): S holds [E1 rows ; (donor, us_j) rows] and is the operand of the Mix product itself
     const bool fold = bg->kin && bg->kin_fold;
-    const size_t s_bytes = !bg->kin ? 0 : sizeof(double) * (fold ? (size_t)bg->kin_kdim : (size_t)bg->kin_groups_pad * KK) * ld_ah;
+    const long s_rows = fold ? bg->kin_kdim + (bg->kin_wb ? GEMM_BK : 0) : 0;
+    const size_t s_bytes = !bg->kin ? 0 : sizeof(double) * (fold ? (size_t)s_rows : (size_t)bg->kin_groups_pad * KK) * ld_ah;
     // The route pays when its flops per variant -- per-donor sums over runs padded to whole 16-cell stages, the E1 rows /
     // the contraction over the donors, and the product with the mixing matrix -- stay under the direct contraction's
     // 2 n r k0 (thousands of tiny donors: every run is mostly padding); a multi-gene test that forces one of the other
@@ -1491,6 +1628,22 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
     const bool kin_route = bg->kin && bg->fast_T && ctx->fast_T && !collapsed && ctx->kin_route > 0 && kin_pays &&
                            !(ng > 1 && ctx->tune.shared_h >= 0) && s_bytes <= ((size_t)48 << 30);
     const bool kfold = kin_route && fold;
+    // Unrelated donors (objects.h: kin_wb): Q and F through the per-donor Woodbury inverse, no A~ = MixK(rho*)'S.  Decided
+    // by the background and the shapes alone, so that every entry point and every block computes a variant alike.  Taken
+    // where the Gram over the donors k2 positions with k1 more rows costs less than the MixK product it replaces.
+    const int wb_k1 = bg->kin ? bg->kin_k1 : 0;
+    bool wb = false;
+    // (k0 + c + 2 + k1 <= 144: the single-workgroup Gram forms; wider shapes keep the MixK route)
+    constexpr int WB_MAX_ROWS = 144;
+    if (kfold && bg->kin_wb && !slow_forms && c + 1 <= 128 && KT + wb_k1 <= WB_MAX_ROWS && woodbury_lds_bytes(KT, wb_k1) <= 150 * 1024) {
+        double rbar = 1.0;
+        for (int i = 0; i < nrho; i++) rbar = std::max(rbar, (double)bg->r[i]);
+        // (8x: the per-block rotations and the capacitance solves are fixed costs that small products do not repay --
+        // mode B at config 3, 150 x 150 spectra: 328 000 -> 222 000 variant-tests/s at 1x)
+        wb = (double)bg->kin_kdim * rbar * k0 > 8.0 * (KT + wb_k1) * (KT + wb_k1) * (double)bg->wb_P || form("kin_diag", 1) >= 2;
+    }
+    const long ldAw = wb ? std::max<long>(ldA, bg->wb_ldp) : ldA;   // (rows of the rotated S: donors k2 positions)
+    const long ldwb = wb ? bg->wb_ldp : 0;
     const long kdim = kfold ? bg->kin_kdim : bg->ldh;       // contraction length of the products with the mixing matrices
     // cell-axis slices of the folded form's all-cells launches for the E1 rows (few output tiles, long contraction)
     int fold_split6 = 1, fold_split3 = 1;
@@ -1527,8 +1680,8 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
         CRM_TRY(ctx->ws_S2.ensure(sizeof(double) * (size_t)fold_split3 * bg->kin_k1 * ldb));
         // rows between k1 + donors k2 and the padded contraction length stay zero
         const long used = bg->kin_k1 + bg->kin_groups * (long)bg->kin_k2;
-        if (kdim > used)
-            CRM_HIP(hipMemsetAsync(ctx->ws_S.as<double>() + (size_t)used * ld_ah, 0, sizeof(double) * (size_t)(kdim - used) * ld_ah, st));
+        if (s_rows > used)
+            CRM_HIP(hipMemsetAsync(ctx->ws_S.as<double>() + (size_t)used * ld_ah, 0, sizeof(double) * (size_t)(s_rows - used) * ld_ah, st));
     } else if (kin_route) {
         CRM_TRY(ctx->ws_S.ensure(s_bytes));
         CRM_TRY(ctx->ws_Gk.ensure(sizeof(double) * (size_t)bg->kin_rows * std::max(ldb, ldp)));
@@ -1714,6 +1867,57 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             CRM_HIP(hipMemsetAsync(ctx->ws_AH.ptr, 0, sizeof(double) * (size_t)bg->ldh * ld_ah, st));
     }
     const long xrows = collapsed ? mp : np;  // length of the contraction axis in this mode
+    // Unrelated-donor form: per gene Phi'[y, W] ((1 + c) rows over the positions) and E1'[y, W] (k1 x 128); per block
+    // Phi'gx; the Gram of the KT + k1 rows; the rotated S in ws_A.
+    double *wb_yW = nullptr, *wb_E1yW = nullptr, *wb_g = nullptr, *wb_Gw = nullptr;
+    if (wb) {
+        const int k2 = bg->kin_k2, k2pad = bg->wb_k2pad;
+        const long groups = bg->kin_groups, brows = groups * k2 + GEMM_BK;
+        const size_t n_yW = (size_t)ng * (1 + c) * ldwb, n_E1 = (size_t)ng * wb_k1 * 128, n_g = (size_t)BLK * ldwb,
+                     n_Gw = (size_t)BLK * (KT + wb_k1) * (KT + wb_k1), n_tmp = (size_t)(bg->kin_rows + brows) * 128;
+        CRM_TRY(ctx->ws_WB.ensure(sizeof(double) * (n_yW + n_E1 + n_g + n_Gw + n_tmp)));
+        CRM_TRY(ctx->ws_A.ensure(sizeof(double) * (size_t)std::max(max_pairs, BLK) * k0 * ldAw));
+        CRM_TRY(ctx->ws_Anone.ensure(sizeof(double) * (size_t)ldAw));
+        CRM_HIP(hipMemsetAsync(ctx->ws_Anone.ptr, 0, sizeof(double) * (size_t)ldAw, st));
+        wb_yW = ctx->ws_WB.as<double>();
+        wb_E1yW = wb_yW + n_yW;
+        wb_g = wb_E1yW + n_E1;
+        wb_Gw = wb_g + n_g;
+        double* yWk = wb_Gw + n_Gw;            // [y, W] in donor order
+        double* Bk = yWk + (size_t)bg->kin_rows * 128;   // us_d'[y, W]_d, rows d k2 + j
+        CRM_HIP(hipMemsetAsync(Bk, 0, sizeof(double) * (size_t)brows * 128, st));
+        std::vector<GemmProblem> kp((size_t)2 * groups);
+        GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
+        for (int gi = 0; gi < ng; gi++) {
+            crm_gene* g = genes[gi];
+            CRM_TRY(launch_gather_rows(st, g->yW.as<double>(), g->ld_yw, bg->kin_map.as<int>(), bg->kin_rows, 1 + c, yWk, 128));
+            long maxlen = GEMM_BK;
+            for (long d = 0; d < groups; d++) {
+                GemmProblem p{};
+                p.X = bg->kin_Y.as<double>() + bg->kin_row0[d] * bg->kin_ldy; p.ldx = bg->kin_ldy;
+                p.Y = yWk + bg->kin_row0[d] * 128; p.ldy = 128;
+                p.C = Bk + (size_t)d * k2 * 128; p.ldc = 128;
+                p.M = k2; p.N = 1 + c; p.cells = bg->kin_len[d];
+                maxlen = std::max(maxlen, bg->kin_len[d]);
+                kp[d] = p;
+                GemmProblem q{};   // Phi_d'[y, W]_d, stored transposed: rows y, W_1 .. W_c over the positions
+                q.X = Bk + (size_t)d * k2 * 128; q.ldx = 128;
+                q.Y = bg->wb_U.as<double>() + (size_t)d * k2pad * 128; q.ldy = 128;
+                q.C = wb_yW + (size_t)gi * (1 + c) * ldwb + d * k2; q.ldc = ldwb;
+                q.M = 1 + c; q.N = k2; q.cells = k2pad;
+                kp[groups + d] = q;
+            }
+            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * kp.size(), hipMemcpyHostToDevice, st));
+            CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, k2, 1 + c, maxlen, false, 0, 1, 0));
+            CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, (int)groups, 1 + c, k2, k2pad, false, 0, 1, 0));
+            GemmProblem e{};   // E1'[y, W] over all cells
+            e.X = bg->H.as<double>(); e.ldx = bg->ldh; e.Y = g->yW.as<double>(); e.ldy = g->ld_yw;
+            e.C = wb_E1yW + (size_t)gi * wb_k1 * 128; e.ldc = 128; e.M = wb_k1; e.N = 1 + c;
+            CRM_HIP(hipMemcpyAsync(d_probs, &e, sizeof e, hipMemcpyHostToDevice, st));
+            CRM_TRY(launch_gemm_tn(ctx, d_probs, 1, wb_k1, 1 + c, np, false, 0, 1, 0));
+            CRM_HIP(hipStreamSynchronize(st));   // (kp, e live on this stack frame)
+        }
+    }
     std::vector<NullFitOut> h_fit((size_t)BLK * ng);
     std::vector<int> h_pos((size_t)BLK * ng), h_ord(max_pairs);
     std::vector<GemmProblem> probs(CRM_MAX_RHO + 4);
@@ -1775,22 +1979,7 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
         // from the first one's record -- neither depends on the permutation hooks)
         const bool replaying = ctx->replay_mode == 2;
         std::vector<double> flat_obj;
-        if (replaying) {
-            if (ng != 1 || ctx->replay_cursor >= ctx->replay_blocks.size()) {
-                set_error("scan: the replayed pass visits a block the recorded one did not");
-                return CRM_ERR_INTERNAL;
-            }
-            crm_ctx::ReplayBlock* rb = ctx->replay_blocks[ctx->replay_cursor++];
-            if (rb->col0 != col0 || rb->nb != nb || rb->collapsed != collapsed || rb->fit.size() != sizeof(NullFitOut) * (size_t)nb) {
-                set_error("scan: the replayed pass visits its blocks in another order than the recorded one");
-                return CRM_ERR_INTERNAL;
-            }
-            CRM_HIP(hipMemcpyAsync(d_fit, rb->fit.data(), rb->fit.size(), hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((ldT + 255) / 256), nb), dim3(256), 0, st, ctx->ws_T.as<double>(),
-                               (long)BLK, ldT, d_fit, nb, (int)ldT, rb->T.as<double>(), 1);
-            CRM_HIP(hipGetLastError());
-        } else {
-        if (fastT && kfold) {
+        auto fold_TH = [&]() -> int {
             // folded form: rows [0, k1) = E1'G over all cells (sliced along the cell axis), rows k1 + d' k2 + j = per-donor
             // us_j'G over the donor's own cells; the contraction over the donors sits in MixK (objects.h)
             double* Gk = ctx->ws_Gk.as<double>();
@@ -1823,6 +2012,27 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             CRM_TRY(launch_reduce_splits(st, ctx->ws_S2.as<double>(), e1_slab, fold_split3, e1_slab));
             CRM_HIP(hipMemcpyAsync(TH, ctx->ws_S2.ptr, sizeof(double) * (size_t)e1_slab, hipMemcpyDeviceToDevice, st));
             CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
+            return CRM_OK;
+        };
+        if (replaying) {
+            if (ng != 1 || ctx->replay_cursor >= ctx->replay_blocks.size()) {
+                set_error("scan: the replayed pass visits a block the recorded one did not");
+                return CRM_ERR_INTERNAL;
+            }
+            crm_ctx::ReplayBlock* rb = ctx->replay_blocks[ctx->replay_cursor++];
+            if (rb->col0 != col0 || rb->nb != nb || rb->collapsed != collapsed || rb->fit.size() != sizeof(NullFitOut) * (size_t)nb) {
+                set_error("scan: the replayed pass visits its blocks in another order than the recorded one");
+                return CRM_ERR_INTERNAL;
+            }
+            CRM_HIP(hipMemcpyAsync(d_fit, rb->fit.data(), rb->fit.size(), hipMemcpyHostToDevice, st));
+            // (unrelated-donor form: the assembly reads Phi'gx and E1'gx of the block from H'Gx -- formed again, same bits)
+            if (wb) CRM_TRY(fold_TH());
+            hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((ldT + 255) / 256), nb), dim3(256), 0, st, ctx->ws_T.as<double>(),
+                               (long)BLK, ldT, d_fit, nb, (int)ldT, rb->T.as<double>(), 1);
+            CRM_HIP(hipGetLastError());
+        } else {
+        if (fastT && kfold) {
+            CRM_TRY(fold_TH());
         } else if (fastT && kin_route) {
             // H'G donor by donor (as H'(g o E0) in step 6): per donor [us | E1]' G over its own cells, then the L rows by a
             // contraction over the donors with hKd and the E1 rows as sums over the donors
@@ -1926,7 +2136,23 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             }
         }
         CRM_HIP(hipMemcpyAsync(d_probs + 1, probs.data(), sizeof(GemmProblem) * n_main, hipMemcpyHostToDevice, st));
+        // (unrelated-donor form: the kernel timer brackets this launch, the rotations MixK(rho)'(H'Gx) -- the step's largest)
+        const bool timing_T = wb && ctx->timing && ctx->timed_used < 65536;
+        if (timing_T) {
+            if (ctx->timed_used == ctx->timed.size()) {
+                hipEvent_t ea, eb;
+                CRM_HIP(hipEventCreate(&ea));
+                CRM_HIP(hipEventCreate(&eb));
+                ctx->timed.emplace_back(ea, eb);
+            }
+            CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].first, st));
+        }
         CRM_TRY(launch_gemm_tn(ctx, d_probs + 1, n_main, nb, (int)ldq, fastT ? kdim : xrows, false, 0, 1, 0));
+        if (timing_T) {
+            CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].second, st));
+            ctx->timed_used++;
+            for (int q = 0; q < n_main; q++) ctx->kr_flops += 2.0 * (double)kdim * (double)nb * (double)probs[q].N;
+        }
         // 4. null fits + rho* per gene
         trace_push("crm null fits");
         for (int gi = 0; gi < ng; gi++) {
@@ -1966,6 +2192,24 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             return CRM_OK;
         }
         }   // (not replaying)
+        if (wb) {   // Phi'gx of the block: per donor U_d Lambda_d^-1/2 applied to its rows of H'Gx (stored transposed)
+            const int k1 = bg->kin_k1, k2 = bg->kin_k2, k2pad = bg->wb_k2pad;
+            const long groups = bg->kin_groups;
+            std::vector<GemmProblem> kp((size_t)groups);
+            for (long d = 0; d < groups; d++) {
+                GemmProblem p{};
+                p.X = ctx->ws_TH.as<double>() + (size_t)(k1 + d * k2) * ldb; p.ldx = ldb;
+                p.Y = bg->wb_U.as<double>() + (size_t)d * k2pad * 128; p.ldy = 128;
+                p.C = wb_g + d * k2; p.ldc = ldwb;
+                p.M = nb; p.N = k2; p.cells = k2pad;
+                kp[d] = p;
+            }
+            GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
+            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * kp.size(), hipMemcpyHostToDevice, st));
+            CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, nb, k2, k2pad, false, 0, 1, 0));
+            CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
+            ctx->unrelated_donor_blocks++;
+        }
         // 5. the (rho, variant) pairs some gene selected, ordered by rho (host; nb*ng*48 bytes cross PCIe)
         CRM_HIP(hipMemcpyAsync(h_fit.data(), d_fit, sizeof(NullFitOut) * (size_t)BLK * ng, hipMemcpyDeviceToHost, st));
         if (collapsed && near_out) CRM_HIP(hipMemcpyAsync(h_near.data(), d_near, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
@@ -2072,6 +2316,14 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
                 h_pos[(size_t)gi * BLK + b] = no_kinship_term(f) ? -1 : pair_of[(size_t)f.rho_index * BLK + b];
             }
         CRM_HIP(hipMemcpyAsync(d_pos, h_pos.data(), sizeof(int) * (size_t)BLK * ng, hipMemcpyHostToDevice, st));
+        if (wb && ng > 1) {   // (S in block order: a variant's rows of the rotated S sit at its own position)
+            std::vector<int> h_posw((size_t)BLK * ng, -1);
+            for (int gi = 0; gi < ng; gi++)
+                for (int b = 0; b < nb; b++)
+                    if (h_pos[(size_t)gi * BLK + b] >= 0) h_posw[(size_t)gi * BLK + b] = b;
+            CRM_HIP(hipMemcpyAsync(d_posw, h_posw.data(), sizeof(int) * h_posw.size(), hipMemcpyHostToDevice, st));
+            CRM_HIP(hipStreamSynchronize(st));   // (h_posw lives on this scope)
+        }
         CRM_HIP(hipMemcpyAsync(d_ord, h_ord.data(), sizeof(int) * npairs, hipMemcpyHostToDevice, st));
         double* Gs = ctx->ws_Gs.as<double>();
         CRM_TRY(launch_gather_block(st, Gt, ldb, xrows, xrows, nullptr, d_ord, npairs, Gs, ldp, (int)ldp));
@@ -2140,7 +2392,7 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             }
         }
         for (int i = 0; i < nrho; i++) {
-            if (cnt[i] == 0) continue;
+            if (cnt[i] == 0 || wb) continue;   // (unrelated-donor form: no A~ at all)
             GemmProblem p{};
             p.X = Gs + start[i]; p.ldx = ldp;
             p.C = ctx->ws_A.as<double>() + (size_t)start[i] * k0 * ldA;
@@ -2194,7 +2446,7 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             max_n = std::max(max_n, p.N);
             probs[nz++] = p;
         }
-        const bool timing = ctx->timing && ctx->timed_used < 65536;  // bounded: a forgotten timer cannot grow for ever
+        const bool timing = !wb && ctx->timing && ctx->timed_used < 65536;  // bounded: a forgotten timer cannot grow for ever
         if (timing) {
             if (ctx->timed_used == ctx->timed.size()) {
                 hipEvent_t a, b;
@@ -2295,7 +2547,7 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             }
             // (2 kin_rows k2 k0 + 2 n k1 k0 flops per variant, outside the timed pair: the roofline figure is the MixK product's own;
             // bench.py's whole_path counts them)
-            if (!in_pair_order) {
+            if (!in_pair_order && !wb) {
                 const int xg_cols = (int)std::min<long>(ld_xg, round_up((long)npairs * k0, 128) + 128);
                 CRM_TRY(launch_gather_slabs(st, S, ld_ah, kdim, d_ord, npairs, k0, ctx->ws_XG.as<double>(), ld_xg, xg_cols));
             }
@@ -2404,7 +2656,26 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
         CRM_HIP(hipMemcpyAsync(d_probs, probs.data(), sizeof(GemmProblem) * nz, hipMemcpyHostToDevice, st));
         if (collapsed)
             CRM_TRY(launch_gemm_tn(ctx, d_probs, nz, max_m, (int)((long)k0 * ldq), mp, false, 0, 1, 0));
-        else if (via_H && kin_route) {
+        else if (via_H && kin_route && wb) {
+            // Unrelated-donor form: the rotated S, rows (col k0 + i) over the donors k2 positions -- per donor
+            // (U_d Lambda_d^-1/2)' S_d, stored transposed into ws_A; col = the pair (one phenotype) or the block position
+            const int k1 = bg->kin_k1, k2 = bg->kin_k2, k2pad = bg->wb_k2pad;
+            const long groups = bg->kin_groups;
+            const int ncol = ng == 1 ? npairs : nb;
+            std::vector<GemmProblem> kp((size_t)groups);
+            for (long d = 0; d < groups; d++) {
+                GemmProblem p{};
+                p.X = ctx->ws_S.as<double>() + (size_t)(k1 + d * k2) * ld_ah; p.ldx = ld_ah;
+                p.Y = bg->wb_U.as<double>() + (size_t)d * k2pad * 128; p.ldy = 128;
+                p.C = ctx->ws_A.as<double>() + d * k2; p.ldc = ldAw;
+                p.M = ncol * k0; p.N = k2; p.cells = k2pad;
+                kp[d] = p;
+            }
+            GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
+            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * kp.size(), hipMemcpyHostToDevice, st));
+            CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol * k0, k2, k2pad, false, 0, 1, 0));
+            CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
+        } else if (via_H && kin_route) {
             if (timing) CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].first, st));
             struct Restore { crm_ctx* c; ~Restore() { c->tune.tag = 0; } } restore{ctx};
             ctx->tune.tag = 1;
@@ -2509,6 +2780,26 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             aa.gg = d_gg; aa.gy = d_gy + (size_t)gi * BLK; aa.gW = d_gW; aa.ld_gW = ld_gW;
             aa.coef = collapsed ? nullptr : d_coef; aa.ld_coef = ldb;
             aa.Q = d_Q; aa.F = ctx->ws_F.as<double>();
+            for (int i = 0; i < nrho; i++) aa.rho[i].rho = bg->rho[i];
+            if (wb) {   // (assemble.hip: woodbury_kernel)
+                for (int i = 0; i < nrho; i++) {
+                    AssembleRho& R = aa.rho[i];
+                    R.ty = wb_yW + (size_t)gi * (1 + c) * ldwb;
+                    R.tW = R.ty + ldwb; R.ldW = ldwb;
+                    R.S0 = bg->wb_S0[i].as<double>();
+                    R.T = wb_g + (size_t)sb0 * ldwb; R.ldT = ldwb;
+                    R.r = (int)bg->wb_P;
+                }
+                aa.sorted_pos = (ng == 1 ? d_pos : d_posw) + (size_t)gi * BLK;
+                aa.A = ctx->ws_A.as<double>(); aa.ldA = ldAw;
+                aa.wb_k1 = bg->kin_k1;
+                aa.wb_R = bg->wb_R.as<double>(); aa.wb_ldR = ldwb;
+                aa.wb_E1X = ctx->ws_S.as<double>(); aa.wb_ldE1X = ld_ah;
+                aa.wb_E1yW = wb_E1yW + (size_t)gi * bg->kin_k1 * 128; aa.wb_ldE1yW = 128;
+                aa.wb_E1g = ctx->ws_TH.as<double>() + sb0; aa.wb_ldE1g = ldb;
+                aa.wb_EE = bg->wb_EE.as<double>();
+                aa.wb_Gw = wb_Gw;
+            }
             double* slow_ws = nullptr;
             if (slow_forms) {
                 CRM_TRY(ctx->ws_xwide.ensure(sizeof(double) * std::max(std::max(assemble_rows_scratch_doubles(BLK, k0, c), eig_scratch_doubles(BLK, k0)),
@@ -2763,6 +3054,14 @@ long crm_test_spectrum_tail_launches(const crm_ctx* ctx) { return ctx ? ctx->spe
 long crm_test_dense_repeats(const crm_ctx* ctx) { return ctx ? ctx->dense_repeats : -1; }
 
 long crm_test_donor_pair_blocks(const crm_ctx* ctx) { return ctx ? ctx->donor_pair_blocks : -1; }
+
+int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks) {
+    return crm::guarded("crm_test_unrelated_donor_blocks", [&]() -> int {
+    if (!ctx || !blocks) return CRM_ERR_ARG;
+    *blocks = ctx->unrelated_donor_blocks;
+    return CRM_OK;
+    });
+}
 
 long crm_test_tests_without_pair(const crm_ctx* ctx) { return ctx ? ctx->tests_without_pair : -1; }
 

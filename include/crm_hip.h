@@ -299,7 +299,9 @@ int crm_set_null_fit_polish(crm_ctx* ctx, int on);
 
 /* ---- instrumentation ----------------------------------------------------------------
  * Sum of HIP-event durations (ms) and launch count of the dominant kernel (the Khatri-Rao
- * contraction) since the last reset, measured on the context's stream. */
+ * contraction) since the last reset, measured on the context's stream.  On the unrelated-donor
+ * form (donor-level kinship diagonal: no A~ is formed) the timed launch is the block's largest
+ * remaining one, the rotations MixK(rho)'(H'Gx), and kr_flops counts its executed flops. */
 int crm_kernel_timer_reset(crm_ctx* ctx);
 int crm_kernel_timer_read(crm_ctx* ctx, double* kr_ms, long* kr_launches, double* kr_flops,
                           double* total_ms);

@@ -76,6 +76,11 @@ long crm_test_dense_repeats(const crm_ctx* ctx);
  * features E (x) E (scan.hip: donor pairs -- the kinship term's contexts are the scan's own; form "donor_pairs": 0 never,
  * 1 where its estimated time is the smaller one, 2 always). */
 long crm_test_donor_pair_blocks(const crm_ctx* ctx);
+/* Blocks of this context's scans served by the unrelated-donor form: a folded kinship structure whose donor-level kinship
+ * hKd hKd' is diagonal takes Q and F through a per-donor Woodbury inverse instead of the product A~ = MixK(rho*)'S
+ * (scan.hip: kin_wb; form "kin_diag": 0 never, 1 where the background allows it and the cost model says it pays, 2 wherever
+ * the background and the shapes allow it -- k0 + c + 2 + k1 <= 144).  *blocks: the count so far. */
+int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks);
 /* (phenotype, variant) tests of this context's scans whose selected fit has no kinship term to speak of --
  * (v0 / v1) max S0(rho*) <= 1e-10: delta at its upper clamp -- and for which no rotated test direction A~ was formed
  * (scan.hip; form "pairs_without_kinship_term" = 0 forms it for every test). */

@@ -14,7 +14,8 @@ rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 # the timed steps: everything after the last constructor kernel (trd_* / dc_* / bt_*)
 last_ctor = max(i for i, r in enumerate(rows) if any(t in r["Kernel_Name"] for t in ("trd_", "dc_", "bt_larft")))
 steps = rows[last_ctor + 1:]
-tagged = [i for i, r in enumerate(steps) if "128, 1>" in r["Kernel_Name"]]
+# (cut on the eigenvalue / Davies launch: every step has exactly one, on either kinship route)
+tagged = [i for i, r in enumerate(steps) if "eig_davies_kernel" in r["Kernel_Name"]]
 nsteps = len(tagged)
 # Whole steps only.  Every step holds exactly one tagged launch and issues the same number of launches (the bench scans the
 # same panel every step), so the steps are the trace's last nsteps * L launches cut every L, L = the distance between two

@@ -16,8 +16,10 @@ from ._engine import (
     release_workspaces,
     run_association,
     run_association_fast,
+    run_association_many,
     run_interaction,
     run_interaction_many,
+    scan_association_many,
     scan_interaction_many,
     scan_interaction_resumable,
 )
@@ -40,8 +42,10 @@ __all__ = [
     "detect_groups",
     "run_association",
     "run_association_fast",
+    "run_association_many",
     "run_interaction",
     "run_interaction_many",
+    "scan_association_many",
     "scan_interaction_many",
     "scan_interaction_resumable",
     "compute_maf",

@@ -1374,6 +1374,108 @@ def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progr
     return out["pv"], {k: out[k] for k in ("rho1", "e2", "g2", "eps2")}
 
 
+def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=False, progress=False):
+    """Association LRTs (``scan_association``, or ``scan_association_fast`` with ``fast=True``) of several phenotypes
+    against one genotype panel in a single pass.
+
+    ``crms``: ``CellRegMap`` objects that share the background, ``W`` and ``E``.  The null models are fitted once per
+    call; the block of variants, its rotations and g'W are shared by all phenotypes.  Returns ``(pvalues, info)``:
+    ``pvalues`` of shape (len(crms), p), row i equal to ``crms[i].scan_association(_fast)(G)``; ``info`` holds ``rho1``,
+    ``e2``, ``g2``, ``eps2`` as (len(crms),) arrays.  ``cis_index`` as in ``scan_interaction_many``: ``pvalues`` is then a
+    list whose entry i follows the columns of ``cis_index[i]`` (repeats included).  ``return_stats`` adds ``alt_lml`` (the
+    shape of ``pvalues``), ``null_lml`` and ``null_delta`` (len(crms),) to ``info``.  ``progress``: ``True`` for a tqdm
+    bar, or a callable ``(done, total)`` counted in variants of the panel that at least one phenotype tests."""
+    lib = _lib.load()
+    crms = list(crms)
+    if not crms:
+        raise ValueError("no phenotypes given")
+    first = crms[0]
+    for c in crms[1:]:
+        if c._bg is not first._bg:
+            raise ValueError("all CellRegMap objects must share one background (pass background=...)")
+        if c._W.shape != first._W.shape or c._E0.shape != first._E0.shape:
+            raise ValueError("all CellRegMap objects must share W and E")
+        if not (c._W is first._W or np.array_equal(c._W, first._W)):
+            raise ValueError("all CellRegMap objects of one pass must hold the same covariates W")
+        if not (c._E0 is first._E0 or np.array_equal(c._E0, first._E0)):
+            raise ValueError("all CellRegMap objects of one pass must hold the same contexts E")
+    panel = first._panel(G)
+    n, p = panel.shape
+    first._bind_gene()
+    _bind_genes_like(first, [c for c in crms[1:] if c._gene is None and c._bg is first._bg])
+    genes = [c._bind_gene(like=first) for c in crms]
+    ng = len(genes)
+    handles = (ctypes.c_void_p * ng)(*[g.value for g in genes])
+    null = np.empty((ng, 6))
+    _lib.check(lib.crm_association_null_multi(handles, ng, _lib.ptr(null)))
+    info = {"rho1": null[:, 0].copy(), "e2": null[:, 1].copy(), "g2": null[:, 2].copy(), "eps2": null[:, 3].copy()}
+    if return_stats:
+        info["null_lml"] = null[:, 4].copy()
+        info["null_delta"] = null[:, 5].copy()
+    fast = int(bool(fast))
+
+    def scan(idx, a, count, pv, alt, offset, total):
+        hs = (ctypes.c_void_p * len(idx))(*[genes[i].value for i in idx])
+        rows = np.ascontiguousarray(null[idx])
+        with _progress(first._device, progress, count, offset=offset, grand_total=total):
+            _lib.check(lib.crm_scan_association_multi(hs, len(idx), panel.handle, a, count, fast, _lib.ptr(rows),
+                                                      _lib.ptr(pv), _lib.ptr(alt)))
+
+    if cis_index is None:
+        columns, runs = None, ([(0, p, np.arange(ng))] if p else [])
+    else:
+        columns, runs = _cis_runs(cis_index, ng, p)
+    tested = int(sum(count for _, count, _ in runs))
+    bar = None
+    if progress is True:   # one bar over the whole pass
+        from tqdm import tqdm
+
+        bar = tqdm(total=tested)
+        state = {"done": 0}
+
+        def progress(done, total, _bar=bar, _state=state):
+            _bar.update(done - _state["done"])
+            _state["done"] = done
+    try:
+        if columns is None:
+            pv, alt = np.empty((ng, p)), np.empty((ng, p))
+            if p:
+                scan(np.arange(ng), 0, p, pv, alt, 0, p)
+            if return_stats:
+                info["alt_lml"] = alt
+            return pv, info
+        full_pv = [np.full(p, np.nan) if columns[i].size else None for i in range(ng)]
+        full_alt = [np.full(p, np.nan) if columns[i].size else None for i in range(ng)]
+        seen = 0
+        for a, count, active in runs:
+            pv, alt = np.empty((len(active), count)), np.empty((len(active), count))
+            scan(active, a, count, pv, alt, seen, tested)
+            seen += count
+            for row, i in enumerate(active):
+                full_pv[i][a:a + count] = pv[row]
+                full_alt[i][a:a + count] = alt[row]
+        pvs = [full_pv[i][columns[i]] if columns[i].size else np.empty(0) for i in range(ng)]
+        if return_stats:
+            info["alt_lml"] = [full_alt[i][columns[i]] if columns[i].size else np.empty(0) for i in range(ng)]
+        return pvs, info
+    finally:
+        if bar is not None:
+            bar.close()
+
+
+def run_association_many(Y, W, E, G, hK=None, *, cis_index=None, fast=False, device=0):
+    """``run_association`` (``run_association_fast`` with ``fast=True``) for the columns of ``Y`` (n x genes) with one
+    background decomposition, one genotype upload and shared per-variant work.  Keeps the reference's positional
+    binding (_cellregmap.py:498, :529): ``W`` goes to the contexts slot, ``E`` to the fixed effects.  Returns
+    ``(pvalues, info)`` as ``scan_association_many``."""
+    Y = np.asarray(Y, float)
+    if Y.ndim != 2:
+        raise ValueError("Y must be n x genes")
+    first = CellRegMap(Y[:, 0], W, E, hK=hK, device=device)
+    crms = [first] + [CellRegMap(Y[:, i], W, E, hK=hK, device=device, background=first._bg) for i in range(1, Y.shape[1])]
+    return scan_association_many(crms, G, cis_index=cis_index, fast=fast)
+
+
 def scan_interaction_resumable(crm, G, checkpoint, idx_E=None, idx_G=None, chunk=8192, scan=None):
     """``crm.scan_interaction(G, idx_E, idx_G)`` over column chunks of the host matrix ``G`` with the finished chunks kept in
     ``checkpoint`` (an ``.npz`` file, rewritten atomically after every chunk): a job that is killed -- a pre-empted node, a

@@ -64,6 +64,9 @@ SIGNATURES = {
     "crm_scan_interaction_permuted": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int] + [vp] * 8),
     "crm_scan_interaction_multi": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long] + [vp] * 8),
     "crm_scan_association": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, vp, vp, vp]),
+    "crm_association_null_multi": (ctypes.c_int, [vp, ctypes.c_int, vp]),
+    "crm_scan_association_multi": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, vp, vp,
+                                                  vp]),
     "crm_lmm_fit": (ctypes.c_int, [vp, ctypes.c_int, vp, vp]),
     "crm_cov_solve": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp, ctypes.c_int, vp]),
     "crm_set_block_variants": (ctypes.c_int, [vp, ctypes.c_int]),

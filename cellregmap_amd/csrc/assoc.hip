@@ -34,10 +34,9 @@ __device__ inline double block_sum(double v, double* red) {
 // Null-model quantities at the frozen delta: L = chol(W'K^-1W), zy = L^-1 W'K^-1y,
 // rss0 = y'K^-1y - zy'zy, logdet K, and the spectrum weights w_j = 1/((1-d) S0_j + d).
 // prep layout: [0] rss0, [1] logdetK, [2] delta, [3] ok, [8 .. 8+c) zy, [8+CMAX ..) L (c x c, ld CMAX)
-__global__ __launch_bounds__(256) void fastscan_prep_kernel(AssocArgs a, double* __restrict__ prep,
-                                                             double* __restrict__ wts) {
-    __shared__ double red[256];
-    __shared__ double hy[CMAX];
+// (the body of the one-gene kernel and of the batched one: one workgroup per gene, the same record per gene)
+__device__ __forceinline__ void fastscan_prep_body(const AssocArgs& a, double* __restrict__ prep,
+                                                   double* __restrict__ wts, double* red, double* hy) {
     double* const H = prep + 8 + CMAX;   // (c x c, ld CMAX: in the record itself -- 128 x 128 doubles do not fit static LDS;
                                          // one workgroup, its own writes read back past the L1 by thread 0 only)
     const int tid = threadIdx.x;
@@ -105,6 +104,21 @@ __global__ __launch_bounds__(256) void fastscan_prep_kernel(AssocArgs a, double*
         prep[2] = delta;
         prep[3] = ok ? 1.0 : 0.0;
     }
+}
+
+__global__ __launch_bounds__(256) void fastscan_prep_kernel(AssocArgs a, double* __restrict__ prep,
+                                                             double* __restrict__ wts) {
+    __shared__ double red[256];
+    __shared__ double hy[CMAX];
+    fastscan_prep_body(a, prep, wts, red, hy);
+}
+
+__global__ __launch_bounds__(256) void fastscan_prep_batch_kernel(const AssocArgs* __restrict__ args, double* __restrict__ prep,
+                                                                   long prep_stride, double* __restrict__ wts, long wts_stride) {
+    __shared__ double red[256];
+    __shared__ double hy[CMAX];
+    const long g = blockIdx.x;
+    fastscan_prep_body(args[g], prep + g * prep_stride, wts + g * wts_stride, red, hy);
 }
 
 // Per SNP: h_gg, h_gy, h_gW in the frozen metric, Schur complement against W, ML log-likelihood.
@@ -191,6 +205,17 @@ int launch_fastscan_prep(hipStream_t st, const AssocArgs& a, double* prep, doubl
         return CRM_ERR_UNSUPPORTED;
     }
     hipLaunchKernelGGL(fastscan_prep_kernel, dim3(1), dim3(256), 0, st, a, prep, wts);
+    CRM_HIP(hipGetLastError());
+    return CRM_OK;
+}
+int launch_fastscan_prep_batch(hipStream_t st, const AssocArgs* args_dev, int genes, int c, double* prep, long prep_stride,
+                               double* wts, long wts_stride) {
+    if (genes <= 0) return CRM_OK;
+    if (c > CMAX) {
+        set_error("association: %d covariate columns (supported up to %d)", c, CMAX);
+        return CRM_ERR_UNSUPPORTED;
+    }
+    hipLaunchKernelGGL(fastscan_prep_batch_kernel, dim3(genes), dim3(256), 0, st, args_dev, prep, prep_stride, wts, wts_stride);
     CRM_HIP(hipGetLastError());
     return CRM_OK;
 }

@@ -84,6 +84,9 @@ struct AssocArgs {
 };
 size_t fastscan_prep_doubles();
 int launch_fastscan_prep(hipStream_t st, const AssocArgs& a, double* prep, double* wts);
+// one workgroup per gene: args_dev[g] (device memory) -> record prep + g prep_stride, weights wts + g wts_stride
+int launch_fastscan_prep_batch(hipStream_t st, const AssocArgs* args_dev, int genes, int c, double* prep, long prep_stride,
+                               double* wts, long wts_stride);
 int launch_fastscan(hipStream_t st, const AssocArgs& a, const double* prep, const double* wts,
                     int variants, double* alt_lml);
 int launch_lrt(hipStream_t st, const double* alt_lml, double null_lml, int count, double* pv);

@@ -264,6 +264,19 @@ int crm_scan_interaction_multi(crm_gene* const* genes, int ngenes, crm_panel* pa
 int crm_scan_association(crm_gene* gene, crm_panel* panel, long first, long count, int fast,
                          double* out_pvalue, double* out_alt_lml, double* out_null);
 
+/* ---- association scans of several phenotypes (shared background and W) against one panel.
+ * crm_association_null_multi: the null model of crm_scan_association for each gene; out_null is ngenes x 6
+ * {rho1, e2, g2, eps2, lml, delta}, row i bit for bit the out_null of crm_scan_association(genes[i], ...).
+ * crm_scan_association_multi: the association LRT of every gene against variants [first, first + count) of the
+ * panel, the null model taken from `null` (the rows crm_association_null_multi returned for these genes: rho1 must
+ * be a grid point and lml finite, else CRM_ERR_ARG) -- a cis walk calls it once per run of constant phenotypes
+ * without refitting the nulls.  The block of variants, its rotations Q0(rho)'G per distinct rho* and g'[W, y_j]
+ * are computed once for all genes.  out_pvalue / out_alt_lml: ngenes x count, gene-major (may be NULL); results
+ * per gene are those of crm_scan_association (fast as there) up to the order of the sums. */
+int crm_association_null_multi(crm_gene* const* genes, int ngenes, double* out_null);
+int crm_scan_association_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
+                               int fast, const double* null, double* out_pvalue, double* out_alt_lml);
+
 /* ---- effect sizes: the device operations behind predict_interaction (_cellregmap.py:137-205) and
  * estimate_aggregate_environment (:207-244).
  * crm_lmm_fit: LMM(y, M, QS(rho), restricted).fit() for every grid point of the gene's background

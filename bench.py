@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the interaction score test on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = the whole hot path (null fits over the rho grid, Khatri-Rao contraction, score statistic,
 eigenvalues, Davies) over one batch of `--batch` synthetic variants of BASELINE config 3 (20 000 cells,
@@ -11,12 +11,17 @@ starts one process per GPU itself (or runs under torch.distributed.run); variant
 ranks with no data-path collective, the grid points of the background are decomposed by different ranks
 and broadcast (RCCL), and the per-variant results are all-gathered at the end.
 
-Legs of one run (one JSON line on rank 0):
+A plain run does what its headline needs -- data, constructor, W warm-up and K timed steps, the dump, one JSON line
+on rank 0:
   value / ms_per_step   weak scaling: every rank times K steps on its own shard (the driver's contract)
+  roofline              the dominant kernel by HIP events around its launches inside the timed steps
+  whole_path, hbm_view  the headline rate against the executed / algorithmic flops and bytes of a variant
+--full adds the legs that scan, construct or time anything of their own (null in a plain run's line):
   full_panel            strong scaling on the FIXED 50 000-variant panel of the config, sharded over the ranks:
                         scan-only and end-to-end (constructor + upload + scan + gather) rates
   config4               64 phenotypes against one panel, variants sharded (BASELINE config 4's shape)
-  donor_collapsed, cpu_baseline (N = 1)
+  direct_route, rotated_kinship_factor, donor_collapsed (N = 1)
+  cpu_baseline (N = 1)  the CPU oracle on a sample of the variants, and config-4 pairs against it
 
 CRM_BENCH_SHARE_GPU=1 python bench.py --gpus 2 ...: dry run of the N > 1 code path on a box with ONE GPU (both ranks
 on device 0, gloo instead of RCCL; flagged in the line's "data" -- not a scaling measurement).
@@ -314,23 +319,28 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=4096, help="variants per step")
     ap.add_argument("--config", default="cfg3", help="cfg2 | cfg3 | cfg5 (BASELINE.json configs[1] / [2] / [4])")
-    ap.add_argument("--cpu-variants", type=int, default=32, help="variants of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side legs (full panel, config 4, direct route, rotated kinship factor, donor-collapsed "
+                         "path, CPU baseline); a plain run times the headline steps alone")
+    ap.add_argument("--cpu-variants", type=int, default=32, help="variants of the CPU-baseline sample (--full; 0 = skip)")
     ap.add_argument("--cpu-repeats", type=int, default=3)
     ap.add_argument("--mode", default="C", choices=["C", "B"],
                     help="background: C = E1E1' + K o EE' (headline), B = E1E1' + hK hK' (r = k + m)")
     ap.add_argument("--block", type=int, default=0, help="variants per internal block (0 = library default)")
     ap.add_argument("--polish", type=int, default=0)
-    ap.add_argument("--collapsed", type=int, default=1, help="also time the donor-collapsed path (N=1)")
-    ap.add_argument("--full-panel", type=int, default=1, help="strong-scaling leg on the config's fixed panel")
+    ap.add_argument("--collapsed", type=int, default=1, help="also time the donor-collapsed path (--full; N=1)")
+    ap.add_argument("--full-panel", type=int, default=1,
+                    help="strong-scaling leg on the config's fixed panel (--full); the timed steps scan this rank's shard "
+                         "of that panel when it holds enough variants, with 0 a panel of their own")
     ap.add_argument("--kinship", default="indicator", choices=["indicator", "rotated"],
                     help="kinship factor of the synthetic cohort: donor indicators, or the dense U sqrt(S) of the same K")
     ap.add_argument("--direct-steps", type=int, default=3,
                     help="timed steps of the general-input side leg (the direct contraction against Q0(rho*), what a "
-                         "cell-level hK / Ls gets; N = 1 only; 0 = skip)")
+                         "cell-level hK / Ls gets; --full, N = 1 only; 0 = skip)")
     ap.add_argument("--rotated-steps", type=int, default=3,
                     help="timed steps of the side leg on the kinship factor as the reference's simulator forms it (U sqrt(S): "
-                         "dense, donor-expanded; N = 1 and --kinship indicator only; 0 = skip)")
-    ap.add_argument("--genes", type=int, default=64, help="phenotypes of the config-4 leg (0 = skip)")
+                         "dense, donor-expanded; --full, N = 1 and --kinship indicator only; 0 = skip)")
+    ap.add_argument("--genes", type=int, default=64, help="phenotypes of the config-4 leg (--full; 0 = skip)")
     ap.add_argument("--genes-variants", type=int, default=0,
                     help="variants of the config-4 leg, all ranks together (0 = the config's whole fixed panel when "
                          "--full-panel is on, i.e. BASELINE config 4 itself at --genes 64; else the weak-scaling panel)")
@@ -412,13 +422,15 @@ def main():
     # a dense donor-expanded n x m factor of the same K (cellregmap_amd/synth.py: kinship_factor)
     cohort = make_cohort(donors, cells, k0, 16, seed=20, kinship=args.kinship)
     f_first, f_count = variant_shard(p_total, rank, world)
+    weak_blocks = max(1, min(steps, 12 if world == 1 else 4))   # (N ranks generate their panels side by side on one host)
     G_full = None
-    if args.full_panel:
+    # (a plain run makes the fixed panel only when the timed steps scan it: the whole shard, so that the steps read
+    # the same device panel -- same columns, same row pitch -- as under --full)
+    if args.full_panel and (args.full or f_count >= weak_blocks * batch):
         # the same panel for every world size; a rank expands only its own shard of it to cells
         full = make_cohort(donors, cells, k0, p_total, seed=77, with_phenotype=False, columns=(f_first, f_count))
         G_full, donor_of_cell = full.G, full.donor_of_cell
         del full
-    weak_blocks = max(1, min(steps, 12 if world == 1 else 4))   # (N ranks generate their panels side by side on one host)
     if G_full is not None and f_count >= weak_blocks * batch:
         G_weak = G_full[:, :weak_blocks * batch]
     else:
@@ -488,6 +500,7 @@ def main():
         if "panel" not in uploaded:
             upload_full_panel()
         fpanel, t_up = uploaded["panel"], uploaded["seconds"]
+    if G_full is not None and args.full:
         fpv, frho = np.empty(f_count), np.empty(f_count)
         fence()
         t0 = time.perf_counter()
@@ -544,6 +557,7 @@ def main():
             del crm_s, spv
             full_panel["end_to_end_best_s"] = min(full_panel["end_to_end_s"], full_panel["streamed"]["end_to_end_s"])
             full_panel["end_to_end_best_rate"] = round(p_total / full_panel["end_to_end_best_s"], 1)
+    if G_full is not None:
         if f_count >= weak_blocks * batch:
             panel = fpanel
             fpanel_kept = fpanel
@@ -600,7 +614,7 @@ def main():
     #      Q0(rho*) over all cells, i.e. SURVEY 8(d)'s 2 n r* k0 flops per variant.  Same steps, same panel, same results.
     direct = None
     kin_on = lib.crm_background_kinship_groups(crm._bg.handle) if os.environ.get("CRM_KIN_ROUTE", "1") != "0" else 0
-    if world == 1 and args.direct_steps > 0 and kin_on:
+    if args.full and world == 1 and args.direct_steps > 0 and kin_on:
         dpv, drho, dQ = np.empty(batch), np.empty(batch), np.empty(batch)
         _lib.check(lib.crm_test_set_kinship_route(ctx, 0))
         try:
@@ -643,7 +657,7 @@ def main():
     #      phenotype (y_k is drawn through hK), the same genotype panel.  The engine finds the donor structure of either factor
     #      and folds the donor-level m x m block into its mixing matrices, so the two rates should agree.
     rotated = None
-    if world == 1 and args.rotated_steps > 0 and args.kinship == "indicator":
+    if args.full and world == 1 and args.rotated_steps > 0 and args.kinship == "indicator":
         t0 = time.perf_counter()
         coh2 = make_cohort(donors, cells, k0, 16, seed=20, kinship="rotated")
         Ls2 = get_L_values(coh2.hK, coh2.E)
@@ -678,7 +692,7 @@ def main():
     # ---- config 4's shape: `genes` phenotypes against one panel, the variants sharded over the ranks ---------------
     config4 = None
     multi_keep = None
-    if args.genes > 1:
+    if args.full and args.genes > 1:
         from cellregmap_amd import scan_interaction_many
 
         rng = np.random.default_rng(99)  # same phenotypes on every rank
@@ -778,7 +792,7 @@ def main():
     #      the synthetic cohort -- like every expanded CellRegMap genotype matrix -- is); reported
     #      beside the dense headline, never as `value`
     collapsed = None
-    if args.collapsed and world == 1:
+    if args.full and args.collapsed and world == 1:
         t0 = time.time()
         dpanel = GenotypePanel.from_donors(G_weak[::cells], donor_of_cell, device=local_rank)
         dense_panel = panel
@@ -805,7 +819,7 @@ def main():
 
     # ---- CPU baseline: the oracle on this host's cores, a bounded sample (rank 0, N = 1 only) ------------------------
     cpu = None
-    if args.cpu_variants > 0 and world == 1:
+    if args.full and args.cpu_variants > 0 and world == 1:
         cpu = cpu_baseline_leg(crm, cohort, Ls, n, min(steps, weak_blocks) * batch, G_weak, G_full, pv_dense, args.cpu_variants,
                                args.cpu_repeats, multi_keep, config4)
     out = {

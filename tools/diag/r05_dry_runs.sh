@@ -8,12 +8,12 @@ out=gpurun_out/${1:-dry_runs}
 mkdir -p $out
 free -g | tee $out/host_memory.txt
 mem=$(free -g | awk '/^Mem:/{print $7}')
-python3 bench.py --cpu-variants 0 > $out/bench_n1.json 2> $out/bench_n1.err; echo "n1 rc=$?"
+python3 bench.py --full --cpu-variants 0 > $out/bench_n1.json 2> $out/bench_n1.err; echo "n1 rc=$?"
 for n in 4 8; do
   if [ "$mem" -lt $((n * 8 + 16)) ]; then echo "skip world $n: only $mem GiB of host memory available"; continue; fi
   # internal blocks of 1024 variants and small pair buffers: eight ranks' work buffers beside each other in one GPU's HBM
   CRM_BENCH_SHARE_GPU=1 CRM_PAIR_BUFFER_GB=6 CRM_BENCH_COLLECTIVE_TIMEOUT_S=300 timeout 1500 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n \
-      --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --gpus $n --steps 4 --warmup 1 --block 1024 \
+      --master-addr 127.0.0.1 --master-port $((29500 + n)) bench.py --full --gpus $n --steps 4 --warmup 1 --block 1024 \
       > $out/bench_dry_run_world$n.json 2> $out/bench_dry_run_world$n.err; echo "world $n rc=$?"
   tail -3 $out/bench_dry_run_world$n.err
 done

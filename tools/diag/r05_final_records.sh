@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/r05final
 mkdir -p $out
 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "default rc=$?"
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "default rc=$?"
 bash tools/diag/steps_profile.sh r05final_steps > $out/steps_profile.log 2>&1
 cp gpurun_out/r05final_steps/bench_steps_under_rocprof.json $out/bench_timed_steps_only_under_rocprof.json
 cp gpurun_out/r05final_steps/kernel_stats.csv $out/rocprofv3_kernel_stats_timed_steps_only.csv

@@ -8,7 +8,7 @@ out=gpurun_out/${1:-side_profiles}
 mkdir -p $out
 prof() {   # name, bench flags...
   name=$1; shift
-  python3 bench.py --cpu-variants 0 --genes 0 "$@" > $out/bench_$name.json 2> $out/bench_$name.err; echo "$name rc=$?"
+  python3 bench.py --full --cpu-variants 0 --genes 0 "$@" > $out/bench_$name.json 2> $out/bench_$name.err; echo "$name rc=$?"
   rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$name -o t -- python3 bench.py --cpu-variants 0 --genes 0 --full-panel 0 --collapsed 0 --direct-steps 0 "$@" \
       > $out/bench_${name}_steps_under_rocprof.json 2> $out/rocprof_$name.err; echo "$name rocprof rc=$?"
   f=$(find $out/prof_$name -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $out/kernel_stats_$name.csv

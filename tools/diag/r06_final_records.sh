@@ -8,8 +8,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/r06final
 mkdir -p $out
 python3 -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"
-python3 bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "default rc=$?"
-CRM_BENCH_FORCE_EXCHANGE=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 \
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "default rc=$?"
+CRM_BENCH_FORCE_EXCHANGE=1 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 1 \
     > $out/bench_nccl_world1.json 2> $out/bench_nccl_world1.err; echo "nccl world 1 rc=$?"
 bash tools/diag/steps_profile.sh r06final_steps > $out/steps_profile.log 2>&1
 cp gpurun_out/r06final_steps/bench_steps_under_rocprof.json $out/bench_timed_steps_only_under_rocprof.json

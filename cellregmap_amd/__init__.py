@@ -11,8 +11,10 @@ from ._engine import (
     detect_groups,
     compute_maf,
     estimate_betas,
+    estimate_betas_many,
     get_L_values,
     lrt_pvalues,
+    predict_interaction_many,
     release_workspaces,
     run_association,
     run_association_fast,
@@ -50,8 +52,10 @@ __all__ = [
     "scan_interaction_resumable",
     "compute_maf",
     "estimate_betas",
+    "estimate_betas_many",
     "get_L_values",
     "lrt_pvalues",
+    "predict_interaction_many",
     "release_workspaces",
     "Term",
 ]

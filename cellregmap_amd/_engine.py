@@ -1114,6 +1114,7 @@ class CellRegMap:
         finally:
             lib.crm_gene_destroy(h)
         beta = Vt.T @ beta
+        self._last_fit = fit
         return fit[0], fit[1], fit[2], beta, int(fit[5])
 
     def _snp_background(self, gE):
@@ -1638,3 +1639,183 @@ def estimate_betas(y, W, E, G, maf=None, E1=None, E2=None, hK=None, *, device=0)
     if maf is None:
         maf = compute_maf(G)
     return crm.predict_interaction(G, maf)
+
+
+# -- batched effect sizes --------------------------------------------------------------------------
+_EFFECTS_MAX_COLUMNS = 130   # c_W + 2 k0 + 2: the packed systems of csrc/effects_multi.hip (as nullfit_xwide.hip)
+
+
+def _l_halves(crm):
+    """The L part of the per-SNP covariance halves (``_snp_background``): HadamardHalves, an n x cols matrix or None."""
+    if isinstance(crm._Ls, HadamardHalves):
+        return crm._Ls
+    if len(crm._Ls) == 0:
+        return None
+    return np.concatenate(crm._Ls, axis=1)
+
+
+def _same_ls(a, b):
+    if a is b:
+        return True
+    if isinstance(a, HadamardHalves) or isinstance(b, HadamardHalves):
+        if not (isinstance(a, HadamardHalves) and isinstance(b, HadamardHalves)):
+            return False
+        return (a.shape_us == b.shape_us and np.array_equal(a.hK, b.hK)
+                and np.array_equal(a.device_us, b.device_us))
+    return len(a) == len(b) and all(x.shape == y.shape and np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def _full_rank_gram(gram):
+    """get_L_values' certificate of full column rank from a Gram matrix (smallest eigenvalue above 1e-8 of the largest
+    and above 1e-6): far on the safe side of the reference's sqrt(eps) rule for the singular values."""
+    lam = np.linalg.eigvalsh(gram)
+    return bool(np.all(np.isfinite(lam)) and lam[0] > 1e-8 * lam[-1] and lam[0] > 1e-6)
+
+
+def predict_interaction_many(crms, G, MAF, pairs=None, return_info=False):
+    """``predict_interaction`` for many (phenotype, variant) pairs in one call.
+
+    ``crms``: ``CellRegMap`` objects that share ``W``, ``E`` and ``Ls`` (one phenotype each).  ``G``: n x p genotypes,
+    ``MAF``: (p,).  ``pairs``: a (P, 2) integer array of (index into ``crms``, column of ``G``); ``None`` means every
+    phenotype x every variant (phenotype-major).  Returns ``(beta_g (P,), beta_gxe (1, n, P))``; pair i equals
+    ``crms[pairs[i, 0]].predict_interaction(G[:, [pairs[i, 1]]], MAF[[pairs[i, 1]]])`` to the reference's tolerances.
+    ``return_info`` adds a dict with ``rho1``, ``v0``, ``v1``, ``lml`` (P,), ``u`` (P, k0) and ``route`` (P,): "woodbury" for
+    pairs of the batched rank-k0 form, "per_snp" for those of the per-SNP decompositions (routing rules: DESIGN.md
+    section 9)."""
+    crms = list(crms)
+    if not crms:
+        raise ValueError("no phenotypes given")
+    first = crms[0]
+    n = first.n_samples
+    for c in crms[1:]:
+        if c._W.shape != first._W.shape or not (c._W is first._W or np.array_equal(c._W, first._W)):
+            raise ValueError("all CellRegMap objects must hold the same covariates W")
+        if c._E0.shape != first._E0.shape or not (c._E0 is first._E0 or np.array_equal(c._E0, first._E0)):
+            raise ValueError("all CellRegMap objects must hold the same contexts E")
+        if not _same_ls(c._Ls, first._Ls) or not np.array_equal(np.asarray(c._rho1), np.asarray(first._rho1)):
+            raise ValueError("all CellRegMap objects must hold the same Ls")
+    for c in crms:
+        if not np.all(np.isfinite(c._y)):
+            raise ValueError("There are non-finite values in the outcome.")
+    G = np.asarray(G, float)
+    if G.ndim != 2 or G.shape[0] != n:
+        raise ValueError(f"G must be {n} x p, got {G.shape}")
+    if not np.all(np.isfinite(G)):
+        raise ValueError("There are non-finite values in the genotypes.")
+    p = G.shape[1]
+    maf = np.asarray(np.atleast_1d(MAF), float).ravel()
+    if maf.shape != (p,):
+        raise ValueError(f"MAF must hold one value per variant ({p}), got {maf.shape[0]}")
+    ny = len(crms)
+    if pairs is None:
+        pairs = np.stack(np.meshgrid(np.arange(ny), np.arange(p), indexing="ij"), axis=-1).reshape(-1, 2)
+    pairs = np.asarray(pairs)
+    if pairs.size == 0:
+        pairs = pairs.reshape(0, 2)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or not np.issubdtype(pairs.dtype, np.integer):
+        raise ValueError("pairs must be a (P, 2) integer array of (phenotype, variant)")
+    if np.any(pairs[:, 0] < 0) or np.any(pairs[:, 0] >= ny) or np.any(pairs[:, 1] < 0) or np.any(pairs[:, 1] >= p):
+        raise ValueError(f"pairs index outside {ny} phenotypes x {p} variants")
+    npairs = pairs.shape[0]
+    W, E0 = first._W, first._E0
+    cW, k0 = W.shape[1], E0.shape[1]
+    if not np.all(np.isfinite(W)):
+        raise ValueError("There are non-finite values in the covariates matrix.")
+
+    normalization = 1 / np.sqrt(2 * maf * (1 - maf))
+    beta_g = np.empty(npairs)
+    beta_gxe = np.empty((n, npairs))
+    rho1, v0, v1, lml = (np.empty(npairs) for _ in range(4))
+    u = np.empty((npairs, k0))
+    route = np.full(npairs, "per_snp", dtype=object)
+
+    # routing (from the input alone): the packed-system width, n > k0 + columns of L, and M = [W, g, E0] of full rank
+    halves = _l_halves(first)
+    if halves is None:
+        l_cols = 0
+    elif isinstance(halves, HadamardHalves):
+        l_cols = halves.shape_us[1] * halves.hK.shape[1]
+    else:
+        l_cols = halves.shape[1]
+    cohort_ok = cW + 2 * k0 + 2 <= _EFFECTS_MAX_COLUMNS and n > k0 + l_cols
+    fast = np.zeros(npairs, bool)
+    if cohort_ok and npairs:
+        variants = np.unique(pairs[:, 1])
+        WE = np.concatenate((W, E0), axis=1)
+        base = WE.T @ WE
+        cross = G[:, variants].T @ WE
+        gg = np.einsum("ij,ij->j", G[:, variants], G[:, variants])
+        ok = np.zeros(p, bool)
+        for t, v in enumerate(variants):
+            gram = np.empty((cW + k0 + 1,) * 2)
+            gram[:cW + k0, :cW + k0] = base
+            gram[cW + k0, :cW + k0] = gram[:cW + k0, cW + k0] = cross[t]
+            gram[cW + k0, cW + k0] = gg[t]
+            ok[v] = _full_rank_gram(gram)
+        fast = ok[pairs[:, 1]]
+
+    if np.any(fast):
+        lib = _lib.load()
+        dev = first._device
+        bg = None
+        if halves is not None:
+            bg = _make_background(np.zeros((n, 1)), halves, [0.0], dev)
+        sel = np.flatnonzero(fast)
+        used_y = np.unique(pairs[sel, 0])
+        used_g = np.unique(pairs[sel, 1])
+        Y = _lib.f64(np.stack([crms[i]._y for i in used_y], axis=1))
+        Gs = _lib.f64(G[:, used_g])
+        sub = np.ascontiguousarray(np.stack([np.searchsorted(used_y, pairs[sel, 0]),
+                                             np.searchsorted(used_g, pairs[sel, 1])], axis=1), dtype=np.int32)
+        grid = _lib.f64(np.asarray(first._rho1, float))
+        fit = np.empty((sel.size, 6))
+        beta = np.empty((sel.size, cW + 1 + k0))
+        uu = np.empty((sel.size, k0))
+        Wc, Ec = _lib.f64(W), _lib.f64(E0)
+        _lib.check(lib.crm_effects_multi(_context(dev), None if bg is None else bg.handle, n, _lib.ptr(Wc), cW,
+                                         _lib.ptr(Ec), k0, _lib.ptr(Y), Y.shape[1], _lib.ptr(Gs), Gs.shape[1],
+                                         _lib.ptr(sub), sel.size, grid.shape[0], _lib.ptr(grid), _lib.ptr(fit),
+                                         _lib.ptr(beta), _lib.ptr(uu)))
+        if not np.all(np.isfinite(fit[:, 3])):
+            raise _lib.CrmError("effects: a model could not be fitted (non-finite log-likelihood)")
+        beta_g[sel] = beta[:, cW]
+        rho1[sel], v0[sel], v1[sel], lml[sel] = fit[:, 0], fit[:, 1], fit[:, 2], fit[:, 3]
+        u[sel] = uu
+        route[sel] = "woodbury"
+        for t, i in enumerate(sel):   # (one product per pair: a pair's result does not depend on its batch)
+            beta_gxe[:, i] = (E0 @ ((fit[t, 1] * fit[t, 0]) * uu[t])) * normalization[pairs[i, 1]]
+
+    for i in np.flatnonzero(~fast):   # today's per-SNP path, statement for statement predict_interaction
+        c = crms[pairs[i, 0]]
+        g = G[:, [pairs[i, 1]]]
+        M = np.concatenate((W, g, E0), axis=1)
+        gE = g * E0
+        bgs = c._snp_background(gE)
+        r1, a0, a1, beta, ri = c._lmm_fit(bgs, M)
+        yadj = (c._y - M @ beta).reshape(-1, 1)
+        vv = c._cov_solve(bgs, ri, a0, a1, yadj)
+        beta_g[i] = beta[W.shape[1]]
+        u[i] = (gE.T @ vv)[:, 0]
+        beta_gxe[:, i] = ((a0 * r1) * E0 @ (gE.T @ vv) * normalization[pairs[i, 1]])[:, 0]
+        rho1[i], v0[i], v1[i], lml[i] = r1, a0, a1, c._last_fit[3]
+    out = beta_g, beta_gxe[None, :, :]
+    if return_info:
+        return out + ({"rho1": rho1, "v0": v0, "v1": v1, "lml": lml, "u": u, "route": route},)
+    return out
+
+
+def estimate_betas_many(Y, W, E, G, maf=None, E1=None, E2=None, hK=None, *, pairs=None, device=0, return_info=False):
+    """``estimate_betas`` (same bindings and defaults) for the columns of ``Y`` (n x phenotypes) against the variants of
+    ``G``: ``pairs`` (P, 2) of (column of Y, column of G), ``None`` for all of them.  Returns ``(beta_g (P,), beta_gxe
+    (1, n, P))`` as ``predict_interaction_many``.  As in the reference, ``E1`` is accepted and not used."""
+    Y = np.asarray(Y, float)
+    if Y.ndim != 2:
+        raise ValueError("Y must be n x phenotypes")
+    E1 = E if E1 is None else E1
+    E2 = E if E2 is None else E2
+    Ls = None if hK is None else get_L_values(hK, E2)
+    crms = [CellRegMap(y=Y[:, i], E=E, W=W, E1=E1, Ls=Ls, device=device, background=_DEFERRED)
+            for i in range(Y.shape[1])]
+    if maf is None:
+        maf = compute_maf(G)
+    return predict_interaction_many(crms, G, maf, pairs=pairs, return_info=return_info)

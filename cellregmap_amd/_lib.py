@@ -69,6 +69,8 @@ SIGNATURES = {
                                                   vp]),
     "crm_lmm_fit": (ctypes.c_int, [vp, ctypes.c_int, vp, vp]),
     "crm_cov_solve": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp, ctypes.c_int, vp]),
+    "crm_effects_multi": (ctypes.c_int, [vp, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp,
+                                         ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]),
     "crm_set_block_variants": (ctypes.c_int, [vp, ctypes.c_int]),
     "crm_set_null_fit_polish": (ctypes.c_int, [vp, ctypes.c_int]),
     "crm_set_progress_callback": (ctypes.c_int, [vp, vp, vp]),

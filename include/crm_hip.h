@@ -290,6 +290,21 @@ int crm_lmm_fit(crm_gene* gene, int restricted, double* out_fit, double* out_bet
 int crm_cov_solve(crm_background* bg, int rho_index, double v0, double v1, const double* rhs, int m,
                   double* out);
 
+/* Batched effect sizes (predict_interaction, _cellregmap.py:137-205) for many (phenotype, variant) pairs through the rank-k0
+ * (Woodbury) form of Sigma_p(rho) = rho (g o E0)(g o E0)' + (1 - rho) L L' (DESIGN.md section 9).
+ *   bg      the decomposition of L L' alone: a background of [0 * E1, L] at the single grid point rho = 0, on `ctx`, with
+ *           n cells; NULL when there is no L (mode A)
+ *   W       n x cW, E0 n x k0, Y n x ny, G n x nv: row-major host arrays; M = [W, g, E0] is used as given (the caller
+ *           keeps it of full column rank)
+ *   pairs   np x 2 ints (phenotype column of Y, variant column of G), any order, repeats allowed
+ *   rho     the grid (nrho <= 16 values in [0, 1])
+ * Out, per pair in the order given: out_fit 6 doubles {rho, v0, v1, lml, delta, grid index}; out_beta cW + 1 + k0 doubles,
+ * the fixed effects as coefficients of [W, g, E0]; out_u k0 doubles, u = (g o E0)'K^-1 (y - M beta) at the kept fit.
+ * CRM_ERR_ARG on bad sizes or indices; CRM_ERR_UNSUPPORTED when cW + 2 k0 + 2 > 130 or n <= k0 + rank(L). */
+int crm_effects_multi(crm_ctx* ctx, crm_background* bg, long n, const double* W, int cW, const double* E0, int k0,
+                      const double* Y, int ny, const double* G, int nv, const int* pairs, int np, int nrho,
+                      const double* rho, double* out_fit, double* out_beta, double* out_u);
+
 /* Block size (variants per internal batch); 0 restores the default (automatic: up to 4096 variants of
  * the interaction scan while its largest work buffer stays within 16 GB; 1024 for the association scans). */
 int crm_set_block_variants(crm_ctx* ctx, int variants);

@@ -665,6 +665,15 @@ class _progress:
         return False
 
 
+def _exact_pvalues(pvalue):
+    """``pvalue=`` of the interaction scans: ``"reference"`` (Davies at the reference's absolute accuracy 1e-6, modified
+    Liu where it fails: the reference's numbers) or ``"exact"`` (the tail probability to ~1e-12 relative at every size,
+    DESIGN.md section 10).  Returns True for ``"exact"``."""
+    if isinstance(pvalue, str) and pvalue in ("reference", "exact"):
+        return pvalue == "exact"
+    raise ValueError(f"pvalue must be 'reference' or 'exact', got {pvalue!r}")
+
+
 def _permutation(idx, n):
     """Index argument of the permutation hooks (_cellregmap.py:398-413) as int32 row indices: a
     boolean mask selects rows like numpy's ``E0[idx, :]`` does, negative entries count from the
@@ -824,7 +833,7 @@ class CellRegMap:
 
     # -- interaction scan (_cellregmap.py:317-440) ----------------------------------------------
     def scan_interaction(self, G, idx_E: Optional[any] = None, idx_G: Optional[any] = None,
-                         return_stats: bool = False, progress=None, groups="auto"):
+                         return_stats: bool = False, progress=None, groups="auto", pvalue="reference"):
         """Per-variant GxC score test.  ``G`` is n x p (array-like) or a ``GenotypePanel``; an array goes to the device as
         ``GenotypePanel(G, groups=groups)`` would take it (``"auto"``: donor-constant genotypes are found and scanned on
         the donor-collapsed path; ``None``: kept dense), in column chunks beside the scan when it has many variants
@@ -835,7 +844,15 @@ class CellRegMap:
 
         Returns ``(pvalues, info)`` with ``info = {rho1, e2, g2, eps2}`` as the reference
         (:439-440); with ``return_stats=True`` additionally a dict holding Q, the eigenvalues
-        of F, F itself and the null-fit scalars (for parity tests)."""
+        of F, F itself and the null-fit scalars (for parity tests).
+
+        ``pvalue``: ``"reference"`` (default) reports the reference's p-values -- Davies' method at an absolute accuracy
+        of 1e-6 and the modified-Liu approximation where it fails, so that below about 1e-4 no digit is guaranteed.
+        ``"exact"`` reports P(Q > q) under the same mixture of chi-squares to ~1e-12 relative at every size (DESIGN.md
+        section 10) and adds ``info["log_pvalue"]`` (natural log, finite where p underflows) and
+        ``info["pvalue_status"]`` (0 converged; 1 saddle point not found, 2 non-finite, 3 no eigenvalue kept by the
+        filter: p and log p NaN).  Q, F and everything else are the same bit for bit."""
+        exact = _exact_pvalues(pvalue)
         lib = _lib.load()
         k0 = self._E0.shape[1]
         if not isinstance(G, GenotypePanel) and np.asarray(G).ndim == 2 and np.asarray(G).shape[1] == 0:
@@ -843,6 +860,8 @@ class CellRegMap:
             if np.asarray(G).shape[0] != self.n_samples:
                 raise ValueError(f"G must be {self.n_samples} x p, got {np.asarray(G).shape}")
             empty = {key: np.empty(0) for key in ("rho1", "e2", "g2", "eps2")}
+            if exact:
+                empty.update(log_pvalue=np.empty(0), pvalue_status=np.empty(0, np.int32))
             if return_stats:
                 return np.empty(0), empty, {"Q": np.empty(0), "lml": np.empty(0), "delta": np.empty(0),
                                             "scale": np.empty(0), "lambda": np.empty((0, k0)),
@@ -851,14 +870,14 @@ class CellRegMap:
         if not isinstance(G, GenotypePanel):
             G = np.asarray(G, float)
             if G.ndim == 2 and G.shape[0] == self.n_samples and G.shape[1] >= 2 * _stream_chunk() > 0:
-                return self._scan_streamed(lib, G, k0, idx_E, idx_G, return_stats, progress, groups)
+                return self._scan_streamed(lib, G, k0, idx_E, idx_G, return_stats, progress, groups, exact)
         panel = self._panel(G, groups)
         n, p = panel.shape
         gene = self._bind_gene()
 
         iE, iG = _permutation(idx_E, n), _permutation(idx_G, n)
         with _progress(self._device, progress, p):
-            return self._scan_interaction(lib, gene, panel, p, k0, iE, iG, return_stats)
+            return self._scan_interaction(lib, gene, panel, p, k0, iE, iG, return_stats, exact)
 
     def _streamed_panels(self, G, groups="auto"):
         """Generator over ``(first, last, panel)``: the column chunks of a host matrix, uploaded one after the other by a
@@ -923,7 +942,7 @@ class CellRegMap:
 
         return advance, bar
 
-    def _scan_streamed(self, lib, G, k0, idx_E, idx_G, return_stats, progress, groups="auto"):
+    def _scan_streamed(self, lib, G, k0, idx_E, idx_G, return_stats, progress, groups="auto", exact=False):
         """A host matrix of many variants goes to the device in column chunks from a second thread while this one scans
         the chunks that have arrived: PCIe beside the scan, and device memory for three chunks instead of the whole
         matrix.  Every chunk is scanned as a panel of its own: where the chunk bounds fall on the block bounds of the
@@ -939,7 +958,7 @@ class CellRegMap:
             gene = self._bind_gene()      # (beside the first chunk's upload)
             for j0, j1, panel in panels:
                 with _progress(self._device, progress, j1 - j0, offset=j0, grand_total=p):
-                    parts.append(self._scan_interaction(lib, gene, panel, j1 - j0, k0, iE, iG, return_stats))
+                    parts.append(self._scan_interaction(lib, gene, panel, j1 - j0, k0, iE, iG, return_stats, exact))
                 panel = None      # (released before the next chunk is taken from the queue)
         finally:
             panels.close()
@@ -951,24 +970,28 @@ class CellRegMap:
             return pv, info, {key: np.concatenate([part[2][key] for part in parts]) for key in parts[0][2]}
         return pv, info
 
-    def _scan_interaction(self, lib, gene, panel, p, k0, iE, iG, return_stats):
+    def _scan_interaction(self, lib, gene, panel, p, k0, iE, iG, return_stats, exact=False):
         out = {k: np.empty(p) for k in ("pv", "rho1", "e2", "g2", "eps2")}
         extra = {}
         if return_stats:
             extra = {"Q": np.empty(p), "lml": np.empty(p), "delta": np.empty(p), "scale": np.empty(p),
                      "lambda": np.empty((p, k0)), "F": np.empty((p, k0, k0))}
-        _lib.check(lib.crm_scan_interaction(
-            gene, panel.handle, 0, p, _lib.ptr(iE), _lib.ptr(iG),
-            _lib.ptr(out["pv"]), _lib.ptr(out["rho1"]), _lib.ptr(out["e2"]), _lib.ptr(out["g2"]),
-            _lib.ptr(out["eps2"]), _lib.ptr(extra.get("Q")), _lib.ptr(extra.get("lml")),
-            _lib.ptr(extra.get("delta")), _lib.ptr(extra.get("scale")), _lib.ptr(extra.get("lambda")),
-            _lib.ptr(extra.get("F"))))
-        info = {key: out[key] for key in ("rho1", "e2", "g2", "eps2")}
+        args = (gene, panel.handle, 0, p, _lib.ptr(iE), _lib.ptr(iG),
+                _lib.ptr(out["pv"]), _lib.ptr(out["rho1"]), _lib.ptr(out["e2"]), _lib.ptr(out["g2"]),
+                _lib.ptr(out["eps2"]), _lib.ptr(extra.get("Q")), _lib.ptr(extra.get("lml")),
+                _lib.ptr(extra.get("delta")), _lib.ptr(extra.get("scale")), _lib.ptr(extra.get("lambda")),
+                _lib.ptr(extra.get("F")))
+        if exact:
+            out["log_pvalue"], out["pvalue_status"] = np.empty(p), np.empty(p, np.int32)
+            _lib.check(lib.crm_scan_interaction_tail(*args, _lib.ptr(out["log_pvalue"]), _lib.ptr(out["pvalue_status"])))
+        else:
+            _lib.check(lib.crm_scan_interaction(*args))
+        info = {key: out[key] for key in ("rho1", "e2", "g2", "eps2", "log_pvalue", "pvalue_status") if key in out}
         if return_stats:
             return out["pv"], info, extra
         return out["pv"], info
 
-    def scan_interaction_permutations(self, G, idx_E_list=None, idx_G_list=None, return_Q=False):
+    def scan_interaction_permutations(self, G, idx_E_list=None, idx_G_list=None, return_Q=False, pvalue="reference"):
         """``scan_interaction(G, idx_E=perm)`` for a whole list of permutations in one call -- the loop of the reference's
         calibration test (cellregmap/test/test_struct_lmm2.py:208-209) and of any permutation driver around the hooks at
         cellregmap/_cellregmap.py:398-413.  The hooks enter only the test direction ``ddot(g[idx_G], E0[idx_E])``: the
@@ -978,7 +1001,9 @@ class CellRegMap:
         ``idx_E_list`` / ``idx_G_list``: sequences of B index arrays (either may be ``None``: no permutation of that kind;
         an entry may be ``None`` too = the identity).  Returns ``(pvalues (B, p), info)`` with the reference's four ``info``
         arrays (they are the same for every permutation); row b of ``pvalues`` is bit for bit what
-        ``scan_interaction(G, idx_E_list[b], idx_G_list[b])`` returns.  ``return_Q``: also the score statistics (B, p)."""
+        ``scan_interaction(G, idx_E_list[b], idx_G_list[b])`` returns.  ``return_Q``: also the score statistics (B, p).
+        ``pvalue="exact"``: as in ``scan_interaction``; ``info`` then also holds ``log_pvalue`` and ``pvalue_status`` (B, p)."""
+        exact = _exact_pvalues(pvalue)
         lib = _lib.load()
         panel = self._panel(G)
         n, p = panel.shape
@@ -998,11 +1023,17 @@ class CellRegMap:
         pv = np.empty((nb, p))
         Q = np.empty((nb, p)) if return_Q else None
         info = {k: np.empty(p) for k in ("rho1", "e2", "g2", "eps2")}
+        if exact:
+            info.update(log_pvalue=np.empty((nb, p)), pvalue_status=np.empty((nb, p), np.int32))
         if p > 0:
+            args = (gene, panel.handle, 0, p, nb, _lib.ptr(iE), _lib.ptr(iG), _lib.ptr(pv), _lib.ptr(info["rho1"]),
+                    _lib.ptr(info["e2"]), _lib.ptr(info["g2"]), _lib.ptr(info["eps2"]), _lib.ptr(Q))
             with _progress(self._device, False, p):
-                _lib.check(lib.crm_scan_interaction_permuted(gene, panel.handle, 0, p, nb, _lib.ptr(iE), _lib.ptr(iG), _lib.ptr(pv),
-                                                             _lib.ptr(info["rho1"]), _lib.ptr(info["e2"]), _lib.ptr(info["g2"]),
-                                                             _lib.ptr(info["eps2"]), _lib.ptr(Q)))
+                if exact:
+                    _lib.check(lib.crm_scan_interaction_permuted_tail(*args, _lib.ptr(info["log_pvalue"]),
+                                                                      _lib.ptr(info["pvalue_status"])))
+                else:
+                    _lib.check(lib.crm_scan_interaction_permuted(*args))
         return (pv, info, Q) if return_Q else (pv, info)
 
     def scan_interaction_info(self, G, idx_E=None, idx_G=None):
@@ -1264,7 +1295,7 @@ def _cis_runs(cis_index, ngenes, p, dense_limit=1 << 26):
     return columns, runs
 
 
-def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progress=False):
+def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progress=False, pvalue="reference"):
     """Interaction scans of several phenotypes against one genotype panel in a single pass.
 
     ``crms``: ``CellRegMap`` objects that share the background, ``W`` and ``E`` (e.g. built with
@@ -1279,7 +1310,11 @@ def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progr
     results are then lists: entry i holds the arrays of ``crms[i].scan_interaction(G[:, cis_index[i]], ...)``.
 
     ``progress`` (default off -- this entry point has no counterpart in the reference): ``True`` for a tqdm bar, or a
-    callable ``(done, total)`` counted in variants of the panel that at least one phenotype tests."""
+    callable ``(done, total)`` counted in variants of the panel that at least one phenotype tests.
+
+    ``pvalue="exact"``: as in ``CellRegMap.scan_interaction``; ``info`` then also holds ``log_pvalue`` and
+    ``pvalue_status`` of the same shape (lists with ``cis_index``)."""
+    exact = _exact_pvalues(pvalue)
     lib = _lib.load()
     crms = list(crms)
     if not crms:
@@ -1305,7 +1340,12 @@ def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progr
     ng = len(genes)
 
     iE, iG = _permutation(idx_E, n), _permutation(idx_G, n)
-    keys = ("pv", "rho1", "e2", "g2", "eps2")
+    keys = ("pv", "rho1", "e2", "g2", "eps2") + (("log_pvalue", "pvalue_status") if exact else ())
+    dtypes = {"pvalue_status": np.int32}
+
+    def tail(out):   # the two extra outputs of the _tail entry points
+        return (_lib.ptr(out["log_pvalue"]), _lib.ptr(out["pvalue_status"])) if exact else ()
+
     if cis_index is not None:
         columns, runs = _cis_runs(cis_index, ng, p)
         # Donor-level panels (the collapsed path): what the phenotypes of a run share is small there, and a call per run of
@@ -1324,11 +1364,11 @@ def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progr
                 bar = tqdm(total=tested)
             seen = 0
             for i, cols in enumerate(columns):
-                out = {k: np.empty(cols.size) for k in keys}
+                out = {k: np.empty(cols.size, dtypes.get(k, float)) for k in keys}
                 if cols.size:
-                    _lib.check(lib.crm_scan_interaction(genes[i], panel.handle, int(cols[0]), int(cols.size), _lib.ptr(iE),
-                                                        _lib.ptr(iG), *[_lib.ptr(out[k]) for k in keys],
-                                                        None, None, None, None, None, None))
+                    scan = lib.crm_scan_interaction_tail if exact else lib.crm_scan_interaction
+                    _lib.check(scan(genes[i], panel.handle, int(cols[0]), int(cols.size), _lib.ptr(iE), _lib.ptr(iG),
+                                    *[_lib.ptr(out[k]) for k in keys[:5]], None, None, None, None, None, None, *tail(out)))
                 seen += cols.size
                 if bar is not None:
                     bar.update(cols.size)
@@ -1339,7 +1379,8 @@ def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progr
             if bar is not None:
                 bar.close()
             return res["pv"], {k: res[k] for k in keys[1:]}
-        full = {k: [np.full(p, np.nan) if columns[i].size else None for i in range(ng)] for k in keys}
+        full = {k: [np.full(p, -1 if k == "pvalue_status" else np.nan, dtypes.get(k, float)) if columns[i].size else None
+                    for i in range(ng)] for k in keys}
         tested = int(sum(count for _, count, _ in runs))
         bar = None
         if progress is True:   # one bar over all runs
@@ -1354,25 +1395,28 @@ def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progr
         seen = 0
         for a, count, active in runs:
             handles = (ctypes.c_void_p * len(active))(*[genes[i].value for i in active])
-            out = {k: np.empty((len(active), count)) for k in keys}
+            out = {k: np.empty((len(active), count), dtypes.get(k, float)) for k in keys}
+            scan = lib.crm_scan_interaction_multi_tail if exact else lib.crm_scan_interaction_multi
             with _progress(first._device, progress, count, offset=seen, grand_total=tested):
-                _lib.check(lib.crm_scan_interaction_multi(handles, len(active), panel.handle, a, count, _lib.ptr(iE),
-                                                          _lib.ptr(iG), *[_lib.ptr(out[k]) for k in keys], None))
+                _lib.check(scan(handles, len(active), panel.handle, a, count, _lib.ptr(iE), _lib.ptr(iG),
+                                *[_lib.ptr(out[k]) for k in keys[:5]], None, *tail(out)))
             seen += count
             for row, i in enumerate(active):
                 for k in keys:
                     full[k][i][a:a + count] = out[k][row]
         if bar is not None:
             bar.close()
-        res = {k: [full[k][i][columns[i]] if columns[i].size else np.empty(0) for i in range(ng)] for k in keys}
+        res = {k: [full[k][i][columns[i]] if columns[i].size else np.empty(0, dtypes.get(k, float)) for i in range(ng)]
+               for k in keys}
         return res["pv"], {k: res[k] for k in keys[1:]}
     handles = (ctypes.c_void_p * ng)(*[g.value for g in genes])
-    out = {k: np.empty((ng, p)) for k in keys}
+    out = {k: np.empty((ng, p), dtypes.get(k, float)) for k in keys}
+    scan = lib.crm_scan_interaction_multi_tail if exact else lib.crm_scan_interaction_multi
     with _progress(first._device, progress, p):
-        _lib.check(lib.crm_scan_interaction_multi(handles, ng, panel.handle, 0, p, _lib.ptr(iE), _lib.ptr(iG),
-                                                  _lib.ptr(out["pv"]), _lib.ptr(out["rho1"]), _lib.ptr(out["e2"]),
-                                                  _lib.ptr(out["g2"]), _lib.ptr(out["eps2"]), None))
-    return out["pv"], {k: out[k] for k in ("rho1", "e2", "g2", "eps2")}
+        _lib.check(scan(handles, ng, panel.handle, 0, p, _lib.ptr(iE), _lib.ptr(iG),
+                        _lib.ptr(out["pv"]), _lib.ptr(out["rho1"]), _lib.ptr(out["e2"]),
+                        _lib.ptr(out["g2"]), _lib.ptr(out["eps2"]), None, *tail(out)))
+    return out["pv"], {k: out[k] for k in keys[1:]}
 
 
 def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=False, progress=False):
@@ -1542,11 +1586,12 @@ def scan_interaction_resumable(crm, G, checkpoint, idx_E=None, idx_G=None, chunk
     return out["pv"], {k: out[k] for k in keys[1:]}
 
 
-def run_interaction_many(Y, E, G, W=None, E1=None, E2=None, hK=None, *, cis_index=None, device=0):
+def run_interaction_many(Y, E, G, W=None, E1=None, E2=None, hK=None, *, cis_index=None, device=0, pvalue="reference"):
     """``run_interaction`` for the columns of ``Y`` (n x genes) with one background decomposition,
     one genotype upload and shared per-variant work.  Returns arrays of shape (genes, p); with
     ``cis_index`` (see ``scan_interaction_many``) lists of per-phenotype arrays over each phenotype's own
-    variants."""
+    variants.  ``pvalue``: as in ``CellRegMap.scan_interaction``."""
+    _exact_pvalues(pvalue)
     Y = np.asarray(Y, float)
     if Y.ndim != 2:
         raise ValueError("Y must be n x genes")
@@ -1558,7 +1603,7 @@ def run_interaction_many(Y, E, G, W=None, E1=None, E2=None, hK=None, *, cis_inde
     first = CellRegMap(y=Y[:, 0], E=E, W=W, E1=E1, Ls=Ls, device=device)
     crms = [first] + [CellRegMap(y=Y[:, i], E=E, W=W, E1=E1, Ls=Ls, device=device, background=first._bg)
                       for i in range(1, Y.shape[1])]
-    return scan_interaction_many(crms, G, cis_index=cis_index)
+    return scan_interaction_many(crms, G, cis_index=cis_index, pvalue=pvalue)
 
 
 def lrt_pvalues(null_lml, alt_lmls, dof=1):
@@ -1572,8 +1617,8 @@ def lrt_pvalues(null_lml, alt_lmls, dof=1):
     return np.clip(pv, super_tiny, 1 - tiny)
 
 
-def run_interaction(y, E, G, W=None, E1=None, E2=None, hK=None, idx_G=None, *, device=0):
-    """Interaction test (_cellregmap.py:547-587).
+def run_interaction(y, E, G, W=None, E1=None, E2=None, hK=None, idx_G=None, *, device=0, pvalue="reference"):
+    """Interaction test (_cellregmap.py:547-587).  ``pvalue``: as in ``CellRegMap.scan_interaction``.
 
     As in the reference, ``idx_G`` is forwarded positionally and therefore lands in
     ``scan_interaction``'s ``idx_E`` slot (:586 vs :318): it permutes the rows of the
@@ -1586,8 +1631,9 @@ def run_interaction(y, E, G, W=None, E1=None, E2=None, hK=None, idx_G=None, *, d
         Ls = None
     else:
         Ls = get_L_values(hK, E2)
+    _exact_pvalues(pvalue)
     crm = CellRegMap(y=y, E=E, W=W, E1=E1, Ls=Ls, device=device)
-    pv = crm.scan_interaction(G, idx_G)
+    pv = crm.scan_interaction(G, idx_G, pvalue=pvalue)
     return pv
 
 

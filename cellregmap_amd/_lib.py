@@ -63,6 +63,9 @@ SIGNATURES = {
     "crm_scan_interaction_bounds": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long] + [vp] * 8),
     "crm_scan_interaction_permuted": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int] + [vp] * 8),
     "crm_scan_interaction_multi": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long] + [vp] * 8),
+    "crm_scan_interaction_tail": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long] + [vp] * 15),
+    "crm_scan_interaction_permuted_tail": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int] + [vp] * 10),
+    "crm_scan_interaction_multi_tail": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long] + [vp] * 10),
     "crm_scan_association": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, vp, vp, vp]),
     "crm_association_null_multi": (ctypes.c_int, [vp, ctypes.c_int, vp]),
     "crm_scan_association_multi": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, vp, vp,
@@ -108,6 +111,7 @@ SIGNATURES = {
                                         c_int_p, vp]),
     "crm_test_eigvalsh": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "crm_test_davies": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
+    "crm_test_tail_pvalue": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
 }
 
 _lib = None

@@ -587,4 +587,27 @@ int crm_test_davies(crm_ctx* c, int count, int k, const double* Q, const double*
     });
 }
 
+int crm_test_tail_pvalue(crm_ctx* c, int count, int k, const double* Q, const double* lambda, double* pvalue,
+                         double* logp, int* status) {
+    return crm::guarded_on("crm_test_tail_pvalue", c, [&]() -> int {
+    if (!c || count <= 0 || k <= 0 || !Q || !lambda || !pvalue || !logp || !status) return CRM_ERR_ARG;
+    CRM_HIP(hipSetDevice(c->device));
+    ScopedBuf bQ, bL, bP, bG, bS;
+    CRM_TRY(bQ.ensure(sizeof(double) * count));
+    CRM_TRY(bL.ensure(sizeof(double) * (size_t)count * k));
+    CRM_TRY(bP.ensure(sizeof(double) * count));
+    CRM_TRY(bG.ensure(sizeof(double) * count));
+    CRM_TRY(bS.ensure(sizeof(int) * count));
+    CRM_HIP(hipMemcpyAsync(bQ.ptr, Q, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    CRM_HIP(hipMemcpyAsync(bL.ptr, lambda, sizeof(double) * (size_t)count * k, hipMemcpyHostToDevice, c->stream));
+    CRM_TRY(launch_tail_pvalue(c->stream, bQ.as<double>(), bL.as<double>(), count, k, bP.as<double>(), bG.as<double>(),
+                               bS.as<int>()));
+    CRM_HIP(hipMemcpyAsync(pvalue, bP.ptr, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    CRM_HIP(hipMemcpyAsync(logp, bG.ptr, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    CRM_HIP(hipMemcpyAsync(status, bS.ptr, sizeof(int) * count, hipMemcpyDeviceToHost, c->stream));
+    CRM_HIP(hipStreamSynchronize(c->stream));
+    return CRM_OK;
+    });
+}
+
 }  // extern "C"

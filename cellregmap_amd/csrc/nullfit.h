@@ -216,4 +216,9 @@ int launch_eig_davies(hipStream_t st, const double* F, const double* Q, int coun
                       double* lambda, double* pvalue, int* ifault, double* liu, bool do_eig, double* scratch = nullptr);
 size_t eig_scratch_doubles(int count, int k);
 
+// ---- exact tail p-values (tail_pvalue.hip) ------------------------------------------------------
+// Q [count], lambda [count x k] (as launch_eig_davies writes them) -> pvalue, logp (natural log), status (CRM_TAIL_*).
+int launch_tail_pvalue(hipStream_t st, const double* Q, const double* lambda, int count, int k, double* pvalue,
+                       double* logp, int* status);
+
 }  // namespace crm

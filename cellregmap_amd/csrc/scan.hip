@@ -1343,6 +1343,9 @@ struct ScanOut {  // per-gene output bases (host), each `count` long (lambda: co
     int* flags = nullptr;    // CRM_MODEL_* bits per variant (include/crm_hip.h)
     double* bound_Q = nullptr;   // crm_scan_interaction_bounds: how far Q / p of two faithful runs may differ (relative)
     double* bound_p = nullptr;
+    bool exact = false;      // the p-value by the exact tail method (tail_pvalue.hip) instead of Davies / Liu
+    double* logp = nullptr;  // exact method: log p and CRM_TAIL_* status per variant
+    int* status = nullptr;
 };
 
 // Variants per block of a scan of `count` variants.  Automatic: as many as keep the A~ buffer (block x k0 x ldq doubles)
@@ -1564,7 +1567,8 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
                  o_part = carve(stats_ws), o_queue = carve(sizeof(unsigned) * CRM_MAX_RHO),
                  o_coef = carve(sizeof(double) * (size_t)c * ldb), o_thr = carve(sizeof(double) * BLK),
                  o_drop = carve(sizeof(int) * BLK), o_near = carve(sizeof(int) * BLK),
-                 o_posw = carve(sizeof(int) * BLK * ng);
+                 o_posw = carve(sizeof(int) * BLK * ng), o_tp = carve(sizeof(double) * BLK),
+                 o_tlp = carve(sizeof(double) * BLK), o_tst = carve(sizeof(int) * BLK);
     CRM_TRY(ctx->ws_small.ensure(off));
     char* sm = ctx->ws_small.as<char>();
     double* d_gg = (double*)(sm + o_gg);
@@ -1586,6 +1590,9 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
     int* d_drop = (int*)(sm + o_drop);               // 1: the variant's direction is dropped from [W, g]
     int* d_near = (int*)(sm + o_near);               // collapsed path: 1 = repeat this variant on the dense path
     int* d_posw = (int*)(sm + o_posw);               // unrelated-donor form, several phenotypes: block position or -1
+    double* d_tp = (double*)(sm + o_tp);             // exact tail method: p, log p, status
+    double* d_tlp = (double*)(sm + o_tlp);
+    int* d_tst = (int*)(sm + o_tst);
     const int kin_probs = bg->kin ? bg->kin_groups * (bg->kin_wb ? 2 : 1) + bg->kin_k2 + 16 : 0;
     CRM_TRY(ctx->ws_probs.ensure(sizeof(GemmProblem) * (2 * CRM_MAX_RHO + 4 + kin_probs + ng)));
     GemmProblem* d_probs = ctx->ws_probs.as<GemmProblem>();
@@ -2808,7 +2815,12 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             }
             CRM_TRY(launch_assemble(st, aa, nb, ctx->ws_Gext.as<double>(), slow_ws));
             CRM_TRY(launch_eig_davies(st, ctx->ws_F.as<double>(), d_Q, nb, k0, d_lam, d_pv, d_if, d_liu, true, slow_ws));
-            if (o.pv) CRM_HIP(hipMemcpyAsync(o.pv + done, d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+            if (o.exact) {
+                CRM_TRY(launch_tail_pvalue(st, d_Q, d_lam, nb, k0, d_tp, d_tlp, d_tst));
+                if (o.logp) CRM_HIP(hipMemcpyAsync(o.logp + done, d_tlp, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+                if (o.status) CRM_HIP(hipMemcpyAsync(o.status + done, d_tst, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+            }
+            if (o.pv) CRM_HIP(hipMemcpyAsync(o.pv + done, o.exact ? d_tp : d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
             if (o.Q) CRM_HIP(hipMemcpyAsync(o.Q + done, d_Q, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
             if (o.lambda) CRM_HIP(hipMemcpyAsync(o.lambda + done * k0, d_lam, sizeof(double) * nb * k0, hipMemcpyDeviceToHost, st));
             if (o.F) CRM_HIP(hipMemcpyAsync(o.F + done * k0 * k0, ctx->ws_F.ptr, sizeof(double) * nb * k0 * k0, hipMemcpyDeviceToHost, st));
@@ -2942,8 +2954,9 @@ static int scan_core(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             auto at = [&](double* p, long stride) { return p ? p + off * stride : nullptr; };
             o.pv = at(o.pv, 1); o.rho1 = at(o.rho1, 1); o.e2 = at(o.e2, 1); o.g2 = at(o.g2, 1); o.eps2 = at(o.eps2, 1);
             o.Q = at(o.Q, 1); o.lml = at(o.lml, 1); o.delta = at(o.delta, 1); o.scale = at(o.scale, 1);
-            o.lambda = at(o.lambda, k0); o.F = at(o.F, (long)k0 * k0); o.liu = at(o.liu, 1);
+            o.lambda = at(o.lambda, k0); o.F = at(o.F, (long)k0 * k0); o.liu = at(o.liu, 1); o.logp = at(o.logp, 1);
             if (o.ifault) o.ifault += off;
+            if (o.status) o.status += off;
             if (o.flags) o.flags += off;
         }
         CRM_TRY(scan_pass(genes, panel, first + off, len, idx_E, idx_G, shifted, false, nullptr));
@@ -2969,6 +2982,23 @@ int crm_scan_interaction(crm_gene* gene, crm_panel* panel, long first, long coun
     });
 }
 
+int crm_scan_interaction_tail(crm_gene* gene, crm_panel* panel, long first, long count, const int* idx_E,
+                              const int* idx_G, double* out_pvalue, double* out_rho1, double* out_e2,
+                              double* out_g2, double* out_eps2, double* out_Q, double* out_lml,
+                              double* out_delta, double* out_scale, double* out_lambda, double* out_F,
+                              double* out_logp, int* out_status) {
+    return crm::guarded_on("crm_scan_interaction_tail", gene ? gene->ctx : nullptr, [&]() -> int {
+    if (!gene || !panel) return CRM_ERR_ARG;
+    std::vector<crm_gene*> genes{gene};
+    ScanOut o{out_pvalue, out_rho1, out_e2, out_g2, out_eps2, out_Q, out_lml, out_delta, out_scale, out_lambda, out_F};
+    o.exact = true;
+    o.logp = out_logp;
+    o.status = out_status;
+    std::vector<ScanOut> outs{o};
+    return scan_core(genes, panel, first, count, idx_E, idx_G, outs);
+    });
+}
+
 int crm_scan_interaction_info(crm_gene* gene, crm_panel* panel, long first, long count, const int* idx_E,
                               const int* idx_G, double* out_pvalue, int* out_ifault, double* out_liu_pvalue,
                               int* out_model_flags) {
@@ -2986,10 +3016,9 @@ int crm_scan_interaction_info(crm_gene* gene, crm_panel* panel, long first, long
 
 // B permutations of one scan (include/crm_hip.h): the first permutation's pass records, per block, the fits and the rows
 // T(rho*); the others replay them.  The panel is walked in chunks that keep the record within REPLAY_CAP_BYTES.
-int crm_scan_interaction_permuted(crm_gene* gene, crm_panel* panel, long first, long count, int nperm, const int* idx_E,
-                                  const int* idx_G, double* out_pvalue, double* out_rho1, double* out_e2, double* out_g2,
-                                  double* out_eps2, double* out_Q) {
-    return crm::guarded_on("crm_scan_interaction_permuted", gene ? gene->ctx : nullptr, [&]() -> int {
+static int scan_permuted(crm_gene* gene, crm_panel* panel, long first, long count, int nperm, const int* idx_E,
+                         const int* idx_G, double* out_pvalue, double* out_rho1, double* out_e2, double* out_g2,
+                         double* out_eps2, double* out_Q, bool exact, double* out_logp, int* out_status) {
     if (!gene || !panel || nperm < 1 || !out_pvalue) return CRM_ERR_ARG;
     if (first < 0 || count < 0 || first + count > panel->p) {
         set_error("scan: variants [%ld, %ld) outside the panel (p = %ld)", first, first + count, panel->p);
@@ -3020,6 +3049,9 @@ int crm_scan_interaction_permuted(crm_gene* gene, crm_panel* panel, long first, 
                 o.rho1 = out_rho1 ? out_rho1 + at : nullptr; o.e2 = out_e2 ? out_e2 + at : nullptr;
                 o.g2 = out_g2 ? out_g2 + at : nullptr; o.eps2 = out_eps2 ? out_eps2 + at : nullptr;
             }
+            o.exact = exact;
+            o.logp = out_logp ? out_logp + (size_t)q * count + at : nullptr;
+            o.status = out_status ? out_status + (size_t)q * count + at : nullptr;
             std::vector<ScanOut> outs{o};
             const int rc = scan_core(genes, panel, first + at, len, idx_E ? idx_E + (size_t)q * n : nullptr,
                                      idx_G ? idx_G + (size_t)q * n : nullptr, outs);
@@ -3027,6 +3059,24 @@ int crm_scan_interaction_permuted(crm_gene* gene, crm_panel* panel, long first, 
         }
     }
     return CRM_OK;
+}
+
+int crm_scan_interaction_permuted(crm_gene* gene, crm_panel* panel, long first, long count, int nperm, const int* idx_E,
+                                  const int* idx_G, double* out_pvalue, double* out_rho1, double* out_e2, double* out_g2,
+                                  double* out_eps2, double* out_Q) {
+    return crm::guarded_on("crm_scan_interaction_permuted", gene ? gene->ctx : nullptr, [&]() -> int {
+    return scan_permuted(gene, panel, first, count, nperm, idx_E, idx_G, out_pvalue, out_rho1, out_e2, out_g2, out_eps2,
+                         out_Q, false, nullptr, nullptr);
+    });
+}
+
+int crm_scan_interaction_permuted_tail(crm_gene* gene, crm_panel* panel, long first, long count, int nperm,
+                                       const int* idx_E, const int* idx_G, double* out_pvalue, double* out_rho1,
+                                       double* out_e2, double* out_g2, double* out_eps2, double* out_Q,
+                                       double* out_logp, int* out_status) {
+    return crm::guarded_on("crm_scan_interaction_permuted_tail", gene ? gene->ctx : nullptr, [&]() -> int {
+    return scan_permuted(gene, panel, first, count, nperm, idx_E, idx_G, out_pvalue, out_rho1, out_e2, out_g2, out_eps2,
+                         out_Q, true, out_logp, out_status);
     });
 }
 
@@ -3073,10 +3123,9 @@ int crm_test_set_shared_h(crm_ctx* ctx, int mode) {
     });
 }
 
-int crm_scan_interaction_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
-                               const int* idx_E, const int* idx_G, double* out_pvalue, double* out_rho1,
-                               double* out_e2, double* out_g2, double* out_eps2, double* out_Q) {
-    return crm::guarded_on("crm_scan_interaction_multi", (genes && ngenes > 0 && genes[0]) ? genes[0]->ctx : nullptr, [&]() -> int {
+static int scan_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count, const int* idx_E,
+                      const int* idx_G, double* out_pvalue, double* out_rho1, double* out_e2, double* out_g2,
+                      double* out_eps2, double* out_Q, bool exact, double* out_logp, int* out_status) {
     if (!genes || ngenes < 1 || !panel) return CRM_ERR_ARG;
     std::vector<crm_gene*> gs(genes, genes + ngenes);
     for (crm_gene* g : gs)
@@ -3086,8 +3135,30 @@ int crm_scan_interaction_multi(crm_gene* const* genes, int ngenes, crm_panel* pa
         auto at = [&](double* base) { return base ? base + (size_t)i * count : nullptr; };
         outs[i] = ScanOut{at(out_pvalue), at(out_rho1), at(out_e2), at(out_g2), at(out_eps2), at(out_Q),
                           nullptr, nullptr, nullptr, nullptr, nullptr};
+        outs[i].exact = exact;
+        outs[i].logp = at(out_logp);
+        outs[i].status = out_status ? out_status + (size_t)i * count : nullptr;
     }
     return scan_core(gs, panel, first, count, idx_E, idx_G, outs);
+}
+
+int crm_scan_interaction_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
+                               const int* idx_E, const int* idx_G, double* out_pvalue, double* out_rho1,
+                               double* out_e2, double* out_g2, double* out_eps2, double* out_Q) {
+    return crm::guarded_on("crm_scan_interaction_multi", (genes && ngenes > 0 && genes[0]) ? genes[0]->ctx : nullptr, [&]() -> int {
+    return scan_multi(genes, ngenes, panel, first, count, idx_E, idx_G, out_pvalue, out_rho1, out_e2, out_g2, out_eps2, out_Q,
+                      false, nullptr, nullptr);
+    });
+}
+
+int crm_scan_interaction_multi_tail(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
+                                    const int* idx_E, const int* idx_G, double* out_pvalue, double* out_rho1,
+                                    double* out_e2, double* out_g2, double* out_eps2, double* out_Q, double* out_logp,
+                                    int* out_status) {
+    return crm::guarded_on("crm_scan_interaction_multi_tail", (genes && ngenes > 0 && genes[0]) ? genes[0]->ctx : nullptr,
+                           [&]() -> int {
+    return scan_multi(genes, ngenes, panel, first, count, idx_E, idx_G, out_pvalue, out_rho1, out_e2, out_g2, out_eps2, out_Q,
+                      true, out_logp, out_status);
     });
 }
 

@@ -246,6 +246,37 @@ int crm_scan_interaction_permuted(crm_gene* gene, crm_panel* panel, long first, 
                                   const int* idx_G, double* out_pvalue, double* out_rho1, double* out_e2, double* out_g2,
                                   double* out_eps2, double* out_Q);
 
+/* ---- exact tail p-values.  crm_scan_interaction's p-value is the reference's: 1 - qfc(Q; lambda) at Davies' ABSOLUTE
+ * accuracy 1e-6, replaced by the modified-Liu approximation where that difference rounds to <= 0 -- below about 1e-4
+ * it guarantees no correct digit.  The _tail forms of the three scans take the same arguments and return the same
+ * results except for the p-value, which is P(sum_j lambda_j chi2_1 > Q) over the eigenvalues SKAT's filter keeps, by a
+ * saddle-point contour integral accurate to ~1e-12 relative at every size, and two more outputs
+ * of the shape of out_pvalue (may be NULL):
+ *   out_logp    natural log of the p-value, finite where p underflows (p < 1e-308)
+ *   out_status  CRM_TAIL_CONVERGED, or why p and log p are NaN: NOT_BRACKETED (the saddle-point search failed),
+ *               NON_FINITE (Q, an eigenvalue or the integral not finite), NO_WEIGHTS (no eigenvalue above the filter's
+ *               threshold: the reference raises there)
+ * Q and the eigenvalues are those of the plain scan bit for bit. */
+#define CRM_TAIL_CONVERGED 0
+#define CRM_TAIL_NOT_BRACKETED 1
+#define CRM_TAIL_NON_FINITE 2
+#define CRM_TAIL_NO_WEIGHTS 3
+int crm_scan_interaction_tail(crm_gene* gene, crm_panel* panel, long first, long count, const int* idx_E,
+                              const int* idx_G, double* out_pvalue, double* out_rho1, double* out_e2,
+                              double* out_g2, double* out_eps2, double* out_Q, double* out_lml,
+                              double* out_delta, double* out_scale, double* out_lambda, double* out_F,
+                              double* out_logp, int* out_status);
+/* out_logp / out_status: nperm x count */
+int crm_scan_interaction_permuted_tail(crm_gene* gene, crm_panel* panel, long first, long count, int nperm,
+                                       const int* idx_E, const int* idx_G, double* out_pvalue, double* out_rho1,
+                                       double* out_e2, double* out_g2, double* out_eps2, double* out_Q,
+                                       double* out_logp, int* out_status);
+/* out_logp / out_status: ngenes x count */
+int crm_scan_interaction_multi_tail(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
+                                    const int* idx_E, const int* idx_G, double* out_pvalue, double* out_rho1,
+                                    double* out_e2, double* out_g2, double* out_eps2, double* out_Q, double* out_logp,
+                                    int* out_status);
+
 /* Several phenotypes against one panel in one pass ("genes" that share the background, W and E0):
  * everything that does not depend on y -- G'Q0(rho), the Khatri-Rao contraction per (variant, rho)
  * pair selected by at least one gene, the y-free side contractions -- is computed once per block.

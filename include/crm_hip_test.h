@@ -100,6 +100,10 @@ int crm_test_eigvalsh(crm_ctx* ctx, int count, int k, const double* F, double* l
 /* Davies/Liu p-values for `count` (Q, lambda[k]) pairs after the eigenvalue filter. */
 int crm_test_davies(crm_ctx* ctx, int count, int k, const double* Q, const double* lambda,
                     double* pvalue, int* ifault, double* liu);
+/* Exact tail p-values (crm_scan_interaction_tail's method) for `count` (Q, lambda[k]) pairs, lambda as the scan's
+ * eigenvalues (the filter is applied here): p, log p (natural) and CRM_TAIL_* status per pair. */
+int crm_test_tail_pvalue(crm_ctx* ctx, int count, int k, const double* Q, const double* lambda, double* pvalue,
+                         double* logp, int* status);
 
 /* The background constructor's symmetric eigen-solver on `batch` host matrices A (dim x dim each, row-major,
  * tight): lam (batch x dim, ascending), Z (batch x dim x dim, column j = eigenvector j; may be NULL).

@@ -630,6 +630,183 @@ int launch_donor_pairs_expand(hipStream_t st, const double* P, long p_slab, long
     return CRM_OK;
 }
 
+// ---- the unrelated-donor form's rotated S straight from the pair products (scan.hip, step 6) ----------------------------
+//     A[(b k0 + i), d k2 + j] = sum_k S_d[k, i] Psi_d[k, j],   S_d[k, i] = P[d][b][pair(min(k, i), max(k, i))]
+// with Psi_d = U_d Lambda_d^-1/2 (wb_U: k2pad x 128 per donor, zero beyond k2 rows and columns) and k2 = k0: the product of the
+// per-donor rotation launch without the rows of S in between.  Every output is accumulated as that launch does it: one
+// v_mfma_f64_16x16x4f64 accumulator, k ascending in groups of four from k = 0.  The groups wholly past k0 meet zero rows of
+// Psi_d and are left out (their products are zeros); in the last group the lanes k >= k0 read pair (0, 0) where the launch read
+// the next donor's rows -- finite times zero either way -- so A is the same bit for bit up to the sign of a zero.
+// A workgroup takes four variants and a range of donors and walks them in order, as donor_pairs_expand_kernel does (and forms
+// the same donor sums Psum, the E1 rows); wavefront w computes the rows i = 16 w .. 16 w + 15 of each variant, all columns j.
+constexpr int DR_LDU = 80;   // LDS row of Psi_d: 64 columns + 16, rows k and k + 1 on the two halves of the banks
+typedef double v4d __attribute__((ext_vector_type(4)));
+
+// a barrier that waits for this wavefront's LDS operations alone: __syncthreads() also drains every global store in flight,
+// and each donor's 80 KB of rotated S would then be waited for before the next donor's loads are issued
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+template <int DP_SLOTS>   // (a multiple of 8)
+__global__ __launch_bounds__(256, 2) void donor_pairs_rotate_kernel(const double* __restrict__ P, long p_slab, long ldp, int donors,
+                                                                     int variants, int k0, const double* __restrict__ U, long u_slab,
+                                                                     long ldu, double* __restrict__ A, long lda,
+                                                                     double* __restrict__ Psum, long psum_slab) {
+    extern __shared__ __align__(16) double smem[];
+    const int npair = k0 * (k0 + 1) / 2, total = DP_VARIANTS * npair;
+    const int KS = (k0 + 3) / 4, JT = (k0 + 15) / 16, urows = 4 * KS;
+    double* const tile = smem;                          // [DP_VARIANTS][npair]
+    double* const ut = smem + ((total + 1) & ~1);       // [4 KS][DR_LDU]
+    const int v0 = blockIdx.x * DP_VARIANTS, tid = threadIdx.x;
+    const int per = (donors + gridDim.y - 1) / gridDim.y;
+    const int d0 = blockIdx.y * per, d1 = min(donors, d0 + per);
+    if (d0 >= d1) return;
+    double acc[DP_SLOTS];
+#pragma unroll
+    for (int q = 0; q < DP_SLOTS; q++) acc[q] = 0.0;
+    // entry e = tid + 256 q of the four variants' pair rows: its offset from variant v0's row, -1 none (recomputed where it is
+    // used -- a float quotient and one correction, exact for e < 2^13 -- instead of a register per entry)
+    const float inv_npair = 1.0f / (float)npair;
+    const int vmax = min(DP_VARIANTS, variants - v0);
+    auto src_of = [&](int q) __attribute__((always_inline)) -> int {
+        int e = tid + 256 * q;
+        asm volatile("" : "+v"(e));   // (recomputed per donor, not hoisted out of the donor loop into registers)
+        int v = (int)((float)e * inv_npair);
+        v = v * npair > e ? v - 1 : ((v + 1) * npair <= e ? v + 1 : v);
+        return e < total && v < vmax ? v * (int)ldp + (e - v * npair) : -1;   // (< 2^31: 4 rows of at most 2 048)
+    };
+    // fragment addresses: lane (l15, lq) of k-step ks reads S_d[k = 4 ks + lq, i = 16 w + l15] (pair (0, 0) off the matrix)
+    const int lane = tid & 63, l15 = lane & 15, lq = lane >> 4;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int i = 16 * w + l15;
+    int pidx[16];
+#pragma unroll
+    for (int ks = 0; ks < 16; ks++) {
+        const int k = 4 * ks + lq, lo = k < i ? k : i, hi = k < i ? i : k;
+        pidx[ks] = k < k0 && i < k0 ? lo * k0 - lo * (lo - 1) / 2 + (hi - lo) : 0;
+    }
+    // (no prefetch into registers: they go to the products; two workgroups per CU overlap one's loads with the other's MFMAs)
+    for (int d = d0; d < d1; d++) {
+        // every load unconditional (entries off the tile re-read a valid one), so that they are all in flight at once
+        // (eight at a time: the registers of a whole donor's loads would push the sums out to scratch)
+        const double* __restrict__ Pd = P + (size_t)d * p_slab + (long)v0 * ldp;
+#pragma unroll
+        for (int q0 = 0; q0 < DP_SLOTS; q0 += 8) {
+            double x[8];
+            int sq[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++) sq[q] = src_of(q0 + q);
+#pragma unroll
+            for (int q = 0; q < 8; q++) x[q] = Pd[sq[q] >= 0 ? sq[q] : 0];
+#pragma unroll
+            for (int q = 0; q < 8; q++)
+                if (tid + 256 * (q0 + q) < total) {
+                    const double xv = sq[q] >= 0 ? x[q] : 0.0;
+                    acc[q0 + q] += xv;
+                    tile[tid + 256 * (q0 + q)] = xv;
+                }
+        }
+        // Psi_d: rows k < 4 KS, columns j < 64 -- 16 entries per thread at most (k0 <= 63)
+        const double* __restrict__ Ud = U + (size_t)d * u_slab + (tid & 63);
+        double* __restrict__ ud = ut + (tid >> 6) * DR_LDU + (tid & 63);
+#pragma unroll
+        for (int q0 = 0; q0 < 16; q0 += 8) {
+            double u[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                int r = min((tid >> 6) + 4 * (q0 + q), urows - 1);
+                asm volatile("" : "+v"(r));
+                u[q] = Ud[(long)r * ldu];
+            }
+#pragma unroll
+            for (int q = 0; q < 8; q++)
+                if ((tid >> 6) + 4 * (q0 + q) < urows) ud[4 * (q0 + q) * DR_LDU] = u[q];
+        }
+        lds_barrier();
+        if (w < JT) {
+            for (int b = 0; b < DP_VARIANTS && v0 + b < variants; b++) {
+                // (re-read per variant: hoisted out of this loop, the fragments of Psi_d would hold 128 registers)
+                unsigned uo = (unsigned)(lq * DR_LDU + l15);
+                asm volatile("" : "+v"(uo));
+                const double* __restrict__ ub = ut + uo;
+                const double* __restrict__ pb = tile + b * npair;
+                v4d c[4];
+#pragma unroll
+                for (int t = 0; t < 4; t++) c[t] = (v4d){0.0, 0.0, 0.0, 0.0};
+                // the fragments of k-step ks + 1 are read before the MFMAs of k-step ks are issued, and no further ahead (the
+                // scheduler would otherwise pull every read of the sixteen k-steps up front: 160 registers)
+                double a[2], bf[2][4];
+                auto frag = [&](int ks, int slot) __attribute__((always_inline)) {
+                    a[slot] = pb[pidx[ks]];
+#pragma unroll
+                    for (int t = 0; t < 4; t++)
+                        if (t < JT) bf[slot][t] = ub[4 * ks * DR_LDU + 16 * t];
+                };
+                frag(0, 0);
+#pragma unroll
+                for (int ks = 0; ks < 16; ks++) {
+                    if (ks < KS) {
+                        if (ks + 1 < KS) frag(ks + 1, (ks + 1) & 1);
+#pragma unroll
+                        for (int t = 0; t < 4; t++)
+                            if (t < JT) c[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[ks & 1], bf[ks & 1][t], c[t], 0, 0, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+                double* __restrict__ Ab = A + (size_t)((long)(v0 + b) * k0) * lda + (long)d * k0;
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    int r = 16 * w + lq + 4 * reg;
+                    asm volatile("" : "+v"(r));   // (row offsets recomputed here, not held across the loops)
+                    if (r < k0) {
+#pragma unroll
+                        for (int t = 0; t < 4; t++) {
+                            const int j = 16 * t + l15;
+                            if (t < JT && j < k0) Ab[(long)r * lda + j] = c[t][reg];
+                        }
+                    }
+                }
+            }
+        }
+        lds_barrier();
+    }
+    double* __restrict__ out = Psum + (size_t)blockIdx.y * psum_slab + (long)v0 * ldp;
+#pragma unroll
+    for (int q = 0; q < DP_SLOTS; q++) {
+        const int sq = src_of(q);
+        if (sq >= 0) out[sq] = acc[q];
+    }
+}
+
+// (24 entries per thread at most: 32 would not fit the registers of two workgroups per CU -- k0 <= 54)
+bool donor_pairs_rotate_serves(int k0) { return donor_pairs_serves(k0) && DP_VARIANTS * (k0 * (k0 + 1) / 2) <= 256 * 24; }
+
+int launch_donor_pairs_rotate(hipStream_t st, const double* P, long p_slab, long ldp, int donors, int variants, int k0,
+                              const double* U, long u_slab, long ldu, int k2pad, double* A, long lda, double* Psum, long psum_slab,
+                              int splits) {
+    if (variants <= 0 || donors <= 0) return CRM_OK;
+    if (!donor_pairs_rotate_serves(k0) || splits < 1 || k2pad < 4 * ((k0 + 3) / 4) || ldu < 64) {
+        set_error("donor pairs rotation: k0=%d / k2pad=%d outside the supported range", k0, k2pad);
+        return CRM_ERR_UNSUPPORTED;
+    }
+    const int total = DP_VARIANTS * (k0 * (k0 + 1) / 2);
+    const size_t lds_bytes = sizeof(double) * ((size_t)((total + 1) & ~1) + (size_t)4 * ((k0 + 3) / 4) * DR_LDU);
+    dim3 grid((unsigned)((variants + DP_VARIANTS - 1) / DP_VARIANTS), (unsigned)splits);
+    const int slots = (total + 255) / 256;
+#define CRM_DR_LAUNCH(SL)                                                                                                         \
+    do {                                                                                                                          \
+        CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&donor_pairs_rotate_kernel<SL>),                                \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));                                 \
+        hipLaunchKernelGGL(donor_pairs_rotate_kernel<SL>, grid, dim3(256), lds_bytes, st, P, p_slab, ldp, donors, variants, k0, \
+                           U, u_slab, ldu, A, lda, Psum, psum_slab);                                                              \
+    } while (0)
+    if (slots <= 8) CRM_DR_LAUNCH(8);   // (whole batches of eight loads)
+    else if (slots <= 16) CRM_DR_LAUNCH(16);
+    else CRM_DR_LAUNCH(24);
+#undef CRM_DR_LAUNCH
+    CRM_HIP(hipGetLastError());
+    return CRM_OK;
+}
+
 // dst[k, j] = src[k, j] * scale[k * ld_scale]  (j < cols): the contexts times the single column of us, donor order
 __global__ void scale_rows_kernel(const double* __restrict__ src, long ld_src, const double* __restrict__ scale, long ld_scale,
                                   int cols, double* __restrict__ dst, long ld_dst) {

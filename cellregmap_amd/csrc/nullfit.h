@@ -137,6 +137,12 @@ bool donor_pairs_serves(int k0);
 // (row_d, row_j: row of (donor d, context j) = k1 + d row_d + j row_j; default (k0, 1): the folded form's layout)
 int launch_donor_pairs_expand(hipStream_t st, const double* P, long p_slab, long ldp, int donors, int variants, int k0, int k1,
                               double* S, long lds, double* Psum, long psum_slab, int splits, long row_d = 0, long row_j = 0);
+bool donor_pairs_rotate_serves(int k0);
+// unrelated-donor form: A[(b k0 + i), d k0 + j] = sum_k S_d[k, i] U_d[k, j] with S_d expanded from the pair products, the
+// donor sums as launch_donor_pairs_expand forms them (k2 = k0; U: donors slabs of k2pad x ldu)
+int launch_donor_pairs_rotate(hipStream_t st, const double* P, long p_slab, long ldp, int donors, int variants, int k0,
+                              const double* U, long u_slab, long ldu, int k2pad, double* A, long lda, double* Psum, long psum_slab,
+                              int splits);
 // dst[k, :cols] = src[k, :cols] * scale[k * ld_scale]
 int launch_scale_rows(hipStream_t st, const double* src, long ld_src, const double* scale, long ld_scale, long rows, int cols,
                       double* dst, long ld_dst);

@@ -83,6 +83,7 @@ struct crm_background {
     crm::DevBuf wb_R;                           // [k1 x wb_ldp]: R[a, d k2 + j] = (Phi_d' E1_d)[j, a]
     crm::DevBuf wb_EE;                          // [k1 x k1]: E1'E1
     crm::DevBuf wb_S0[crm::CRM_MAX_RHO];        // [wb_ldp]: s_p(rho)
+    unsigned long wb_gen = 0;                   // process-unique stamp of the tables above (per-gene constants are keyed on it)
     // shared donor tables, most recently used first (at most DT_CACHE entries)
     static constexpr int DT_CACHE = 2;
     std::vector<crm_donor_tables*> dt_cache;
@@ -115,6 +116,10 @@ struct crm_gene {
     crm::DevBuf kinP;     // pair products E1_a o E0_i of the folded kinship-structure form (E1 rows of step 6)
     crm::DevBuf kinUE;    // us o E0 in donor order (folded form with a single column of us: mode B)
     crm::DevBuf kinEE;    // E (x) E (pairs j <= j') in donor order (folded form whose kinship contexts are the scan's own)
+    // unrelated-donor form (crm_background::kin_wb): Phi'[y, W] ((1 + c) rows of wb_ld over the positions) and then E1'[y, W]
+    // (k1 x 128) -- they depend on the gene and its background alone, so they are formed on the gene's first scan
+    crm::DevBuf wb_yW;
+    unsigned long wb_gen = 0;   // crm_background::wb_gen of the tables they were formed from (0: not formed)
     long ld_ep = 0, ld_ye = 0, ld_ee = 0;
     // donor tables of the collapsed path (valid for one grouped panel and the identity permutation)
     unsigned long e0_key = 0;    // content hash of E0 (key of the background's shared donor tables)

@@ -182,6 +182,8 @@ static int seal_unrelated_donors(crm_background* bg, const double* hKd, long m) 
     bg->wb_P = P;
     bg->wb_ldp = ldp;
     bg->wb_k2pad = k2pad;
+    static std::atomic<unsigned long> wb_tables_made{0};
+    bg->wb_gen = ++wb_tables_made;
     bg->kin_wb = true;
     return CRM_OK;
 }
@@ -860,7 +862,7 @@ void crm_gene_destroy(crm_gene* g) {
     (void)hipStreamSynchronize(g->ctx->stream);
     g->dt_own.release();
     for (auto* b : {&g->yW, &g->E0, &g->WW, &g->Wy, &g->Wproj, &g->rot, &g->Ep, &g->YE, &g->EE, &g->idx, &g->dt_Z1, &g->dt_sums,
-                    &g->dt_Zt, &g->kinEp, &g->kinP, &g->kinUE, &g->kinEE})
+                    &g->dt_Zt, &g->kinEp, &g->kinP, &g->kinUE, &g->kinEE, &g->wb_yW})
         b->release();
     delete g;
     } catch (...) {  // (nothing may unwind into the caller; a destroy has no status to return)
@@ -1822,6 +1824,10 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
                                       (size_t)std::max<long>(pd_slab, (std::max<long>(BLK, max_pairs) + 128) * ldP)));
         }
     }
+    // Unrelated-donor form with the pair products: the rotated S of every donor, (U_d Lambda_d^-1/2)' S_d, is formed from P_d
+    // in one pass (blockops.hip: donor_pairs_rotate_kernel) instead of the rows of S and a per-donor product over them --
+    // bit for bit the same ws_A; form("donor_pairs_rotate", 0) keeps the two launches
+    const bool wb_rotate = wb && donor_pairs && donor_pairs_rotate_serves(k0) && form("donor_pairs_rotate", 1) != 0;
     // The same idea on the UNFOLDED kinship-structure route (few contexts: BASELINE config 2's 20): with E1 = E2 = E the
     // per-donor blocks [us | E1]'(g o E0) are one symmetric matrix S_d = sum_c g_c e_c e_c' twice over -- one batched plain
     // product per donor against E (x) E in donor order (P_d), the contraction over the donors with the kinship factor ON THE
@@ -1892,11 +1898,12 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
         wb_Gw = wb_g + n_g;
         double* yWk = wb_Gw + n_Gw;            // [y, W] in donor order
         double* Bk = yWk + (size_t)bg->kin_rows * 128;   // us_d'[y, W]_d, rows d k2 + j
-        CRM_HIP(hipMemsetAsync(Bk, 0, sizeof(double) * (size_t)brows * 128, st));
         std::vector<GemmProblem> kp((size_t)2 * groups);
         GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
-        for (int gi = 0; gi < ng; gi++) {
-            crm_gene* g = genes[gi];
+        const size_t n_yW1 = (size_t)(1 + c) * ldwb, n_E11 = (size_t)wb_k1 * 128;
+        // Phi'[y, W] into Cphi (row length ldphi) and E1'[y, W] into Ce1 (k1 x 128) for gene g
+        auto wb_gene_constants = [&](crm_gene* g, double* Cphi, long ldphi, double* Ce1) -> int {
+            CRM_HIP(hipMemsetAsync(Bk, 0, sizeof(double) * (size_t)brows * 128, st));
             CRM_TRY(launch_gather_rows(st, g->yW.as<double>(), g->ld_yw, bg->kin_map.as<int>(), bg->kin_rows, 1 + c, yWk, 128));
             long maxlen = GEMM_BK;
             for (long d = 0; d < groups; d++) {
@@ -1910,7 +1917,7 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
                 GemmProblem q{};   // Phi_d'[y, W]_d, stored transposed: rows y, W_1 .. W_c over the positions
                 q.X = Bk + (size_t)d * k2 * 128; q.ldx = 128;
                 q.Y = bg->wb_U.as<double>() + (size_t)d * k2pad * 128; q.ldy = 128;
-                q.C = wb_yW + (size_t)gi * (1 + c) * ldwb + d * k2; q.ldc = ldwb;
+                q.C = Cphi + d * k2; q.ldc = ldphi;
                 q.M = 1 + c; q.N = k2; q.cells = k2pad;
                 kp[groups + d] = q;
             }
@@ -1919,10 +1926,24 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, (int)groups, 1 + c, k2, k2pad, false, 0, 1, 0));
             GemmProblem e{};   // E1'[y, W] over all cells
             e.X = bg->H.as<double>(); e.ldx = bg->ldh; e.Y = g->yW.as<double>(); e.ldy = g->ld_yw;
-            e.C = wb_E1yW + (size_t)gi * wb_k1 * 128; e.ldc = 128; e.M = wb_k1; e.N = 1 + c;
+            e.C = Ce1; e.ldc = 128; e.M = wb_k1; e.N = 1 + c;
             CRM_HIP(hipMemcpyAsync(d_probs, &e, sizeof e, hipMemcpyHostToDevice, st));
             CRM_TRY(launch_gemm_tn(ctx, d_probs, 1, wb_k1, 1 + c, np, false, 0, 1, 0));
-            CRM_HIP(hipStreamSynchronize(st));   // (kp, e live on this stack frame)
+            CRM_HIP(hipStreamSynchronize(st));   // (kp, e live on the host)
+            return CRM_OK;
+        };
+        for (int gi = 0; gi < ng; gi++) {
+            crm_gene* g = genes[gi];
+            // formed on the gene's first scan against these tables (crm_gene::wb_yW), copied into this scan's workspace after
+            if (g->wb_gen != bg->wb_gen) {
+                CRM_TRY(g->wb_yW.ensure(sizeof(double) * (n_yW1 + n_E11)));
+                CRM_HIP(hipMemsetAsync(g->wb_yW.ptr, 0, sizeof(double) * (n_yW1 + n_E11), st));
+                CRM_TRY(wb_gene_constants(g, g->wb_yW.as<double>(), ldwb, g->wb_yW.as<double>() + n_yW1));
+                g->wb_gen = bg->wb_gen;
+            }
+            CRM_HIP(hipMemcpyAsync(wb_yW + (size_t)gi * n_yW1, g->wb_yW.as<double>(), sizeof(double) * n_yW1, hipMemcpyDeviceToDevice, st));
+            CRM_HIP(hipMemcpyAsync(wb_E1yW + (size_t)gi * n_E11, g->wb_yW.as<double>() + n_yW1, sizeof(double) * n_E11,
+                                   hipMemcpyDeviceToDevice, st));
         }
     }
     std::vector<NullFitOut> h_fit((size_t)BLK * ng);
@@ -2533,8 +2554,14 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * (size_t)(groups + std::max(slices, 1)), hipMemcpyHostToDevice, st));
             if (donor_pairs) {
                 CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, npair, maxlen, false, 0, 1, 0));
-                CRM_TRY(launch_donor_pairs_expand(st, ctx->ws_Pd.as<double>(), pd_slab, ldPd, (int)groups, ncol, k0, k1, S, ld_ah,
-                                                  ctx->ws_AH.as<double>(), pd_slab, donor_pair_splits));
+                if (wb_rotate)   // (the rotated S straight from the pair products: the rows of S are not formed)
+                    CRM_TRY(launch_donor_pairs_rotate(st, ctx->ws_Pd.as<double>(), pd_slab, ldPd, (int)groups, ncol, k0,
+                                                      bg->wb_U.as<double>(), (long)bg->wb_k2pad * 128, 128, bg->wb_k2pad,
+                                                      ctx->ws_A.as<double>(), ldAw, ctx->ws_AH.as<double>(), pd_slab,
+                                                      donor_pair_splits));
+                else
+                    CRM_TRY(launch_donor_pairs_expand(st, ctx->ws_Pd.as<double>(), pd_slab, ldPd, (int)groups, ncol, k0, k1, S, ld_ah,
+                                                      ctx->ws_AH.as<double>(), pd_slab, donor_pair_splits));
                 CRM_TRY(launch_reduce_splits(st, ctx->ws_AH.as<double>(), (long)ncol * ldPd, donor_pair_splits, pd_slab));
                 CRM_TRY(launch_pair_rows_sym(st, ctx->ws_AH.as<double>(), ldPd, ncol, k0, S, ld_ah));
                 ctx->donor_pair_blocks++;
@@ -2663,7 +2690,9 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
         CRM_HIP(hipMemcpyAsync(d_probs, probs.data(), sizeof(GemmProblem) * nz, hipMemcpyHostToDevice, st));
         if (collapsed)
             CRM_TRY(launch_gemm_tn(ctx, d_probs, nz, max_m, (int)((long)k0 * ldq), mp, false, 0, 1, 0));
-        else if (via_H && kin_route && wb) {
+        else if (via_H && kin_route && wb && wb_rotate) {
+            // (the rotated S is in ws_A already: step 6, launch_donor_pairs_rotate)
+        } else if (via_H && kin_route && wb) {
             // Unrelated-donor form: the rotated S, rows (col k0 + i) over the donors k2 positions -- per donor
             // (U_d Lambda_d^-1/2)' S_d, stored transposed into ws_A; col = the pair (one phenotype) or the block position
             const int k1 = bg->kin_k1, k2 = bg->kin_k2, k2pad = bg->wb_k2pad;

@@ -133,9 +133,11 @@ struct crm_ctx {
     crm::DevBuf ws_T, ws_A, ws_Gb, ws_Gx, ws_Gs, ws_G2, ws_GG, ws_Gt, ws_Z, ws_small, ws_probs, ws_F, ws_Gext, ws_TH, ws_AH, ws_XG;
     crm::DevBuf ws_xwide;  // scratch of the 63..128-column null-fit kernel (nullfit_xwide.hip)
     crm::DevBuf ws_Tcut;   // rotations: the few small products taken out of the batched launch (cut along the contraction axis)
-    crm::DevBuf ws_Gk, ws_S, ws_S2;   // kinship-structure route: the block in donor order, the per-donor sums (step 6 / step 3)
+    crm::DevBuf ws_Gk, ws_S, ws_S2;   // kinship-structure route: the block in donor order, the per-donor sums (ScanPass::folded_S,
+                                      // unfolded_AH / fold_TH, unfolded_TH)
     crm::DevBuf ws_WB;                // unrelated-donor form: Phi'gx of the block, Phi'[y, W] and E1'[y, W] of the genes, scratch
-    crm::DevBuf ws_Pd;                // ... the per-donor products against the symmetric pair features (step 6, donor pairs)
+    crm::DevBuf ws_Pd;                // ... the per-donor products against the symmetric pair features (ScanPass::folded_S,
+                                      // unfolded_AH)
     crm::DevBuf ws_Anone;             // a row of zeros: A~ of the tests whose fit has no kinship term (AssembleArgs::A_none)
     std::vector<crm::DevBuf*> all_bufs() {
         return {&sync_counters, &ws_xwide, &ws_Tcut, &ws_S, &ws_S2, &ws_Gk, &ws_Pd, &ws_WB, &ws_Anone, &ws_AH, &ws_XG, &ws_TH, &ws_T, &ws_A, &ws_Gb, &ws_Gx, &ws_Gs, &ws_G2, &ws_GG, &ws_Gt, &ws_Z, &ws_small, &ws_probs, &ws_F, &ws_Gext};

@@ -60,7 +60,7 @@ struct crm_background {
     crm::DevBuf kin_map;                        // int[kin_rows]: cell of a sorted row, -1 for padding
     crm::DevBuf kin_Y;                          // [kin_rows x kin_ldy]: columns 0..k2-1 us, k2..k2+k1-1 E1, donor order
     long kin_ldy = 128;
-    crm::DevBuf kin_hKd;                        // [kin_groups_pad x kin_ldh]
+    crm::DevBuf kin_hKd;                        // [kin_groups_pad x kin_ldh]: hKd, column m ones (when m < kin_ldh), else 0
     long kin_ldh = 0;
     // The donor-level factor folded into the mixing matrices: with rows ordered [E1_a ; (d', us_j)],
     //   Q0(rho)'(g o E0) = MixK(rho)' [sum over all cells for E1_a ; S[d', us_j, .]],
@@ -113,7 +113,7 @@ struct crm_gene {
     // features of the (possibly row-permuted) contexts, rebuilt per scan call
     crm::DevBuf Ep, YE, EE, idx;
     crm::DevBuf kinEp;    // the (permuted) contexts in the donor order of the background's kinship structure
-    crm::DevBuf kinP;     // pair products E1_a o E0_i of the folded kinship-structure form (E1 rows of step 6)
+    crm::DevBuf kinP;     // pair products E1_a o E0_i of the folded kinship-structure form (E1 rows of ScanPass::folded_S)
     crm::DevBuf kinUE;    // us o E0 in donor order (folded form with a single column of us: mode B)
     crm::DevBuf kinEE;    // E (x) E (pairs j <= j') in donor order (folded form whose kinship contexts are the scan's own)
     // unrelated-donor form (crm_background::kin_wb): Phi'[y, W] ((1 + c) rows of wb_ld over the positions) and then E1'[y, W]

@@ -357,6 +357,15 @@ int crm_background_set_kinship_groups(crm_background* bg, const int* group, long
                   "%.3g against entries up to %.3g)", dmax, hmax);
         return CRM_ERR_ARG;
     }
+    // the column of ones behind hKd's m columns (objects.h: kin_hKd): the contraction over the donors on the pair products
+    // then also gives their sum over the donors (scan_pass: ScanPass::unfolded_AH).  Written after the check, which reads
+    // the m columns alone.
+    if (m + 1 <= bg->kin_ldh) {
+        std::vector<double> ones((size_t)groups, 1.0);
+        CRM_HIP(hipMemcpy2DAsync(bg->kin_hKd.as<double>() + m, sizeof(double) * bg->kin_ldh, ones.data(), sizeof(double),
+                                 sizeof(double), groups, hipMemcpyHostToDevice, st));
+        CRM_HIP(hipStreamSynchronize(st));   // (ones lives on this stack frame)
+    }
     // Fold the donor-level factor into the mixing matrices (objects.h: kin_fold) -- one small product per (grid point, j):
     // MixK[k1 + d' k2 + j, :] = sum_d hKd[d', d] Mix[k1 + j m + d, :], the contraction over d in stages of 16 rows (the
     // rows of hKd' beyond m are zero; the rows of Mix they meet belong to the next j or to Mix's own zero padding, which
@@ -367,7 +376,7 @@ int crm_background_set_kinship_groups(crm_background* bg, const int* group, long
     // (k2 >= 32: the folded form launches the per-donor sums for the us columns alone, 64 columns wide -- with few of them,
     // config 2's 20, one launch over [us | E1] together and the small contraction over the donors per block is the better
     // form: config 2 463 000 against 451 000 variant-tests/s.  k2 == 1 -- mode B, us a single column -- folds too: its us rows
-    // are per-donor sums of the Khatri-Rao rows themselves, a plain batched product, see scan_pass step 6)
+    // are per-donor sums of the Khatri-Rao rows themselves, a plain batched product, see ScanPass::folded_S)
     if ((double)kfold <= 1.25 * (double)bg->cols && bg->cols + (m_pad - m) <= bg->ldh && (k2 >= 32 || k2 == 1 || fold_form > 1) && fold_form != 0) {
         const long kdim = round_up(kfold, GEMM_BK), ldq = bg->ldq, ld_t = round_up(groups, 128);
         ScopedBuf hKdT, probs_dev;
@@ -1366,123 +1375,477 @@ static int scan_block_variants(const crm_ctx* ctx, const crm_gene* g0, long coun
     return BLK;
 }
 
-// One pass over variants [first, first + count) for one or several genes that share the background,
-// the covariates W and the contexts E0 (several phenotypes against one panel).  What does not depend
-// on the phenotype is done once per block: the block copies, T(rho) = G'Q0(rho), the Khatri-Rao
-// contraction per (variant, rho) pair that at least one gene selected, and the y-free side
-// contractions.  Per gene: g'y, the null fits, E'(g o y), assembly, eigenvalues and Davies.
-//
-// allow_collapse = false keeps a grouped panel on the dense path; near_out (collapsed passes only) receives the positions
-// (relative to `first`) of the variants that are nearly collinear with the covariates -- scan_core repeats those on the
-// dense path, where the block is orthogonalised against W in the cell axis (blockops.hip: launch_ortho_block).
-static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long first, long count,
-                     const int* idx_E, const int* idx_G, const std::vector<ScanOut>& outs, bool allow_collapse,
-                     std::vector<long>* near_out) {
-    const int ng = (int)genes.size();
-    crm_gene* g0 = genes[0];
-    crm_background* bg = g0->bg;
-    crm_ctx* ctx = bg->ctx;
-    if (panel->ctx != ctx) {
-        set_error("scan: gene and panel live on different contexts");
-        return CRM_ERR_ARG;
-    }
-    if (panel->n != bg->n) {
-        set_error("scan: panel has %ld cells, background has %ld", panel->n, bg->n);
-        return CRM_ERR_ARG;
-    }
-    if (panel->grouped && panel->m + 1 > BLOCK_SLACK_MAX) {
-        set_error("scan: grouped panel with %ld groups (supported up to %d)", panel->m, BLOCK_SLACK_MAX - 1);
-        return CRM_ERR_UNSUPPORTED;
-    }
-    if (first < 0 || count < 0 || first + count > panel->p) {
-        set_error("scan: variants [%ld, %ld) outside the panel (p = %ld)", first, first + count, panel->p);
-        return CRM_ERR_ARG;
-    }
-    for (crm_gene* g : genes) {
-        // the shared pass computes g'W, the context features and the donor tables once, from the first
-        // gene's W and E0: the others must hold the same values, not just the same shapes
-        if (g->bg != bg || g->c != g0->c || g->k0 != g0->k0 || g->w_key != g0->w_key || g->e0_key != g0->e0_key) {
-            set_error("scan: genes of one call must share the background, W and E0 (contents, not only shapes)");
-            return CRM_ERR_ARG;
-        }
-    }
-    if (count == 0) return CRM_OK;
-    if (ctx->in_scan) {
-        set_error("scan: another scan is running on this context (started from a progress callback?); its work buffers are in use");
-        return CRM_ERR_UNSUPPORTED;
-    }
-    struct InScan { crm_ctx* c; explicit InScan(crm_ctx* c_) : c(c_) { c->in_scan = true; } ~InScan() { c->in_scan = false; } } in_scan(ctx);
-    {
-        // (the Gram kernel stages all k0 + c + 2 rows of a variant in LDS: refused here, before anything is launched, with
-        // the limit named; past 144 rows / 128 contexts the scan runs through the slower forms of its per-variant kernels)
-        if (g0->k0 + g0->c + 2 > CRM_MAX_GRAM_ROWS) {
-            set_error("interaction scan: %d contexts with %d covariate columns (supported: contexts + covariates + 2 <= %d; "
-                      "the association scans take up to %d covariate columns)", g0->k0, g0->c, CRM_MAX_GRAM_ROWS,
-                      CRM_MAX_COV_XWIDE);
-            return CRM_ERR_UNSUPPORTED;
-        }
-    }
-    if (ctx->polish && g0->c > CRM_MAX_COV) {
-        set_error("interaction scan: the null-fit polish is only built for up to %d covariate columns", CRM_MAX_COV);
-        return CRM_ERR_UNSUPPORTED;
-    }
-    CRM_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+// How the rotated test direction A~ = Q0(rho*)'(g o E0) of step 6 is formed -- and with it the rotations of step 3 and the
+// operands the pass prepares
+enum class Route {
+    collapsed,      // donor-level tables of a grouped panel (crm_donor_tables)
+    direct,         // Khatri-Rao contraction over all cells; several phenotypes decide per block whether to go through H
+    kin_unfolded,   // kinship structure (objects.h: crm_background::kin): per-donor sums, then the contraction over the donors
+    kin_folded,     // ... the donors folded into the mixing matrices (objects.h: kin_fold): the sums are the Mix operand
+    unrelated,      // ... unrelated donors (objects.h: kin_wb): Q and F through Woodbury, the rotated S instead of A~
+};
+
+// Slots of the pass's problem records (ctx->ws_probs): [0] a single product -- in step 6 the A~ groups, then their tails;
+// [1, 1 + nrho) the rotations of step 3 (the side contractions at 1 and 2); from 1 + nrho the rotations' cut problems; from
+// SLOT_KIN the records of the kinship-structure routes (ScanPlan::kin_probs); after those, the Z1 problems
+constexpr int SLOT_ONE = 0, SLOT_RHO = 1, SLOT_KIN = 2 * CRM_MAX_RHO + 4;
+
+// What a pass does: sizes, leading dimensions, splits and the route, fixed before anything is launched (plan_scan).
+// e1_sym, donor_pairs, pairs_unfolded and wb_rotate hold what the shapes allow until prepare_kinship has probed the data.
+// What depends on the rho* of a block (through H or not, the splits of the A~ launch, the cut problems) is decided per block.
+struct ScanPlan {
+    Route route = Route::direct;
+    // fastT: T(rho) through the half factor H (H'G, then small products with Mix(rho)); slow_forms: scan_slow_forms;
+    // skip_pairs: ScanPass::no_kinship_term; cross: the collapsed path under the genotype permutation hook
+    bool fastT = false, slow_forms = false, skip_pairs = true, cross = false;
+    bool e1_pairs = false, e1_sym = false, donor_pairs = false, wb_rotate = false, pairs_unfolded = false;
+    int ng = 1, BLK = 0, pair_cap = 0;
+    long ldb = 0, ldp = 0, ldA = 0, ldAw = 0, ldT = 0, ldZ1 = 0, ldZ2 = 0, ldZ3 = 0, ld_ah = 0, ld_xg = 0, ldP = 0, ldPd = 0,
+         pd_slab = 0, ldwb = 0, ld_gW = 0, th_slab = 0, s_rows = 0;
+    size_t s_bytes = 0;
+    int ks1 = 1, ks2 = 1, ks3 = 1, ks_h = 1, fold_split6 = 1, fold_split3 = 1, donor_pair_splits = 1;
+    int npair = 0, KT = 0, KK = 0, kin_probs = 0;
+    // kdim: contraction length of the products with the mixing matrices; mp: groups of a grouped panel, padded; xrows:
+    // contraction length of the block products -- cells, or on the collapsed path the groups
+    long kdim = 0, mp = 0, xrows = 0;
+    bool collapsed() const { return route == Route::collapsed; }
+    bool kin() const { return route == Route::kin_unfolded || route == Route::kin_folded || route == Route::unrelated; }
+    bool folded() const { return route == Route::kin_folded || route == Route::unrelated; }
+    bool wb() const { return route == Route::unrelated; }
+    bool through_H() const { return fastT && (ng > 1 || kin()); }   // (the operands of the routes through H exist)
+    int z1_slot() const { return SLOT_KIN + kin_probs; }
+};
+
+static double largest_rank(const crm_background* bg) {   // (at least 1)
+    double rbar = 1.0;
+    for (int i = 0; i < bg->nrho; i++) rbar = std::max(rbar, (double)bg->r[i]);
+    return rbar;
+}
+
+static ScanPlan plan_scan(const std::vector<crm_gene*>& genes, const crm_panel* panel, const int* idx_G, bool allow_collapse,
+                          long count) {
+    const crm_gene* g0 = genes[0];
+    const crm_background* bg = g0->bg;
+    const crm_ctx* ctx = bg->ctx;
+    const int ng = (int)genes.size(), nrho = bg->nrho, c = g0->c, k0 = g0->k0;
     const long n = bg->n, np = bg->n_pad, ldq = bg->ldq;
-    const int nrho = bg->nrho, c = g0->c, k0 = g0->k0;
-    for (long i = 0; i < n; i++) {
-        if ((idx_E && (idx_E[i] < 0 || idx_E[i] >= n)) || (idx_G && (idx_G[i] < 0 || idx_G[i] >= n))) {
-            set_error("scan: permutation index out of range at position %ld", i);
-            return CRM_ERR_ARG;
-        }
-    }
-    // several genes may ask for several rho* per variant: keep the (variant, rho) pair list bounded
-    const bool slow_forms = scan_slow_forms(g0);
-    int BLK = scan_block_variants(ctx, g0, count);
+    ScanPlan P;
+    P.ng = ng;
+    P.slow_forms = scan_slow_forms(g0);
+    const int BLK = P.BLK = scan_block_variants(ctx, g0, count);
     // Several phenotypes: the pair-ordered buffers (A~ and, on the routes through H, its gathered operand) grow with the
     // number of distinct (variant, rho*) pairs, up to min(nrho, ng) per variant.  They are kept within 128 GB (under half of the
     // device) by running the pair stage of a block -- steps 5 to 11 -- over sub-ranges of its variants, while the stages
     // before it (block copies, rotations and, above all, the per-phenotype null fits, which run twice as fast per variant in
     // launches of 4096 variants as in launches of 2048) keep the full block.
-    int pair_cap = BLK;
+    P.pair_cap = BLK;
     if (ng > 1) {
         const char* cap_env = getenv("CRM_PAIR_BUFFER_GB");
         const double cap_gb = cap_env && atof(cap_env) > 0 ? atof(cap_env) : 128.0;
-        const double per_pair = 2.0 * sizeof(double) * g0->k0 * (double)bg->ldq;
+        const double per_pair = 2.0 * sizeof(double) * k0 * (double)ldq;
         const long most = (long)std::min(nrho, ng) * BLK, least = (long)std::min(nrho, ng) * std::min(BLK, 128);
-        pair_cap = (int)std::max<long>(least, std::min<long>(most, (long)(cap_gb * (1ull << 30) / per_pair)));
+        P.pair_cap = (int)std::max<long>(least, std::min<long>(most, (long)(cap_gb * (1ull << 30) / per_pair)));
     }
-    const int max_pairs = pair_cap;
-    const long ldb = BLK + 128;              // slack columns for the Khatri-Rao tile over-read
-    const long ldp = max_pairs + 128;        // pair-ordered copy of the block
-    const long ldA = ldq, ldT = ldq;
-    const int npair = k0 * (k0 + 1) / 2;
-    const long ldZ1 = round_up((long)k0 * (1 + c), 128), ldZ2 = round_up(k0, 128), ldZ3 = round_up(npair, 128);
-    const int KT = k0 + c + 2;
-    const long ld_gW = round_up(std::max(c, CRM_MAX_COV), 8);
+    const int max_pairs = P.pair_cap;
+    P.ldb = BLK + 128;              // slack columns for the Khatri-Rao tile over-read
+    P.ldp = max_pairs + 128;        // pair-ordered copy of the block
+    P.ldA = P.ldT = ldq;
+    P.npair = k0 * (k0 + 1) / 2;
+    P.ldZ1 = round_up((long)k0 * (1 + c), 128), P.ldZ2 = round_up(k0, 128), P.ldZ3 = round_up(P.npair, 128);
+    P.KT = k0 + c + 2;
+    P.ld_gW = round_up(std::max(c, CRM_MAX_COV), 8);
+    const int mt_blk = (BLK + GEMM_BM - 1) / GEMM_BM;
+    // Z1 = Gt' [y o E, W o E] of all phenotypes in ONE batched launch per block (a problem per phenotype, each with its own
+    // output region) instead of a skinny launch + reduction per phenotype -- at config 4 those 64 pairs of launches were an
+    // eighth of the scan.  The slices along the cell axis shrink with the number of problems.
+    P.ks1 = pick_split(np, (long)mt_blk * (P.ldZ1 / GEMM_BN) * ng);
+    P.ks2 = pick_split(np, (long)mt_blk * (P.ldZ2 / GEMM_BN));
+    P.ks3 = pick_split(np, (long)mt_blk * (P.ldZ3 / GEMM_BN));
+    // H'G of step 3: few output tiles (cols x block) against a long contraction (cells) -- slices along the cell axis
+    // until the launch fills the chip twice with 128-wide tiles (mode B at config 3: 64 tiles, cfg3 mode C: 320)
+    // (rows of the operand of the rotations' Mix products: the half factor's columns, or -- folded kinship structure,
+    // objects.h: kin_fold -- k1 + donors k2)
+    // (unrelated-donor form: the per-donor rotations read up to a stage past the last donor's rows -- zeros)
+    P.th_slab = std::max<long>(bg->ldh, bg->kin && bg->kin_fold ? bg->kin_kdim + (bg->kin_wb ? GEMM_BK : 0) : 0) * P.ldb;
+    if (bg->fast_T) {
+        const long tiles_h = (long)((bg->cols + GEMM_BM - 1) / GEMM_BM) * ((BLK + 127) / 128);
+        while (tiles_h * P.ks_h < 1024 && P.ks_h < 16 && np / GEMM_BK / (P.ks_h + 1) >= 16) P.ks_h++;
+    }
+    // donor-collapsed mode: exact when every variant is constant within the panel's groups and the
+    // genotype permutation hook is not in use
+    const bool grouped = panel->grouped;
+    const size_t bd_bytes = grouped ? sizeof(double) * (size_t)nrho * panel->m_pad * k0 * ldq : 0;
+    // (with the genotype permutation hook the test direction is constant within the permuted groups;
+    // its mixed table needs the indicators as Khatri-Rao "contexts": m <= 128)
+    const bool collapsed = grouped && ctx->collapse && allow_collapse && bd_bytes <= ((size_t)48 << 30) &&
+                           (!idx_G || panel->m <= 128);
+    P.fastT = !collapsed && bg->fast_T && ctx->fast_T;
+    P.cross = collapsed && idx_G;
+    P.mp = grouped ? panel->m_pad : 0;
+    P.xrows = collapsed ? P.mp : np;
+    P.ld_ah = round_up((long)BLK * k0, 128) + 128, P.ld_xg = round_up((long)max_pairs * k0, 128) + 128;
+    // Kinship-structure route (objects.h, crm_background::kin): H'(g o E0) donor by donor, then Mix(rho*)' -- the dense
+    // scan's default whenever the background knows the donor structure of its kinship factor.  S: per-donor sums.
+    P.KK = bg->kin ? bg->kin_k1 + bg->kin_k2 : 0;   // rows of S per donor: [us | E1]
+    // folded form (objects.h: kin_fold): S holds [E1 rows ; (donor, us_j) rows] and is the operand of the Mix product itself
+    const bool fold = bg->kin && bg->kin_fold;
+    P.s_rows = fold ? bg->kin_kdim + (bg->kin_wb ? GEMM_BK : 0) : 0;
+    P.s_bytes = !bg->kin ? 0 : sizeof(double) * (fold ? (size_t)P.s_rows : (size_t)bg->kin_groups_pad * P.KK) * P.ld_ah;
+    // The route pays when its flops per variant -- per-donor sums over runs padded to whole 16-cell stages, the E1 rows /
+    // the contraction over the donors, and the product with the mixing matrix -- stay under the direct contraction's
+    // 2 n r k0 (thousands of tiny donors: every run is mostly padding); a multi-gene test that forces one of the other
+    // two routes (crm_test_set_shared_h 0 / 1) gets that route.
+    bool kin_pays = false;
+    if (bg->kin) {
+        const double rbar = largest_rank(bg);
+        const double kk = fold ? (double)bg->kin_kdim : (double)bg->ldh;
+        const double prep = fold ? 2.0 * bg->kin_rows * bg->kin_k2 + 2.0 * (double)np * bg->kin_k1
+                                 : 2.0 * bg->kin_rows * P.KK + 2.0 * (double)bg->kin_groups_pad * bg->kin_cols * bg->kin_k2;
+        kin_pays = prep + 2.0 * kk * rbar < 0.9 * 2.0 * (double)n * rbar || ctx->kin_route >= 2;
+    }
+    const bool kin_route = bg->kin && P.fastT && ctx->kin_route > 0 && kin_pays && !(ng > 1 && ctx->tune.shared_h >= 0) &&
+                           P.s_bytes <= ((size_t)48 << 30);
+    const bool kfold = kin_route && fold;
+    // Unrelated donors (objects.h: kin_wb): Q and F through the per-donor Woodbury inverse, no A~ = MixK(rho*)'S.  Decided
+    // by the background and the shapes alone, so that every entry point and every block computes a variant alike.  Taken
+    // where the Gram over the donors k2 positions with k1 more rows costs less than the MixK product it replaces.
+    const int wb_k1 = bg->kin ? bg->kin_k1 : 0;
+    bool wb = false;
+    // (k0 + c + 2 + k1 <= 144: the single-workgroup Gram forms; wider shapes keep the MixK route)
+    constexpr int WB_MAX_ROWS = 144;
+    if (kfold && bg->kin_wb && !P.slow_forms && c + 1 <= 128 && P.KT + wb_k1 <= WB_MAX_ROWS &&
+        woodbury_lds_bytes(P.KT, wb_k1) <= 150 * 1024) {
+        // (8x: the per-block rotations and the capacitance solves are fixed costs that small products do not repay --
+        // mode B at config 3, 150 x 150 spectra: 328 000 -> 222 000 variant-tests/s at 1x)
+        wb = (double)bg->kin_kdim * largest_rank(bg) * k0 > 8.0 * (P.KT + wb_k1) * (P.KT + wb_k1) * (double)bg->wb_P ||
+             form("kin_diag", 1) >= 2;
+    }
+    P.route = collapsed ? Route::collapsed : wb ? Route::unrelated : kfold ? Route::kin_folded
+            : kin_route ? Route::kin_unfolded : Route::direct;
+    P.ldAw = wb ? std::max<long>(P.ldA, bg->wb_ldp) : P.ldA;   // (rows of the rotated S: donors k2 positions)
+    P.ldwb = wb ? bg->wb_ldp : 0;
+    P.kdim = kfold ? bg->kin_kdim : bg->ldh;
+    // E1 rows of step 6: as a plain product G'P with the pair products P = E1_a o E0_i (n x k1 k0; the contraction kernel's
+    // best form) followed by a re-ordering of its rows, unless P would be large (> 8 GB): then as a Khatri-Rao contraction
+    // over all cells with the transposed store (64-wide tiles when k1 <= 64: 50 of 64 columns at config 3)
+    P.ldP = round_up((long)(bg->kin ? bg->kin_k1 : 0) * k0, 128);
+    P.e1_pairs = kfold && sizeof(double) * (double)np * (double)P.ldP <= 8.0 * (1ull << 30);
+    if (kfold) {   // cell-axis slices of the folded form's all-cells launches for the E1 rows (few output tiles, long contraction)
+        const long tiles6 = P.e1_pairs ? ((long)BLK + GEMM_BM - 1) / GEMM_BM * (P.ldP / 128) : ((long)BLK * k0 + GEMM_BM - 1) / GEMM_BM;
+        const long slots6 = P.e1_pairs || bg->kin_k1 > 64 ? 512 : 768;
+        double best = 0.0;
+        for (int sps = 1; sps <= 8 && np / GEMM_BK / sps >= 64; sps++) {
+            const double rounds = (double)(tiles6 * sps) / (double)slots6, eff = rounds / std::ceil(rounds);
+            if (eff > best + 0.02) { best = eff; P.fold_split6 = sps; }
+        }
+        const long tiles3 = (long)((bg->kin_k1 + GEMM_BM - 1) / GEMM_BM) * ((BLK + 127) / 128);
+        while (tiles3 * P.fold_split3 < 1024 && P.fold_split3 < 16 && np / GEMM_BK / (P.fold_split3 + 1) >= 16) P.fold_split3++;
+    }
+    // E1 = E, the reference's default (and no context permutation): the pair features E1_a o E0_i are the symmetric
+    // E_a E_i that the scan holds anyway for E0'diag(g^2)E0 (EE: k0 (k0 + 1) / 2 columns) -- half the product
+    P.e1_sym = P.e1_pairs && bg->kin_k1 == k0;
+    // The kinship term's contexts are E as well (the reference's default E2 = E): the per-donor sums S_d = sum_c g_c e_c e_c'
+    // are symmetric -- one batched product per donor against E (x) E in donor order, half the flops of the Khatri-Rao form and
+    // a plain product, then a pass that writes the rows of S (blockops.hip: donor_pairs_expand_kernel); the E1 rows are the
+    // sum of those products over the donors, so their product over all cells goes as well.  Taken where its time is the
+    // smaller one (many tiny donors: the pass over S costs more than the products save).
+    P.ldPd = round_up((long)P.npair, 128);
+    P.pd_slab = (std::max<long>(BLK, max_pairs) + 128) * P.ldPd;
+    if (P.e1_sym && bg->kin_k2 == k0 && donor_pairs_serves(k0) && form("donor_pairs", 1)) {
+        const double peak = 78.6e12, hbm = 4.0e12;
+        const double t_kr = 2.0 * bg->kin_rows * (double)k0 * k0 / (0.6 * peak) + 2.0 * (double)np * P.npair / (0.92 * peak);
+        const double t_pairs = 2.0 * bg->kin_rows * (double)P.npair / (0.8 * peak) +
+                               (double)bg->kin_groups * (2.0 * P.npair + (double)k0 * k0) * sizeof(double) / hbm;
+        const bool fits = sizeof(double) * (double)bg->kin_groups * (double)P.pd_slab <= 8.0 * (1ull << 30);
+        P.donor_pairs = fits && (t_pairs < t_kr || form("donor_pairs", 1) >= 2);
+        // the expansion pass: four variants per workgroup, three workgroups per CU -- donor ranges fill its rounds
+        const long wgs = (std::max<long>(BLK, 1) + 3) / 4;
+        while ((wgs * P.donor_pair_splits) % 768 != 0 && wgs * P.donor_pair_splits < 4 * 768 && P.donor_pair_splits < 8 &&
+               P.donor_pair_splits < bg->kin_groups)
+            P.donor_pair_splits++;
+    }
+    // Unrelated-donor form with the pair products: the rotated S of every donor, (U_d Lambda_d^-1/2)' S_d, is formed from P_d
+    // in one pass (blockops.hip: donor_pairs_rotate_kernel) instead of the rows of S and a per-donor product over them --
+    // bit for bit the same ws_A; form("donor_pairs_rotate", 0) keeps the two launches
+    P.wb_rotate = wb && P.donor_pairs && donor_pairs_rotate_serves(k0) && form("donor_pairs_rotate", 1) != 0;
+    // The same idea on the UNFOLDED kinship-structure route (few contexts: BASELINE config 2's 20): with E1 = E2 = E the
+    // per-donor blocks [us | E1]'(g o E0) are one symmetric matrix S_d = sum_c g_c e_c e_c' twice over -- one batched plain
+    // product per donor against E (x) E in donor order (P_d), the contraction over the donors with the kinship factor ON THE
+    // PAIR PRODUCTS (Z_c = sum_d hKd[d, c] P_d: 210 columns per variant instead of 400, and the column of ones behind hKd
+    // gives the sum over the donors that the E1 rows are), then the rows of AH = H'(g o E0) written from Z in one pass --
+    // instead of the Khatri-Rao launch per donor (64-wide tiles a third full), the contraction over the donors on k0 x k0
+    // blocks and the E1 sums.  Config 2: 1.7 -> 0.7 ms of a 8.6 ms step.
+    if (kin_route && !kfold && bg->kin_k1 == k0 && bg->kin_k2 == k0 && donor_pairs_serves(k0) && form("donor_pairs", 1) &&
+        bg->kin_cols + 1 <= bg->kin_ldh) {
+        const double cost_kr = 2.0 * bg->kin_rows * (double)P.KK * k0 + 2.0 * (double)bg->kin_groups_pad * bg->kin_cols * bg->kin_k2 * k0;
+        const double cost_pairs = 2.0 * bg->kin_rows * (double)P.npair + 2.0 * (double)(bg->kin_cols + 1) * bg->kin_groups_pad * (double)P.ldPd;
+        const bool fits = sizeof(double) * (double)bg->kin_groups_pad * (double)P.pd_slab <= 8.0 * (1ull << 30) &&
+                          sizeof(double) * (double)(bg->kin_cols + 1) * (double)P.pd_slab <= (double)P.s_bytes;
+        P.pairs_unfolded = fits && (cost_pairs < 0.8 * cost_kr || form("donor_pairs", 1) >= 2);
+    }
+    P.skip_pairs = form("pairs_without_kinship_term", 1) != 0;
+    P.kin_probs = bg->kin ? bg->kin_groups * (bg->kin_wb ? 2 : 1) + bg->kin_k2 + 16 : 0;
+    return P;
+}
 
-    // ---- context features for this permutation (E, E (x) E shared; y o E per gene) --------------
-    CRM_TRY(g0->idx.ensure(sizeof(int) * 2 * n));
-    int* d_idxE = nullptr;
-    int* d_idxG = nullptr;
-    if (idx_E) {
-        d_idxE = g0->idx.as<int>();
-        CRM_HIP(hipMemcpyAsync(d_idxE, idx_E, sizeof(int) * n, hipMemcpyHostToDevice, st));
+// Records of one product per donor over the donor's own run of cells (kin_row0 / kin_len): the operands X, E and Y of p
+// start at the run's first row, C at d c_step.  Returns the longest run (the launch's contraction length).
+static long donor_run_records(const crm_background* bg, const GemmProblem& p, long c_step, GemmProblem* out) {
+    long maxlen = GEMM_BK;
+    for (long d = 0; d < bg->kin_groups; d++) {
+        const long r0 = bg->kin_row0[d];
+        GemmProblem q = p;
+        q.X = p.X + r0 * p.ldx;
+        if (p.E) q.E = p.E + r0 * p.lde;
+        q.Y = p.Y + r0 * p.ldy; q.C = p.C + d * c_step; q.cells = bg->kin_len[d];
+        maxlen = std::max(maxlen, bg->kin_len[d]);
+        out[d] = q;
     }
-    if (idx_G) {
-        d_idxG = g0->idx.as<int>() + n;
-        CRM_HIP(hipMemcpyAsync(d_idxG, idx_G, sizeof(int) * n, hipMemcpyHostToDevice, st));
+    return maxlen;
+}
+
+// Records of the unrelated-donor form's per-donor rotation by U_d Lambda_d^-1/2 (wb_U) over the donor's k2pad rows: X of
+// donor d at p.X + d x_step, its k2 output columns at column d k2 of p.C
+static void woodbury_records(const crm_background* bg, const GemmProblem& p, long x_step, GemmProblem* out) {
+    for (long d = 0; d < bg->kin_groups; d++) {
+        GemmProblem q = p;
+        q.X = p.X + d * x_step; q.Y = bg->wb_U.as<double>() + (size_t)d * bg->wb_k2pad * 128; q.ldy = 128;
+        q.C = p.C + d * bg->kin_k2; q.N = bg->kin_k2; q.cells = bg->wb_k2pad;
+        out[d] = q;
     }
-    for (crm_gene* g : genes) {
-        g->ld_ep = round_up(k0, 128);
-        g->ld_ye = ldZ1;
-        g->ld_ee = ldZ3;
+}
+
+// Does every pair of operands hold the same first k columns?  (the probes of the pair-product forms; one flag for all)
+struct SameColumns { const double* A; long lda; const double* B; long ldb; long rows; };
+static int same_columns(hipStream_t st, int* d_flag, int k, std::initializer_list<SameColumns> pairs, bool& same) {
+    int h_flag = 0;
+    CRM_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
+    for (const SameColumns& q : pairs) CRM_TRY(launch_same_columns(st, q.A, q.lda, q.B, q.ldb, q.rows, k, d_flag));
+    CRM_HIP(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
+    CRM_HIP(hipStreamSynchronize(st));
+    same = h_flag == 0;
+    return CRM_OK;
+}
+
+struct Block {      // variants [col0, col0 + nb) of the panel, `done` into the call
+    long done = 0, col0 = 0;
+    int nb = 0;
+    double* Gb = nullptr;   // the aligned copy (collapsed path: the group dosage slab)
+    double* Gt = nullptr;   // the test direction's role (rows permuted under the genotype hook)
+    double* Gx = nullptr;   // the fixed effects' role (orthogonalised against W)
+    std::vector<double> flat_obj;   // (info calls) the selected fits' decision margins, [ng][BLK]
+};
+struct SubRange {   // the pair stage's part of a block: its positions [b0, b0 + nb), `done` into the call
+    int b0 = 0, nb = 0;
+    long done = 0;
+};
+struct Pairs {      // the sub-range's (variant, rho*) pairs in rho order: cnt[i] of them from start[i]
+    int cnt[CRM_MAX_RHO] = {0}, start[CRM_MAX_RHO + 1] = {0}, npairs = 0;
+};
+struct AGroups {    // step 6's problems: [0, nz) in probs, their tails, the splits along the cell axis
+    int nz = 0, max_m = 0, max_n = 1, kr_split = 1, tail_split = 1, tail_maxn = 0;
+    double kr_flops = 0.0;
+    size_t a_slab = 0;
+    std::vector<GemmProblem> tails, spectrum_tails;
+};
+
+// One pass: its inputs, plan, workspaces and host scratch, and a member function per stage
+struct ScanPass {
+    const std::vector<crm_gene*>& genes;
+    crm_panel* panel;
+    const long first, count;
+    const int *idx_E, *idx_G;
+    const std::vector<ScanOut>& outs;
+    std::vector<long>* near_out;
+    const int ng;
+    crm_gene* const g0;
+    crm_background* const bg;
+    crm_ctx* const ctx;
+    const hipStream_t st;
+    const long n, np, ldq, slab;
+    const int nrho, c, k0;
+    ScanPlan P;
+    int *d_idxE = nullptr, *d_idxG = nullptr;
+    const double *d_Ep = nullptr, *d_EE = nullptr;   // the permuted contexts and their pair products E (x) E, shared by the genes
+    crm_donor_tables* tab = nullptr;   // phenotype-free donor tables of this call (collapsed path)
+    // workspaces (workspaces())
+    GemmProblem* d_probs = nullptr;
+    double *dZ1 = nullptr, *dZ2 = nullptr, *dZ3 = nullptr;
+    long z1_sz = 0, z2_sz = 0, z3_sz = 0;
+    double *d_gg, *d_gy, *d_gW, *d_Q, *d_pv, *d_lam, *d_liu, *d_part, *d_coef, *d_thr, *d_tp, *d_tlp;   // (ws_small)
+    int *d_pos, *d_ord, *d_if, *d_drop, *d_near, *d_posw, *d_tst;
+    NullFitTrial* d_trial;
+    NullFitOut* d_fit;
+    unsigned* d_queue;
+    double *wb_yW = nullptr, *wb_E1yW = nullptr, *wb_g = nullptr, *wb_Gw = nullptr, *wb_tmp = nullptr;
+    // host scratch of the pass
+    std::vector<NullFitOut> h_fit = std::vector<NullFitOut>((size_t)P.BLK * ng);
+    std::vector<int> h_pos = std::vector<int>((size_t)P.BLK * ng), h_ord = std::vector<int>(P.pair_cap);
+    std::vector<GemmProblem> probs = std::vector<GemmProblem>(CRM_MAX_RHO + 4);
+    std::vector<int> pair_of = std::vector<int>((size_t)nrho * P.BLK), h_near = std::vector<int>(P.BLK);
+
+    ScanPass(const std::vector<crm_gene*>& genes_, crm_panel* panel_, long first_, long count_, const int* idx_E_,
+             const int* idx_G_, const std::vector<ScanOut>& outs_, bool allow_collapse, std::vector<long>* near_out_)
+        : genes(genes_), panel(panel_), first(first_), count(count_), idx_E(idx_E_), idx_G(idx_G_), outs(outs_),
+          near_out(near_out_), ng((int)genes_.size()), g0(genes_[0]), bg(g0->bg), ctx(bg->ctx), st(ctx->stream), n(bg->n),
+          np(bg->n_pad), ldq(bg->ldq), slab((long)(1 + g0->c) * bg->ldq), nrho(bg->nrho), c(g0->c), k0(g0->k0),
+          P(plan_scan(genes_, panel_, idx_G_, allow_collapse, count_)) {}
+
+    // ---- helpers --------------------------------------------------------------------------------------------------------
+    int upload(int slot, const GemmProblem* p, size_t k) {
+        CRM_HIP(hipMemcpyAsync(d_probs + slot, p, sizeof(GemmProblem) * k, hipMemcpyHostToDevice, st));
+        return CRM_OK;
     }
+    // records of this stack frame at a slot: `launches` reads them from d_probs + slot; the stream is synchronised after
+    // them, before the host copy goes away
+    template <class F>
+    int with_records(int slot, const std::vector<GemmProblem>& kp, F&& launches) {
+        CRM_TRY(upload(slot, kp.data(), kp.size()));
+        CRM_TRY(launches(d_probs + slot));
+        CRM_HIP(hipStreamSynchronize(st));
+        return CRM_OK;
+    }
+    // the kernel timer (crm_ctx::timed): the event pair of the next timed launch, its start recorded now or by the caller
+    int timer_open(bool record_start) {
+        if (ctx->timed_used == ctx->timed.size()) {
+            hipEvent_t a, b;
+            CRM_HIP(hipEventCreate(&a));
+            CRM_HIP(hipEventCreate(&b));
+            ctx->timed.emplace_back(a, b);
+        }
+        if (record_start) CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].first, st));
+        return CRM_OK;
+    }
+    int timer_close() {
+        CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].second, st));
+        ctx->timed_used++;
+        return CRM_OK;
+    }
+    // A fit that ends with (practically) no kinship term -- delta at the upper clamp, v0 = 2.2e-16 scale: a phenotype without
+    // a random effect, half of an eQTL run -- has K0 = v1 (I + (v0 / v1) Q0 S0 Q0'): where (v0 / v1) max S0 <= 1e-10 the
+    // rotated test direction A~ enters Q and F with weights d_j <= 1e-10, below the tolerance of the test by four orders of
+    // magnitude, while its product is most of a step.  Such tests get no (variant, rho*) pair: their Gram reads rows of zeros
+    // (AssembleArgs::A_none).  rho* of such a fit is decided by rounding (the likelihood is flat in rho), so over many
+    // phenotypes these are also the fits that would scatter a variant's pairs over the whole grid.
+    bool no_kinship_term(const NullFitOut& f) const {
+        return P.skip_pairs && f.v1 > 0.0 && f.v0 >= 0.0 && f.v0 * bg->s0_max[f.rho_index] <= 1e-10 * f.v1;
+    }
+
+    // ---- workspaces -----------------------------------------------------------------------------------------------------
+    int workspaces() {
+        const int BLK = P.BLK, max_pairs = P.pair_cap;
+        const long ldb = P.ldb;
+        CRM_TRY(ctx->ws_T.ensure(sizeof(double) * (size_t)nrho * BLK * P.ldT));
+        // (unrelated-donor form: the rotated S stays in block order for several phenotypes -- BLK of them at most)
+        CRM_TRY(ctx->ws_A.ensure(sizeof(double) * (size_t)(P.wb() ? std::max(max_pairs, BLK) : max_pairs) * k0 * P.ldAw));
+        CRM_TRY(ctx->ws_Anone.ensure(sizeof(double) * (size_t)P.ldAw));
+        CRM_HIP(hipMemsetAsync(ctx->ws_Anone.ptr, 0, sizeof(double) * (size_t)P.ldAw, st));
+        CRM_TRY(ctx->ws_Gb.ensure(sizeof(double) * (size_t)np * ldb));
+        CRM_TRY(ctx->ws_Gs.ensure(sizeof(double) * (size_t)np * P.ldp));
+        CRM_TRY(ctx->ws_G2.ensure(sizeof(double) * (size_t)np * ldb));
+        if (idx_G)   // (unused when the scan ends up on the collapsed path)
+            CRM_TRY(ctx->ws_Gt.ensure(sizeof(double) * (size_t)np * ldb));
+        z1_sz = (long)BLK * P.ldZ1, z2_sz = (long)BLK * P.ldZ2, z3_sz = (long)BLK * P.ldZ3;
+        const long z1_all = z1_sz * P.ks1 * ng;
+        CRM_TRY(ctx->ws_Z.ensure(sizeof(double) * (size_t)(z1_all + z2_sz * P.ks2 + z3_sz * P.ks3)));
+        dZ1 = ctx->ws_Z.as<double>();
+        dZ2 = dZ1 + z1_all;
+        dZ3 = dZ2 + z2_sz * P.ks2;
+        if (bg->fast_T) {
+            CRM_TRY(ctx->ws_TH.ensure(sizeof(double) * (size_t)P.th_slab * P.ks_h));
+            CRM_HIP(hipMemsetAsync(ctx->ws_TH.ptr, 0, sizeof(double) * (size_t)P.th_slab, st));
+        }
+        CRM_TRY(ctx->ws_F.ensure(sizeof(double) * (size_t)BLK * k0 * k0));
+        CRM_TRY(ctx->ws_Gext.ensure(sizeof(double) * (size_t)BLK * P.KT * P.KT));
+        // the null fits' scratch with more than CRM_MAX_COV_WIDE covariate columns; the slower per-variant kernels take it
+        // over once the null fits of a block are done
+        if (c > CRM_MAX_COV_WIDE || P.slow_forms) {
+            size_t xw = c > CRM_MAX_COV_WIDE ? nullfit_xwide_scratch_doubles(BLK, nrho, c) : 0;
+            if (P.slow_forms) xw = std::max(xw, std::max(assemble_rows_scratch_doubles(BLK, k0, c), eig_scratch_doubles(BLK, k0)));
+            CRM_TRY(ctx->ws_xwide.ensure(sizeof(double) * xw));
+        }
+        // ws_small: the block's vectors, each from a 256-byte boundary (a first pass over the list sizes it)
+        const size_t stats_ws = variant_stats_workspace(BLK, std::min(c, CRM_MAX_COV));
+        auto carve_small = [&](char* base) {
+            size_t off = 0;
+            auto carve = [&](auto*& ptr, size_t bytes) {
+                ptr = base ? reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(base + off) : nullptr;
+                off += (bytes + 255) / 256 * 256;
+            };
+            carve(d_gg, sizeof(double) * BLK), carve(d_gy, sizeof(double) * BLK * ng);   // (d_gy, d_fit, d_pos: [ng][BLK])
+            carve(d_gW, sizeof(double) * BLK * P.ld_gW), carve(d_trial, sizeof(NullFitTrial) * BLK * nrho);
+            carve(d_fit, sizeof(NullFitOut) * BLK * ng), carve(d_pos, sizeof(int) * BLK * ng), carve(d_ord, sizeof(int) * max_pairs);
+            carve(d_Q, sizeof(double) * BLK), carve(d_pv, sizeof(double) * BLK), carve(d_lam, sizeof(double) * BLK * k0);
+            carve(d_if, sizeof(int) * BLK), carve(d_liu, sizeof(double) * BLK), carve(d_part, stats_ws);
+            carve(d_queue, sizeof(unsigned) * CRM_MAX_RHO);    // work queue of the null fits (one counter per grid point)
+            carve(d_coef, sizeof(double) * (size_t)c * ldb);   // [c][ldb] projection coefficients of the block onto W
+            carve(d_thr, sizeof(double) * BLK);                // the reference's rank rule as a bound on |gx|^2
+            carve(d_drop, sizeof(int) * BLK);                  // 1: the variant's direction is dropped from [W, g]
+            carve(d_near, sizeof(int) * BLK);   // collapsed path: 1 = repeat this variant on the dense path (also the probes' flag)
+            carve(d_posw, sizeof(int) * BLK * ng);             // unrelated-donor form, several phenotypes: block position or -1
+            carve(d_tp, sizeof(double) * BLK), carve(d_tlp, sizeof(double) * BLK), carve(d_tst, sizeof(int) * BLK);   // exact tail method
+            return off;
+        };
+        CRM_TRY(ctx->ws_small.ensure(carve_small(nullptr)));
+        carve_small(ctx->ws_small.as<char>());
+        CRM_TRY(ctx->ws_probs.ensure(sizeof(GemmProblem) * (P.z1_slot() + ng)));
+        d_probs = ctx->ws_probs.as<GemmProblem>();
+        if (!P.collapsed()) {   // the block in the fixed effects' own basis, and its product with the test direction
+            CRM_TRY(ctx->ws_Gx.ensure(sizeof(double) * (size_t)np * ldb));
+            CRM_TRY(ctx->ws_GG.ensure(sizeof(double) * (size_t)np * ldb));
+        }
+        if (P.through_H()) {   // operands of the routes through H (step 6)
+            if (P.folded()) {
+                // (scratch of the sliced all-cells launch for the E1 rows)
+                CRM_TRY(ctx->ws_AH.ensure(sizeof(double) * (size_t)P.fold_split6 *
+                                          (P.e1_pairs ? (size_t)(std::max<long>(BLK, max_pairs) + 128) * P.ldP : (size_t)bg->kin_k1 * P.ld_ah)));
+            } else {
+                CRM_TRY(ctx->ws_AH.ensure(sizeof(double) * (size_t)bg->ldh * P.ld_ah));
+                // (zeroed by prepare_kinship, once the form of the per-donor sums is known: all of it, or its padding rows alone)
+            }
+            if (ng > 1) CRM_TRY(ctx->ws_XG.ensure(sizeof(double) * (size_t)P.kdim * P.ld_xg));
+        }
+        const long KK = P.KK;
+        if (P.folded()) {
+            CRM_TRY(ctx->ws_S.ensure(P.s_bytes));
+            CRM_TRY(ctx->ws_Gk.ensure(sizeof(double) * (size_t)bg->kin_rows * std::max(ldb, P.ldp)));
+            CRM_TRY(ctx->ws_S2.ensure(sizeof(double) * (size_t)P.fold_split3 * bg->kin_k1 * ldb));
+            // rows between k1 + donors k2 and the padded contraction length stay zero
+            const long used = bg->kin_k1 + bg->kin_groups * (long)bg->kin_k2;
+            if (P.s_rows > used)
+                CRM_HIP(hipMemsetAsync(ctx->ws_S.as<double>() + (size_t)used * P.ld_ah, 0, sizeof(double) * (size_t)(P.s_rows - used) * P.ld_ah, st));
+        } else if (P.kin()) {
+            CRM_TRY(ctx->ws_S.ensure(P.s_bytes));
+            CRM_TRY(ctx->ws_Gk.ensure(sizeof(double) * (size_t)bg->kin_rows * std::max(ldb, P.ldp)));
+            CRM_TRY(ctx->ws_S2.ensure(sizeof(double) * (size_t)bg->kin_groups_pad * KK * ldb));
+            if (bg->kin_groups_pad > bg->kin_groups)
+                CRM_HIP(hipMemsetAsync(ctx->ws_S2.as<double>() + (size_t)bg->kin_groups * KK * ldb, 0,
+                                       sizeof(double) * (size_t)(bg->kin_groups_pad - bg->kin_groups) * KK * ldb, st));
+            // rows of the padding donors (kin_groups .. kin_groups_pad) are operands of the contraction over the donors
+            if (bg->kin_groups_pad > bg->kin_groups)
+                CRM_HIP(hipMemsetAsync(ctx->ws_S.as<double>() + (size_t)bg->kin_groups * KK * P.ld_ah, 0,
+                                       sizeof(double) * (size_t)(bg->kin_groups_pad - bg->kin_groups) * KK * P.ld_ah, st));
+        }
+        if (P.wb()) {
+            // Unrelated-donor form: per gene Phi'[y, W] ((1 + c) rows over the positions) and E1'[y, W] (k1 x 128); per block
+            // Phi'gx; the Gram of the KT + k1 rows; scratch of the per-gene constants
+            const long brows = bg->kin_groups * bg->kin_k2 + GEMM_BK, kt = P.KT + bg->kin_k1;
+            const size_t n_yW = (size_t)ng * (1 + c) * P.ldwb, n_E1 = (size_t)ng * bg->kin_k1 * 128, n_g = (size_t)BLK * P.ldwb,
+                         n_Gw = (size_t)BLK * kt * kt, n_tmp = (size_t)(bg->kin_rows + brows) * 128;
+            CRM_TRY(ctx->ws_WB.ensure(sizeof(double) * (n_yW + n_E1 + n_g + n_Gw + n_tmp)));
+            wb_yW = ctx->ws_WB.as<double>();
+            wb_E1yW = wb_yW + n_yW;
+            wb_g = wb_E1yW + n_E1;
+            wb_Gw = wb_g + n_g;
+            wb_tmp = wb_Gw + n_Gw;
+        }
+        return CRM_OK;
+    }
+
+    // ---- per-pass preparation -------------------------------------------------------------------------------------------
     // y o E, W o E per gene; the permuted contexts and their pair products E (x) E once -- unless the
     // scan runs collapsed on donor tables the background already holds (then nothing reads them)
-    const double* d_Ep = nullptr;
-    const double* d_EE = nullptr;
-    auto context_features = [&](bool shared_too) -> int {
+    int context_features(bool shared_too) {
         for (int gi = 0; gi < ng; gi++) {
             crm_gene* g = genes[gi];
             const bool both = gi == 0 && shared_too;
@@ -1501,213 +1864,27 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             d_EE = g0->EE.as<double>();
         }
         return CRM_OK;
-    };
+    }
 
-    // ---- workspaces ----------------------------------------------------------------------------
-    CRM_TRY(ctx->ws_T.ensure(sizeof(double) * (size_t)nrho * BLK * ldT));
-    CRM_TRY(ctx->ws_A.ensure(sizeof(double) * (size_t)max_pairs * k0 * ldA));
-    CRM_TRY(ctx->ws_Anone.ensure(sizeof(double) * (size_t)ldA));
-    CRM_HIP(hipMemsetAsync(ctx->ws_Anone.ptr, 0, sizeof(double) * (size_t)ldA, st));
-    // A fit that ends with (practically) no kinship term -- delta at the upper clamp, v0 = 2.2e-16 scale: a phenotype without
-    // a random effect, half of an eQTL run -- has K0 = v1 (I + (v0 / v1) Q0 S0 Q0'): where (v0 / v1) max S0 <= 1e-10 the
-    // rotated test direction A~ enters Q and F with weights d_j <= 1e-10, below the tolerance of the test by four orders of
-    // magnitude, while its product is most of a step.  Such tests get no (variant, rho*) pair: their Gram reads rows of zeros
-    // (AssembleArgs::A_none).  rho* of such a fit is decided by rounding (the likelihood is flat in rho), so over many
-    // phenotypes these are also the fits that would scatter a variant's pairs over the whole grid.
-    if ((int)bg->s0_max.size() != nrho) {   // (filled when the background was sealed / created)
-        set_error("scan: the background was not sealed");
-        return CRM_ERR_INTERNAL;
-    }
-    const bool skip_pairs = form("pairs_without_kinship_term", 1) == 0 ? false : true;
-    auto no_kinship_term = [&](const NullFitOut& f) {
-        return skip_pairs && f.v1 > 0.0 && f.v0 >= 0.0 && f.v0 * bg->s0_max[f.rho_index] <= 1e-10 * f.v1;
-    };
-    CRM_TRY(ctx->ws_Gb.ensure(sizeof(double) * (size_t)np * ldb));
-    CRM_TRY(ctx->ws_Gs.ensure(sizeof(double) * (size_t)np * ldp));
-    CRM_TRY(ctx->ws_G2.ensure(sizeof(double) * (size_t)np * ldb));
-    if (idx_G)   // (unused when the scan ends up on the collapsed path)
-        CRM_TRY(ctx->ws_Gt.ensure(sizeof(double) * (size_t)np * ldb));
-    const int mt_blk = (BLK + GEMM_BM - 1) / GEMM_BM;
-    const int ks1 = pick_split(np, (long)mt_blk * (ldZ1 / GEMM_BN));
-    const int ks2 = pick_split(np, (long)mt_blk * (ldZ2 / GEMM_BN));
-    const int ks3 = pick_split(np, (long)mt_blk * (ldZ3 / GEMM_BN));
-    const long z1_sz = (long)BLK * ldZ1, z2_sz = (long)BLK * ldZ2, z3_sz = (long)BLK * ldZ3;
-    // several phenotypes: Z1 = Gt' [y o E, W o E] of all of them in ONE batched launch per block (a problem per phenotype,
-    // each with its own output region) instead of a skinny launch + reduction per phenotype -- at config 4 those 64 pairs of
-    // launches were an eighth of the scan.  The slices along the cell axis shrink with the number of problems.
-    const bool z1_batched = ng > 1;
-    const int ks1b = z1_batched ? pick_split(np, (long)mt_blk * (ldZ1 / GEMM_BN) * ng) : ks1;
-    const long z1_all = z1_batched ? z1_sz * ks1b * ng : z1_sz * ks1;
-    CRM_TRY(ctx->ws_Z.ensure(sizeof(double) * (size_t)(z1_all + z2_sz * ks2 + z3_sz * ks3)));
-    double* dZ1 = ctx->ws_Z.as<double>();
-    double* dZ2 = dZ1 + z1_all;
-    double* dZ3 = dZ2 + z2_sz * ks2;
-    // H'G of step 3: few output tiles (cols x block) against a long contraction (cells) -- slices along the cell axis
-    // until the launch fills the chip twice with 128-wide tiles (mode B at config 3: 64 tiles, cfg3 mode C: 320)
-    int ks_h = 1;
-    // (rows of the operand of the rotations' Mix products: the half factor's columns, or -- folded kinship structure,
-    // objects.h: kin_fold -- k1 + donors k2)
-    // (unrelated-donor form: the per-donor rotations read up to a stage past the last donor's rows -- zeros)
-    const long th_slab = std::max<long>(bg->ldh, bg->kin && bg->kin_fold ? bg->kin_kdim + (bg->kin_wb ? GEMM_BK : 0) : 0) * ldb;
-    if (bg->fast_T) {
-        const long tiles_h = (long)((bg->cols + GEMM_BM - 1) / GEMM_BM) * ((BLK + 127) / 128);
-        while (tiles_h * ks_h < 1024 && ks_h < 16 && np / GEMM_BK / (ks_h + 1) >= 16) ks_h++;
-        CRM_TRY(ctx->ws_TH.ensure(sizeof(double) * (size_t)th_slab * ks_h));
-        CRM_HIP(hipMemsetAsync(ctx->ws_TH.ptr, 0, sizeof(double) * (size_t)th_slab, st));
-    }
-    CRM_TRY(ctx->ws_F.ensure(sizeof(double) * (size_t)BLK * k0 * k0));
-    CRM_TRY(ctx->ws_Gext.ensure(sizeof(double) * (size_t)BLK * KT * KT));
-    const size_t stats_ws = variant_stats_workspace(BLK, std::min(c, CRM_MAX_COV));
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_gg = carve(sizeof(double) * BLK), o_gy = carve(sizeof(double) * BLK * ng),
-                 o_gW = carve(sizeof(double) * BLK * ld_gW), o_trial = carve(sizeof(NullFitTrial) * BLK * nrho),
-                 o_fit = carve(sizeof(NullFitOut) * BLK * ng), o_pos = carve(sizeof(int) * BLK * ng),
-                 o_ord = carve(sizeof(int) * max_pairs), o_Q = carve(sizeof(double) * BLK),
-                 o_pv = carve(sizeof(double) * BLK), o_lam = carve(sizeof(double) * BLK * k0),
-                 o_if = carve(sizeof(int) * BLK), o_liu = carve(sizeof(double) * BLK),
-                 o_part = carve(stats_ws), o_queue = carve(sizeof(unsigned) * CRM_MAX_RHO),
-                 o_coef = carve(sizeof(double) * (size_t)c * ldb), o_thr = carve(sizeof(double) * BLK),
-                 o_drop = carve(sizeof(int) * BLK), o_near = carve(sizeof(int) * BLK),
-                 o_posw = carve(sizeof(int) * BLK * ng), o_tp = carve(sizeof(double) * BLK),
-                 o_tlp = carve(sizeof(double) * BLK), o_tst = carve(sizeof(int) * BLK);
-    CRM_TRY(ctx->ws_small.ensure(off));
-    char* sm = ctx->ws_small.as<char>();
-    double* d_gg = (double*)(sm + o_gg);
-    double* d_gy = (double*)(sm + o_gy);          // [ng][BLK]
-    double* d_gW = (double*)(sm + o_gW);
-    NullFitTrial* d_trial = (NullFitTrial*)(sm + o_trial);
-    NullFitOut* d_fit = (NullFitOut*)(sm + o_fit);  // [ng][BLK]
-    int* d_pos = (int*)(sm + o_pos);               // [ng][BLK]
-    int* d_ord = (int*)(sm + o_ord);
-    double* d_Q = (double*)(sm + o_Q);
-    double* d_pv = (double*)(sm + o_pv);
-    double* d_lam = (double*)(sm + o_lam);
-    int* d_if = (int*)(sm + o_if);
-    double* d_liu = (double*)(sm + o_liu);
-    double* d_part = (double*)(sm + o_part);
-    unsigned* d_queue = (unsigned*)(sm + o_queue);   // work queue of the null fits (one counter per grid point)
-    double* d_coef = (double*)(sm + o_coef);         // [c][ldb] projection coefficients of the block onto W
-    double* d_thr = (double*)(sm + o_thr);           // the reference's rank rule as a bound on |gx|^2
-    int* d_drop = (int*)(sm + o_drop);               // 1: the variant's direction is dropped from [W, g]
-    int* d_near = (int*)(sm + o_near);               // collapsed path: 1 = repeat this variant on the dense path
-    int* d_posw = (int*)(sm + o_posw);               // unrelated-donor form, several phenotypes: block position or -1
-    double* d_tp = (double*)(sm + o_tp);             // exact tail method: p, log p, status
-    double* d_tlp = (double*)(sm + o_tlp);
-    int* d_tst = (int*)(sm + o_tst);
-    const int kin_probs = bg->kin ? bg->kin_groups * (bg->kin_wb ? 2 : 1) + bg->kin_k2 + 16 : 0;
-    CRM_TRY(ctx->ws_probs.ensure(sizeof(GemmProblem) * (2 * CRM_MAX_RHO + 4 + kin_probs + ng)));
-    GemmProblem* d_probs = ctx->ws_probs.as<GemmProblem>();
-
-    const long slab = (long)(1 + c) * ldq;  // rotations of [y, W] per grid point
-    // donor-collapsed mode: exact when every variant is constant within the panel's groups and the
-    // genotype permutation hook is not in use
-    const bool grouped = panel->grouped;
-    const size_t bd_bytes = grouped ? sizeof(double) * (size_t)nrho * panel->m_pad * k0 * ldq : 0;
-    // (with the genotype permutation hook the test direction is constant within the permuted groups;
-    // its mixed table needs the indicators as Khatri-Rao "contexts": m <= 128)
-    const bool collapsed = grouped && ctx->collapse && allow_collapse && bd_bytes <= ((size_t)48 << 30) &&
-                           (!idx_G || panel->m <= 128);
-    if (!collapsed) {   // the block in the fixed effects' own basis, and its product with the test direction
-        CRM_TRY(ctx->ws_Gx.ensure(sizeof(double) * (size_t)np * ldb));
-        CRM_TRY(ctx->ws_GG.ensure(sizeof(double) * (size_t)np * ldb));
-    }
-    const bool cross = collapsed && idx_G;
-    const long ld_ah = round_up((long)BLK * k0, 128) + 128, ld_xg = round_up((long)max_pairs * k0, 128) + 128;
-    // Kinship-structure route (objects.h, crm_background::kin): H'(g o E0) donor by donor, then Mix(rho*)' -- the dense
-    // scan's default whenever the background knows the donor structure of its kinship factor.  S: per-donor sums.
-    const int KK = bg->kin ? bg->kin_k1 + bg->kin_k2 : 0;   // rows of S per donor: [us | E1]
-    // folded form (objects.h: kin_fold): S holds [E1 rows ; (donor, us_j) rows] and is the operand of the Mix product itself
-    const bool fold = bg->kin && bg->kin_fold;
-    const long s_rows = fold ? bg->kin_kdim + (bg->kin_wb ? GEMM_BK : 0) : 0;
-    const size_t s_bytes = !bg->kin ? 0 : sizeof(double) * (fold ? (size_t)s_rows : (size_t)bg->kin_groups_pad * KK) * ld_ah;
-    // The route pays when its flops per variant -- per-donor sums over runs padded to whole 16-cell stages, the E1 rows /
-    // the contraction over the donors, and the product with the mixing matrix -- stay under the direct contraction's
-    // 2 n r k0 (thousands of tiny donors: every run is mostly padding); a multi-gene test that forces one of the other
-    // two routes (crm_test_set_shared_h 0 / 1) gets that route.
-    bool kin_pays = false;
-    if (bg->kin) {
-        double rbar = 1.0;
-        for (int i = 0; i < nrho; i++) rbar = std::max(rbar, (double)bg->r[i]);
-        const double kk = fold ? (double)bg->kin_kdim : (double)bg->ldh;
-        const double prep = fold ? 2.0 * bg->kin_rows * bg->kin_k2 + 2.0 * (double)np * bg->kin_k1
-                                 : 2.0 * bg->kin_rows * KK + 2.0 * (double)bg->kin_groups_pad * bg->kin_cols * bg->kin_k2;
-        kin_pays = prep + 2.0 * kk * rbar < 0.9 * 2.0 * (double)n * rbar || ctx->kin_route >= 2;
-    }
-    const bool kin_route = bg->kin && bg->fast_T && ctx->fast_T && !collapsed && ctx->kin_route > 0 && kin_pays &&
-                           !(ng > 1 && ctx->tune.shared_h >= 0) && s_bytes <= ((size_t)48 << 30);
-    const bool kfold = kin_route && fold;
-    // Unrelated donors (objects.h: kin_wb): Q and F through the per-donor Woodbury inverse, no A~ = MixK(rho*)'S.  Decided
-    // by the background and the shapes alone, so that every entry point and every block computes a variant alike.  Taken
-    // where the Gram over the donors k2 positions with k1 more rows costs less than the MixK product it replaces.
-    const int wb_k1 = bg->kin ? bg->kin_k1 : 0;
-    bool wb = false;
-    // (k0 + c + 2 + k1 <= 144: the single-workgroup Gram forms; wider shapes keep the MixK route)
-    constexpr int WB_MAX_ROWS = 144;
-    if (kfold && bg->kin_wb && !slow_forms && c + 1 <= 128 && KT + wb_k1 <= WB_MAX_ROWS && woodbury_lds_bytes(KT, wb_k1) <= 150 * 1024) {
-        double rbar = 1.0;
-        for (int i = 0; i < nrho; i++) rbar = std::max(rbar, (double)bg->r[i]);
-        // (8x: the per-block rotations and the capacitance solves are fixed costs that small products do not repay --
-        // mode B at config 3, 150 x 150 spectra: 328 000 -> 222 000 variant-tests/s at 1x)
-        wb = (double)bg->kin_kdim * rbar * k0 > 8.0 * (KT + wb_k1) * (KT + wb_k1) * (double)bg->wb_P || form("kin_diag", 1) >= 2;
-    }
-    const long ldAw = wb ? std::max<long>(ldA, bg->wb_ldp) : ldA;   // (rows of the rotated S: donors k2 positions)
-    const long ldwb = wb ? bg->wb_ldp : 0;
-    const long kdim = kfold ? bg->kin_kdim : bg->ldh;       // contraction length of the products with the mixing matrices
-    // cell-axis slices of the folded form's all-cells launches for the E1 rows (few output tiles, long contraction)
-    int fold_split6 = 1, fold_split3 = 1;
-    // E1 rows of step 6: as a plain product G'P with the pair products P = E1_a o E0_i (n x k1 k0; the contraction kernel's
-    // best form) followed by a re-ordering of its rows, unless P would be large (> 8 GB): then as a Khatri-Rao contraction
-    // over all cells with the transposed store (64-wide tiles when k1 <= 64: 50 of 64 columns at config 3)
-    const long ldP = round_up((long)(bg->kin ? bg->kin_k1 : 0) * k0, 128);
-    const bool e1_pairs = kfold && sizeof(double) * (double)np * (double)ldP <= 8.0 * (1ull << 30);
-    if (kfold) {
-        const long tiles6 = e1_pairs ? ((long)BLK + GEMM_BM - 1) / GEMM_BM * (ldP / 128) : ((long)BLK * k0 + GEMM_BM - 1) / GEMM_BM;
-        const long slots6 = e1_pairs || bg->kin_k1 > 64 ? 512 : 768;
-        double best = 0.0;
-        for (int sps = 1; sps <= 8 && np / GEMM_BK / sps >= 64; sps++) {
-            const double rounds = (double)(tiles6 * sps) / (double)slots6, eff = rounds / std::ceil(rounds);
-            if (eff > best + 0.02) { best = eff; fold_split6 = sps; }
+    // context features for this permutation (E, E (x) E shared; y o E per gene) and the collapsed path's donor tables
+    int prepare_contexts() {
+        CRM_TRY(g0->idx.ensure(sizeof(int) * 2 * n));
+        if (idx_E) {
+            d_idxE = g0->idx.as<int>();
+            CRM_HIP(hipMemcpyAsync(d_idxE, idx_E, sizeof(int) * n, hipMemcpyHostToDevice, st));
         }
-        const long tiles3 = (long)((bg->kin_k1 + GEMM_BM - 1) / GEMM_BM) * ((BLK + 127) / 128);
-        while (tiles3 * fold_split3 < 1024 && fold_split3 < 16 && np / GEMM_BK / (fold_split3 + 1) >= 16) fold_split3++;
-    }
-    if (bg->fast_T && ctx->fast_T && (ng > 1 || kin_route) && !collapsed) {  // operands of the routes through H (step 6)
-        if (kfold) {
-            // (scratch of the sliced all-cells launch for the E1 rows)
-            CRM_TRY(ctx->ws_AH.ensure(sizeof(double) * (size_t)fold_split6 *
-                                      (e1_pairs ? (size_t)(std::max<long>(BLK, max_pairs) + 128) * ldP : (size_t)bg->kin_k1 * ld_ah)));
-        } else {
-            CRM_TRY(ctx->ws_AH.ensure(sizeof(double) * (size_t)bg->ldh * ld_ah));
-            // (zeroed further down, once the form of the per-donor sums is known: all of it, or its padding rows alone)
+        if (idx_G) {
+            d_idxG = g0->idx.as<int>() + n;
+            CRM_HIP(hipMemcpyAsync(d_idxG, idx_G, sizeof(int) * n, hipMemcpyHostToDevice, st));
         }
-        if (ng > 1) CRM_TRY(ctx->ws_XG.ensure(sizeof(double) * (size_t)kdim * ld_xg));
-    }
-    if (kfold) {
-        CRM_TRY(ctx->ws_S.ensure(s_bytes));
-        CRM_TRY(ctx->ws_Gk.ensure(sizeof(double) * (size_t)bg->kin_rows * std::max(ldb, ldp)));
-        CRM_TRY(ctx->ws_S2.ensure(sizeof(double) * (size_t)fold_split3 * bg->kin_k1 * ldb));
-        // rows between k1 + donors k2 and the padded contraction length stay zero
-        const long used = bg->kin_k1 + bg->kin_groups * (long)bg->kin_k2;
-        if (s_rows > used)
-            CRM_HIP(hipMemsetAsync(ctx->ws_S.as<double>() + (size_t)used * ld_ah, 0, sizeof(double) * (size_t)(s_rows - used) * ld_ah, st));
-    } else if (kin_route) {
-        CRM_TRY(ctx->ws_S.ensure(s_bytes));
-        CRM_TRY(ctx->ws_Gk.ensure(sizeof(double) * (size_t)bg->kin_rows * std::max(ldb, ldp)));
-        CRM_TRY(ctx->ws_S2.ensure(sizeof(double) * (size_t)bg->kin_groups_pad * KK * ldb));
-        if (bg->kin_groups_pad > bg->kin_groups)
-            CRM_HIP(hipMemsetAsync(ctx->ws_S2.as<double>() + (size_t)bg->kin_groups * KK * ldb, 0,
-                                   sizeof(double) * (size_t)(bg->kin_groups_pad - bg->kin_groups) * KK * ldb, st));
-        // rows of the padding donors (kin_groups .. kin_groups_pad) are operands of the contraction over the donors
-        if (bg->kin_groups_pad > bg->kin_groups)
-            CRM_HIP(hipMemsetAsync(ctx->ws_S.as<double>() + (size_t)bg->kin_groups * KK * ld_ah, 0,
-                                   sizeof(double) * (size_t)(bg->kin_groups_pad - bg->kin_groups) * KK * ld_ah, st));
-    }
-    const long mp = grouped ? panel->m_pad : 0;
-    crm_donor_tables* tab = nullptr;  // phenotype-free donor tables of this call (collapsed mode)
-    if (collapsed) {
+        for (crm_gene* g : genes) {
+            g->ld_ep = round_up(k0, 128);
+            g->ld_ye = P.ldZ1;
+            g->ld_ee = P.ldZ3;
+        }
+        if (!P.collapsed()) return context_features(true);
         const double* Zt = panel->Z.as<double>();
-        if (cross) {
+        if (P.cross) {
             CRM_TRY(g0->dt_Zt.ensure(sizeof(double) * (size_t)np * panel->ldz + sizeof(int) * n));
             int* gperm = reinterpret_cast<int*>(g0->dt_Zt.as<double>() + (size_t)np * panel->ldz);
             hipLaunchKernelGGL(permute_group_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
@@ -1747,7 +1924,7 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             const bool have = reusable && g->dt_group == panel->group_key && !(gi == 0 && build_shared);
             if (!have) {
                 g->dt_group = 0;
-                CRM_TRY(build_donor_tables(g, panel, (gi == 0 && build_shared) ? tab : nullptr, d_Ep, d_EE, Zt, cross));
+                CRM_TRY(build_donor_tables(g, panel, (gi == 0 && build_shared) ? tab : nullptr, d_Ep, d_EE, Zt, P.cross));
                 if (reusable) g->dt_group = panel->group_key;
             }
         }
@@ -1755,433 +1932,312 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             tab->e0_key = g0->e0_key;
             tab->group_key = panel->group_key;
         }
+        return CRM_OK;
     }
-    if (!collapsed) CRM_TRY(context_features(true));
-    if (kin_route) {   // the (permuted) contexts in donor order
-        CRM_TRY(g0->kinEp.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ep));
-        CRM_TRY(launch_gather_rows(st, d_Ep, g0->ld_ep, bg->kin_map.as<int>(), bg->kin_rows, (int)g0->ld_ep,
-                                   g0->kinEp.as<double>(), g0->ld_ep));
-    }
-    if (kfold && bg->kin_k2 == 1) {
-        // one column of us: S[(k1 + d'), (b, i)] = sum over the cells of donor d' of us(c) g_b(c) E0(c, i) is the plain product
-        // G_d'' (us o E0)_d' of the donor's own cells -- its (b, i) layout is the row of S as it stands.  kinUE = us o E0 in
-        // donor order.
-        CRM_TRY(g0->kinUE.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ep));
-        CRM_TRY(launch_scale_rows(st, g0->kinEp.as<double>(), g0->ld_ep, bg->kin_Y.as<double>(), bg->kin_ldy, bg->kin_rows,
-                                  (int)g0->ld_ep, g0->kinUE.as<double>(), g0->ld_ep));
-    }
-    // E1 = E, the reference's default (and no context permutation): the pair features E1_a o E0_i are the symmetric
-    // E_a E_i that the scan holds anyway for E0'diag(g^2)E0 (EE: k0 (k0 + 1) / 2 columns) -- half the product
-    bool e1_sym = false;
-    if (e1_pairs && bg->kin_k1 == k0 && d_EE) {
-        int h_flag = 0;
-        int* d_flag = reinterpret_cast<int*>(d_near);
-        CRM_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-        CRM_TRY(launch_same_columns(st, bg->H.as<double>(), bg->ldh, d_Ep, g0->ld_ep, n, k0, d_flag));
-        CRM_HIP(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-        CRM_HIP(hipStreamSynchronize(st));
-        e1_sym = h_flag == 0;
-    }
-    if (e1_pairs && !e1_sym) {
-        CRM_TRY(g0->kinP.ensure(sizeof(double) * (size_t)np * ldP));
-        CRM_TRY(launch_pair_features(st, bg->H.as<double>(), bg->ldh, bg->kin_k1, d_Ep, g0->ld_ep, k0, np, g0->kinP.as<double>(), ldP));
-    }
-    // The kinship term's contexts are E as well (the reference's default E2 = E): the per-donor sums S_d = sum_c g_c e_c e_c'
-    // are symmetric -- one batched product per donor against E (x) E in donor order, half the flops of the Khatri-Rao form and
-    // a plain product, then a pass that writes the rows of S (blockops.hip: donor_pairs_expand_kernel); the E1 rows are the
-    // sum of those products over the donors, so their product over all cells goes as well.  Taken where its time is the
-    // smaller one (many tiny donors: the pass over S costs more than the products save).
-    bool donor_pairs = false;
-    const long ldPd = round_up((long)npair, 128);
-    const long pd_rows = std::max<long>(BLK, max_pairs) + 128, pd_slab = pd_rows * ldPd;
-    int donor_pair_splits = 1;
-    if (kfold && e1_sym && bg->kin_k2 == k0 && donor_pairs_serves(k0) && form("donor_pairs", 1)) {
-        const double peak = 78.6e12, hbm = 4.0e12;
-        const double t_kr = 2.0 * bg->kin_rows * (double)k0 * k0 / (0.6 * peak) + 2.0 * (double)np * npair / (0.92 * peak);
-        const double t_pairs = 2.0 * bg->kin_rows * (double)npair / (0.8 * peak) +
-                               (double)bg->kin_groups * (2.0 * npair + (double)k0 * k0) * sizeof(double) / hbm;
-        const bool fits = sizeof(double) * (double)bg->kin_groups * (double)pd_slab <= 8.0 * (1ull << 30);
-        if (fits && (t_pairs < t_kr || form("donor_pairs", 1) >= 2)) {
-            int h_flag = 0;
-            int* d_flag = reinterpret_cast<int*>(d_near);
-            CRM_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-            CRM_TRY(launch_same_columns(st, bg->kin_Y.as<double>(), bg->kin_ldy, g0->kinEp.as<double>(), g0->ld_ep, bg->kin_rows, k0, d_flag));
-            CRM_HIP(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-            CRM_HIP(hipStreamSynchronize(st));
-            donor_pairs = h_flag == 0;
+
+    // The kinship-structure routes' operands in donor order, the probes that settle the pair-product forms (plan_scan), and
+    // the zero rows of AH, the operand of every route through H but the folded one
+    int prepare_kinship() {
+        const long ldh = bg->ldh;
+        const double* H = bg->H.as<double>();
+        if (P.kin()) {   // the (permuted) contexts in donor order
+            CRM_TRY(g0->kinEp.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ep));
+            CRM_TRY(launch_gather_rows(st, d_Ep, g0->ld_ep, bg->kin_map.as<int>(), bg->kin_rows, (int)g0->ld_ep,
+                                       g0->kinEp.as<double>(), g0->ld_ep));
         }
-        if (donor_pairs) {
+        if (P.folded() && bg->kin_k2 == 1) {
+            // one column of us: S[(k1 + d'), (b, i)] = sum over the cells of donor d' of us(c) g_b(c) E0(c, i) is the plain product
+            // G_d'' (us o E0)_d' of the donor's own cells -- its (b, i) layout is the row of S as it stands.  kinUE = us o E0 in
+            // donor order.
+            CRM_TRY(g0->kinUE.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ep));
+            CRM_TRY(launch_scale_rows(st, g0->kinEp.as<double>(), g0->ld_ep, bg->kin_Y.as<double>(), bg->kin_ldy, bg->kin_rows,
+                                      (int)g0->ld_ep, g0->kinUE.as<double>(), g0->ld_ep));
+        }
+        const SameColumns e1_is_E{H, ldh, d_Ep, g0->ld_ep, n};   // E1 = E
+        const SameColumns us_is_E{bg->kin_Y.as<double>(), bg->kin_ldy, g0->kinEp.as<double>(), g0->ld_ep, bg->kin_rows};   // E2 = E
+        if (P.e1_sym) CRM_TRY(same_columns(st, d_near, k0, {e1_is_E}, P.e1_sym));
+        if (P.e1_pairs && !P.e1_sym) {
+            CRM_TRY(g0->kinP.ensure(sizeof(double) * (size_t)np * P.ldP));
+            CRM_TRY(launch_pair_features(st, H, ldh, bg->kin_k1, d_Ep, g0->ld_ep, k0, np, g0->kinP.as<double>(), P.ldP));
+        }
+        P.donor_pairs = P.donor_pairs && P.e1_sym;
+        if (P.donor_pairs) CRM_TRY(same_columns(st, d_near, k0, {us_is_E}, P.donor_pairs));
+        if (P.pairs_unfolded) CRM_TRY(same_columns(st, d_near, k0, {e1_is_E, us_is_E}, P.pairs_unfolded));
+        P.wb_rotate = P.wb_rotate && P.donor_pairs;
+        if (P.donor_pairs || P.pairs_unfolded) {   // (the folded and the unfolded form respectively)
             CRM_TRY(g0->kinEE.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ee));
             CRM_TRY(launch_gather_rows(st, d_EE, g0->ld_ee, bg->kin_map.as<int>(), bg->kin_rows, (int)g0->ld_ee, g0->kinEE.as<double>(),
                                        g0->ld_ee));
-            CRM_TRY(ctx->ws_Pd.ensure(sizeof(double) * (size_t)bg->kin_groups * pd_slab));
-            // the expansion pass: four variants per workgroup, three workgroups per CU -- donor ranges fill its rounds
-            const long wgs = (std::max<long>(BLK, 1) + 3) / 4;
-            while ((wgs * donor_pair_splits) % 768 != 0 && wgs * donor_pair_splits < 4 * 768 && donor_pair_splits < 8 &&
-                   donor_pair_splits < bg->kin_groups)
-                donor_pair_splits++;
-            CRM_TRY(ctx->ws_AH.ensure(sizeof(double) * (size_t)std::max<long>(donor_pair_splits, fold_split6) *
-                                      (size_t)std::max<long>(pd_slab, (std::max<long>(BLK, max_pairs) + 128) * ldP)));
+            CRM_TRY(ctx->ws_Pd.ensure(sizeof(double) * (size_t)(P.donor_pairs ? bg->kin_groups : bg->kin_groups_pad) * P.pd_slab));
         }
-    }
-    // Unrelated-donor form with the pair products: the rotated S of every donor, (U_d Lambda_d^-1/2)' S_d, is formed from P_d
-    // in one pass (blockops.hip: donor_pairs_rotate_kernel) instead of the rows of S and a per-donor product over them --
-    // bit for bit the same ws_A; form("donor_pairs_rotate", 0) keeps the two launches
-    const bool wb_rotate = wb && donor_pairs && donor_pairs_rotate_serves(k0) && form("donor_pairs_rotate", 1) != 0;
-    // The same idea on the UNFOLDED kinship-structure route (few contexts: BASELINE config 2's 20): with E1 = E2 = E the
-    // per-donor blocks [us | E1]'(g o E0) are one symmetric matrix S_d = sum_c g_c e_c e_c' twice over -- one batched plain
-    // product per donor against E (x) E in donor order (P_d), the contraction over the donors with the kinship factor ON THE
-    // PAIR PRODUCTS (Z_c = sum_d hKd[d, c] P_d: 210 columns per variant instead of 400, and an extra column of ones in hKd
-    // gives the sum over the donors that the E1 rows are), then the rows of AH = H'(g o E0) written from Z in one pass --
-    // instead of the Khatri-Rao launch per donor (64-wide tiles a third full), the contraction over the donors on k0 x k0
-    // blocks and the E1 sums.  Config 2: 1.7 -> 0.7 ms of a 8.6 ms step.
-    bool pairs_unfolded = false;
-    if (kin_route && !kfold && d_EE && bg->kin_k1 == k0 && bg->kin_k2 == k0 && donor_pairs_serves(k0) && form("donor_pairs", 1) &&
-        bg->kin_cols + 1 <= bg->kin_ldh) {
-        const double cost_kr = 2.0 * bg->kin_rows * (double)KK * k0 + 2.0 * (double)bg->kin_groups_pad * bg->kin_cols * bg->kin_k2 * k0;
-        const double cost_pairs = 2.0 * bg->kin_rows * (double)npair + 2.0 * (double)(bg->kin_cols + 1) * bg->kin_groups_pad * (double)ldPd;
-        const bool fits = sizeof(double) * (double)bg->kin_groups_pad * (double)pd_slab <= 8.0 * (1ull << 30) &&
-                          sizeof(double) * (double)(bg->kin_cols + 1) * (double)pd_slab <= (double)s_bytes;
-        if (fits && (cost_pairs < 0.8 * cost_kr || form("donor_pairs", 1) >= 2)) {
-            int h_flag = 0;
-            int* d_flag = reinterpret_cast<int*>(d_near);
-            CRM_HIP(hipMemsetAsync(d_flag, 0, sizeof(int), st));
-            CRM_TRY(launch_same_columns(st, bg->H.as<double>(), bg->ldh, d_Ep, g0->ld_ep, n, k0, d_flag));
-            CRM_TRY(launch_same_columns(st, bg->kin_Y.as<double>(), bg->kin_ldy, g0->kinEp.as<double>(), g0->ld_ep, bg->kin_rows, k0, d_flag));
-            CRM_HIP(hipMemcpyAsync(&h_flag, d_flag, sizeof(int), hipMemcpyDeviceToHost, st));
-            CRM_HIP(hipStreamSynchronize(st));
-            pairs_unfolded = h_flag == 0;
+        if (P.donor_pairs)   // (ws_AH, the folded form's scratch, also holds the sliced pair products of the expansion pass)
+            CRM_TRY(ctx->ws_AH.ensure(sizeof(double) * (size_t)std::max<long>(P.donor_pair_splits, P.fold_split6) *
+                                      (size_t)std::max<long>(P.pd_slab, (std::max<long>(P.BLK, P.pair_cap) + 128) * P.ldP)));
+        // (unfolded form: the slabs of the padding donors meet zero rows of hKd in the contraction over the donors: they must be
+        // finite -- cleared here, not left to whatever the allocation or an earlier call put there)
+        if (P.pairs_unfolded && bg->kin_groups_pad > bg->kin_groups)
+            CRM_HIP(hipMemsetAsync(ctx->ws_Pd.as<double>() + (size_t)bg->kin_groups * P.pd_slab, 0,
+                                   sizeof(double) * (size_t)(bg->kin_groups_pad - bg->kin_groups) * P.pd_slab, st));
+        if (P.through_H() && !P.folded()) {
+            // AH = H'(g o E0), the operand of the products with the mixing matrices: its rows beyond the half factor's columns meet
+            // zero rows of Mix and must be finite -- zero.  The pair-feature form writes every row below them for every column it
+            // is read at (columns beyond the block's only feed output rows that are never stored), so the padding rows are all
+            // there is to clear: 4 rows instead of 0.67 GB per call at config 2.
+            if (P.pairs_unfolded && ldh > bg->cols)
+                CRM_HIP(hipMemsetAsync(ctx->ws_AH.as<double>() + (size_t)bg->cols * P.ld_ah, 0, sizeof(double) * (size_t)(ldh - bg->cols) * P.ld_ah, st));
+            else if (!P.pairs_unfolded)
+                CRM_HIP(hipMemsetAsync(ctx->ws_AH.ptr, 0, sizeof(double) * (size_t)ldh * P.ld_ah, st));
         }
-        if (pairs_unfolded) {
-            CRM_TRY(g0->kinEE.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ee));
-            CRM_TRY(launch_gather_rows(st, d_EE, g0->ld_ee, bg->kin_map.as<int>(), bg->kin_rows, (int)g0->ld_ee, g0->kinEE.as<double>(),
-                                       g0->ld_ee));
-            // (the slabs of the padding donors meet zero rows of hKd in the contraction over the donors: they must be finite --
-            // cleared here, not left to whatever the allocation or an earlier call put there)
-            CRM_TRY(ctx->ws_Pd.ensure(sizeof(double) * (size_t)bg->kin_groups_pad * pd_slab));
-            if (bg->kin_groups_pad > bg->kin_groups)
-                CRM_HIP(hipMemsetAsync(ctx->ws_Pd.as<double>() + (size_t)bg->kin_groups * pd_slab, 0,
-                                       sizeof(double) * (size_t)(bg->kin_groups_pad - bg->kin_groups) * pd_slab, st));
-            // the column of ones behind the kinship factor's m columns (kin_hKd: kin_groups_pad x kin_ldh, zero beyond m)
-            std::vector<double> ones((size_t)bg->kin_groups, 1.0);
-            CRM_HIP(hipMemcpy2DAsync(bg->kin_hKd.as<double>() + bg->kin_cols, sizeof(double) * bg->kin_ldh, ones.data(), sizeof(double),
-                                     sizeof(double), bg->kin_groups, hipMemcpyHostToDevice, st));
-            CRM_HIP(hipStreamSynchronize(st));   // (ones lives on this stack frame)
-        }
+        return CRM_OK;
     }
-    if (bg->fast_T && ctx->fast_T && (ng > 1 || kin_route) && !collapsed && !kfold) {
-        // AH = H'(g o E0), the operand of the products with the mixing matrices: its rows beyond the half factor's columns meet
-        // zero rows of Mix and must be finite -- zero.  The pair-feature form writes every row below them for every column it
-        // is read at (columns beyond the block's only feed output rows that are never stored), so the padding rows are all
-        // there is to clear: 4 rows instead of 0.67 GB per call at config 2.
-        if (pairs_unfolded && bg->ldh > bg->cols)
-            CRM_HIP(hipMemsetAsync(ctx->ws_AH.as<double>() + (size_t)bg->cols * ld_ah, 0, sizeof(double) * (size_t)(bg->ldh - bg->cols) * ld_ah, st));
-        else if (!pairs_unfolded)
-            CRM_HIP(hipMemsetAsync(ctx->ws_AH.ptr, 0, sizeof(double) * (size_t)bg->ldh * ld_ah, st));
-    }
-    const long xrows = collapsed ? mp : np;  // length of the contraction axis in this mode
-    // Unrelated-donor form: per gene Phi'[y, W] ((1 + c) rows over the positions) and E1'[y, W] (k1 x 128); per block
-    // Phi'gx; the Gram of the KT + k1 rows; the rotated S in ws_A.
-    double *wb_yW = nullptr, *wb_E1yW = nullptr, *wb_g = nullptr, *wb_Gw = nullptr;
-    if (wb) {
-        const int k2 = bg->kin_k2, k2pad = bg->wb_k2pad;
+
+    // Unrelated-donor form: Phi'[y, W] and E1'[y, W] per gene -- formed on the gene's first scan against these tables
+    // (crm_gene::wb_yW), copied into this scan's workspace after
+    int prepare_woodbury() {
+        if (!P.wb()) return CRM_OK;
+        const int k2 = bg->kin_k2, k1 = bg->kin_k1;
         const long groups = bg->kin_groups, brows = groups * k2 + GEMM_BK;
-        const size_t n_yW = (size_t)ng * (1 + c) * ldwb, n_E1 = (size_t)ng * wb_k1 * 128, n_g = (size_t)BLK * ldwb,
-                     n_Gw = (size_t)BLK * (KT + wb_k1) * (KT + wb_k1), n_tmp = (size_t)(bg->kin_rows + brows) * 128;
-        CRM_TRY(ctx->ws_WB.ensure(sizeof(double) * (n_yW + n_E1 + n_g + n_Gw + n_tmp)));
-        CRM_TRY(ctx->ws_A.ensure(sizeof(double) * (size_t)std::max(max_pairs, BLK) * k0 * ldAw));
-        CRM_TRY(ctx->ws_Anone.ensure(sizeof(double) * (size_t)ldAw));
-        CRM_HIP(hipMemsetAsync(ctx->ws_Anone.ptr, 0, sizeof(double) * (size_t)ldAw, st));
-        wb_yW = ctx->ws_WB.as<double>();
-        wb_E1yW = wb_yW + n_yW;
-        wb_g = wb_E1yW + n_E1;
-        wb_Gw = wb_g + n_g;
-        double* yWk = wb_Gw + n_Gw;            // [y, W] in donor order
-        double* Bk = yWk + (size_t)bg->kin_rows * 128;   // us_d'[y, W]_d, rows d k2 + j
-        std::vector<GemmProblem> kp((size_t)2 * groups);
-        GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
-        const size_t n_yW1 = (size_t)(1 + c) * ldwb, n_E11 = (size_t)wb_k1 * 128;
-        // Phi'[y, W] into Cphi (row length ldphi) and E1'[y, W] into Ce1 (k1 x 128) for gene g
-        auto wb_gene_constants = [&](crm_gene* g, double* Cphi, long ldphi, double* Ce1) -> int {
-            CRM_HIP(hipMemsetAsync(Bk, 0, sizeof(double) * (size_t)brows * 128, st));
-            CRM_TRY(launch_gather_rows(st, g->yW.as<double>(), g->ld_yw, bg->kin_map.as<int>(), bg->kin_rows, 1 + c, yWk, 128));
-            long maxlen = GEMM_BK;
-            for (long d = 0; d < groups; d++) {
-                GemmProblem p{};
-                p.X = bg->kin_Y.as<double>() + bg->kin_row0[d] * bg->kin_ldy; p.ldx = bg->kin_ldy;
-                p.Y = yWk + bg->kin_row0[d] * 128; p.ldy = 128;
-                p.C = Bk + (size_t)d * k2 * 128; p.ldc = 128;
-                p.M = k2; p.N = 1 + c; p.cells = bg->kin_len[d];
-                maxlen = std::max(maxlen, bg->kin_len[d]);
-                kp[d] = p;
-                GemmProblem q{};   // Phi_d'[y, W]_d, stored transposed: rows y, W_1 .. W_c over the positions
-                q.X = Bk + (size_t)d * k2 * 128; q.ldx = 128;
-                q.Y = bg->wb_U.as<double>() + (size_t)d * k2pad * 128; q.ldy = 128;
-                q.C = Cphi + d * k2; q.ldc = ldphi;
-                q.M = 1 + c; q.N = k2; q.cells = k2pad;
-                kp[groups + d] = q;
-            }
-            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * kp.size(), hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, k2, 1 + c, maxlen, false, 0, 1, 0));
-            CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, (int)groups, 1 + c, k2, k2pad, false, 0, 1, 0));
-            GemmProblem e{};   // E1'[y, W] over all cells
-            e.X = bg->H.as<double>(); e.ldx = bg->ldh; e.Y = g->yW.as<double>(); e.ldy = g->ld_yw;
-            e.C = Ce1; e.ldc = 128; e.M = wb_k1; e.N = 1 + c;
-            CRM_HIP(hipMemcpyAsync(d_probs, &e, sizeof e, hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_gemm_tn(ctx, d_probs, 1, wb_k1, 1 + c, np, false, 0, 1, 0));
-            CRM_HIP(hipStreamSynchronize(st));   // (kp, e live on the host)
-            return CRM_OK;
-        };
+        const size_t n_yW1 = (size_t)(1 + c) * P.ldwb, n_E11 = (size_t)k1 * 128;
+        double* yWk = wb_tmp;                              // [y, W] in donor order
+        double* Bk = yWk + (size_t)bg->kin_rows * 128;     // us_d'[y, W]_d, rows d k2 + j
         for (int gi = 0; gi < ng; gi++) {
             crm_gene* g = genes[gi];
-            // formed on the gene's first scan against these tables (crm_gene::wb_yW), copied into this scan's workspace after
             if (g->wb_gen != bg->wb_gen) {
                 CRM_TRY(g->wb_yW.ensure(sizeof(double) * (n_yW1 + n_E11)));
                 CRM_HIP(hipMemsetAsync(g->wb_yW.ptr, 0, sizeof(double) * (n_yW1 + n_E11), st));
-                CRM_TRY(wb_gene_constants(g, g->wb_yW.as<double>(), ldwb, g->wb_yW.as<double>() + n_yW1));
+                CRM_HIP(hipMemsetAsync(Bk, 0, sizeof(double) * (size_t)brows * 128, st));
+                CRM_TRY(launch_gather_rows(st, g->yW.as<double>(), g->ld_yw, bg->kin_map.as<int>(), bg->kin_rows, 1 + c, yWk, 128));
+                std::vector<GemmProblem> kp((size_t)2 * groups);
+                GemmProblem p{};
+                p.X = bg->kin_Y.as<double>(); p.ldx = bg->kin_ldy; p.Y = yWk; p.ldy = 128; p.C = Bk; p.ldc = 128;
+                p.M = k2; p.N = 1 + c;
+                const long maxlen = donor_run_records(bg, p, (long)k2 * 128, kp.data());
+                GemmProblem q{};   // Phi_d'[y, W]_d, stored transposed: rows y, W_1 .. W_c over the positions
+                q.X = Bk; q.ldx = 128; q.C = g->wb_yW.as<double>(); q.ldc = P.ldwb; q.M = 1 + c;
+                woodbury_records(bg, q, (long)k2 * 128, kp.data() + groups);
+                GemmProblem e{};   // E1'[y, W] over all cells
+                e.X = bg->H.as<double>(); e.ldx = bg->ldh; e.Y = g->yW.as<double>(); e.ldy = g->ld_yw;
+                e.C = g->wb_yW.as<double>() + n_yW1; e.ldc = 128; e.M = k1; e.N = 1 + c;
+                CRM_TRY(with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) -> int {
+                    CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, k2, 1 + c, maxlen, false, 0, 1, 0));
+                    CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, (int)groups, 1 + c, k2, bg->wb_k2pad, false, 0, 1, 0));
+                    CRM_TRY(upload(SLOT_ONE, &e, 1));
+                    return launch_gemm_tn(ctx, d_probs + SLOT_ONE, 1, k1, 1 + c, np, false, 0, 1, 0);
+                }));
                 g->wb_gen = bg->wb_gen;
             }
             CRM_HIP(hipMemcpyAsync(wb_yW + (size_t)gi * n_yW1, g->wb_yW.as<double>(), sizeof(double) * n_yW1, hipMemcpyDeviceToDevice, st));
             CRM_HIP(hipMemcpyAsync(wb_E1yW + (size_t)gi * n_E11, g->wb_yW.as<double>() + n_yW1, sizeof(double) * n_E11,
                                    hipMemcpyDeviceToDevice, st));
         }
+        return CRM_OK;
     }
-    std::vector<NullFitOut> h_fit((size_t)BLK * ng);
-    std::vector<int> h_pos((size_t)BLK * ng), h_ord(max_pairs);
-    std::vector<GemmProblem> probs(CRM_MAX_RHO + 4);
-    std::vector<int> pair_of((size_t)nrho * BLK);
-    std::vector<int> h_near(BLK);
 
-    for (long done = 0; done < count; done += BLK) {
-        const int nb = (int)std::min<long>(BLK, count - done);
-        const long col0 = first + done;
-        const long done_blk = done;
-        double* Gb = ctx->ws_Gb.as<double>();
-        TraceRange range_block("crm scan block");
-        // 1. aligned copy of the block (and its row-permuted twin for the test direction); in
-        //    collapsed mode the "block" is the donor dosage slab (m_pad rows)
-        double* Gt = Gb;
-        if (collapsed) {
-            CRM_TRY(launch_gather_block(st, panel->Gd.as<double>() + col0, panel->ld, mp, panel->m, nullptr, nullptr, nb, Gb, ldb, (int)ldb));
-        } else if (grouped) {
-            CRM_TRY(launch_expand_block(st, panel->Gd.as<double>() + col0, panel->ld, panel->group.as<int>(), np, n, nullptr, nb, Gb, ldb, (int)ldb));
+    // ---- block stages ---------------------------------------------------------------------------------------------------
+    // 1. aligned copy of the block (and its row-permuted twin for the test direction); in
+    //    collapsed mode the "block" is the donor dosage slab (m_pad rows)
+    int copy_block(Block& B) {
+        const long ldb = P.ldb;
+        const int nb = B.nb;
+        B.Gb = B.Gt = B.Gx = ctx->ws_Gb.as<double>();
+        if (P.collapsed()) {
+            CRM_TRY(launch_gather_block(st, panel->Gd.as<double>() + B.col0, panel->ld, P.mp, panel->m, nullptr, nullptr, nb, B.Gb, ldb, (int)ldb));
+        } else if (panel->grouped) {
+            CRM_TRY(launch_expand_block(st, panel->Gd.as<double>() + B.col0, panel->ld, panel->group.as<int>(), np, n, nullptr, nb, B.Gb, ldb, (int)ldb));
             if (idx_G) {
-                Gt = ctx->ws_Gt.as<double>();
-                CRM_TRY(launch_expand_block(st, panel->Gd.as<double>() + col0, panel->ld, panel->group.as<int>(), np, n, d_idxG, nb, Gt, ldb, (int)ldb));
+                B.Gt = ctx->ws_Gt.as<double>();
+                CRM_TRY(launch_expand_block(st, panel->Gd.as<double>() + B.col0, panel->ld, panel->group.as<int>(), np, n, d_idxG, nb, B.Gt, ldb, (int)ldb));
             }
         } else {
-            CRM_TRY(launch_gather_block(st, panel->G.as<double>() + col0, panel->ld, np, n, nullptr, nullptr, nb, Gb, ldb, (int)ldb));
+            CRM_TRY(launch_gather_block(st, panel->G.as<double>() + B.col0, panel->ld, np, n, nullptr, nullptr, nb, B.Gb, ldb, (int)ldb));
             if (idx_G) {
-                Gt = ctx->ws_Gt.as<double>();
-                CRM_TRY(launch_gather_block(st, panel->G.as<double>() + col0, panel->ld, np, n, d_idxG, nullptr, nb, Gt, ldb, (int)ldb));
+                B.Gt = ctx->ws_Gt.as<double>();
+                CRM_TRY(launch_gather_block(st, panel->G.as<double>() + B.col0, panel->ld, np, n, d_idxG, nullptr, nb, B.Gt, ldb, (int)ldb));
             }
         }
-        // 2. The fixed effects' role of the variants: Gx = G - W (W'W)^-1 W'G, orthogonalised against the covariates in
-        //    the cell axis as the reference's economic_svd([W, g]) basis is (blockops.hip); the test direction keeps G.
-        //    Then g'g, g'W (shared) and g'y per gene of that role.  The collapsed path works on donor-level sums and
-        //    cannot do this: it marks the variants that are nearly collinear with W for a second, dense pass.
-        double* Gx = Gb;
-        if (!collapsed) {
-            Gx = ctx->ws_Gx.as<double>();
-            CRM_TRY(launch_variant_stats(st, Gb, ldb, np, nb, g0->yW.as<double>(), g0->yW.as<double>() + 1, g0->ld_yw, c, d_part, d_gg, d_gy, d_gW, ld_gW));
-            CRM_TRY(launch_ortho_block(st, Gb, ldb, np, nb, (int)ldb, g0->yW.as<double>() + 1, g0->ld_yw, c, g0->Wproj.as<double>(),
-                                       d_gW, ld_gW, d_coef, ldb, d_thr, Gx, ldb));
+        return CRM_OK;
+    }
+
+    // 2. The fixed effects' role of the variants: Gx = G - W (W'W)^-1 W'G, orthogonalised against the covariates in
+    //    the cell axis as the reference's economic_svd([W, g]) basis is (blockops.hip); the test direction keeps G.
+    //    Then g'g, g'W (shared) and g'y per gene of that role.  The collapsed path works on donor-level sums and
+    //    cannot do this: it marks the variants that are nearly collinear with W for a second, dense pass.
+    int block_stats(Block& B) {
+        const long ldb = P.ldb, ld_gW = P.ld_gW;
+        const int nb = B.nb, BLK = P.BLK;
+        if (!P.collapsed()) {
+            B.Gx = ctx->ws_Gx.as<double>();
+            CRM_TRY(launch_variant_stats(st, B.Gb, ldb, np, nb, g0->yW.as<double>(), g0->yW.as<double>() + 1, g0->ld_yw, c, d_part, d_gg, d_gy, d_gW, ld_gW));
+            CRM_TRY(launch_ortho_block(st, B.Gb, ldb, np, nb, (int)ldb, g0->yW.as<double>() + 1, g0->ld_yw, c, g0->Wproj.as<double>(),
+                                       d_gW, ld_gW, d_coef, ldb, d_thr, B.Gx, ldb));
         }
         for (int gi = 0; gi < ng; gi++) {
             crm_gene* g = genes[gi];
-            if (collapsed)
-                CRM_TRY(launch_donor_stats(st, Gb, ldb, (int)panel->m, nb, g->dt_sums.as<double>(), c, d_gg, d_gy + (size_t)gi * BLK, d_gW, ld_gW));
+            if (P.collapsed())
+                CRM_TRY(launch_donor_stats(st, B.Gb, ldb, (int)panel->m, nb, g->dt_sums.as<double>(), c, d_gg, d_gy + (size_t)gi * BLK, d_gW, ld_gW));
             else
-                CRM_TRY(launch_variant_stats(st, Gx, ldb, np, nb, g->yW.as<double>(), g->yW.as<double>() + 1, g->ld_yw, c, d_part, d_gg, d_gy + (size_t)gi * BLK, d_gW, ld_gW));
+                CRM_TRY(launch_variant_stats(st, B.Gx, ldb, np, nb, g->yW.as<double>(), g->yW.as<double>() + 1, g->ld_yw, c, d_part, d_gg, d_gy + (size_t)gi * BLK, d_gW, ld_gW));
         }
-        if (collapsed) {
+        if (P.collapsed()) {
             if (near_out) CRM_TRY(launch_collinear_flag(st, d_gg, d_gW, ld_gW, g0->Wproj.as<double>(), c, nb, COLLINEAR_TAU, d_near));
         } else
             CRM_TRY(launch_ortho_rank(st, d_gg, d_thr, nb, d_drop));
-        // 3. T(rho) = G' Q0(rho) for all grid points.  With Q0(rho) = H Mix(rho) the n-length work is
-        //    done once, (H'G), followed by eleven small products Mix(rho)'(H'G): 2 n cols + 2 cols sum r
-        //    flops per variant instead of 2 n sum r.
-        const bool fastT = !collapsed && bg->fast_T && ctx->fast_T;
-        if (!fastT && !collapsed) CRM_TRY(crm_background_require_q0(bg, -1));
-        // (crm_scan_interaction_permuted: the passes after the first take the rotations at rho* and the fits of this block
-        // from the first one's record -- neither depends on the permutation hooks)
-        const bool replaying = ctx->replay_mode == 2;
-        std::vector<double> flat_obj;
-        auto fold_TH = [&]() -> int {
-            // folded form: rows [0, k1) = E1'G over all cells (sliced along the cell axis), rows k1 + d' k2 + j = per-donor
-            // us_j'G over the donor's own cells; the contraction over the donors sits in MixK (objects.h)
-            double* Gk = ctx->ws_Gk.as<double>();
-            double* TH = ctx->ws_TH.as<double>();
-            const int k1 = bg->kin_k1, k2 = bg->kin_k2;
-            const long groups = bg->kin_groups;
-            CRM_TRY(launch_gather_rows(st, Gx, ldb, bg->kin_map.as<int>(), bg->kin_rows, (int)ldb, Gk, ldb));
-            std::vector<GemmProblem> kp((size_t)groups + 1);
-            long maxlen = GEMM_BK;
-            for (long d = 0; d < groups; d++) {
-                GemmProblem p{};
-                p.X = bg->kin_Y.as<double>() + bg->kin_row0[d] * bg->kin_ldy; p.ldx = bg->kin_ldy;
-                p.Y = Gk + bg->kin_row0[d] * ldb; p.ldy = ldb;
-                p.C = TH + (size_t)(k1 + d * k2) * ldb; p.ldc = ldb;
-                p.M = k2; p.N = nb; p.cells = bg->kin_len[d];
-                maxlen = std::max(maxlen, bg->kin_len[d]);
-                kp[d] = p;
-            }
-            {
-                GemmProblem p{};
-                p.X = bg->H.as<double>(); p.ldx = bg->ldh; p.Y = Gx; p.ldy = ldb;
-                p.C = ctx->ws_S2.as<double>(); p.ldc = ldb; p.M = k1; p.N = nb;
-                kp[groups] = p;
-            }
-            GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
-            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * kp.size(), hipMemcpyHostToDevice, st));
+        return CRM_OK;
+    }
+
+    // folded form: rows [0, k1) = E1'G over all cells (sliced along the cell axis), rows k1 + d' k2 + j = per-donor
+    // us_j'G over the donor's own cells; the contraction over the donors sits in MixK (objects.h)
+    int fold_TH(const Block& B) {
+        const long ldb = P.ldb;
+        const int nb = B.nb, k1 = bg->kin_k1, k2 = bg->kin_k2;
+        const long groups = bg->kin_groups;
+        double* Gk = ctx->ws_Gk.as<double>();
+        double* TH = ctx->ws_TH.as<double>();
+        CRM_TRY(launch_gather_rows(st, B.Gx, ldb, bg->kin_map.as<int>(), bg->kin_rows, (int)ldb, Gk, ldb));
+        std::vector<GemmProblem> kp((size_t)groups + 1);
+        GemmProblem p{};
+        p.X = bg->kin_Y.as<double>(); p.ldx = bg->kin_ldy; p.Y = Gk; p.ldy = ldb; p.C = TH + (size_t)k1 * ldb; p.ldc = ldb;
+        p.M = k2; p.N = nb;
+        const long maxlen = donor_run_records(bg, p, (long)k2 * ldb, kp.data());
+        GemmProblem& e = kp[groups];
+        e.X = bg->H.as<double>(); e.ldx = bg->ldh; e.Y = B.Gx; e.ldy = ldb;
+        e.C = ctx->ws_S2.as<double>(); e.ldc = ldb; e.M = k1; e.N = nb;
+        const long e1_slab = (long)k1 * ldb;
+        return with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) -> int {
             CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, k2, nb, maxlen, false, 0, 1, 0));
-            const long e1_slab = (long)k1 * ldb;
-            CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, 1, k1, nb, np, false, 0, fold_split3, e1_slab));
-            CRM_TRY(launch_reduce_splits(st, ctx->ws_S2.as<double>(), e1_slab, fold_split3, e1_slab));
+            CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, 1, k1, nb, np, false, 0, P.fold_split3, e1_slab));
+            CRM_TRY(launch_reduce_splits(st, ctx->ws_S2.as<double>(), e1_slab, P.fold_split3, e1_slab));
             CRM_HIP(hipMemcpyAsync(TH, ctx->ws_S2.ptr, sizeof(double) * (size_t)e1_slab, hipMemcpyDeviceToDevice, st));
-            CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
             return CRM_OK;
-        };
-        if (replaying) {
-            if (ng != 1 || ctx->replay_cursor >= ctx->replay_blocks.size()) {
-                set_error("scan: the replayed pass visits a block the recorded one did not");
-                return CRM_ERR_INTERNAL;
-            }
-            crm_ctx::ReplayBlock* rb = ctx->replay_blocks[ctx->replay_cursor++];
-            if (rb->col0 != col0 || rb->nb != nb || rb->collapsed != collapsed || rb->fit.size() != sizeof(NullFitOut) * (size_t)nb) {
-                set_error("scan: the replayed pass visits its blocks in another order than the recorded one");
-                return CRM_ERR_INTERNAL;
-            }
-            CRM_HIP(hipMemcpyAsync(d_fit, rb->fit.data(), rb->fit.size(), hipMemcpyHostToDevice, st));
-            // (unrelated-donor form: the assembly reads Phi'gx and E1'gx of the block from H'Gx -- formed again, same bits)
-            if (wb) CRM_TRY(fold_TH());
-            hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((ldT + 255) / 256), nb), dim3(256), 0, st, ctx->ws_T.as<double>(),
-                               (long)BLK, ldT, d_fit, nb, (int)ldT, rb->T.as<double>(), 1);
-            CRM_HIP(hipGetLastError());
-        } else {
-        if (fastT && kfold) {
-            CRM_TRY(fold_TH());
-        } else if (fastT && kin_route) {
-            // H'G donor by donor (as H'(g o E0) in step 6): per donor [us | E1]' G over its own cells, then the L rows by a
-            // contraction over the donors with hKd and the E1 rows as sums over the donors
-            double* Gk = ctx->ws_Gk.as<double>();
-            double* S2 = ctx->ws_S2.as<double>();
-            const int k1 = bg->kin_k1, k2 = bg->kin_k2;
-            const long groups = bg->kin_groups, mk = bg->kin_cols;
-            CRM_TRY(launch_gather_rows(st, Gx, ldb, bg->kin_map.as<int>(), bg->kin_rows, (int)ldb, Gk, ldb));
-            std::vector<GemmProblem> kp((size_t)groups + k2);
-            long maxlen = GEMM_BK;
-            for (long d = 0; d < groups; d++) {
-                GemmProblem p{};
-                p.X = bg->kin_Y.as<double>() + bg->kin_row0[d] * bg->kin_ldy; p.ldx = bg->kin_ldy;
-                p.Y = Gk + bg->kin_row0[d] * ldb; p.ldy = ldb;
-                p.C = S2 + (size_t)d * KK * ldb; p.ldc = ldb;
-                p.M = KK; p.N = nb; p.cells = bg->kin_len[d];
-                maxlen = std::max(maxlen, bg->kin_len[d]);
-                kp[d] = p;
-            }
-            for (int j = 0; j < k2; j++) {
-                GemmProblem p{};
-                p.X = bg->kin_hKd.as<double>(); p.ldx = bg->kin_ldh;
-                p.Y = S2 + (size_t)j * ldb; p.ldy = (long)KK * ldb;
-                p.C = ctx->ws_TH.as<double>() + (size_t)(k1 + (long)j * mk) * ldb; p.ldc = ldb;
-                p.M = (int)mk; p.N = nb;
-                kp[groups + j] = p;
-            }
-            GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
-            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * kp.size(), hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, KK, nb, maxlen, false, 0, 1, 0));
-            CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, k2, (int)mk, nb, bg->kin_groups_pad, false, 0, 1, 0));
-            CRM_TRY(launch_kin_sum_e1(st, S2, ldb, KK, k2, k1, (int)groups, nb, ctx->ws_TH.as<double>(), ldb));
-            CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
-        } else if (fastT) {
-            GemmProblem p{};
-            p.X = bg->H.as<double>(); p.ldx = bg->ldh; p.Y = Gx; p.ldy = ldb;
-            p.C = ctx->ws_TH.as<double>(); p.ldc = ldb; p.M = (int)bg->cols; p.N = nb;
-            CRM_HIP(hipMemcpyAsync(d_probs, &p, sizeof p, hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_gemm_tn(ctx, d_probs, 1, (int)bg->cols, nb, np, false, 0, ks_h, th_slab));
-            CRM_TRY(launch_reduce_splits(st, ctx->ws_TH.as<double>(), (long)bg->cols * ldb, ks_h, th_slab));
+        });
+    }
+
+    // H'G donor by donor (as H'(g o E0) in step 6): per donor [us | E1]' G over its own cells, then the L rows by a
+    // contraction over the donors with hKd and the E1 rows as sums over the donors
+    int unfolded_TH(const Block& B) {
+        const long ldb = P.ldb, KK = P.KK;
+        const int nb = B.nb, k1 = bg->kin_k1, k2 = bg->kin_k2;
+        const long groups = bg->kin_groups, mk = bg->kin_cols;
+        double* Gk = ctx->ws_Gk.as<double>();
+        double* S2 = ctx->ws_S2.as<double>();
+        CRM_TRY(launch_gather_rows(st, B.Gx, ldb, bg->kin_map.as<int>(), bg->kin_rows, (int)ldb, Gk, ldb));
+        std::vector<GemmProblem> kp((size_t)groups + k2);
+        GemmProblem p{};
+        p.X = bg->kin_Y.as<double>(); p.ldx = bg->kin_ldy; p.Y = Gk; p.ldy = ldb; p.C = S2; p.ldc = ldb;
+        p.M = (int)KK; p.N = nb;
+        const long maxlen = donor_run_records(bg, p, KK * ldb, kp.data());
+        for (int j = 0; j < k2; j++) {
+            GemmProblem& q = kp[groups + j];
+            q.X = bg->kin_hKd.as<double>(); q.ldx = bg->kin_ldh; q.Y = S2 + (size_t)j * ldb; q.ldy = KK * ldb;
+            q.C = ctx->ws_TH.as<double>() + (size_t)(k1 + (long)j * mk) * ldb; q.ldc = ldb; q.M = (int)mk; q.N = nb;
         }
+        return with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) -> int {
+            CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, (int)KK, nb, maxlen, false, 0, 1, 0));
+            CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, k2, (int)mk, nb, bg->kin_groups_pad, false, 0, 1, 0));
+            return launch_kin_sum_e1(st, S2, ldb, (int)KK, k2, k1, (int)groups, nb, ctx->ws_TH.as<double>(), ldb);
+        });
+    }
+
+    int plain_TH(const Block& B) {
+        const long ldb = P.ldb;
+        GemmProblem p{};
+        p.X = bg->H.as<double>(); p.ldx = bg->ldh; p.Y = B.Gx; p.ldy = ldb;
+        p.C = ctx->ws_TH.as<double>(); p.ldc = ldb; p.M = (int)bg->cols; p.N = B.nb;
+        CRM_TRY(upload(SLOT_ONE, &p, 1));
+        CRM_TRY(launch_gemm_tn(ctx, d_probs + SLOT_ONE, 1, (int)bg->cols, B.nb, np, false, 0, P.ks_h, P.th_slab));
+        return launch_reduce_splits(st, ctx->ws_TH.as<double>(), (long)bg->cols * ldb, P.ks_h, P.th_slab);
+    }
+
+    // The eleven products run as one launch of equally long tiles, i.e. in rounds of as many tiles as the chip holds
+    // workgroups (two per CU): at config 3, 12 832 tiles are 25.06 rounds of 512 and the last 0.06 costs a whole one.
+    // The smallest problems that make up that remainder (there: rho = 1, r = 50, 32 tiles) are taken out and run cut
+    // along the contraction axis instead -- a sixteenth of a round plus a reduction.  Returns the problems left in probs.
+    int cut_rotations(const Block& B, int& n_main) {
+        const int nb = B.nb, BLK = P.BLK;
+        n_main = nrho;
+        const long slots = 2L * ctx_cus(ctx), mtl = (nb + GEMM_BM - 1) / GEMM_BM;
+        long tiles[CRM_MAX_RHO], total = 0;
+        int order[CRM_MAX_RHO];
+        for (int i = 0; i < nrho; i++) { tiles[i] = mtl * ((probs[i].N + 127) / 128); total += tiles[i]; order[i] = i; }
+        std::sort(order, order + nrho, [&](int a, int b) { return tiles[a] < tiles[b]; });
+        const long need = total % slots;
+        long acc = 0;
+        int take = 0;
+        while (take < nrho - 1 && acc < need) acc += tiles[order[take++]];
+        if (!(total > slots && need > 0 && acc >= need && acc <= slots / 4)) return CRM_OK;
+        int n_cut = 0, cut_ks = 1;
+        GemmProblem cut_probs[CRM_MAX_RHO];
+        double* cut_dst[CRM_MAX_RHO];
+        bool is_cut[CRM_MAX_RHO] = {false};
+        long cut_doubles = 0;
+        for (int q = 0; q < take; q++) is_cut[order[q]] = true;
+        while ((long)(cut_ks + 1) * acc <= slots && cut_ks < 16 && P.kdim / GEMM_BK / (cut_ks + 1) >= 8) cut_ks++;
+        n_main = 0;
+        for (int i = 0; i < nrho; i++) {
+            if (!is_cut[i]) { probs[n_main++] = probs[i]; continue; }
+            GemmProblem c = probs[i];
+            cut_dst[n_cut] = c.C;
+            c.ldc = round_up(c.N, 128);
+            cut_doubles += (long)BLK * c.ldc;
+            cut_probs[n_cut++] = c;
+        }
+        CRM_TRY(ctx->ws_Tcut.ensure(sizeof(double) * (size_t)cut_doubles * cut_ks));
+        long at = 0;
+        for (int q = 0; q < n_cut; q++) {
+            cut_probs[q].C = ctx->ws_Tcut.as<double>() + at;
+            at += (long)BLK * cut_probs[q].ldc;
+        }
+        const int slot = SLOT_RHO + nrho;
+        CRM_TRY(upload(slot, cut_probs, n_cut));
+        int cut_maxn = 1;
+        for (int q = 0; q < n_cut; q++) cut_maxn = std::max(cut_maxn, cut_probs[q].N);
+        CRM_TRY(launch_gemm_tn(ctx, d_probs + slot, n_cut, nb, cut_maxn, P.kdim, false, 0, cut_ks, cut_doubles));
+        CRM_TRY(launch_reduce_splits(st, ctx->ws_Tcut.as<double>(), cut_doubles, cut_ks, cut_doubles));
+        for (int q = 0; q < n_cut; q++)
+            CRM_HIP(hipMemcpy2DAsync(cut_dst[q], sizeof(double) * P.ldT, cut_probs[q].C, sizeof(double) * cut_probs[q].ldc,
+                                     sizeof(double) * cut_probs[q].N, nb, hipMemcpyDeviceToDevice, st));
+        return CRM_OK;
+    }
+
+    // 3. T(rho) = G' Q0(rho) for all grid points.  With Q0(rho) = H Mix(rho) the n-length work is
+    //    done once, (H'G), followed by eleven small products Mix(rho)'(H'G): 2 n cols + 2 cols sum r
+    //    flops per variant instead of 2 n sum r.
+    int rotations(const Block& B) {
+        const int nb = B.nb;
+        if (P.folded()) CRM_TRY(fold_TH(B));
+        else if (P.kin()) CRM_TRY(unfolded_TH(B));
+        else if (P.fastT) CRM_TRY(plain_TH(B));
         for (int i = 0; i < nrho; i++) {
             GemmProblem p{};
-            if (fastT) {
-                p.X = ctx->ws_TH.as<double>(); p.ldx = ldb;
-                p.Y = kfold ? bg->MixK[i].as<double>() : bg->Mix[i].as<double>(); p.ldy = ldq;
+            if (P.fastT) {
+                p.X = ctx->ws_TH.as<double>(); p.ldx = P.ldb;
+                p.Y = P.folded() ? bg->MixK[i].as<double>() : bg->Mix[i].as<double>(); p.ldy = ldq;
             } else {
-                p.X = Gx; p.ldx = ldb;
-                p.Y = collapsed ? tab->TZ.as<double>() + (size_t)i * mp * ldq : bg->Q0[i].as<double>(); p.ldy = ldq;
+                p.X = B.Gx; p.ldx = P.ldb;
+                p.Y = P.collapsed() ? tab->TZ.as<double>() + (size_t)i * P.mp * ldq : bg->Q0[i].as<double>(); p.ldy = ldq;
             }
-            p.C = ctx->ws_T.as<double>() + (size_t)i * BLK * ldT; p.ldc = ldT;
+            p.C = ctx->ws_T.as<double>() + (size_t)i * P.BLK * P.ldT; p.ldc = P.ldT;
             p.M = nb; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
             probs[i] = p;
         }
-        // The eleven products run as one launch of equally long tiles, i.e. in rounds of as many tiles as the chip holds
-        // workgroups (two per CU): at config 3, 12 832 tiles are 25.06 rounds of 512 and the last 0.06 costs a whole one.
-        // The smallest problems that make up that remainder (there: rho = 1, r = 50, 32 tiles) are taken out and run cut
-        // along the contraction axis instead -- a sixteenth of a round plus a reduction.
-        int n_main = nrho, n_cut = 0;
-        int cut_ks = 1;
-        GemmProblem cut_probs[CRM_MAX_RHO];
-        double* cut_dst[CRM_MAX_RHO];
-        if (fastT) {
-            const long slots = 2L * ctx_cus(ctx), mtl = (nb + GEMM_BM - 1) / GEMM_BM;
-            long tiles[CRM_MAX_RHO], total = 0;
-            int order[CRM_MAX_RHO];
-            for (int i = 0; i < nrho; i++) { tiles[i] = mtl * ((probs[i].N + 127) / 128); total += tiles[i]; order[i] = i; }
-            std::sort(order, order + nrho, [&](int a, int b) { return tiles[a] < tiles[b]; });
-            const long need = total % slots;
-            long acc = 0;
-            int take = 0;
-            while (take < nrho - 1 && acc < need) acc += tiles[order[take++]];
-            if (total > slots && need > 0 && acc >= need && acc <= slots / 4) {
-                bool is_cut[CRM_MAX_RHO] = {false};
-                long cut_doubles = 0;
-                for (int q = 0; q < take; q++) is_cut[order[q]] = true;
-                while ((long)(cut_ks + 1) * acc <= slots && cut_ks < 16 && kdim / GEMM_BK / (cut_ks + 1) >= 8) cut_ks++;
-                n_main = 0;
-                for (int i = 0; i < nrho; i++) {
-                    if (!is_cut[i]) { probs[n_main++] = probs[i]; continue; }
-                    GemmProblem c = probs[i];
-                    cut_dst[n_cut] = c.C;
-                    c.ldc = round_up(c.N, 128);
-                    cut_doubles += (long)BLK * c.ldc;
-                    cut_probs[n_cut++] = c;
-                }
-                CRM_TRY(ctx->ws_Tcut.ensure(sizeof(double) * (size_t)cut_doubles * cut_ks));
-                long at = 0;
-                for (int q = 0; q < n_cut; q++) {
-                    cut_probs[q].C = ctx->ws_Tcut.as<double>() + at;
-                    at += (long)BLK * cut_probs[q].ldc;
-                }
-                CRM_HIP(hipMemcpyAsync(d_probs + 1 + nrho, cut_probs, sizeof(GemmProblem) * n_cut, hipMemcpyHostToDevice, st));
-                int cut_maxn = 1;
-                for (int q = 0; q < n_cut; q++) cut_maxn = std::max(cut_maxn, cut_probs[q].N);
-                CRM_TRY(launch_gemm_tn(ctx, d_probs + 1 + nrho, n_cut, nb, cut_maxn, kdim, false, 0, cut_ks, cut_doubles));
-                CRM_TRY(launch_reduce_splits(st, ctx->ws_Tcut.as<double>(), cut_doubles, cut_ks, cut_doubles));
-                for (int q = 0; q < n_cut; q++)
-                    CRM_HIP(hipMemcpy2DAsync(cut_dst[q], sizeof(double) * ldT, cut_probs[q].C, sizeof(double) * cut_probs[q].ldc,
-                                             sizeof(double) * cut_probs[q].N, nb, hipMemcpyDeviceToDevice, st));
-            }
-        }
-        CRM_HIP(hipMemcpyAsync(d_probs + 1, probs.data(), sizeof(GemmProblem) * n_main, hipMemcpyHostToDevice, st));
+        int n_main = nrho;
+        if (P.fastT) CRM_TRY(cut_rotations(B, n_main));
+        CRM_TRY(upload(SLOT_RHO, probs.data(), n_main));
         // (unrelated-donor form: the kernel timer brackets this launch, the rotations MixK(rho)'(H'Gx) -- the step's largest)
-        const bool timing_T = wb && ctx->timing && ctx->timed_used < 65536;
+        const bool timing_T = P.wb() && ctx->timing && ctx->timed_used < 65536;
+        if (timing_T) CRM_TRY(timer_open(true));
+        CRM_TRY(launch_gemm_tn(ctx, d_probs + SLOT_RHO, n_main, nb, (int)ldq, P.fastT ? P.kdim : P.xrows, false, 0, 1, 0));
         if (timing_T) {
-            if (ctx->timed_used == ctx->timed.size()) {
-                hipEvent_t ea, eb;
-                CRM_HIP(hipEventCreate(&ea));
-                CRM_HIP(hipEventCreate(&eb));
-                ctx->timed.emplace_back(ea, eb);
-            }
-            CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].first, st));
+            CRM_TRY(timer_close());
+            for (int q = 0; q < n_main; q++) ctx->kr_flops += 2.0 * (double)P.kdim * (double)nb * (double)probs[q].N;
         }
-        CRM_TRY(launch_gemm_tn(ctx, d_probs + 1, n_main, nb, (int)ldq, fastT ? kdim : xrows, false, 0, 1, 0));
-        if (timing_T) {
-            CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].second, st));
-            ctx->timed_used++;
-            for (int q = 0; q < n_main; q++) ctx->kr_flops += 2.0 * (double)kdim * (double)nb * (double)probs[q].N;
-        }
-        // 4. null fits + rho* per gene
+        return CRM_OK;
+    }
+
+    // 4. null fits + rho* per gene; the probe hook (ctx->probe_on) keeps the (variant, grid point) records of this block --
+    //    the pass stops after it
+    int null_fits(const Block& B) {
+        const int nb = B.nb, BLK = P.BLK;
         trace_push("crm null fits");
         for (int gi = 0; gi < ng; gi++) {
             crm_gene* g = genes[gi];
@@ -2189,26 +2245,22 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             fa.nrho = nrho; fa.c = c; fa.restricted = 1; fa.n = n; fa.polish = ctx->polish ? 1 : 0; fa.exact = (ctx->nullfit_exact || form("nullfit_exact", 0)) ? 1 : 0;
             for (int i = 0; i < nrho; i++) {
                 NullFitRho& R = fa.rho[i];
-                R.T = ctx->ws_T.as<double>() + (size_t)i * BLK * ldT; R.ldT = ldT;
+                R.T = ctx->ws_T.as<double>() + (size_t)i * BLK * P.ldT; R.ldT = P.ldT;
                 R.ty = g->rot.as<double>() + (long)i * slab;
                 R.tW = R.ty + ldq; R.ldW = ldq;
                 R.S0 = bg->S0[i].as<double>();
                 R.r = bg->r[i];
             }
             fa.WW = g->WW.as<double>(); fa.Wy = g->Wy.as<double>(); fa.yy = g->yy;
-            fa.gg = d_gg; fa.gy = d_gy + (size_t)gi * BLK; fa.gW = d_gW; fa.ld_gW = ld_gW;
-            fa.g_drop = collapsed ? nullptr : d_drop;
-            if (c > CRM_MAX_COV_WIDE) {
-                CRM_TRY(ctx->ws_xwide.ensure(sizeof(double) * nullfit_xwide_scratch_doubles(BLK, nrho, c)));
-                fa.xwide = ctx->ws_xwide.as<double>();
-            }
-            fa.trial = d_trial; fa.out = d_fit + (size_t)gi * BLK;
-            fa.probe = ctx->probe_on ? 1 : 0; fa.probe_x = ctx->probe_x;
+            fa.gg = d_gg; fa.gy = d_gy + (size_t)gi * BLK; fa.gW = d_gW; fa.ld_gW = P.ld_gW;
+            fa.g_drop = P.collapsed() ? nullptr : d_drop;
+            if (c > CRM_MAX_COV_WIDE) fa.xwide = ctx->ws_xwide.as<double>();
+            fa.trial = d_trial; fa.out = d_fit + (size_t)gi * BLK; fa.probe = ctx->probe_on ? 1 : 0; fa.probe_x = ctx->probe_x;
             fa.track = outs[gi].flags ? 1 : 0;
             CRM_TRY(launch_nullfit(st, fa, nb, false, d_queue));
         }
         trace_pop();
-        if (ctx->probe_on) {   // test hook: keep the (variant, grid point) records of this block and stop here
+        if (ctx->probe_on) {
             std::vector<NullFitTrial> h_trial((size_t)nb * nrho);
             CRM_HIP(hipMemcpyAsync(h_trial.data(), d_trial, sizeof(NullFitTrial) * h_trial.size(), hipMemcpyDeviceToHost, st));
             CRM_HIP(hipStreamSynchronize(st));
@@ -2217,39 +2269,60 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
                 ctx->probe_out[2 * q] = h_trial[q].lml;
                 ctx->probe_out[2 * q + 1] = h_trial[q].scale;
             }
-            return CRM_OK;
         }
-        }   // (not replaying)
-        if (wb) {   // Phi'gx of the block: per donor U_d Lambda_d^-1/2 applied to its rows of H'Gx (stored transposed)
-            const int k1 = bg->kin_k1, k2 = bg->kin_k2, k2pad = bg->wb_k2pad;
-            const long groups = bg->kin_groups;
-            std::vector<GemmProblem> kp((size_t)groups);
-            for (long d = 0; d < groups; d++) {
-                GemmProblem p{};
-                p.X = ctx->ws_TH.as<double>() + (size_t)(k1 + d * k2) * ldb; p.ldx = ldb;
-                p.Y = bg->wb_U.as<double>() + (size_t)d * k2pad * 128; p.ldy = 128;
-                p.C = wb_g + d * k2; p.ldc = ldwb;
-                p.M = nb; p.N = k2; p.cells = k2pad;
-                kp[d] = p;
-            }
-            GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
-            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * kp.size(), hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, nb, k2, k2pad, false, 0, 1, 0));
-            CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
-            ctx->unrelated_donor_blocks++;
+        return CRM_OK;
+    }
+
+    // 3.-4. replayed (crm_scan_interaction_permuted): the passes after the first take the rotations at rho* and the fits of
+    // this block from the first one's record -- neither depends on the permutation hooks
+    int replay_block(const Block& B) {
+        if (ng != 1 || ctx->replay_cursor >= ctx->replay_blocks.size()) {
+            set_error("scan: the replayed pass visits a block the recorded one did not");
+            return CRM_ERR_INTERNAL;
         }
-        // 5. the (rho, variant) pairs some gene selected, ordered by rho (host; nb*ng*48 bytes cross PCIe)
+        crm_ctx::ReplayBlock* rb = ctx->replay_blocks[ctx->replay_cursor++];
+        if (rb->col0 != B.col0 || rb->nb != B.nb || rb->collapsed != P.collapsed() || rb->fit.size() != sizeof(NullFitOut) * (size_t)B.nb) {
+            set_error("scan: the replayed pass visits its blocks in another order than the recorded one");
+            return CRM_ERR_INTERNAL;
+        }
+        CRM_HIP(hipMemcpyAsync(d_fit, rb->fit.data(), rb->fit.size(), hipMemcpyHostToDevice, st));
+        // (unrelated-donor form: the assembly reads Phi'gx and E1'gx of the block from H'Gx -- formed again, same bits)
+        if (P.wb()) CRM_TRY(fold_TH(B));
+        hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((P.ldT + 255) / 256), B.nb), dim3(256), 0, st, ctx->ws_T.as<double>(),
+                           (long)P.BLK, P.ldT, d_fit, B.nb, (int)P.ldT, rb->T.as<double>(), 1);
+        CRM_HIP(hipGetLastError());
+        return CRM_OK;
+    }
+
+    // Phi'gx of the block: per donor U_d Lambda_d^-1/2 applied to its rows of H'Gx (stored transposed)
+    int woodbury_phi(const Block& B) {
+        const long groups = bg->kin_groups;
+        std::vector<GemmProblem> kp((size_t)groups);
+        GemmProblem p{};
+        p.X = ctx->ws_TH.as<double>() + (size_t)bg->kin_k1 * P.ldb; p.ldx = P.ldb; p.C = wb_g; p.ldc = P.ldwb; p.M = B.nb;
+        woodbury_records(bg, p, (long)bg->kin_k2 * P.ldb, kp.data());
+        CRM_TRY(with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) {
+            return launch_gemm_tn(ctx, d_kp, (int)groups, B.nb, bg->kin_k2, bg->wb_k2pad, false, 0, 1, 0);
+        }));
+        ctx->unrelated_donor_blocks++;
+        return CRM_OK;
+    }
+
+    // 5. the fits of the block on the host (nb*ng*48 bytes cross PCIe): the collapsed path's near flags, the permutation
+    //    replay's record, the flat-optimum margins
+    int collect_fits(Block& B) {
+        const int nb = B.nb, BLK = P.BLK;
         CRM_HIP(hipMemcpyAsync(h_fit.data(), d_fit, sizeof(NullFitOut) * (size_t)BLK * ng, hipMemcpyDeviceToHost, st));
-        if (collapsed && near_out) CRM_HIP(hipMemcpyAsync(h_near.data(), d_near, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+        if (P.collapsed() && near_out) CRM_HIP(hipMemcpyAsync(h_near.data(), d_near, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
         CRM_HIP(hipStreamSynchronize(st));
-        if (collapsed && near_out)
+        if (P.collapsed() && near_out)
             for (int b = 0; b < nb; b++)
-                if (h_near[b]) near_out->push_back(done + b);
+                if (h_near[b]) near_out->push_back(B.done + b);
         for (int gi = 0; gi < ng; gi++)
             for (int b = 0; b < nb; b++) {
                 const int ri = h_fit[(size_t)gi * BLK + b].rho_index;
                 if (ri < 0 || ri >= nrho) {   // (indexes host arrays below: never trust it unchecked)
-                    set_error("scan: the null fit of variant %ld (phenotype %d) did not run (grid index %d)", col0 + b, gi, ri);
+                    set_error("scan: the null fit of variant %ld (phenotype %d) did not run (grid index %d)", B.col0 + b, gi, ri);
                     return CRM_ERR_NUMERIC;
                 }
             }
@@ -2260,12 +2333,12 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             }
             crm_ctx::ReplayBlock* rb = new crm_ctx::ReplayBlock();
             ctx->replay_blocks.push_back(rb);
-            rb->col0 = col0; rb->nb = nb; rb->collapsed = collapsed;
+            rb->col0 = B.col0; rb->nb = nb; rb->collapsed = P.collapsed();
             rb->fit.resize(sizeof(NullFitOut) * (size_t)nb);
             memcpy(rb->fit.data(), h_fit.data(), rb->fit.size());
-            CRM_TRY(rb->T.ensure(sizeof(double) * (size_t)nb * ldT));
-            hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((ldT + 255) / 256), nb), dim3(256), 0, st, ctx->ws_T.as<double>(),
-                               (long)BLK, ldT, d_fit, nb, (int)ldT, rb->T.as<double>(), 0);
+            CRM_TRY(rb->T.ensure(sizeof(double) * (size_t)nb * P.ldT));
+            hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((P.ldT + 255) / 256), nb), dim3(256), 0, st, ctx->ws_T.as<double>(),
+                               (long)BLK, P.ldT, d_fit, nb, (int)P.ldT, rb->T.as<double>(), 0);
             CRM_HIP(hipGetLastError());
         }
         // Flat-optimum flag, first half (info calls only; include/crm_hip.h: CRM_MODEL_FLAT_OPTIMUM): how far the search of the
@@ -2274,77 +2347,74 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
         // (nullfit.hip: cur_noise; select_rho_kernel: decision).  NaN: a fit whose kernel did not measure it.
         for (int gi = 0; gi < ng; gi++) {
             if (!outs[gi].flags) continue;
-            if (flat_obj.empty()) flat_obj.assign((size_t)BLK * ng, -1.0);
+            if (B.flat_obj.empty()) B.flat_obj.assign((size_t)BLK * ng, -1.0);
             for (int b = 0; b < nb; b++) {
                 const double dec = h_fit[(size_t)gi * BLK + b].decision;
-                flat_obj[(size_t)gi * BLK + b] = dec == dec ? dec : -1.0;
+                B.flat_obj[(size_t)gi * BLK + b] = dec == dec ? dec : -1.0;
             }
         }
-        // ---- the pair stage, over sub-ranges [sb0, sb0 + nsb) of the block (one sub-range unless several phenotypes ask for
-        //      more (variant, rho*) pairs than the pair-ordered buffers hold).  Inside, the block-order names below stand for
-        //      the sub-range: the same code serves a whole block and a part of it.
-        const int nb_blk = nb;
-        auto& h_fit_blk = h_fit;
-        double* const Gt_blk = Gt; double* const Gx_blk = Gx; double* const Gb_blk = Gb;
-        double* const d_gg_blk = d_gg; double* const d_gy_blk = d_gy; double* const d_gW_blk = d_gW;
-        double* const d_coef_blk = d_coef; NullFitOut* const d_fit_blk = d_fit;
-        for (int sb0 = 0; sb0 < nb_blk;) {
-        int nsb = nb_blk - sb0;
+        return CRM_OK;
+    }
+
+    // The pair stage runs over sub-ranges of the block: one unless several phenotypes ask for more (variant, rho*) pairs
+    // than the pair-ordered buffers hold
+    SubRange sub_range(const Block& B, int b0) const {
+        SubRange R;
+        R.b0 = b0;
+        R.nb = B.nb - b0;
+        R.done = B.done + b0;
         if (ng > 1) {
             long pairs = 0;
             int take = 0;
-            for (; sb0 + take < nb_blk; take++) {
+            for (; b0 + take < B.nb; take++) {
                 unsigned seen = 0;
                 for (int gi = 0; gi < ng; gi++) {
-                    const NullFitOut& f = h_fit_blk[(size_t)gi * BLK + sb0 + take];
+                    const NullFitOut& f = h_fit[(size_t)gi * P.BLK + b0 + take];
                     if (!no_kinship_term(f)) seen |= 1u << f.rho_index;
                 }
                 const int here = __builtin_popcount(seen);
-                if (take > 0 && pairs + here > pair_cap) break;
+                if (take > 0 && pairs + here > P.pair_cap) break;
                 pairs += here;
             }
-            nsb = take;
+            R.nb = take;
         }
-        const int nb = nsb;
-        const long done = done_blk + sb0;
-        struct FitView { const NullFitOut* p; const NullFitOut& operator[](size_t i) const { return p[i]; } } h_fit{h_fit_blk.data() + sb0};
-        double* const Gt = Gt_blk + sb0; double* const Gx = Gx_blk + sb0; double* const Gb = Gb_blk + sb0;
-        double* const d_gg = d_gg_blk + sb0; double* const d_gy = d_gy_blk + sb0;
-        double* const d_gW = d_gW_blk + (size_t)sb0 * ld_gW; double* const d_coef = d_coef_blk + sb0;
-        NullFitOut* const d_fit = d_fit_blk + sb0;
-        const int blk_cols = (int)(ldb - sb0);      // columns of the block buffers from the sub-range's first one on
+        return R;
+    }
+
+    // 5. the (rho, variant) pairs some gene selected, ordered by rho; the sub-range's columns of the block in that order (Gs)
+    int select_pairs(const Block& B, const SubRange& R, Pairs& Q) {
+        const int nb = R.nb, BLK = P.BLK;
+        const NullFitOut* fit = h_fit.data() + R.b0;
         std::fill(pair_of.begin(), pair_of.end(), -1);
         long with_pair = 0;
         for (int gi = 0; gi < ng; gi++)
             for (int b = 0; b < nb; b++) {
-                const NullFitOut& f = h_fit[(size_t)gi * BLK + b];
+                const NullFitOut& f = fit[(size_t)gi * BLK + b];
                 if (no_kinship_term(f)) continue;
                 pair_of[(size_t)f.rho_index * BLK + b] = 0;
                 with_pair++;
             }
         ctx->tests_without_pair += (long)ng * nb - with_pair;
         // (a sub-range without any pair keeps its first test's: the launches below always have something to do)
-        if (with_pair == 0) pair_of[(size_t)h_fit[0].rho_index * BLK] = 0;
-        int cnt[CRM_MAX_RHO] = {0}, start[CRM_MAX_RHO + 1] = {0};
-        int npairs = 0;
+        if (with_pair == 0) pair_of[(size_t)fit[0].rho_index * BLK] = 0;
         for (int i = 0; i < nrho; i++) {
-            start[i] = npairs;
+            Q.start[i] = Q.npairs;
             for (int b = 0; b < nb; b++) {
                 if (pair_of[(size_t)i * BLK + b] == 0) {
-                    pair_of[(size_t)i * BLK + b] = npairs;
-                    h_ord[npairs++] = b;
+                    pair_of[(size_t)i * BLK + b] = Q.npairs;
+                    h_ord[Q.npairs++] = b;
                 }
             }
-            cnt[i] = npairs - start[i];
+            Q.cnt[i] = Q.npairs - Q.start[i];
         }
-        start[nrho] = npairs;
+        Q.start[nrho] = Q.npairs;
         for (int gi = 0; gi < ng; gi++)
             for (int b = 0; b < nb; b++) {
-                const NullFitOut& f = h_fit[(size_t)gi * BLK + b];
+                const NullFitOut& f = fit[(size_t)gi * BLK + b];
                 h_pos[(size_t)gi * BLK + b] = no_kinship_term(f) ? -1 : pair_of[(size_t)f.rho_index * BLK + b];
             }
         CRM_HIP(hipMemcpyAsync(d_pos, h_pos.data(), sizeof(int) * (size_t)BLK * ng, hipMemcpyHostToDevice, st));
-        if (wb && ng > 1) {   // (S in block order: a variant's rows of the rotated S sit at its own position)
+        if (P.wb() && ng > 1) {   // (S in block order: a variant's rows of the rotated S sit at its own position)
             std::vector<int> h_posw((size_t)BLK * ng, -1);
             for (int gi = 0; gi < ng; gi++)
                 for (int b = 0; b < nb; b++)
@@ -2352,602 +2422,656 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             CRM_HIP(hipMemcpyAsync(d_posw, h_posw.data(), sizeof(int) * h_posw.size(), hipMemcpyHostToDevice, st));
             CRM_HIP(hipStreamSynchronize(st));   // (h_posw lives on this scope)
         }
-        CRM_HIP(hipMemcpyAsync(d_ord, h_ord.data(), sizeof(int) * npairs, hipMemcpyHostToDevice, st));
-        double* Gs = ctx->ws_Gs.as<double>();
-        CRM_TRY(launch_gather_block(st, Gt, ldb, xrows, xrows, nullptr, d_ord, npairs, Gs, ldp, (int)ldp));
-        // 6. A~ = KR(Gs, Ep)' Q0(rho), one problem per non-empty rho group of pairs.
-        //    Several genes can select several rho* for one variant; with Q0(rho) = H Mix(rho) the
-        //    n-length Khatri-Rao contraction is then done once per variant against H (stored transposed)
-        //    and every (variant, rho) pair costs a cols-length product with Mix(rho) instead.
-        bool via_H = kin_route;
-        if (fastT && ng > 1 && !kin_route) {
-            double direct = 0.0, via = (double)nb * (double)bg->cols * (double)n;
-            for (int i = 0; i < nrho; i++) {
-                direct += (double)cnt[i] * bg->r[i] * (double)n;
-                via += (double)cnt[i] * bg->r[i] * (double)bg->ldh;
-            }
-            via_H = ctx->tune.shared_h < 0 ? via < 0.9 * direct : ctx->tune.shared_h > 0;
-        }
-        int nz = 0, max_m = 0, max_n = 1;
-        double kr_flops = 0.0;
-        if (!collapsed && !via_H)
-            for (int i = 0; i < nrho; i++)
-                if (cnt[i] > 0) CRM_TRY(crm_background_require_q0(bg, i));
-        // few-round launches of the direct Khatri-Rao route: slices along the cell axis (see kr_split_for)
-        int kr_split = 1;
-        const size_t a_slab = (size_t)max_pairs * k0 * ldA;
-        if (!collapsed && !via_H) {
-            long row_tiles = 0;
-            int nzz = 0, mn = 1;
-            for (int i = 0; i < nrho; i++)
-                if (cnt[i] > 0) { row_tiles += ((long)cnt[i] * k0 + GEMM_BM - 1) / GEMM_BM; nzz++; mn = std::max(mn, bg->r[i]); }
-            const int cap = (int)std::min<size_t>(8, ((size_t)16 << 30) / std::max<size_t>(sizeof(double) * a_slab, 1));
-            kr_split = kr_split_for(ctx, row_tiles, mn, 1, np, std::max(cap, 1));
-            (void)nzz;
-            if (kr_split > 1) CRM_TRY(ctx->ws_A.ensure(sizeof(double) * a_slab * kr_split));
-        }
-        // A spectrum a little longer than a multiple of the 128-column tile (config 3: r = 5000 = 39 tiles + 8 columns)
-        // would pay a whole last column of tiles -- 1 / 40 of the launch -- for those few columns: the last 128 + rem
-        // columns (rem <= 32) go into a second launch of 160-column tiles instead, cut along the cell axis to fill its
-        // rounds (38 x 128 + 160 = 5024 columns computed instead of 5120).
-        std::vector<GemmProblem> tails, spectrum_tails;
-        int tail_split = 1, tail_maxn = 0;
-        bool tail_of[CRM_MAX_RHO] = {false};
-        if (!collapsed && !via_H && kr_split == 1 && ctx->tune.glds && ctx->tune.bn != 64 && ctx->tune.bn != 160 &&
-            !form("kr_no_tail", 0)) {
-            long tail_row_tiles = 0, main_tiles = 0;
-            for (int i = 0; i < nrho; i++) {
-                if (cnt[i] == 0) continue;
-                const int N = bg->r[i], rem = N % 128;
-                const long rt = ((long)cnt[i] * k0 + GEMM_BM - 1) / GEMM_BM;
-                main_tiles += rt * ((N + 127) / 128);
-                if (N >= 1024 && rem > 0 && rem <= 32) {
-                    tail_of[i] = true;
-                    tail_row_tiles += rt;
-                    tail_maxn = std::max(tail_maxn, 128 + rem);
-                }
-            }
-            if (tail_row_tiles == 0 || main_tiles <= 1024) {
-                std::fill(tail_of, tail_of + CRM_MAX_RHO, false);
-            } else {
-                const int saved_bn = ctx->tune.bn;
-                ctx->tune.bn = 160;
-                const int cap = (int)std::min<size_t>(8, ((size_t)16 << 30) / std::max<size_t>(sizeof(double) * a_slab, 1));
-                tail_split = kr_split_for(ctx, tail_row_tiles, tail_maxn, 1, np, std::max(cap, 1));
-                ctx->tune.bn = saved_bn;
-                // (before the problem records take addresses inside ws_A: growing the buffer does not keep its contents)
-                if (tail_split > 1) CRM_TRY(ctx->ws_A.ensure(sizeof(double) * a_slab * tail_split));
-            }
-        }
+        CRM_HIP(hipMemcpyAsync(d_ord, h_ord.data(), sizeof(int) * Q.npairs, hipMemcpyHostToDevice, st));
+        return launch_gather_block(st, B.Gt + R.b0, P.ldb, P.xrows, P.xrows, nullptr, d_ord, Q.npairs, ctx->ws_Gs.as<double>(),
+                                   P.ldp, (int)P.ldp);
+    }
+
+    // Splits of the direct route's A~ launch along the cell axis (few rounds: see kr_split_for), and its spectrum tails.
+    // A spectrum a little longer than a multiple of the 128-column tile (config 3: r = 5000 = 39 tiles + 8 columns)
+    // would pay a whole last column of tiles -- 1 / 40 of the launch -- for those few columns: the last 128 + rem
+    // columns (rem <= 32) go into a second launch of 160-column tiles instead, cut along the cell axis to fill its
+    // rounds (38 x 128 + 160 = 5024 columns computed instead of 5120).
+    int direct_splits(const Pairs& Q, AGroups& A, bool* tail_of) {
+        A.a_slab = (size_t)P.pair_cap * k0 * P.ldA;
+        long row_tiles = 0;
+        int mn = 1;
+        for (int i = 0; i < nrho; i++)
+            if (Q.cnt[i] > 0) { row_tiles += ((long)Q.cnt[i] * k0 + GEMM_BM - 1) / GEMM_BM; mn = std::max(mn, bg->r[i]); }
+        const int cap = (int)std::min<size_t>(8, ((size_t)16 << 30) / std::max<size_t>(sizeof(double) * A.a_slab, 1));
+        A.kr_split = kr_split_for(ctx, row_tiles, mn, 1, np, std::max(cap, 1));
+        if (A.kr_split > 1) CRM_TRY(ctx->ws_A.ensure(sizeof(double) * A.a_slab * A.kr_split));
+        if (A.kr_split > 1 || !ctx->tune.glds || ctx->tune.bn == 64 || ctx->tune.bn == 160 || form("kr_no_tail", 0)) return CRM_OK;
+        long tail_row_tiles = 0, main_tiles = 0;
         for (int i = 0; i < nrho; i++) {
-            if (cnt[i] == 0 || wb) continue;   // (unrelated-donor form: no A~ at all)
+            if (Q.cnt[i] == 0) continue;
+            const int N = bg->r[i], rem = N % 128;
+            const long rt = ((long)Q.cnt[i] * k0 + GEMM_BM - 1) / GEMM_BM;
+            main_tiles += rt * ((N + 127) / 128);
+            if (N >= 1024 && rem > 0 && rem <= 32) {
+                tail_of[i] = true;
+                tail_row_tiles += rt;
+                A.tail_maxn = std::max(A.tail_maxn, 128 + rem);
+            }
+        }
+        if (tail_row_tiles == 0 || main_tiles <= 1024) {
+            std::fill(tail_of, tail_of + CRM_MAX_RHO, false);
+        } else {
+            const int saved_bn = ctx->tune.bn;
+            ctx->tune.bn = 160;
+            A.tail_split = kr_split_for(ctx, tail_row_tiles, A.tail_maxn, 1, np, std::max(cap, 1));
+            ctx->tune.bn = saved_bn;
+            // (before the problem records take addresses inside ws_A: growing the buffer does not keep its contents)
+            if (A.tail_split > 1) CRM_TRY(ctx->ws_A.ensure(sizeof(double) * A.a_slab * A.tail_split));
+        }
+        return CRM_OK;
+    }
+
+    // the problems of step 6, one per non-empty rho group of pairs, into probs[0, nz) (none on the unrelated-donor route)
+    void a_records(const Pairs& Q, bool via_H, const bool* tail_of, AGroups& A) {
+        const double kin_rows = P.folded() ? bg->kin_k1 + bg->kin_groups * (long)bg->kin_k2 : bg->cols;   // (rows of the Mix products)
+        for (int i = 0; i < nrho; i++) {
+            if (Q.cnt[i] == 0 || P.wb()) continue;   // (unrelated-donor form: no A~ at all)
             GemmProblem p{};
-            p.X = Gs + start[i]; p.ldx = ldp;
-            p.C = ctx->ws_A.as<double>() + (size_t)start[i] * k0 * ldA;
-            if (collapsed) {
+            p.X = ctx->ws_Gs.as<double>() + Q.start[i]; p.ldx = P.ldp;
+            p.C = ctx->ws_A.as<double>() + (size_t)Q.start[i] * k0 * P.ldA;
+            if (P.collapsed()) {
                 // A~(b) = sum_d gamma_d,b * Bd(rho)[d]: rows of Bd are (k0 x ldq) slabs per donor
-                p.Y = tab->Bd.as<double>() + (size_t)i * mp * k0 * ldq; p.ldy = (long)k0 * ldq;
-                p.ldc = (long)k0 * ldA;
-                p.M = cnt[i]; p.N = (int)((long)k0 * ldq);
-            } else if (via_H && kin_route && ng == 1) {   // (AH / S is in pair order already, see below)
-                p.X = (kfold ? ctx->ws_S.as<double>() : ctx->ws_AH.as<double>()) + (size_t)start[i] * k0; p.ldx = ld_ah;
-                p.Y = kfold ? bg->MixK[i].as<double>() : bg->Mix[i].as<double>(); p.ldy = ldq;
-                p.ldc = ldA;
-                p.M = cnt[i] * k0; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-                kr_flops += 2.0 * (double)(kfold ? bg->kin_k1 + bg->kin_groups * (long)bg->kin_k2 : bg->cols) * (double)bg->r[i] *
-                            (double)k0 * (double)cnt[i];
+                p.Y = tab->Bd.as<double>() + (size_t)i * P.mp * k0 * ldq; p.ldy = (long)k0 * ldq; p.ldc = (long)k0 * P.ldA;
+                p.M = Q.cnt[i]; p.N = (int)((long)k0 * ldq);
             } else if (via_H) {
-                p.X = ctx->ws_XG.as<double>() + (size_t)start[i] * k0; p.ldx = ld_xg;
-                p.Y = kfold ? bg->MixK[i].as<double>() : bg->Mix[i].as<double>(); p.ldy = ldq;
-                p.ldc = ldA;
-                p.M = cnt[i] * k0; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-                kr_flops += 2.0 * (double)(kfold ? bg->kin_k1 + bg->kin_groups * (long)bg->kin_k2 : bg->cols) * (double)bg->r[i] *
-                            (double)k0 * (double)cnt[i];
+                if (P.kin() && ng == 1) {   // (AH / S is in pair order already, see folded_S / unfolded_AH)
+                    p.X = (P.folded() ? ctx->ws_S.as<double>() : ctx->ws_AH.as<double>()) + (size_t)Q.start[i] * k0; p.ldx = P.ld_ah;
+                } else {
+                    p.X = ctx->ws_XG.as<double>() + (size_t)Q.start[i] * k0; p.ldx = P.ld_xg;
+                }
+                p.Y = P.folded() ? bg->MixK[i].as<double>() : bg->Mix[i].as<double>(); p.ldy = ldq; p.ldc = P.ldA;
+                p.M = Q.cnt[i] * k0; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
+                A.kr_flops += 2.0 * kin_rows * (double)bg->r[i] * (double)k0 * (double)Q.cnt[i];
             } else {
-                p.E = d_Ep; p.lde = g0->ld_ep; p.k0 = k0;
-                p.Y = bg->Q0[i].as<double>(); p.ldy = ldq;
-                p.ldc = ldA;
-                p.M = cnt[i] * k0; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-                kr_flops += 2.0 * (double)n * (double)bg->r[i] * (double)k0 * (double)cnt[i];
+                p.E = d_Ep; p.lde = g0->ld_ep; p.k0 = k0; p.Y = bg->Q0[i].as<double>(); p.ldy = ldq; p.ldc = P.ldA;
+                p.M = Q.cnt[i] * k0; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
+                A.kr_flops += 2.0 * (double)n * (double)bg->r[i] * (double)k0 * (double)Q.cnt[i];
                 if (tail_of[i]) {
                     GemmProblem t = p;
                     const int rem = 128 + p.N % 128;
                     p.N -= rem;
                     t.Y = p.Y + p.N; t.C = p.C + p.N; t.N = rem;
-                    tails.push_back(t);
+                    A.tails.push_back(t);
                 }
             }
             // The mixing-matrix products of the kinship-structure route: a spectrum a little longer than a multiple of the
             // 128-column tile (config 3: r = 5000 = 39 tiles + 8 columns) would pay a whole last column of tiles -- 1 / 40 of
             // the launch -- for those few columns; they go through one pass over the operand instead (launch_skinny_tn).
-            if (via_H && kin_route && !collapsed && p.N >= 1024 && p.N % 128 > 0 && p.N % 128 <= 16 && p.ldx % 2 == 0 &&
+            if (P.kin() && p.N >= 1024 && p.N % 128 > 0 && p.N % 128 <= 16 && p.ldx % 2 == 0 &&
                 (reinterpret_cast<uintptr_t>(p.X) & 15) == 0 && !form("kr_no_tail", 0)) {
                 GemmProblem t = p;
                 const int rem = p.N % 128;
-                kr_flops -= 2.0 * (double)(kfold ? bg->kin_k1 + bg->kin_groups * (long)bg->kin_k2 : bg->cols) * (double)rem *
-                            (double)k0 * (double)cnt[i];      // (the timed launch is the tiled one alone)
+                A.kr_flops -= 2.0 * kin_rows * (double)rem * (double)k0 * (double)Q.cnt[i];   // (the timed launch is the tiled one alone)
                 p.N -= rem;
                 t.Y = p.Y + p.N; t.C = p.C + p.N; t.N = rem;
-                spectrum_tails.push_back(t);
+                A.spectrum_tails.push_back(t);
             }
-            max_m = std::max(max_m, p.M);
-            max_n = std::max(max_n, p.N);
-            probs[nz++] = p;
+            A.max_m = std::max(A.max_m, p.M);
+            A.max_n = std::max(A.max_n, p.N);
+            probs[A.nz++] = p;
         }
-        const bool timing = !wb && ctx->timing && ctx->timed_used < 65536;  // bounded: a forgotten timer cannot grow for ever
-        if (timing) {
-            if (ctx->timed_used == ctx->timed.size()) {
-                hipEvent_t a, b;
-                CRM_HIP(hipEventCreate(&a));
-                CRM_HIP(hipEventCreate(&b));
-                ctx->timed.emplace_back(a, b);
-            }
-            // (kinship-structure route: the pair brackets the dominant launch alone, the Mix(rho*)' product further down)
-            if (!kin_route) CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].first, st));
+    }
+
+    // The kinship routes' operand columns in donor order (Gk): one phenotype takes them in the rho*-sorted pair order (Gs)
+    // straight away, so that the result is the operand of the Mix products as it stands; several phenotypes share a
+    // variant between pairs: block order, then the pair gather
+    struct DonorCols { bool in_pair_order; const double* G; long ldg; int ncol; };
+    int donor_columns(const Block& B, const SubRange& R, const Pairs& Q, DonorCols& D) {
+        D.in_pair_order = ng == 1;
+        D.G = D.in_pair_order ? ctx->ws_Gs.as<double>() : B.Gt + R.b0;
+        D.ldg = D.in_pair_order ? P.ldp : P.ldb;
+        D.ncol = D.in_pair_order ? Q.npairs : R.nb;
+        const int blk_cols = (int)(P.ldb - R.b0);   // (columns of the block buffers from the sub-range's first one on)
+        return launch_gather_rows(st, D.G, D.ldg, bg->kin_map.as<int>(), bg->kin_rows, D.in_pair_order ? (int)D.ldg : blk_cols,
+                                  ctx->ws_Gk.as<double>(), D.ldg);
+    }
+    int gather_pairs(const double* src, long rows, const Pairs& Q) {   // (several phenotypes: the operand in pair order, XG)
+        const int xg_cols = (int)std::min<long>(P.ld_xg, round_up((long)Q.npairs * k0, 128) + 128);
+        return launch_gather_slabs(st, src, P.ld_ah, rows, d_ord, Q.npairs, k0, ctx->ws_XG.as<double>(), P.ld_xg, xg_cols);
+    }
+
+    // Folded form (objects.h: kin_fold): S = [E1 rows ; (donor, us_j) rows] of "H'(g o E0) before the contraction over
+    // the donors", which MixK carries.  (a) the block in donor order; (b) per donor d' the Khatri-Rao contraction over
+    // its own cells against us (transposed store into rows k1 + d' k2 + j); (c) the E1 rows by one Khatri-Rao
+    // contraction over ALL cells against the E1 columns of the half factor, cut into slices along the cell axis so
+    // that its few output tiles fill the chip, summed, and copied into rows [0, k1).
+    int folded_S(const Block& B, const SubRange& R, const Pairs& Q) {
+        DonorCols D;
+        CRM_TRY(donor_columns(B, R, Q, D));
+        double* S = ctx->ws_S.as<double>();
+        double* Gk = ctx->ws_Gk.as<double>();
+        const int k1 = bg->kin_k1, k2 = bg->kin_k2, ncol = D.ncol, npair = P.npair;
+        const long groups = bg->kin_groups, ld_ah = P.ld_ah;
+        std::vector<GemmProblem> kp((size_t)groups + P.fold_split6);
+        GemmProblem p{};
+        p.X = Gk; p.ldx = D.ldg;
+        if (P.donor_pairs) {   // per donor G_d' (E (x) E)_d, then the rows of S and the E1 rows from it
+            p.Y = g0->kinEE.as<double>(); p.ldy = g0->ld_ee; p.C = ctx->ws_Pd.as<double>(); p.ldc = P.ldPd;
+            p.M = ncol; p.N = npair;
+        } else if (k2 == 1) {  // plain product G_d'' (us o E0)_d': C[b, i] = row k1 + d' of S at column b k0 + i
+            p.Y = g0->kinUE.as<double>(); p.ldy = g0->ld_ep; p.C = S + (size_t)k1 * ld_ah; p.ldc = k0; p.M = ncol; p.N = k0;
+        } else {
+            p.E = g0->kinEp.as<double>(); p.lde = g0->ld_ep; p.k0 = k0; p.Y = bg->kin_Y.as<double>(); p.ldy = bg->kin_ldy;
+            p.C = S + (size_t)k1 * ld_ah; p.ldc = ld_ah; p.M = ncol * k0; p.N = k2;
         }
-        if (via_H && kfold) {
-            // Folded form (objects.h: kin_fold): S = [E1 rows ; (donor, us_j) rows] of "H'(g o E0) before the contraction over
-            // the donors", which MixK carries.  (a) the block in donor order; (b) per donor d' the Khatri-Rao contraction over
-            // its own cells against us (transposed store into rows k1 + d' k2 + j); (c) the E1 rows by one Khatri-Rao
-            // contraction over ALL cells against the E1 columns of the half factor, cut into slices along the cell axis so
-            // that its few output tiles fill the chip, summed, and copied into rows [0, k1).
-            double* Gk = ctx->ws_Gk.as<double>();
-            double* S = ctx->ws_S.as<double>();
-            const int k1 = bg->kin_k1, k2 = bg->kin_k2;
-            const long groups = bg->kin_groups;
-            const bool in_pair_order = ng == 1;
-            const double* Gsrc = in_pair_order ? Gs : Gt;
-            const long ldg_k = in_pair_order ? ldp : ldb;
-            const int ncol = in_pair_order ? npairs : nb;
-            CRM_TRY(launch_gather_rows(st, Gsrc, ldg_k, bg->kin_map.as<int>(), bg->kin_rows, in_pair_order ? (int)ldg_k : blk_cols, Gk, ldg_k));
-            std::vector<GemmProblem> kp((size_t)groups + fold_split6);
-            long maxlen = GEMM_BK;
-            for (long d = 0; d < groups; d++) {
-                GemmProblem p{};
-                p.X = Gk + bg->kin_row0[d] * ldg_k; p.ldx = ldg_k;
-                p.E = g0->kinEp.as<double>() + bg->kin_row0[d] * g0->ld_ep; p.lde = g0->ld_ep; p.k0 = k0;
-                p.Y = bg->kin_Y.as<double>() + bg->kin_row0[d] * bg->kin_ldy; p.ldy = bg->kin_ldy;
-                p.C = S + (size_t)(k1 + d * k2) * ld_ah; p.ldc = ld_ah;
-                p.M = ncol * k0; p.N = k2; p.cells = bg->kin_len[d];
-                if (k2 == 1) {   // plain product G_d'' (us o E0)_d': C[b, i] = row k1 + d' of S at column b k0 + i
-                    p.E = nullptr; p.lde = 0; p.k0 = 0;
-                    p.Y = g0->kinUE.as<double>() + bg->kin_row0[d] * g0->ld_ep; p.ldy = g0->ld_ep;
-                    p.ldc = k0; p.M = ncol; p.N = k0;
-                }
-                maxlen = std::max(maxlen, bg->kin_len[d]);
-                kp[d] = p;
-            }
-            // slices of whole stages along the cell axis, the last one shorter
-            const long stages_all = np / GEMM_BK, per = (stages_all + fold_split6 - 1) / fold_split6;
-            const long e1_slab = (long)k1 * ld_ah;
-            int slices = 0;
-            long chunk_max = GEMM_BK;
-            if (e1_pairs) {
-                GemmProblem p{};
-                p.X = Gsrc; p.ldx = ldg_k; p.Y = g0->kinP.as<double>(); p.ldy = ldP;
-                p.C = ctx->ws_AH.as<double>(); p.ldc = ldP; p.M = ncol; p.N = k1 * k0;
-                if (e1_sym) { p.Y = d_EE; p.ldy = g0->ld_ee; p.N = npair; }
-                kp[groups] = p;
-            }
-            for (int sps = 0; sps < fold_split6 && !e1_pairs; sps++) {
-                const long s0 = sps * per, s1 = std::min(stages_all, s0 + per);
-                if (s1 <= s0) break;
-                GemmProblem p{};
-                p.X = Gsrc + s0 * GEMM_BK * ldg_k; p.ldx = ldg_k;
-                p.E = d_Ep + s0 * GEMM_BK * g0->ld_ep; p.lde = g0->ld_ep; p.k0 = k0;
-                p.Y = bg->H.as<double>() + s0 * GEMM_BK * bg->ldh; p.ldy = bg->ldh;
-                p.C = ctx->ws_AH.as<double>() + (size_t)sps * e1_slab; p.ldc = ld_ah;
-                p.M = ncol * k0; p.N = k1; p.cells = (s1 - s0) * GEMM_BK;
-                chunk_max = std::max(chunk_max, p.cells);
-                kp[groups + slices++] = p;
-            }
-            GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
-            if (donor_pairs) {     // per donor G_d' (E (x) E)_d, then the rows of S and the E1 rows from it
-                for (long d = 0; d < groups; d++) {
-                    GemmProblem& p = kp[d];
-                    p.E = nullptr; p.lde = 0; p.k0 = 0;
-                    p.Y = g0->kinEE.as<double>() + bg->kin_row0[d] * g0->ld_ee; p.ldy = g0->ld_ee;
-                    p.C = ctx->ws_Pd.as<double>() + (size_t)d * pd_slab; p.ldc = ldPd;
-                    p.M = ncol; p.N = npair;
-                }
-            }
-            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * (size_t)(groups + std::max(slices, 1)), hipMemcpyHostToDevice, st));
-            if (donor_pairs) {
+        const long maxlen = donor_run_records(bg, p, P.donor_pairs ? P.pd_slab : (long)k2 * ld_ah, kp.data());
+        // slices of whole stages along the cell axis, the last one shorter
+        const long stages_all = np / GEMM_BK, per = (stages_all + P.fold_split6 - 1) / P.fold_split6;
+        const long e1_slab = (long)k1 * ld_ah;
+        int slices = 0;
+        long chunk_max = GEMM_BK;
+        if (P.e1_pairs) {
+            GemmProblem& e = kp[groups];
+            e.X = D.G; e.ldx = D.ldg; e.Y = g0->kinP.as<double>(); e.ldy = P.ldP;
+            e.C = ctx->ws_AH.as<double>(); e.ldc = P.ldP; e.M = ncol; e.N = k1 * k0;
+            if (P.e1_sym) { e.Y = d_EE; e.ldy = g0->ld_ee; e.N = npair; }
+        }
+        for (int sps = 0; sps < P.fold_split6 && !P.e1_pairs; sps++) {
+            const long s0 = sps * per, s1 = std::min(stages_all, s0 + per);
+            if (s1 <= s0) break;
+            GemmProblem& e = kp[groups + slices++];
+            e.X = D.G + s0 * GEMM_BK * D.ldg; e.ldx = D.ldg;
+            e.E = d_Ep + s0 * GEMM_BK * g0->ld_ep; e.lde = g0->ld_ep; e.k0 = k0;
+            e.Y = bg->H.as<double>() + s0 * GEMM_BK * bg->ldh; e.ldy = bg->ldh;
+            e.C = ctx->ws_AH.as<double>() + (size_t)sps * e1_slab; e.ldc = ld_ah;
+            e.M = ncol * k0; e.N = k1; e.cells = (s1 - s0) * GEMM_BK;
+            chunk_max = std::max(chunk_max, e.cells);
+        }
+        kp.resize((size_t)groups + std::max(slices, 1));
+        return with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) -> int {
+            double* AH = ctx->ws_AH.as<double>();
+            if (P.donor_pairs) {
                 CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, npair, maxlen, false, 0, 1, 0));
-                if (wb_rotate)   // (the rotated S straight from the pair products: the rows of S are not formed)
-                    CRM_TRY(launch_donor_pairs_rotate(st, ctx->ws_Pd.as<double>(), pd_slab, ldPd, (int)groups, ncol, k0,
+                if (P.wb_rotate)   // (the rotated S straight from the pair products: the rows of S are not formed)
+                    CRM_TRY(launch_donor_pairs_rotate(st, ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, (int)groups, ncol, k0,
                                                       bg->wb_U.as<double>(), (long)bg->wb_k2pad * 128, 128, bg->wb_k2pad,
-                                                      ctx->ws_A.as<double>(), ldAw, ctx->ws_AH.as<double>(), pd_slab,
-                                                      donor_pair_splits));
+                                                      ctx->ws_A.as<double>(), P.ldAw, AH, P.pd_slab, P.donor_pair_splits));
                 else
-                    CRM_TRY(launch_donor_pairs_expand(st, ctx->ws_Pd.as<double>(), pd_slab, ldPd, (int)groups, ncol, k0, k1, S, ld_ah,
-                                                      ctx->ws_AH.as<double>(), pd_slab, donor_pair_splits));
-                CRM_TRY(launch_reduce_splits(st, ctx->ws_AH.as<double>(), (long)ncol * ldPd, donor_pair_splits, pd_slab));
-                CRM_TRY(launch_pair_rows_sym(st, ctx->ws_AH.as<double>(), ldPd, ncol, k0, S, ld_ah));
+                    CRM_TRY(launch_donor_pairs_expand(st, ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, (int)groups, ncol, k0, k1, S, ld_ah,
+                                                      AH, P.pd_slab, P.donor_pair_splits));
+                CRM_TRY(launch_reduce_splits(st, AH, (long)ncol * P.ldPd, P.donor_pair_splits, P.pd_slab));
+                CRM_TRY(launch_pair_rows_sym(st, AH, P.ldPd, ncol, k0, S, ld_ah));
                 ctx->donor_pair_blocks++;
-            } else if (k2 == 1) CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, k0, maxlen, false, 0, 1, 0));
-            else CRM_TRY(launch_kr_transposed(ctx, d_kp, (int)groups, ncol * k0, k2, maxlen, k0));
-            if (donor_pairs) {
-            } else if (e1_pairs) {
-                const long p_slab = (long)(std::max<long>(BLK, max_pairs) + 128) * ldP;
-                CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, 1, ncol, e1_sym ? npair : k1 * k0, np, false, 0, fold_split6, p_slab));
-                CRM_TRY(launch_reduce_splits(st, ctx->ws_AH.as<double>(), (long)ncol * ldP, fold_split6, p_slab));
-                if (e1_sym) CRM_TRY(launch_pair_rows_sym(st, ctx->ws_AH.as<double>(), ldP, ncol, k0, S, ld_ah));
-                else CRM_TRY(launch_pair_rows(st, ctx->ws_AH.as<double>(), ldP, ncol, k1, k0, S, ld_ah));
             } else {
-                CRM_TRY(launch_kr_transposed(ctx, d_kp + groups, slices, ncol * k0, k1, chunk_max, k0));
-                CRM_TRY(launch_reduce_splits(st, ctx->ws_AH.as<double>(), e1_slab, slices, e1_slab));
-                CRM_HIP(hipMemcpyAsync(S, ctx->ws_AH.ptr, sizeof(double) * (size_t)e1_slab, hipMemcpyDeviceToDevice, st));
+                if (k2 == 1) CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, k0, maxlen, false, 0, 1, 0));
+                else CRM_TRY(launch_kr_transposed(ctx, d_kp, (int)groups, ncol * k0, k2, maxlen, k0));
+                if (P.e1_pairs) {
+                    const long p_slab = (long)(std::max<long>(P.BLK, P.pair_cap) + 128) * P.ldP;
+                    CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, 1, ncol, P.e1_sym ? npair : k1 * k0, np, false, 0, P.fold_split6, p_slab));
+                    CRM_TRY(launch_reduce_splits(st, AH, (long)ncol * P.ldP, P.fold_split6, p_slab));
+                    if (P.e1_sym) CRM_TRY(launch_pair_rows_sym(st, AH, P.ldP, ncol, k0, S, ld_ah));
+                    else CRM_TRY(launch_pair_rows(st, AH, P.ldP, ncol, k1, k0, S, ld_ah));
+                } else {
+                    CRM_TRY(launch_kr_transposed(ctx, d_kp + groups, slices, ncol * k0, k1, chunk_max, k0));
+                    CRM_TRY(launch_reduce_splits(st, AH, e1_slab, slices, e1_slab));
+                    CRM_HIP(hipMemcpyAsync(S, AH, sizeof(double) * (size_t)e1_slab, hipMemcpyDeviceToDevice, st));
+                }
             }
             // (2 kin_rows k2 k0 + 2 n k1 k0 flops per variant, outside the timed pair: the roofline figure is the MixK product's own;
             // bench.py's whole_path counts them)
-            if (!in_pair_order && !wb) {
-                const int xg_cols = (int)std::min<long>(ld_xg, round_up((long)npairs * k0, 128) + 128);
-                CRM_TRY(launch_gather_slabs(st, S, ld_ah, kdim, d_ord, npairs, k0, ctx->ws_XG.as<double>(), ld_xg, xg_cols));
-            }
-            CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
-        } else if (via_H && kin_route) {
-            // AH = H'(g o E0) without an n-length contraction against the cols columns of H:
-            // (a) the block in donor order; (b) per donor d' the Khatri-Rao contraction over its own cells against
-            // [us | E1] (transposed store: S[(d' KK + q), (b, i)]); (c) the L rows: for every j a contraction over the
-            // donors with hKd, AH[(k1 + j m + d), .] = sum_d' hKd[d', d] S[(d' KK + j), .]; (d) the E1 rows: sums over d'
-            double* Gk = ctx->ws_Gk.as<double>();
-            double* S = ctx->ws_S.as<double>();
-            const int k1 = bg->kin_k1, k2 = bg->kin_k2;
-            const long groups = bg->kin_groups, mk = bg->kin_cols;
-            // one phenotype: the columns are taken in the rho*-sorted pair order (Gs) straight away, so that AH is the
-            // operand of the Mix products as it stands; several phenotypes share a variant between pairs: block order, then
-            // the pair gather below
-            const bool in_pair_order = ng == 1;
-            const double* Gsrc = in_pair_order ? Gs : Gt;
-            const long ldg_k = in_pair_order ? ldp : ldb;
-            const int ncol = in_pair_order ? npairs : nb;
-            CRM_TRY(launch_gather_rows(st, Gsrc, ldg_k, bg->kin_map.as<int>(), bg->kin_rows, in_pair_order ? (int)ldg_k : blk_cols, Gk, ldg_k));
-            std::vector<GemmProblem> kp((size_t)groups + k2);
-            long maxlen = GEMM_BK;
-            if (pairs_unfolded) {
-                // P_d = G_d'(E (x) E)_d per donor; Z = [hKd | 1]' P over the donors (in ws_S: the per-donor blocks are not formed);
-                // rows k1 + j m + c of AH from Z_c, rows [0, k1) from the sums over the donors Z_m
-                double* Pd = ctx->ws_Pd.as<double>();
-                double* Z = S;
-                for (long d = 0; d < groups; d++) {
-                    GemmProblem p{};
-                    p.X = Gk + bg->kin_row0[d] * ldg_k; p.ldx = ldg_k;
-                    p.Y = g0->kinEE.as<double>() + bg->kin_row0[d] * g0->ld_ee; p.ldy = g0->ld_ee;
-                    p.C = Pd + (size_t)d * pd_slab; p.ldc = ldPd;
-                    p.M = ncol; p.N = npair; p.cells = bg->kin_len[d];
-                    maxlen = std::max(maxlen, bg->kin_len[d]);
-                    kp[d] = p;
-                }
-                {
-                    GemmProblem p{};
-                    p.X = bg->kin_hKd.as<double>(); p.ldx = bg->kin_ldh;
-                    p.Y = Pd; p.ldy = pd_slab;
-                    p.C = Z; p.ldc = pd_slab;
-                    p.M = (int)mk + 1; p.N = (int)((long)ncol * ldPd);
-                    kp[groups] = p;
-                }
-                GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
-                CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * (size_t)(groups + 1), hipMemcpyHostToDevice, st));
+            if (!D.in_pair_order && !P.wb()) CRM_TRY(gather_pairs(S, P.kdim, Q));
+            return CRM_OK;
+        });
+    }
+
+    // AH = H'(g o E0) without an n-length contraction against the cols columns of H:
+    // (a) the block in donor order; (b) per donor d' the Khatri-Rao contraction over its own cells against
+    // [us | E1] (transposed store: S[(d' KK + q), (b, i)]); (c) the L rows: for every j a contraction over the
+    // donors with hKd, AH[(k1 + j m + d), .] = sum_d' hKd[d', d] S[(d' KK + j), .]; (d) the E1 rows: sums over d'
+    int unfolded_AH(const Block& B, const SubRange& R, const Pairs& Q) {
+        DonorCols D;
+        CRM_TRY(donor_columns(B, R, Q, D));
+        double* S = ctx->ws_S.as<double>();
+        double* AH = ctx->ws_AH.as<double>();
+        const int k1 = bg->kin_k1, k2 = bg->kin_k2, ncol = D.ncol, npair = P.npair;
+        const long groups = bg->kin_groups, mk = bg->kin_cols, KK = P.KK, ld_ah = P.ld_ah;
+        GemmProblem p{};
+        p.X = ctx->ws_Gk.as<double>(); p.ldx = D.ldg;
+        if (P.pairs_unfolded) {
+            // P_d = G_d'(E (x) E)_d per donor; Z = [hKd | 1]' P over the donors (in ws_S: the per-donor blocks are not formed);
+            // rows k1 + j m + c of AH from Z_c, rows [0, k1) from the sums over the donors Z_m
+            double* Pd = ctx->ws_Pd.as<double>();
+            double* Z = S;
+            std::vector<GemmProblem> kp((size_t)groups + 1);
+            p.Y = g0->kinEE.as<double>(); p.ldy = g0->ld_ee; p.C = Pd; p.ldc = P.ldPd; p.M = ncol; p.N = npair;
+            const long maxlen = donor_run_records(bg, p, P.pd_slab, kp.data());
+            GemmProblem& z = kp[groups];
+            z.X = bg->kin_hKd.as<double>(); z.ldx = bg->kin_ldh;   // (column m of hKd: ones)
+            z.Y = Pd; z.ldy = P.pd_slab; z.C = Z; z.ldc = P.pd_slab; z.M = (int)mk + 1; z.N = (int)((long)ncol * P.ldPd);
+            return with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) -> int {
                 CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, npair, maxlen, false, 0, 1, 0));
-                CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, 1, (int)mk + 1, (int)((long)ncol * ldPd), bg->kin_groups_pad, false, 0, 1, 0));
-                CRM_TRY(launch_donor_pairs_expand(st, Z, pd_slab, ldPd, (int)mk, ncol, k0, k1, ctx->ws_AH.as<double>(), ld_ah, Pd, pd_slab, 1,
-                                                  1, mk));
-                CRM_TRY(launch_pair_rows_sym(st, Z + (size_t)mk * pd_slab, ldPd, ncol, k0, ctx->ws_AH.as<double>(), ld_ah));
+                CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, 1, (int)mk + 1, (int)((long)ncol * P.ldPd), bg->kin_groups_pad, false, 0, 1, 0));
+                CRM_TRY(launch_donor_pairs_expand(st, Z, P.pd_slab, P.ldPd, (int)mk, ncol, k0, k1, AH, ld_ah, Pd, P.pd_slab, 1, 1, mk));
+                CRM_TRY(launch_pair_rows_sym(st, Z + (size_t)mk * P.pd_slab, P.ldPd, ncol, k0, AH, ld_ah));
                 ctx->donor_pair_blocks++;
-                if (!in_pair_order) {
-                    const int xg_cols = (int)std::min<long>(ld_xg, round_up((long)npairs * k0, 128) + 128);
-                    CRM_TRY(launch_gather_slabs(st, ctx->ws_AH.as<double>(), ld_ah, bg->ldh, d_ord, npairs, k0,
-                                                ctx->ws_XG.as<double>(), ld_xg, xg_cols));
-                }
-                CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
-            } else {
-            for (long d = 0; d < groups; d++) {
-                GemmProblem p{};
-                p.X = Gk + bg->kin_row0[d] * ldg_k; p.ldx = ldg_k;
-                p.E = g0->kinEp.as<double>() + bg->kin_row0[d] * g0->ld_ep; p.lde = g0->ld_ep; p.k0 = k0;
-                p.Y = bg->kin_Y.as<double>() + bg->kin_row0[d] * bg->kin_ldy; p.ldy = bg->kin_ldy;
-                p.C = S + (size_t)d * KK * ld_ah; p.ldc = ld_ah;
-                p.M = ncol * k0; p.N = KK; p.cells = bg->kin_len[d];
-                maxlen = std::max(maxlen, bg->kin_len[d]);
-                kp[d] = p;
-            }
-            for (int j = 0; j < k2; j++) {
-                GemmProblem p{};
-                p.X = bg->kin_hKd.as<double>(); p.ldx = bg->kin_ldh;
-                p.Y = S + (size_t)j * ld_ah; p.ldy = (long)KK * ld_ah;
-                p.C = ctx->ws_AH.as<double>() + (size_t)(k1 + (long)j * mk) * ld_ah; p.ldc = ld_ah;
-                p.M = (int)mk; p.N = ncol * k0;
-                kp[groups + j] = p;
-            }
-            GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
-            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * kp.size(), hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_kr_transposed(ctx, d_kp, (int)groups, ncol * k0, KK, maxlen, k0));
+                if (!D.in_pair_order) CRM_TRY(gather_pairs(AH, bg->ldh, Q));
+                return CRM_OK;
+            });
+        }
+        std::vector<GemmProblem> kp((size_t)groups + k2);
+        p.E = g0->kinEp.as<double>(); p.lde = g0->ld_ep; p.k0 = k0; p.Y = bg->kin_Y.as<double>(); p.ldy = bg->kin_ldy;
+        p.C = S; p.ldc = ld_ah; p.M = ncol * k0; p.N = (int)KK;
+        const long maxlen = donor_run_records(bg, p, KK * ld_ah, kp.data());
+        for (int j = 0; j < k2; j++) {
+            GemmProblem& q = kp[groups + j];
+            q.X = bg->kin_hKd.as<double>(); q.ldx = bg->kin_ldh; q.Y = S + (size_t)j * ld_ah; q.ldy = KK * ld_ah;
+            q.C = AH + (size_t)(k1 + (long)j * mk) * ld_ah; q.ldc = ld_ah; q.M = (int)mk; q.N = ncol * k0;
+        }
+        return with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) -> int {
+            CRM_TRY(launch_kr_transposed(ctx, d_kp, (int)groups, ncol * k0, (int)KK, maxlen, k0));
             CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, k2, (int)mk, ncol * k0, bg->kin_groups_pad, false, 0, 1, 0));
-            CRM_TRY(launch_kin_sum_e1(st, S, ld_ah, KK, k2, k1, (int)groups, (long)ncol * k0, ctx->ws_AH.as<double>(), ld_ah));
+            CRM_TRY(launch_kin_sum_e1(st, S, ld_ah, (int)KK, k2, k1, (int)groups, (long)ncol * k0, AH, ld_ah));
             // (2 kin_rows KK k0 + 2 groups_pad m k2 k0 flops per variant, outside the timed pair: the roofline figure is the Mix
             // product's own; bench.py's whole_path counts them)
-            if (!in_pair_order) {
-                const int xg_cols = (int)std::min<long>(ld_xg, round_up((long)npairs * k0, 128) + 128);
-                CRM_TRY(launch_gather_slabs(st, ctx->ws_AH.as<double>(), ld_ah, bg->ldh, d_ord, npairs, k0,
-                                            ctx->ws_XG.as<double>(), ld_xg, xg_cols));
+            if (!D.in_pair_order) CRM_TRY(gather_pairs(AH, bg->ldh, Q));
+            return CRM_OK;
+        });
+    }
+
+    // several phenotypes on the direct route through H: AH = H'(g o E0) over all cells, then the pair gather
+    int direct_AH(const Block& B, const SubRange& R, const Pairs& Q, AGroups& A) {
+        GemmProblem p{};
+        p.X = B.Gt + R.b0; p.ldx = P.ldb; p.E = d_Ep; p.lde = g0->ld_ep; p.k0 = k0; p.Y = bg->H.as<double>(); p.ldy = bg->ldh;
+        p.C = ctx->ws_AH.as<double>(); p.ldc = P.ld_ah; p.M = R.nb * k0; p.N = (int)bg->cols;
+        CRM_TRY(upload(SLOT_ONE, &p, 1));
+        CRM_TRY(launch_kr_transposed(ctx, d_probs + SLOT_ONE, 1, p.M, p.N, np, k0));
+        A.kr_flops += 2.0 * (double)n * (double)bg->cols * (double)k0 * (double)R.nb;
+        return gather_pairs(ctx->ws_AH.as<double>(), bg->ldh, Q);
+    }
+
+    // Unrelated-donor form: the rotated S, rows (col k0 + i) over the donors k2 positions -- per donor
+    // (U_d Lambda_d^-1/2)' S_d, stored transposed into ws_A; col = the pair (one phenotype) or the block position
+    int woodbury_S(const SubRange& R, const Pairs& Q) {
+        const long groups = bg->kin_groups;
+        const int ncol = ng == 1 ? Q.npairs : R.nb;
+        std::vector<GemmProblem> kp((size_t)groups);
+        GemmProblem p{};
+        p.X = ctx->ws_S.as<double>() + (size_t)bg->kin_k1 * P.ld_ah; p.ldx = P.ld_ah;
+        p.C = ctx->ws_A.as<double>(); p.ldc = P.ldAw; p.M = ncol * k0;
+        woodbury_records(bg, p, (long)bg->kin_k2 * P.ld_ah, kp.data());
+        return with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) {
+            return launch_gemm_tn(ctx, d_kp, (int)groups, ncol * k0, bg->kin_k2, bg->wb_k2pad, false, 0, 1, 0);
+        });
+    }
+
+    // 6. A~ = KR(Gs, Ep)' Q0(rho), one problem per non-empty rho group of pairs.
+    //    Several genes can select several rho* for one variant; with Q0(rho) = H Mix(rho) the
+    //    n-length Khatri-Rao contraction is then done once per variant against H (stored transposed)
+    //    and every (variant, rho) pair costs a cols-length product with Mix(rho) instead.
+    int form_A(const Block& B, const SubRange& R, const Pairs& Q) {
+        bool via_H = P.kin();
+        if (P.fastT && ng > 1 && !P.kin()) {
+            double direct = 0.0, via = (double)R.nb * (double)bg->cols * (double)n;
+            for (int i = 0; i < nrho; i++) {
+                direct += (double)Q.cnt[i] * bg->r[i] * (double)n;
+                via += (double)Q.cnt[i] * bg->r[i] * (double)bg->ldh;
             }
-            CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
-            }   // (the Khatri-Rao form of the per-donor blocks)
-        } else if (via_H) {
-            GemmProblem p{};
-            p.X = Gt; p.ldx = ldb; p.E = d_Ep; p.lde = g0->ld_ep; p.k0 = k0;
-            p.Y = bg->H.as<double>(); p.ldy = bg->ldh;
-            p.C = ctx->ws_AH.as<double>(); p.ldc = ld_ah;
-            p.M = nb * k0; p.N = (int)bg->cols;
-            CRM_HIP(hipMemcpyAsync(d_probs, &p, sizeof p, hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_kr_transposed(ctx, d_probs, 1, p.M, p.N, np, k0));
-            kr_flops += 2.0 * (double)n * (double)bg->cols * (double)k0 * (double)nb;
-            const int xg_cols = (int)std::min<long>(ld_xg, round_up((long)npairs * k0, 128) + 128);
-            CRM_TRY(launch_gather_slabs(st, ctx->ws_AH.as<double>(), ld_ah, bg->ldh, d_ord, npairs, k0,
-                                        ctx->ws_XG.as<double>(), ld_xg, xg_cols));
+            via_H = ctx->tune.shared_h < 0 ? via < 0.9 * direct : ctx->tune.shared_h > 0;
         }
-        CRM_HIP(hipMemcpyAsync(d_probs, probs.data(), sizeof(GemmProblem) * nz, hipMemcpyHostToDevice, st));
-        if (collapsed)
-            CRM_TRY(launch_gemm_tn(ctx, d_probs, nz, max_m, (int)((long)k0 * ldq), mp, false, 0, 1, 0));
-        else if (via_H && kin_route && wb && wb_rotate) {
-            // (the rotated S is in ws_A already: step 6, launch_donor_pairs_rotate)
-        } else if (via_H && kin_route && wb) {
-            // Unrelated-donor form: the rotated S, rows (col k0 + i) over the donors k2 positions -- per donor
-            // (U_d Lambda_d^-1/2)' S_d, stored transposed into ws_A; col = the pair (one phenotype) or the block position
-            const int k1 = bg->kin_k1, k2 = bg->kin_k2, k2pad = bg->wb_k2pad;
-            const long groups = bg->kin_groups;
-            const int ncol = ng == 1 ? npairs : nb;
-            std::vector<GemmProblem> kp((size_t)groups);
-            for (long d = 0; d < groups; d++) {
-                GemmProblem p{};
-                p.X = ctx->ws_S.as<double>() + (size_t)(k1 + d * k2) * ld_ah; p.ldx = ld_ah;
-                p.Y = bg->wb_U.as<double>() + (size_t)d * k2pad * 128; p.ldy = 128;
-                p.C = ctx->ws_A.as<double>() + d * k2; p.ldc = ldAw;
-                p.M = ncol * k0; p.N = k2; p.cells = k2pad;
-                kp[d] = p;
-            }
-            GemmProblem* d_kp = d_probs + 2 * CRM_MAX_RHO + 4;
-            CRM_HIP(hipMemcpyAsync(d_kp, kp.data(), sizeof(GemmProblem) * kp.size(), hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol * k0, k2, k2pad, false, 0, 1, 0));
-            CRM_HIP(hipStreamSynchronize(st));   // (kp lives on this stack frame)
-        } else if (via_H && kin_route) {
+        const bool direct = !P.collapsed() && !via_H;
+        if (direct)
+            for (int i = 0; i < nrho; i++)
+                if (Q.cnt[i] > 0) CRM_TRY(crm_background_require_q0(bg, i));
+        AGroups A;
+        bool tail_of[CRM_MAX_RHO] = {false};
+        if (direct) CRM_TRY(direct_splits(Q, A, tail_of));
+        a_records(Q, via_H, tail_of, A);
+        const bool timing = !P.wb() && ctx->timing && ctx->timed_used < 65536;  // bounded: a forgotten timer cannot grow for ever
+        // (kinship-structure route: the pair brackets the dominant launch alone, the Mix(rho*)' product further down)
+        if (timing) CRM_TRY(timer_open(!P.kin()));
+        if (P.folded()) CRM_TRY(folded_S(B, R, Q));
+        else if (P.kin()) CRM_TRY(unfolded_AH(B, R, Q));
+        else if (via_H) CRM_TRY(direct_AH(B, R, Q, A));
+        CRM_TRY(upload(SLOT_ONE, probs.data(), A.nz));
+        GemmProblem* d_A = d_probs + SLOT_ONE;
+        if (P.collapsed()) {
+            CRM_TRY(launch_gemm_tn(ctx, d_A, A.nz, A.max_m, (int)((long)k0 * ldq), P.mp, false, 0, 1, 0));
+        } else if (P.wb()) {
+            if (!P.wb_rotate) CRM_TRY(woodbury_S(R, Q));   // (else the rotated S is in ws_A already: launch_donor_pairs_rotate)
+        } else if (P.kin()) {
             if (timing) CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].first, st));
             struct Restore { crm_ctx* c; ~Restore() { c->tune.tag = 0; } } restore{ctx};
             ctx->tune.tag = 1;
-            CRM_TRY(launch_gemm_tn(ctx, d_probs, nz, max_m, max_n, kdim, false, 0, 1, 0));
-        } else if (via_H)
-            CRM_TRY(launch_gemm_tn(ctx, d_probs, nz, max_m, max_n, kdim, false, 0, 1, 0));
-        else {
-            CRM_TRY(launch_gemm_tn(ctx, d_probs, nz, max_m, max_n, np, true, k0, kr_split, (long)a_slab));
-            CRM_TRY(launch_reduce_splits(st, ctx->ws_A.as<double>(), (long)npairs * k0 * ldA, kr_split, (long)a_slab));
-            if (!tails.empty()) {
+            CRM_TRY(launch_gemm_tn(ctx, d_A, A.nz, A.max_m, A.max_n, P.kdim, false, 0, 1, 0));
+        } else if (via_H) {
+            CRM_TRY(launch_gemm_tn(ctx, d_A, A.nz, A.max_m, A.max_n, P.kdim, false, 0, 1, 0));
+        } else {
+            CRM_TRY(launch_gemm_tn(ctx, d_A, A.nz, A.max_m, A.max_n, np, true, k0, A.kr_split, (long)A.a_slab));
+            CRM_TRY(launch_reduce_splits(st, ctx->ws_A.as<double>(), (long)Q.npairs * k0 * P.ldA, A.kr_split, (long)A.a_slab));
+            if (!A.tails.empty()) {
                 const int saved_bn = ctx->tune.bn;
                 ctx->tune.bn = 160;
                 struct Restore { crm_ctx* c; int bn; ~Restore() { c->tune.bn = bn; } } restore{ctx, saved_bn};
-                CRM_HIP(hipMemcpyAsync(d_probs + nz, tails.data(), sizeof(GemmProblem) * tails.size(), hipMemcpyHostToDevice, st));
-                CRM_TRY(launch_gemm_tn(ctx, d_probs + nz, (int)tails.size(), max_m, tail_maxn, np, true, k0, tail_split, (long)a_slab));
+                CRM_TRY(upload(A.nz, A.tails.data(), A.tails.size()));
+                CRM_TRY(launch_gemm_tn(ctx, d_probs + A.nz, (int)A.tails.size(), A.max_m, A.tail_maxn, np, true, k0, A.tail_split, (long)A.a_slab));
                 ctx->tail_launches++;
-                for (const GemmProblem& t : tails)
-                    CRM_TRY(launch_reduce_splits_band(st, t.C, (long)t.M, t.ldc, 0, t.N, tail_split, (long)a_slab));
+                for (const GemmProblem& t : A.tails)
+                    CRM_TRY(launch_reduce_splits_band(st, t.C, (long)t.M, t.ldc, 0, t.N, A.tail_split, (long)A.a_slab));
             }
         }
         if (timing) {
-            CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].second, st));
-            ctx->timed_used++;
-            ctx->kr_flops += kr_flops;
+            CRM_TRY(timer_close());
+            ctx->kr_flops += A.kr_flops;
         }
-        if (!spectrum_tails.empty()) {
-            CRM_HIP(hipMemcpyAsync(d_probs + nz, spectrum_tails.data(), sizeof(GemmProblem) * spectrum_tails.size(), hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_skinny_tn(st, d_probs + nz, (int)spectrum_tails.size(), max_m, kdim));
+        if (!A.spectrum_tails.empty()) {
+            CRM_TRY(upload(A.nz, A.spectrum_tails.data(), A.spectrum_tails.size()));
+            CRM_TRY(launch_skinny_tn(st, d_probs + A.nz, (int)A.spectrum_tails.size(), A.max_m, P.kdim));
             ctx->spectrum_tail_launches++;
             CRM_HIP(hipStreamSynchronize(st));   // (the records live on this stack frame)
         }
-        // 7. elementwise products for the side contractions
+        return CRM_OK;
+    }
+
+    // 7. elementwise products for the side contractions
+    // 8. y-free side contractions: Z2 = (Gt o G)' E, Z3 = (Gt o Gt)' (E (x) E)
+    int side_contractions(const Block& B, const SubRange& R) {
+        const long ldb = P.ldb;
+        const int nb = R.nb;
+        double* const Gt = B.Gt + R.b0;
         double* G2 = ctx->ws_G2.as<double>();
-        double* GG = !collapsed ? ctx->ws_GG.as<double>() : nullptr;   // (test direction) o (fixed-effect role)
-        CRM_TRY(launch_square_block(st, Gt, Gx, ldb, ldb, xrows, blk_cols, G2, GG, ldb));
+        double* GG = !P.collapsed() ? ctx->ws_GG.as<double>() : nullptr;   // (test direction) o (fixed-effect role)
+        CRM_TRY(launch_square_block(st, Gt, B.Gx + R.b0, ldb, ldb, P.xrows, (int)(ldb - R.b0), G2, GG, ldb));
         if (!GG) GG = G2;
-        // 8. y-free side contractions: Z2 = (Gt o G)' E, Z3 = (Gt o Gt)' (E (x) E)
-        const int s1 = collapsed ? 1 : ks1, s2 = collapsed ? 1 : ks2, s3 = collapsed ? 1 : ks3;
-        {
-            GemmProblem p{};
-            p.ldx = ldb; p.M = nb;
-            p.X = GG; p.Y = collapsed ? tab->Z2.as<double>() : d_Ep; p.ldy = g0->ld_ep; p.C = dZ2; p.ldc = ldZ2; p.N = k0;
-            probs[1] = p;
-            p.X = G2; p.Y = collapsed ? tab->Z3.as<double>() : d_EE; p.ldy = g0->ld_ee; p.C = dZ3; p.ldc = ldZ3; p.N = npair;
-            probs[2] = p;
-            CRM_HIP(hipMemcpyAsync(d_probs + 1, probs.data() + 1, sizeof(GemmProblem) * 2, hipMemcpyHostToDevice, st));
-            if (cross) {
-                hipLaunchKernelGGL(donor_cross_kernel, dim3(nb), dim3(128), 0, st, Gb, ldb, (int)panel->m,
-                                   tab->Z2.as<double>(), ldZ2, k0, dZ2, ldZ2);
-                CRM_HIP(hipGetLastError());
-            } else {
-                CRM_TRY(launch_gemm_tn(ctx, d_probs + 1, 1, nb, k0, xrows, false, 0, s2, z2_sz));
-                CRM_TRY(launch_reduce_splits(st, dZ2, z2_sz, s2, z2_sz));
-            }
-            CRM_TRY(launch_gemm_tn(ctx, d_probs + 2, 1, nb, npair, xrows, false, 0, s3, z3_sz));
-            CRM_TRY(launch_reduce_splits(st, dZ3, z3_sz, s3, z3_sz));
+        const int s2 = P.collapsed() ? 1 : P.ks2, s3 = P.collapsed() ? 1 : P.ks3;
+        GemmProblem p{};
+        p.ldx = ldb; p.M = nb;
+        p.X = GG; p.Y = P.collapsed() ? tab->Z2.as<double>() : d_Ep; p.ldy = g0->ld_ep; p.C = dZ2; p.ldc = P.ldZ2; p.N = k0;
+        probs[1] = p;
+        p.X = G2; p.Y = P.collapsed() ? tab->Z3.as<double>() : d_EE; p.ldy = g0->ld_ee; p.C = dZ3; p.ldc = P.ldZ3; p.N = P.npair;
+        probs[2] = p;
+        CRM_TRY(upload(SLOT_RHO, probs.data() + 1, 2));
+        if (P.cross) {
+            hipLaunchKernelGGL(donor_cross_kernel, dim3(nb), dim3(128), 0, st, B.Gb + R.b0, ldb, (int)panel->m,
+                               tab->Z2.as<double>(), P.ldZ2, k0, dZ2, P.ldZ2);
+            CRM_HIP(hipGetLastError());
+        } else {
+            CRM_TRY(launch_gemm_tn(ctx, d_probs + SLOT_RHO, 1, nb, k0, P.xrows, false, 0, s2, z2_sz));
+            CRM_TRY(launch_reduce_splits(st, dZ2, z2_sz, s2, z2_sz));
         }
-        // 9.-11. per gene: Z1 = Gt' [y o E, W o E], Q and F, eigenvalues + Davies, results
-        const int s1g = collapsed ? 1 : ks1b;
-        if (z1_batched) {
-            std::vector<GemmProblem> zp((size_t)ng);
-            for (int gi = 0; gi < ng; gi++) {
-                crm_gene* g = genes[gi];
-                GemmProblem p{};
-                p.X = Gt; p.ldx = ldb; p.Y = collapsed ? g->dt_Z1.as<double>() : g->YE.as<double>(); p.ldy = g->ld_ye;
-                p.C = dZ1 + (size_t)gi * z1_sz * ks1b; p.ldc = ldZ1; p.M = nb; p.N = k0 * (1 + c);
-                zp[(size_t)gi] = p;
-            }
-            GemmProblem* d_zp = d_probs + 2 * CRM_MAX_RHO + 4 + kin_probs;
-            CRM_HIP(hipMemcpyAsync(d_zp, zp.data(), sizeof(GemmProblem) * zp.size(), hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_gemm_tn(ctx, d_zp, ng, nb, k0 * (1 + c), xrows, false, 0, s1g, z1_sz));
-            if (s1g > 1)
-                for (int gi = 0; gi < ng; gi++)
-                    CRM_TRY(launch_reduce_splits(st, dZ1 + (size_t)gi * z1_sz * ks1b, z1_sz, s1g, z1_sz));
-        }
+        CRM_TRY(launch_gemm_tn(ctx, d_probs + SLOT_RHO + 1, 1, nb, P.npair, P.xrows, false, 0, s3, z3_sz));
+        return launch_reduce_splits(st, dZ3, z3_sz, s3, z3_sz);
+    }
+
+    // 9. Z1 = Gt' [y o E, W o E] of every phenotype, one launch (ScanPlan::ks1)
+    int z1_products(const Block& B, const SubRange& R) {
+        const int s1 = P.collapsed() ? 1 : P.ks1;
+        std::vector<GemmProblem> zp((size_t)ng);
         for (int gi = 0; gi < ng; gi++) {
             crm_gene* g = genes[gi];
-            const ScanOut& o = outs[gi];
-            double* const dZ1g = z1_batched ? dZ1 + (size_t)gi * z1_sz * ks1b : dZ1;
-            if (!z1_batched) {
-                GemmProblem p{};
-                p.X = Gt; p.ldx = ldb; p.Y = collapsed ? g->dt_Z1.as<double>() : g->YE.as<double>(); p.ldy = g->ld_ye;
-                p.C = dZ1; p.ldc = ldZ1; p.M = nb; p.N = k0 * (1 + c);
-                CRM_HIP(hipMemcpyAsync(d_probs, &p, sizeof p, hipMemcpyHostToDevice, st));
-                CRM_TRY(launch_gemm_tn(ctx, d_probs, 1, nb, k0 * (1 + c), xrows, false, 0, s1, z1_sz));
-                CRM_TRY(launch_reduce_splits(st, dZ1, z1_sz, s1, z1_sz));
-            }
-            AssembleArgs aa{};
-            for (int i = 0; i < nrho; i++) {
-                AssembleRho& R = aa.rho[i];
-                R.ty = g->rot.as<double>() + (long)i * slab;
-                R.tW = R.ty + ldq; R.ldW = ldq;
-                R.S0 = bg->S0[i].as<double>();
-                R.T = ctx->ws_T.as<double>() + ((size_t)i * BLK + sb0) * ldT; R.ldT = ldT;
-                R.r = bg->r[i];
-            }
-            aa.fit = d_fit + (size_t)gi * BLK; aa.sorted_pos = d_pos + (size_t)gi * BLK;
-            aa.A = ctx->ws_A.as<double>(); aa.ldA = ldA; aa.k0 = k0; aa.c = c; aa.n = n;
-            aa.A_none = ctx->ws_Anone.as<double>();
-            aa.Z1 = dZ1g; aa.ldZ1 = ldZ1; aa.Z2 = dZ2; aa.ldZ2 = ldZ2; aa.Z3 = dZ3; aa.ldZ3 = ldZ3;
-            aa.WW = g->WW.as<double>(); aa.Wy = g->Wy.as<double>(); aa.yy = g->yy;
-            aa.gg = d_gg; aa.gy = d_gy + (size_t)gi * BLK; aa.gW = d_gW; aa.ld_gW = ld_gW;
-            aa.coef = collapsed ? nullptr : d_coef; aa.ld_coef = ldb;
-            aa.Q = d_Q; aa.F = ctx->ws_F.as<double>();
-            for (int i = 0; i < nrho; i++) aa.rho[i].rho = bg->rho[i];
-            if (wb) {   // (assemble.hip: woodbury_kernel)
-                for (int i = 0; i < nrho; i++) {
-                    AssembleRho& R = aa.rho[i];
-                    R.ty = wb_yW + (size_t)gi * (1 + c) * ldwb;
-                    R.tW = R.ty + ldwb; R.ldW = ldwb;
-                    R.S0 = bg->wb_S0[i].as<double>();
-                    R.T = wb_g + (size_t)sb0 * ldwb; R.ldT = ldwb;
-                    R.r = (int)bg->wb_P;
-                }
-                aa.sorted_pos = (ng == 1 ? d_pos : d_posw) + (size_t)gi * BLK;
-                aa.A = ctx->ws_A.as<double>(); aa.ldA = ldAw;
-                aa.wb_k1 = bg->kin_k1;
-                aa.wb_R = bg->wb_R.as<double>(); aa.wb_ldR = ldwb;
-                aa.wb_E1X = ctx->ws_S.as<double>(); aa.wb_ldE1X = ld_ah;
-                aa.wb_E1yW = wb_E1yW + (size_t)gi * bg->kin_k1 * 128; aa.wb_ldE1yW = 128;
-                aa.wb_E1g = ctx->ws_TH.as<double>() + sb0; aa.wb_ldE1g = ldb;
-                aa.wb_EE = bg->wb_EE.as<double>();
-                aa.wb_Gw = wb_Gw;
-            }
-            double* slow_ws = nullptr;
-            if (slow_forms) {
-                CRM_TRY(ctx->ws_xwide.ensure(sizeof(double) * std::max(std::max(assemble_rows_scratch_doubles(BLK, k0, c), eig_scratch_doubles(BLK, k0)),
-                                                                       c > CRM_MAX_COV_WIDE ? nullfit_xwide_scratch_doubles(BLK, nrho, c) : (size_t)0)));
-                slow_ws = ctx->ws_xwide.as<double>();   // (the null fits of the block are done: their scratch is free)
-            }
-            CRM_TRY(launch_assemble(st, aa, nb, ctx->ws_Gext.as<double>(), slow_ws));
-            CRM_TRY(launch_eig_davies(st, ctx->ws_F.as<double>(), d_Q, nb, k0, d_lam, d_pv, d_if, d_liu, true, slow_ws));
-            if (o.exact) {
-                CRM_TRY(launch_tail_pvalue(st, d_Q, d_lam, nb, k0, d_tp, d_tlp, d_tst));
-                if (o.logp) CRM_HIP(hipMemcpyAsync(o.logp + done, d_tlp, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-                if (o.status) CRM_HIP(hipMemcpyAsync(o.status + done, d_tst, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-            }
-            if (o.pv) CRM_HIP(hipMemcpyAsync(o.pv + done, o.exact ? d_tp : d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-            if (o.Q) CRM_HIP(hipMemcpyAsync(o.Q + done, d_Q, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-            if (o.lambda) CRM_HIP(hipMemcpyAsync(o.lambda + done * k0, d_lam, sizeof(double) * nb * k0, hipMemcpyDeviceToHost, st));
-            if (o.F) CRM_HIP(hipMemcpyAsync(o.F + done * k0 * k0, ctx->ws_F.ptr, sizeof(double) * nb * k0 * k0, hipMemcpyDeviceToHost, st));
-            if (o.ifault) CRM_HIP(hipMemcpyAsync(o.ifault + done, d_if, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-            if (o.liu) CRM_HIP(hipMemcpyAsync(o.liu + done, d_liu, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-            // flat-optimum probes (info calls only): the score test again with delta one stopping tolerance of the
-            // reference's search to either side; how far Q and p move says whether the search's last comparison matters
-            std::vector<char> flat;
-            std::vector<double> probe_rec;
-            const double flat_kappa = FLAT_KAPPA * 1e-3 * form("flat_kappa_milli", 1000);
-            const double rho_kappa = RHO_KAPPA * 1e-3 * form("flat_kappa_milli", 1000);
-            if (o.flags) {
-                probe_rec.assign((size_t)nb * FLAT_REC, 0.0);
-                std::vector<double> q0(nb), p0(nb), q1(nb), p1(nb), lam0((size_t)nb * k0);
-                CRM_HIP(hipMemcpyAsync(lam0.data(), d_lam, sizeof(double) * (size_t)nb * k0, hipMemcpyDeviceToHost, st));
-                CRM_HIP(hipMemcpyAsync(q0.data(), d_Q, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-                CRM_HIP(hipMemcpyAsync(p0.data(), d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-                ScopedBuf probe;
-                CRM_TRY(probe.ensure(sizeof(NullFitOut) * (size_t)nb + 64));
-                flat.assign(nb, 0);
-                for (int side = 0; side < 2; side++) {
-                    hipLaunchKernelGGL(flat_probe_fit_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, aa.fit, nb,
-                                       side == 0 ? 1.0 : -1.0, probe.as<NullFitOut>());
-                    CRM_HIP(hipGetLastError());
-                    AssembleArgs ap = aa;
-                    ap.fit = probe.as<NullFitOut>();
-                    CRM_TRY(launch_assemble(st, ap, nb, ctx->ws_Gext.as<double>(), slow_ws));
-                    CRM_TRY(launch_eig_davies(st, ctx->ws_F.as<double>(), d_Q, nb, k0, d_lam, d_pv, d_if, d_liu, true, slow_ws));
-                    CRM_HIP(hipMemcpyAsync(q1.data(), d_Q, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-                    CRM_HIP(hipMemcpyAsync(p1.data(), d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-                    CRM_HIP(hipStreamSynchronize(st));
-                    for (int b = 0; b < nb; b++) {
-                        // (Q against max(Q, its expectation under the null = tr F): a score vector that nearly vanishes,
-                        // p ~ 1, leaves Q itself ill-conditioned)
-                        double trace = 0.0;
-                        for (int j = 0; j < k0; j++) trace += lam0[(size_t)b * k0 + j];
-                        // (equal values -- a p-value that underflows to zero on both sides included -- have not moved)
-                        const double mq = q1[b] == q0[b] ? 0.0 : std::fabs(q1[b] - q0[b]) / std::max(std::fabs(q0[b]), trace);
-                        const double mp = p1[b] == p0[b] ? 0.0 : std::fabs(p1[b] - p0[b]) / std::fabs(p0[b]);
-                        const NullFitOut& fo = h_fit[(size_t)gi * BLK + b];
-                        double* rec = &probe_rec[(size_t)b * FLAT_REC];
-                        // (NaN -- a probe that could not be evaluated -- must survive the maximum)
-                        rec[1] = (mq == mq && rec[1] == rec[1]) ? std::max(rec[1], mq) : NAN;
-                        rec[2] = (mp == mp && rec[2] == rec[2]) ? std::max(rec[2], mp) : NAN;
-                        rec[0] = flat_obj.empty() ? -1.0 : flat_obj[(size_t)gi * BLK + sb0 + b];
-                        rec[3] = fo.margin; rec[4] = fo.noise; rec[5] = fo.rho_decision; rec[6] = fo.gap; rec[7] = fo.lml;
-                        rec[8] = fo.curv; rec[9] = fo.delta;
-                    }
-                }
-                // the bounds: (movement of Q / p over one tolerance) x (the largest distance, in tolerances, at which two
-                // faithful searches stop: STOP_SHIFT_C / relative gain of the objective over one tolerance, at most one --
-                // and one outright where a decision of the search itself was within the objective's noise bound)
-                for (int b = 0; b < nb; b++) {
-                    const NullFitOut& fo = h_fit[(size_t)gi * BLK + b];
-                    const double* rec = &probe_rec[(size_t)b * FLAT_REC];
-                    const double gain = fo.curv / std::fabs(fo.lml);
-                    double shift = (gain > 0.0 && gain == gain) ? std::min(1.0, STOP_SHIFT_C / gain) : 1.0;
-                    if (!(rec[0] > flat_kappa)) shift = 1.0;
-                    const double bq = rec[1] * shift, bp = rec[2] * shift;
-                    if (o.bound_Q) o.bound_Q[done + b] = bq;
-                    if (o.bound_p) o.bound_p[done + b] = bp;
-                    if (!(bp <= 1e-5)) flat[b] |= 1;
-                    if (!(bq <= 1e-6)) flat[b] |= 2;
-                }
-            }
-            if (o.flags && ng == 1) {   // (diagnostics: what the probes measured, crm_test_null_fit_probe_read)
-                if (done == 0) ctx->probe_out.clear();
-                ctx->probe_out.insert(ctx->probe_out.end(), probe_rec.begin(), probe_rec.end());
-            }
-            int rmax = 0;
-            for (int i = 0; i < nrho; i++) rmax = std::max(rmax, bg->r[i]);
-            const bool saturated = (long)rmax + c + 1 >= n;
-            for (int b = 0; b < nb; b++) {
-                const NullFitOut& f = h_fit[(size_t)gi * BLK + b];
-                const double rho = bg->rho[f.rho_index];
-                if (o.flags) {
-                    int fl = saturated ? CRM_MODEL_SATURATED : 0;
-                    if (!(f.delta > 1e-8)) fl |= CRM_MODEL_DELTA_AT_ZERO;
-                    if (!f.use_g) fl |= CRM_MODEL_G_IN_SPAN_W;
-                    if (!flat.empty() && (flat[b] & 1)) fl |= CRM_MODEL_FLAT_OPTIMUM;
-                    if (!flat.empty() && (flat[b] & 2)) fl |= CRM_MODEL_STATISTIC_AT_TOLERANCE;
-                    if (f.rho_decision == f.rho_decision && !(f.rho_decision > rho_kappa)) fl |= CRM_MODEL_RHO_TIE;
-                    o.flags[done + b] = fl;
-                }
-                if (o.rho1) o.rho1[done + b] = rho;
-                if (o.e2) o.e2[done + b] = f.v0 * rho;
-                if (o.g2) o.g2[done + b] = f.v0 * (1 - rho);
-                if (o.eps2) o.eps2[done + b] = f.v1;
-                if (o.lml) o.lml[done + b] = f.lml;
-                if (o.delta) o.delta[done + b] = f.delta;
-                if (o.scale) o.scale[done + b] = f.scale;
-            }
-            // the per-gene device buffers (Z1, Q, F, pv) are reused by the next gene
-            CRM_HIP(hipStreamSynchronize(st));
+            GemmProblem& p = zp[(size_t)gi];
+            p.X = B.Gt + R.b0; p.ldx = P.ldb; p.Y = P.collapsed() ? g->dt_Z1.as<double>() : g->YE.as<double>(); p.ldy = g->ld_ye;
+            p.C = dZ1 + (size_t)gi * z1_sz * P.ks1; p.ldc = P.ldZ1; p.M = R.nb; p.N = k0 * (1 + c);
         }
-        sb0 += nsb;
-        }   // pair stage over the sub-ranges of the block
-        ctx->report(done + nb, count);   // (the reference's tqdm, :340)
+        CRM_TRY(upload(P.z1_slot(), zp.data(), zp.size()));
+        CRM_TRY(launch_gemm_tn(ctx, d_probs + P.z1_slot(), ng, R.nb, k0 * (1 + c), P.xrows, false, 0, s1, z1_sz));
+        for (int gi = 0; gi < ng; gi++)
+            CRM_TRY(launch_reduce_splits(st, dZ1 + (size_t)gi * z1_sz * P.ks1, z1_sz, s1, z1_sz));
+        return CRM_OK;
+    }
+
+    // flat-optimum probes (info calls only): the score test again with delta one stopping tolerance of the
+    // reference's search to either side; how far Q and p move says whether the search's last comparison matters.
+    // flat[b]: 1 = FLAT_OPTIMUM, 2 = STATISTIC_AT_TOLERANCE
+    int flat_probes(const Block& B, const SubRange& R, int gi, const AssembleArgs& aa, double* slow_ws, std::vector<char>& flat,
+                    std::vector<double>& probe_rec) {
+        const ScanOut& o = outs[gi];
+        const int nb = R.nb;
+        const NullFitOut* fit = h_fit.data() + (size_t)gi * P.BLK + R.b0;
+        const double flat_kappa = FLAT_KAPPA * 1e-3 * form("flat_kappa_milli", 1000);
+        probe_rec.assign((size_t)nb * FLAT_REC, 0.0);
+        std::vector<double> q0(nb), p0(nb), q1(nb), p1(nb), lam0((size_t)nb * k0);
+        CRM_HIP(hipMemcpyAsync(lam0.data(), d_lam, sizeof(double) * (size_t)nb * k0, hipMemcpyDeviceToHost, st));
+        CRM_HIP(hipMemcpyAsync(q0.data(), d_Q, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+        CRM_HIP(hipMemcpyAsync(p0.data(), d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+        ScopedBuf probe;
+        CRM_TRY(probe.ensure(sizeof(NullFitOut) * (size_t)nb + 64));
+        flat.assign(nb, 0);
+        for (int side = 0; side < 2; side++) {
+            hipLaunchKernelGGL(flat_probe_fit_kernel, dim3((nb + 255) / 256), dim3(256), 0, st, aa.fit, nb,
+                               side == 0 ? 1.0 : -1.0, probe.as<NullFitOut>());
+            CRM_HIP(hipGetLastError());
+            AssembleArgs ap = aa;
+            ap.fit = probe.as<NullFitOut>();
+            CRM_TRY(launch_assemble(st, ap, nb, ctx->ws_Gext.as<double>(), slow_ws));
+            CRM_TRY(launch_eig_davies(st, ctx->ws_F.as<double>(), d_Q, nb, k0, d_lam, d_pv, d_if, d_liu, true, slow_ws));
+            CRM_HIP(hipMemcpyAsync(q1.data(), d_Q, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+            CRM_HIP(hipMemcpyAsync(p1.data(), d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+            CRM_HIP(hipStreamSynchronize(st));
+            for (int b = 0; b < nb; b++) {
+                // (Q against max(Q, its expectation under the null = tr F): a score vector that nearly vanishes,
+                // p ~ 1, leaves Q itself ill-conditioned)
+                double trace = 0.0;
+                for (int j = 0; j < k0; j++) trace += lam0[(size_t)b * k0 + j];
+                // (equal values -- a p-value that underflows to zero on both sides included -- have not moved)
+                const double mq = q1[b] == q0[b] ? 0.0 : std::fabs(q1[b] - q0[b]) / std::max(std::fabs(q0[b]), trace);
+                const double mp = p1[b] == p0[b] ? 0.0 : std::fabs(p1[b] - p0[b]) / std::fabs(p0[b]);
+                const NullFitOut& fo = fit[b];
+                double* rec = &probe_rec[(size_t)b * FLAT_REC];
+                // (NaN -- a probe that could not be evaluated -- must survive the maximum)
+                rec[1] = (mq == mq && rec[1] == rec[1]) ? std::max(rec[1], mq) : NAN;
+                rec[2] = (mp == mp && rec[2] == rec[2]) ? std::max(rec[2], mp) : NAN;
+                rec[0] = B.flat_obj.empty() ? -1.0 : B.flat_obj[(size_t)gi * P.BLK + R.b0 + b];
+                rec[3] = fo.margin; rec[4] = fo.noise; rec[5] = fo.rho_decision; rec[6] = fo.gap; rec[7] = fo.lml;
+                rec[8] = fo.curv; rec[9] = fo.delta;
+            }
+        }
+        // the bounds: (movement of Q / p over one tolerance) x (the largest distance, in tolerances, at which two
+        // faithful searches stop: STOP_SHIFT_C / relative gain of the objective over one tolerance, at most one --
+        // and one outright where a decision of the search itself was within the objective's noise bound)
+        for (int b = 0; b < nb; b++) {
+            const NullFitOut& fo = fit[b];
+            const double* rec = &probe_rec[(size_t)b * FLAT_REC];
+            const double gain = fo.curv / std::fabs(fo.lml);
+            double shift = (gain > 0.0 && gain == gain) ? std::min(1.0, STOP_SHIFT_C / gain) : 1.0;
+            if (!(rec[0] > flat_kappa)) shift = 1.0;
+            const double bq = rec[1] * shift, bp = rec[2] * shift;
+            if (o.bound_Q) o.bound_Q[R.done + b] = bq;
+            if (o.bound_p) o.bound_p[R.done + b] = bp;
+            if (!(bp <= 1e-5)) flat[b] |= 1;
+            if (!(bq <= 1e-6)) flat[b] |= 2;
+        }
+        return CRM_OK;
+    }
+
+    // 10.-11. per gene: Q and F, eigenvalues + Davies (or the exact tail), results
+    int gene_results(const Block& B, const SubRange& R, int gi) {
+        crm_gene* g = genes[gi];
+        const ScanOut& o = outs[gi];
+        const int nb = R.nb, BLK = P.BLK, b0 = R.b0;
+        const long done = R.done;
+        AssembleArgs aa{};
+        for (int i = 0; i < nrho; i++) {
+            AssembleRho& Rr = aa.rho[i];
+            Rr.ty = g->rot.as<double>() + (long)i * slab;
+            Rr.tW = Rr.ty + ldq; Rr.ldW = ldq;
+            Rr.S0 = bg->S0[i].as<double>();
+            Rr.T = ctx->ws_T.as<double>() + ((size_t)i * BLK + b0) * P.ldT; Rr.ldT = P.ldT;
+            Rr.r = bg->r[i];
+        }
+        aa.fit = d_fit + (size_t)gi * BLK + b0; aa.sorted_pos = d_pos + (size_t)gi * BLK;
+        aa.A = ctx->ws_A.as<double>(); aa.ldA = P.ldA; aa.k0 = k0; aa.c = c; aa.n = n; aa.A_none = ctx->ws_Anone.as<double>();
+        aa.Z1 = dZ1 + (size_t)gi * z1_sz * P.ks1; aa.ldZ1 = P.ldZ1; aa.Z2 = dZ2; aa.ldZ2 = P.ldZ2; aa.Z3 = dZ3; aa.ldZ3 = P.ldZ3;
+        aa.WW = g->WW.as<double>(); aa.Wy = g->Wy.as<double>(); aa.yy = g->yy;
+        aa.gg = d_gg + b0; aa.gy = d_gy + b0 + (size_t)gi * BLK; aa.gW = d_gW + (size_t)b0 * P.ld_gW; aa.ld_gW = P.ld_gW;
+        aa.coef = P.collapsed() ? nullptr : d_coef + b0; aa.ld_coef = P.ldb; aa.Q = d_Q; aa.F = ctx->ws_F.as<double>();
+        for (int i = 0; i < nrho; i++) aa.rho[i].rho = bg->rho[i];
+        if (P.wb()) {   // (assemble.hip: woodbury_kernel)
+            for (int i = 0; i < nrho; i++) {
+                AssembleRho& Rr = aa.rho[i];
+                Rr.ty = wb_yW + (size_t)gi * (1 + c) * P.ldwb;
+                Rr.tW = Rr.ty + P.ldwb; Rr.ldW = P.ldwb;
+                Rr.S0 = bg->wb_S0[i].as<double>();
+                Rr.T = wb_g + (size_t)b0 * P.ldwb; Rr.ldT = P.ldwb;
+                Rr.r = (int)bg->wb_P;
+            }
+            aa.sorted_pos = (ng == 1 ? d_pos : d_posw) + (size_t)gi * BLK; aa.A = ctx->ws_A.as<double>(); aa.ldA = P.ldAw;
+            aa.wb_k1 = bg->kin_k1; aa.wb_R = bg->wb_R.as<double>(); aa.wb_ldR = P.ldwb;
+            aa.wb_E1X = ctx->ws_S.as<double>(); aa.wb_ldE1X = P.ld_ah;
+            aa.wb_E1yW = wb_E1yW + (size_t)gi * bg->kin_k1 * 128; aa.wb_ldE1yW = 128;
+            aa.wb_E1g = ctx->ws_TH.as<double>() + b0; aa.wb_ldE1g = P.ldb; aa.wb_EE = bg->wb_EE.as<double>(); aa.wb_Gw = wb_Gw;
+        }
+        double* slow_ws = P.slow_forms ? ctx->ws_xwide.as<double>() : nullptr;   // (the null fits of the block are done: their scratch is free)
+        CRM_TRY(launch_assemble(st, aa, nb, ctx->ws_Gext.as<double>(), slow_ws));
+        CRM_TRY(launch_eig_davies(st, ctx->ws_F.as<double>(), d_Q, nb, k0, d_lam, d_pv, d_if, d_liu, true, slow_ws));
+        if (o.exact) {
+            CRM_TRY(launch_tail_pvalue(st, d_Q, d_lam, nb, k0, d_tp, d_tlp, d_tst));
+            if (o.logp) CRM_HIP(hipMemcpyAsync(o.logp + done, d_tlp, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+            if (o.status) CRM_HIP(hipMemcpyAsync(o.status + done, d_tst, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+        }
+        if (o.pv) CRM_HIP(hipMemcpyAsync(o.pv + done, o.exact ? d_tp : d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+        if (o.Q) CRM_HIP(hipMemcpyAsync(o.Q + done, d_Q, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+        if (o.lambda) CRM_HIP(hipMemcpyAsync(o.lambda + done * k0, d_lam, sizeof(double) * nb * k0, hipMemcpyDeviceToHost, st));
+        if (o.F) CRM_HIP(hipMemcpyAsync(o.F + done * k0 * k0, ctx->ws_F.ptr, sizeof(double) * nb * k0 * k0, hipMemcpyDeviceToHost, st));
+        if (o.ifault) CRM_HIP(hipMemcpyAsync(o.ifault + done, d_if, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+        if (o.liu) CRM_HIP(hipMemcpyAsync(o.liu + done, d_liu, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+        std::vector<char> flat;
+        std::vector<double> probe_rec;
+        if (o.flags) CRM_TRY(flat_probes(B, R, gi, aa, slow_ws, flat, probe_rec));
+        if (o.flags && ng == 1) {   // (diagnostics: what the probes measured, crm_test_null_fit_probe_read)
+            if (done == 0) ctx->probe_out.clear();
+            ctx->probe_out.insert(ctx->probe_out.end(), probe_rec.begin(), probe_rec.end());
+        }
+        const double rho_kappa = RHO_KAPPA * 1e-3 * form("flat_kappa_milli", 1000);
+        int rmax = 0;
+        for (int i = 0; i < nrho; i++) rmax = std::max(rmax, bg->r[i]);
+        const bool saturated = (long)rmax + c + 1 >= n;
+        const NullFitOut* fit = h_fit.data() + (size_t)gi * BLK + b0;
+        for (int b = 0; b < nb; b++) {
+            const NullFitOut& f = fit[b];
+            const double rho = bg->rho[f.rho_index];
+            if (o.flags) {
+                int fl = saturated ? CRM_MODEL_SATURATED : 0;
+                if (!(f.delta > 1e-8)) fl |= CRM_MODEL_DELTA_AT_ZERO;
+                if (!f.use_g) fl |= CRM_MODEL_G_IN_SPAN_W;
+                if (!flat.empty() && (flat[b] & 1)) fl |= CRM_MODEL_FLAT_OPTIMUM;
+                if (!flat.empty() && (flat[b] & 2)) fl |= CRM_MODEL_STATISTIC_AT_TOLERANCE;
+                if (f.rho_decision == f.rho_decision && !(f.rho_decision > rho_kappa)) fl |= CRM_MODEL_RHO_TIE;
+                o.flags[done + b] = fl;
+            }
+            if (o.rho1) o.rho1[done + b] = rho;
+            if (o.e2) o.e2[done + b] = f.v0 * rho;
+            if (o.g2) o.g2[done + b] = f.v0 * (1 - rho);
+            if (o.eps2) o.eps2[done + b] = f.v1;
+            if (o.lml) o.lml[done + b] = f.lml;
+            if (o.delta) o.delta[done + b] = f.delta;
+            if (o.scale) o.scale[done + b] = f.scale;
+        }
+        // the per-gene device buffers (Q, F, pv) are reused by the next gene
+        CRM_HIP(hipStreamSynchronize(st));
+        return CRM_OK;
+    }
+};
+
+// One pass over variants [first, first + count) for one or several genes that share the background,
+// the covariates W and the contexts E0 (several phenotypes against one panel).  What does not depend
+// on the phenotype is done once per block: the block copies, T(rho) = G'Q0(rho), the Khatri-Rao
+// contraction per (variant, rho) pair that at least one gene selected, and the y-free side
+// contractions.  Per gene: g'y, the null fits, E'(g o y), assembly, eigenvalues and Davies.
+//
+// allow_collapse = false keeps a grouped panel on the dense path; near_out (collapsed passes only) receives the positions
+// (relative to `first`) of the variants that are nearly collinear with the covariates -- scan_core repeats those on the
+// dense path, where the block is orthogonalised against W in the cell axis (blockops.hip: launch_ortho_block).
+static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long first, long count,
+                     const int* idx_E, const int* idx_G, const std::vector<ScanOut>& outs, bool allow_collapse,
+                     std::vector<long>* near_out) {
+    crm_gene* g0 = genes[0];
+    crm_background* bg = g0->bg;
+    crm_ctx* ctx = bg->ctx;
+    if (panel->ctx != ctx) {
+        set_error("scan: gene and panel live on different contexts");
+        return CRM_ERR_ARG;
+    }
+    if (panel->n != bg->n) {
+        set_error("scan: panel has %ld cells, background has %ld", panel->n, bg->n);
+        return CRM_ERR_ARG;
+    }
+    if (panel->grouped && panel->m + 1 > BLOCK_SLACK_MAX) {
+        set_error("scan: grouped panel with %ld groups (supported up to %d)", panel->m, BLOCK_SLACK_MAX - 1);
+        return CRM_ERR_UNSUPPORTED;
+    }
+    if (first < 0 || count < 0 || first + count > panel->p) {
+        set_error("scan: variants [%ld, %ld) outside the panel (p = %ld)", first, first + count, panel->p);
+        return CRM_ERR_ARG;
+    }
+    for (crm_gene* g : genes) {
+        // the shared pass computes g'W, the context features and the donor tables once, from the first
+        // gene's W and E0: the others must hold the same values, not just the same shapes
+        if (g->bg != bg || g->c != g0->c || g->k0 != g0->k0 || g->w_key != g0->w_key || g->e0_key != g0->e0_key) {
+            set_error("scan: genes of one call must share the background, W and E0 (contents, not only shapes)");
+            return CRM_ERR_ARG;
+        }
+    }
+    if (count == 0) return CRM_OK;
+    if (ctx->in_scan) {
+        set_error("scan: another scan is running on this context (started from a progress callback?); its work buffers are in use");
+        return CRM_ERR_UNSUPPORTED;
+    }
+    struct InScan { crm_ctx* c; explicit InScan(crm_ctx* c_) : c(c_) { c->in_scan = true; } ~InScan() { c->in_scan = false; } } in_scan(ctx);
+    // (the Gram kernel stages all k0 + c + 2 rows of a variant in LDS: refused here, before anything is launched, with
+    // the limit named; past 144 rows / 128 contexts the scan runs through the slower forms of its per-variant kernels)
+    if (g0->k0 + g0->c + 2 > CRM_MAX_GRAM_ROWS) {
+        set_error("interaction scan: %d contexts with %d covariate columns (supported: contexts + covariates + 2 <= %d; "
+                  "the association scans take up to %d covariate columns)", g0->k0, g0->c, CRM_MAX_GRAM_ROWS,
+                  CRM_MAX_COV_XWIDE);
+        return CRM_ERR_UNSUPPORTED;
+    }
+    if (ctx->polish && g0->c > CRM_MAX_COV) {
+        set_error("interaction scan: the null-fit polish is only built for up to %d covariate columns", CRM_MAX_COV);
+        return CRM_ERR_UNSUPPORTED;
+    }
+    CRM_HIP(hipSetDevice(ctx->device));
+    const long n = bg->n;
+    for (long i = 0; i < n; i++) {
+        if ((idx_E && (idx_E[i] < 0 || idx_E[i] >= n)) || (idx_G && (idx_G[i] < 0 || idx_G[i] >= n))) {
+            set_error("scan: permutation index out of range at position %ld", i);
+            return CRM_ERR_ARG;
+        }
+    }
+    if ((int)bg->s0_max.size() != bg->nrho) {   // (filled when the background was sealed / created)
+        set_error("scan: the background was not sealed");
+        return CRM_ERR_INTERNAL;
+    }
+    ScanPass S(genes, panel, first, count, idx_E, idx_G, outs, allow_collapse, near_out);
+    const ScanPlan& P = S.P;
+    CRM_TRY(S.workspaces());
+    CRM_TRY(S.prepare_contexts());
+    CRM_TRY(S.prepare_kinship());
+    CRM_TRY(S.prepare_woodbury());
+    for (long done = 0; done < count; done += P.BLK) {
+        Block B;
+        B.done = done;
+        B.col0 = first + done;
+        B.nb = (int)std::min<long>(P.BLK, count - done);
+        TraceRange range_block("crm scan block");
+        CRM_TRY(S.copy_block(B));
+        CRM_TRY(S.block_stats(B));
+        if (!P.fastT && !P.collapsed()) CRM_TRY(crm_background_require_q0(bg, -1));
+        if (ctx->replay_mode == 2) {
+            CRM_TRY(S.replay_block(B));
+        } else {
+            CRM_TRY(S.rotations(B));
+            CRM_TRY(S.null_fits(B));
+            if (ctx->probe_on) return CRM_OK;   // (test hook: the pass ends with this block's records)
+        }
+        if (P.wb()) CRM_TRY(S.woodbury_phi(B));
+        CRM_TRY(S.collect_fits(B));
+        for (int b0 = 0; b0 < B.nb;) {
+            const SubRange R = S.sub_range(B, b0);
+            Pairs Q;
+            CRM_TRY(S.select_pairs(B, R, Q));
+            CRM_TRY(S.form_A(B, R, Q));
+            CRM_TRY(S.side_contractions(B, R));
+            CRM_TRY(S.z1_products(B, R));
+            for (int gi = 0; gi < S.ng; gi++) CRM_TRY(S.gene_results(B, R, gi));
+            b0 += R.nb;
+        }
+        ctx->report(done + B.nb, count);   // (the reference's tqdm, :340)
     }
     return CRM_OK;
 }

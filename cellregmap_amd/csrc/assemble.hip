@@ -211,12 +211,17 @@ __device__ __forceinline__ void gram_dma16(gram_gptr_t src, double* lds_wave_uni
     __builtin_amdgcn_global_load_lds(src, (gram_lptr_t)lds_wave_uniform, 16, 0, 0);
 }
 
+constexpr int GRAM_QLD = 130;   // doubles per DMA instruction slot: 1 KB of operand rows + 2 of padding (both kernels)
+// dynamic LDS of gram_ext_dma_kernel<NTL>, in doubles: two chunk buffers of 8 NTL instruction slots, d [2][CH]
+constexpr int gram_dma_lds_doubles(int ntl) { return 2 * (8 * ntl) * GRAM_QLD + 2 * CH; }
+
 template <int NTL>
 __global__ __launch_bounds__(256) void gram_ext_dma_kernel(AssembleArgs a, double* __restrict__ Gext, int KT) {
     static_assert(NTL % 2 == 0, "row pairs of one DMA instruction must fall into different 16-row tiles");
     constexpr int ROWS = 16 * NTL, HALF = ROWS / 2, NTILES = NTL * (NTL + 1) / 2;
-    constexpr int QLD = 130;                 // doubles per DMA instruction slot (2 x 64 + 2 of padding)
+    constexpr int QLD = GRAM_QLD;            // doubles per DMA instruction slot (2 x 64 + 2 of padding)
     constexpr int BUF = HALF * QLD;          // doubles per chunk buffer
+    static_assert(gram_dma_lds_doubles(NTL) == 2 * BUF + 2 * CH, "the launch allocates what the kernel lays out");
     constexpr int IPW = HALF / 4;            // DMA instructions per wavefront and chunk
     constexpr int KSW = CH / 16;             // k-steps per wavefront and chunk (the four wavefronts split the chunk's columns)
     static_assert(2 * BUF >= 2 * NTILES * 256, "the accumulators of two wavefronts must fit the chunk buffers");
@@ -368,6 +373,171 @@ __global__ __launch_bounds__(256) void gram_ext_dma_kernel(AssembleArgs a, doubl
                     out[(long)row * KT + col] = v;
                     if (ti != tj) out[(long)col * KT + row] = v;
                 }
+            }
+        }
+    }
+}
+
+// The direct-to-LDS Gram for 5 to 9 tile rows (65-144 rows).  Keeping every tile in every wavefront, as the kernel above
+// does, would take 426 registers at 6 tile rows; here the upper-triangle tiles are dealt to the four wavefronts as in the
+// staged kernel (7 of 28 at 7 tile rows, a wavefront's tiles over all columns: no reduction at the end), which leaves
+// room for two wavefronts per SIMD up to 8 tile rows.  Chunks of 32 spectrum entries, so that two buffers of 128 rows
+// (65 KB) fit a CU twice.  A wave-instruction carries row q of four consecutive 16-row tiles (sixteen lanes each); LDS
+// image: instruction slot (16 * (tile / 4) + row in tile) at 130 doubles, the four tiles 32 doubles apart -- the sixteen
+// rows of a fragment read again start two 8-byte slots apart.  Tile rows are loaded in fours (rows past KT read row 0),
+// only the NTL (NTL + 1) / 2 tiles that exist are computed.
+// What is left on the table: every chunk ends in a __syncthreads(), which waits for the next chunk's DMA -- the loads
+// overlap the MFMAs of one chunk, no more (a third buffer with a counted vmcnt and a raw barrier was not tried); and the
+// tile rows loaded past KT are re-reads of row 0 (at 103 rows 25 of 128, a quarter of the DMA instructions' traffic).
+constexpr int GRAM_WCH = 32;    // spectrum entries per chunk of gram_ext_dma_wide_kernel
+// dynamic LDS of gram_ext_dma_wide_kernel<NTL>, in doubles: two chunk buffers of 16 ceil(NTL / 4) instruction slots,
+// d [2][GRAM_WCH], S0 as loaded [2][GRAM_WCH]
+constexpr int gram_dma_wide_lds_doubles(int ntl) { return 2 * (16 * ((ntl + 3) / 4)) * GRAM_QLD + 4 * GRAM_WCH; }
+
+template <int NTL>
+__global__ __launch_bounds__(256, NTL <= 8 ? 2 : 1) void gram_ext_dma_wide_kernel(AssembleArgs a, double* __restrict__ Gext,
+                                                                                  int KT) {
+    constexpr int WCH = GRAM_WCH;                  // spectrum entries per chunk
+    constexpr int SLOTS = 16 * ((NTL + 3) / 4);    // DMA instructions per chunk
+    constexpr int NTILES = NTL * (NTL + 1) / 2, MAXT = (NTILES + 3) / 4;
+    constexpr int QLD = GRAM_QLD;                  // doubles per DMA instruction slot (4 x 32 + 2 of padding)
+    constexpr int BUF = SLOTS * QLD;               // doubles per chunk buffer
+    static_assert(gram_dma_wide_lds_doubles(NTL) == 2 * BUF + 4 * WCH, "the launch allocates what the kernel lays out");
+    constexpr int IPW = SLOTS / 4;                 // DMA instructions per wavefront and chunk
+    extern __shared__ double Ss[];                 // [2][BUF] + d [2][WCH] + S0 [2][WCH]
+    double* const dS = Ss + 2 * BUF;
+    const int b = blockIdx.x;
+    const NullFitOut fit = a.fit[b];
+    const AssembleRho R = a.rho[fit.rho_index];
+    const int r = R.r;
+    const double ratio = fit.v0 / fit.v1;
+    const long pos = a.sorted_pos[b];
+    const double* __restrict__ Arows = pos >= 0 ? a.A + pos * a.k0 * a.ldA : a.A_none;
+    const long a_stride = pos >= 0 ? a.ldA : 0;      // (no position: every row is the row of zeros)
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, lq = lane >> 4;
+    const int k0 = a.k0, c = a.c;
+
+    // row -> pointer (rows past KT read row 0: their outputs are never stored)
+    auto row_ptr = [&](int row) -> const double* {
+        if (row >= KT) row = 0;
+        if (row < k0) return Arows + (long)row * a_stride;
+        const int t = row - k0;
+        if (t > c + 1) return a.wb_R + (long)(t - c - 2) * a.wb_ldR;   // (unrelated-donor form: the E1 rows)
+        return t < c ? R.tW + (long)t * R.ldW : (t == c ? R.T + (long)b * R.ldT : R.ty);
+    };
+    auto row_off = [](int row) { return (16 * (row >> 6) + (row & 15)) * QLD + ((row >> 4) & 3) * WCH; };
+    // this lane's source addresses (column pair 2 * (lane & 15) of the row its sixteen lanes carry)
+    gram_gptr_t src[IPW];
+#pragma unroll
+    for (int q = 0; q < IPW; q++) {
+        const int slot = wave + 4 * q;
+        src[q] = (gram_gptr_t)(row_ptr(64 * (slot >> 4) + 16 * lq + (slot & 15)) + 2 * l15);
+    }
+    // tiles of this wavefront: the entries first, first + 4, ... of the row-major upper triangle (MAXT or MAXT - 1 of
+    // them), rotated by the block index so that the SIMDs of a CU see the same load
+    const int first = (wave + b) & 3;
+    const int ntw = (NTILES - first + 3) / 4;
+    int t_i[MAXT], t_j[MAXT], t_ij[MAXT];
+#pragma unroll
+    for (int t = 0; t < MAXT; t++) {
+        int ti = 0, rem = first + 4 * t < NTILES ? first + 4 * t : 0;
+        while (rem >= NTL - ti) { rem -= NTL - ti; ti++; }
+        t_ij[t] = ti | ((ti + rem) << 8);
+        t_i[t] = row_off(16 * ti + l15) + lq;
+        t_j[t] = row_off(16 * (ti + rem) + l15) + lq;
+    }
+    v4d acc[MAXT];
+#pragma unroll
+    for (int t = 0; t < MAXT; t++) acc[t] = (v4d){0.0, 0.0, 0.0, 0.0};
+
+    const int nfull = r / WCH, nchunks = (r + WCH - 1) / WCH;
+    // d_j of a chunk (wavefront 0).  An ordinary load of S0 inside the loop would make the compiler wait for every LDS-DMA
+    // in flight where its result is first touched, so S0 comes in by LDS-DMA as well: 64 lanes x 4 bytes two chunks
+    // ahead (lanes past r re-read entry r - 1), turned into d_j one chunk ahead, a barrier after each step.
+    double* const sS = dS + 2 * WCH;               // S0 as loaded [2][WCH]
+    auto issue_s0 = [&](int ch) __attribute__((always_inline)) {
+        if (wave == 0 && ch < nchunks) {
+            const int j = ch * WCH + (lane >> 1);
+            const float* s0 = reinterpret_cast<const float*>(R.S0 + (j < r ? j : r - 1)) + (lane & 1);
+            __builtin_amdgcn_global_load_lds((const float __attribute__((address_space(1)))*)s0,
+                                             (gram_lptr_t)(sS + (ch & 1) * WCH), 4, 0, 0);
+        }
+    };
+    auto weights = [&](int ch, double s0) __attribute__((always_inline)) {
+        const double s = ch * WCH + lane < r ? ratio * s0 : 0.0;
+        dS[(ch & 1) * WCH + lane] = s / (1.0 + s);
+    };
+    auto issue = [&](int ch, int buf) __attribute__((always_inline)) {
+        if (ch < nfull) {
+#pragma unroll
+            for (int q = 0; q < IPW; q++)
+                gram_dma16(src[q] + (long)ch * WCH, Ss + buf * BUF + (wave + 4 * q) * QLD);
+        } else {   // the partial chunk: guarded element loads, zeros past r
+            for (int e = tid; e < 16 * NTL * WCH; e += 256) {
+                const int row = e / WCH, col = e - row * WCH;
+                const int j = ch * WCH + col;
+                Ss[buf * BUF + row_off(row) + col] = (j < r && row < KT) ? row_ptr(row)[j] : 0.0;
+            }
+        }
+    };
+    // MFMAs of one chunk for NT tiles; operand fragments are read one k-step ahead, the weight goes onto the B operand
+    auto chunk_mma = [&](int buf, auto nt_tag) __attribute__((always_inline)) {
+        constexpr int NT = decltype(nt_tag)::value;
+        const double* __restrict__ S = Ss + buf * BUF;
+        const double* __restrict__ D = dS + buf * WCH + lq;
+        double fa[2][NT], fb[2][NT];
+        {
+            const double dk = D[0];
+#pragma unroll
+            for (int t = 0; t < NT; t++) {
+                fa[0][t] = S[t_i[t]];
+                fb[0][t] = S[t_j[t]] * dk;
+            }
+        }
+#pragma unroll
+        for (int ks = 0; ks < WCH / 4; ks++) {
+            const int cur = ks & 1, nx = cur ^ 1;
+            if (ks + 1 < WCH / 4) {
+                const double dk = D[4 * (ks + 1)];
+#pragma unroll
+                for (int t = 0; t < NT; t++) {
+                    fa[nx][t] = S[t_i[t] + 4 * (ks + 1)];
+                    fb[nx][t] = S[t_j[t] + 4 * (ks + 1)] * dk;
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < NT; t++)
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cur][t], fb[cur][t], acc[t], 0, 0, 0);
+        }
+    };
+    if (wave == 0 && lane < WCH) weights(0, lane < r ? R.S0[lane] : 0.0);
+    issue_s0(1);
+    issue(0, 0);
+    __syncthreads();   // (drains the LDS-DMA: vmcnt(0) precedes the barrier)
+    for (int ch = 0; ch < nchunks; ch++) {
+        const int buf = ch & 1;
+        if (ch + 1 < nchunks) {
+            if (wave == 0 && lane < WCH) weights(ch + 1, sS[(buf ^ 1) * WCH + lane]);
+            issue(ch + 1, buf ^ 1);
+        }
+        issue_s0(ch + 2);
+        if (ntw == MAXT) chunk_mma(buf, std::integral_constant<int, MAXT>{});
+        else chunk_mma(buf, std::integral_constant<int, MAXT - 1>{});
+        __syncthreads();
+    }
+    double* __restrict__ out = Gext + (long)b * KT * KT;
+#pragma unroll
+    for (int t = 0; t < MAXT; t++) {
+        if (t >= ntw) continue;
+        const int ri = (t_ij[t] & 255) * 16, cj = (t_ij[t] >> 8) * 16;
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) {
+            const int row = ri + lq + 4 * reg, col = cj + l15;
+            if (row < KT && col < KT) {
+                out[(long)row * KT + col] = acc[t][reg];
+                if (ri != cj) out[(long)col * KT + row] = acc[t][reg];
             }
         }
     }
@@ -663,7 +833,8 @@ size_t assemble_rows_scratch_doubles(int variants, int k0, int c) {
     return lds > 150 * 1024 ? (size_t)variants * 2 * k0 * P : 0;
 }
 
-int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double* Gext, double* fin_rows) {
+int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double* Gext, double* fin_rows,
+                    long* dma_launches) {
     if (variants <= 0) return CRM_OK;
     const int KT0 = a.k0 + a.c + 2;
     // (unrelated-donor form: the Gram takes the k1 E1 rows as well, the correction folds them back into KT0 x KT0)
@@ -687,8 +858,8 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
         return CRM_ERR_UNSUPPORTED;
     }
     const int ts = (KT + 15) / 16;
-    // LDS-DMA form: 16-byte loads, so every row must start on a 16-byte boundary and hold an even number of doubles
-    bool dma = ts <= 4 && a.ldA % 2 == 0 && (reinterpret_cast<uintptr_t>(a.A) & 15) == 0 && !form("gram_staged", 0);
+    // LDS-DMA forms: 16-byte loads, so every row must start on a 16-byte boundary and hold an even number of doubles
+    bool dma = ts <= 9 && a.ldA % 2 == 0 && (reinterpret_cast<uintptr_t>(a.A) & 15) == 0 && !form("gram_staged", 0);
     for (int i = 0; dma && i < CRM_MAX_RHO; i++) {
         const AssembleRho& R = a.rho[i];
         if (R.r <= 0 && !R.ty) continue;
@@ -696,18 +867,26 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
                                                     reinterpret_cast<uintptr_t>(R.T)) & 15) == 0;
     }
     if (a.wb_k1 > 0) dma = dma && a.wb_ldR % 2 == 0 && (reinterpret_cast<uintptr_t>(a.wb_R) & 15) == 0;
-#define CRM_GRAM_DMA(NTL)                                                                                     \
+#define CRM_GRAM_DMA(KERNEL, LDS_DOUBLES, NTL)                                                                \
     do {                                                                                                      \
-        const size_t lds = sizeof(double) * (2 * (16 * NTL / 2) * 130 + 2 * CH);                              \
+        const size_t lds = sizeof(double) * LDS_DOUBLES(NTL);                                                 \
         if (lds > 60 * 1024)                                                                                  \
-            CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_ext_dma_kernel<NTL>),             \
+            CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&KERNEL<NTL>),                          \
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));               \
-        hipLaunchKernelGGL(gram_ext_dma_kernel<NTL>, dim3(variants), dim3(256), lds, st, a, Gext, KT);        \
+        hipLaunchKernelGGL(KERNEL<NTL>, dim3(variants), dim3(256), lds, st, a, Gext, KT);                     \
     } while (0)
+#define CRM_GRAM_DMA_WIDE(NTL) CRM_GRAM_DMA(gram_ext_dma_wide_kernel, gram_dma_wide_lds_doubles, NTL)
     if (dma) {
-        if (ts <= 2) CRM_GRAM_DMA(2);
-        else CRM_GRAM_DMA(4);   // (k0 + c + 2 > 64: 21 tiles per wavefront would leave one wavefront per SIMD -- staged kernel)
+        // (up to 4 tile rows every wavefront keeps every tile; past that the tiles are dealt to the wavefronts)
+        if (ts <= 2) CRM_GRAM_DMA(gram_ext_dma_kernel, gram_dma_lds_doubles, 2);
+        else if (ts <= 4) CRM_GRAM_DMA(gram_ext_dma_kernel, gram_dma_lds_doubles, 4);
+        else if (ts == 5) CRM_GRAM_DMA_WIDE(5);
+        else if (ts == 6) CRM_GRAM_DMA_WIDE(6);
+        else if (ts == 7) CRM_GRAM_DMA_WIDE(7);   // (unrelated-donor form at config 3: 50 + 3 + 50 rows)
+        else if (ts == 8) CRM_GRAM_DMA_WIDE(8);
+        else CRM_GRAM_DMA_WIDE(9);
     }
+#undef CRM_GRAM_DMA_WIDE
 #undef CRM_GRAM_DMA
 #define CRM_GRAM(NTL)                                                                                         \
     do {                                                                                                      \
@@ -728,7 +907,7 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
     } else if (ts <= 2) CRM_GRAM(2);
     else if (ts <= 4) CRM_GRAM(4);
     else if (ts <= 6) CRM_GRAM(6);
-    else if (ts <= 7) CRM_GRAM(7);   // (unrelated-donor form at config 3: 50 + 3 + 50 rows)
+    else if (ts <= 7) CRM_GRAM(7);
     else if (ts <= 9) CRM_GRAM(9);
     else if (ts <= 12) CRM_GRAM_GROUPS(12, 2);
     else if (ts <= 15) CRM_GRAM_GROUPS(15, 4);
@@ -736,6 +915,7 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
 #undef CRM_GRAM
 #undef CRM_GRAM_GROUPS
     CRM_HIP(hipGetLastError());
+    if (dma && dma_launches) ++*dma_launches;
     if (a.wb_k1 > 0) {
         const size_t lds = woodbury_lds_bytes(KT0, a.wb_k1);
         if (lds > 60 * 1024)

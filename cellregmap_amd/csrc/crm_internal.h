@@ -101,6 +101,7 @@ struct crm_ctx {
     long spectrum_tail_launches = 0;   // blocks whose last few columns of the spectrum went through the skinny one-pass kernel
     long donor_pair_blocks = 0;   // blocks whose per-donor sums came from the symmetric pair features (crm_test_donor_pair_blocks)
     long unrelated_donor_blocks = 0;   // blocks served by the unrelated-donor form (crm_test_unrelated_donor_blocks)
+    long gram_dma_launches = 0;   // score-statistic Grams that went through a direct-to-LDS kernel (crm_test_gram_dma_launches)
     long tests_without_pair = 0;  // (phenotype, variant) tests whose fit has no kinship term to speak of: no A~ formed for them
     // crm_scan_interaction_permuted: what the scan of a block computes BEFORE the permutation hooks enter -- the eleven
     // rotations T(rho) = G'Q0(rho), the null fits and rho* (cellregmap/_cellregmap.py:345-357 sit above the hooks at

@@ -209,8 +209,10 @@ struct AssembleArgs {
 };
 
 // Gext: workspace [variants x (k0+c+2)^2]; fin_rows: assemble_rows_scratch_doubles(...) doubles (0: not needed -- the
-// per-variant rows D'K^-1X and their solves fit LDS)
-int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double* Gext, double* fin_rows = nullptr);
+// per-variant rows D'K^-1X and their solves fit LDS); *dma_launches grows by one when the Gram went through a
+// direct-to-LDS kernel
+int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double* Gext, double* fin_rows = nullptr,
+                    long* dma_launches = nullptr);
 size_t assemble_rows_scratch_doubles(int variants, int k0, int c);
 // LDS of the unrelated-donor correction (assemble.hip: woodbury_kernel) for KT = k0 + c + 2 rows and k1 E1 columns
 size_t woodbury_lds_bytes(int KT, int k1);

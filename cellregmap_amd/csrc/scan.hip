@@ -2838,7 +2838,7 @@ struct ScanPass {
             CRM_HIP(hipGetLastError());
             AssembleArgs ap = aa;
             ap.fit = probe.as<NullFitOut>();
-            CRM_TRY(launch_assemble(st, ap, nb, ctx->ws_Gext.as<double>(), slow_ws));
+            CRM_TRY(launch_assemble(st, ap, nb, ctx->ws_Gext.as<double>(), slow_ws, &ctx->gram_dma_launches));
             CRM_TRY(launch_eig_davies(st, ctx->ws_F.as<double>(), d_Q, nb, k0, d_lam, d_pv, d_if, d_liu, true, slow_ws));
             CRM_HIP(hipMemcpyAsync(q1.data(), d_Q, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
             CRM_HIP(hipMemcpyAsync(p1.data(), d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
@@ -2917,7 +2917,7 @@ struct ScanPass {
             aa.wb_E1g = ctx->ws_TH.as<double>() + b0; aa.wb_ldE1g = P.ldb; aa.wb_EE = bg->wb_EE.as<double>(); aa.wb_Gw = wb_Gw;
         }
         double* slow_ws = P.slow_forms ? ctx->ws_xwide.as<double>() : nullptr;   // (the null fits of the block are done: their scratch is free)
-        CRM_TRY(launch_assemble(st, aa, nb, ctx->ws_Gext.as<double>(), slow_ws));
+        CRM_TRY(launch_assemble(st, aa, nb, ctx->ws_Gext.as<double>(), slow_ws, &ctx->gram_dma_launches));
         CRM_TRY(launch_eig_davies(st, ctx->ws_F.as<double>(), d_Q, nb, k0, d_lam, d_pv, d_if, d_liu, true, slow_ws));
         if (o.exact) {
             CRM_TRY(launch_tail_pvalue(st, d_Q, d_lam, nb, k0, d_tp, d_tlp, d_tst));
@@ -3258,6 +3258,13 @@ long crm_test_dense_repeats(const crm_ctx* ctx) { return ctx ? ctx->dense_repeat
 
 long crm_test_donor_pair_blocks(const crm_ctx* ctx) { return ctx ? ctx->donor_pair_blocks : -1; }
 
+int crm_test_gram_dma_launches(const crm_ctx* ctx, long* launches) {
+    return crm::guarded("crm_test_gram_dma_launches", [&]() -> int {
+    if (!ctx || !launches) return CRM_ERR_ARG;
+    *launches = ctx->gram_dma_launches;
+    return CRM_OK;
+    });
+}
 int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks) {
     return crm::guarded("crm_test_unrelated_donor_blocks", [&]() -> int {
     if (!ctx || !blocks) return CRM_ERR_ARG;

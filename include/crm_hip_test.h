@@ -11,7 +11,8 @@ extern "C" {
 #endif
 
 /* Kernel forms kept beside the default one (process-wide; reset != 0 returns the form to its default):
- *   "gram_staged" 1       score-statistic Gram through the register-staged kernel instead of the direct-to-LDS one
+ *   "gram_staged" 1       score-statistic Gram through the register-staged kernel instead of the direct-to-LDS ones (which
+ *                         serve up to 144 rows when every operand row starts on a 16-byte boundary)
  *   "kr_no_tail" 1        the product over the spectrum (Khatri-Rao contraction, or the mixing-matrix product of the
  *                         kinship-structure route) of a block in one launch of 128-column tiles whatever the spectrum
  *   "nullfit_per_wave" 1  null fits with one independent wavefront per (variant, grid point), not the LDS-shared queue
@@ -81,6 +82,9 @@ long crm_test_donor_pair_blocks(const crm_ctx* ctx);
  * (scan.hip: kin_wb; form "kin_diag": 0 never, 1 where the background allows it and the cost model says it pays, 2 wherever
  * the background and the shapes allow it -- k0 + c + 2 + k1 <= 144).  *blocks: the count so far. */
 int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks);
+/* Score-statistic Grams of this context's scans that went through a direct-to-LDS kernel (assemble.hip: up to 144 rows
+ * with 16-byte-aligned operands, form "gram_staged" = 0) and not through the register-staged one.  *launches: the count so far. */
+int crm_test_gram_dma_launches(const crm_ctx* ctx, long* launches);
 /* (phenotype, variant) tests of this context's scans whose selected fit has no kinship term to speak of --
  * (v0 / v1) max S0(rho*) <= 1e-10: delta at its upper clamp -- and for which no rotated test direction A~ was formed
  * (scan.hip; form "pairs_without_kinship_term" = 0 forms it for every test). */

@@ -94,6 +94,7 @@ SIGNATURES = {
     "crm_test_set_contraction_sync": (ctypes.c_int, [vp, ctypes.c_int]),
     "crm_test_sync_fallbacks": (ctypes.c_long, [vp]),
     "crm_test_overruns": (ctypes.c_long, []),
+    "crm_test_live_device_bytes": (ctypes.c_long, []),
     "crm_test_set_kinship_route": (ctypes.c_int, [vp, ctypes.c_int]),
     "crm_test_check_context": (ctypes.c_int, [vp]),
     "crm_test_overrun_selftest": (ctypes.c_int, [vp]),

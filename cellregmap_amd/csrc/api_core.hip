@@ -67,6 +67,8 @@ static bool poison_mode() {
 static constexpr size_t REDZONE = 4096;
 static std::atomic<long> g_overruns{0};
 long overruns_detected() { return g_overruns.load(); }
+static std::atomic<long> g_live_bytes{0};
+long live_device_bytes() { return g_live_bytes.load(); }
 
 static void check_redzone(const void* ptr, size_t bytes) {
     if (!ptr || !poison_mode()) return;
@@ -104,6 +106,7 @@ int DevBuf::ensure(size_t need) {
     if (ptr) {
         check_redzone(ptr, bytes);
         CRM_HIP(hipFree(ptr));
+        g_live_bytes -= (long)bytes;
         ptr = nullptr;
         bytes = 0;
     }
@@ -123,6 +126,7 @@ int DevBuf::ensure(size_t need) {
         return CRM_ERR_HIP;
     }
     bytes = need;
+    g_live_bytes += (long)need;
     // Fresh allocations never carry the previous tenant's bytes into a kernel: they are zero-filled (poison mode: 0xFF,
     // above).  The fill runs on the null stream and is waited for here: the contexts' streams are non-blocking and would
     // not order themselves behind it.
@@ -139,7 +143,7 @@ static size_t trim_context(crm_ctx* c) {
     if (!c->eigh_ws || c->eigh_ws_busy) return 0;
     size_t freed = 0;
     for (const DevBuf* b : {&c->eigh_ws->A, &c->eigh_ws->Vt, &c->eigh_ws->Vc, &c->eigh_ws->QA, &c->eigh_ws->QB}) freed += b->bytes;
-    eigh_free(*c->eigh_ws);
+    *c->eigh_ws = EighWork();
     return freed;
 }
 
@@ -164,6 +168,7 @@ size_t trim_idle_workspaces() {
 void DevBuf::release() {
     if (ptr) check_redzone(ptr, bytes);
     if (ptr) (void)hipFree(ptr);
+    g_live_bytes -= (long)bytes;
     ptr = nullptr;
     bytes = 0;
 }
@@ -236,13 +241,11 @@ void crm_ctx_destroy(crm_ctx* c) {
     {
         std::lock_guard<std::mutex> lock(g_ctx_mutex);
         g_contexts.erase(std::remove(g_contexts.begin(), g_contexts.end(), c), g_contexts.end());
-        if (c->eigh_ws) {
-            eigh_free(*c->eigh_ws);
-            delete c->eigh_ws;
-            c->eigh_ws = nullptr;
-        }
+        delete c->eigh_ws;
+        c->eigh_ws = nullptr;
     }
-    for (auto* b : c->all_bufs()) b->release();
+    c->replay_clear();
+    for (auto* b : c->all_bufs()) b->release();   // (before the streams go; `delete c` below finds them empty)
     for (auto& e : c->timed) {
         (void)hipEventDestroy(e.first);
         (void)hipEventDestroy(e.second);
@@ -385,6 +388,7 @@ int crm_test_set_contraction(crm_ctx* c, int tile_width, int lds_dma) {
 
 long crm_test_sync_fallbacks(const crm_ctx* c) { return c ? c->sync_fallbacks : -1; }
 long crm_test_overruns(void) { return crm::overruns_detected(); }
+long crm_test_live_device_bytes(void) { return crm::live_device_bytes(); }
 
 int crm_test_set_kinship_route(crm_ctx* c, int on) {
     return crm::guarded_on("crm_test_set_kinship_route", c, [&]() -> int {
@@ -400,7 +404,7 @@ int crm_test_overrun_selftest(crm_ctx* c) {
     CRM_HIP(hipSetDevice(c->device));
     const long before = overruns_detected();
     {
-        ScopedBuf b;
+        DevBuf b;
         CRM_TRY(b.ensure(1000));
         if (poison_mode()) CRM_HIP(hipMemset(static_cast<char*>(b.ptr) + 1000, 0, 8));   // eight bytes past the end, on purpose
         CRM_HIP(hipDeviceSynchronize());
@@ -455,7 +459,7 @@ int crm_test_contract(crm_ctx* c, long cells, int M, int N, const double* X, con
     CRM_HIP(hipSetDevice(c->device));
     const long cp = round_up(cells, GEMM_BK * (long)ksplit);
     const long ldx = round_up(M, 128), ldy = round_up(N, 128);
-    ScopedBuf bx, by, bc, bp;
+    DevBuf bx, by, bc, bp;
     CRM_TRY(bx.ensure(sizeof(double) * cp * ldx));
     CRM_TRY(by.ensure(sizeof(double) * cp * ldy));
     const long cstride = (long)M * ldy;
@@ -484,7 +488,7 @@ int crm_test_contract_kr(crm_ctx* c, long cells, int B, int k0, int N, const dou
     const long cp = round_up(cells, GEMM_BK);
     const long ldg = round_up(B, 128) + 128, lde = round_up(k0, 32), ldy = round_up(N, 128);
     const int M = B * k0;
-    ScopedBuf bg, be, by, bc, bp;
+    DevBuf bg, be, by, bc, bp;
     CRM_TRY(bg.ensure(sizeof(double) * cp * ldg));
     CRM_TRY(be.ensure(sizeof(double) * cp * lde));
     CRM_TRY(by.ensure(sizeof(double) * cp * ldy));
@@ -515,7 +519,7 @@ int crm_test_contract_kr_t(crm_ctx* c, long cells, int B, int k0, int N, const d
     const long ldg = round_up(B, 128) + 128, lde = round_up(k0, 32), ldy = round_up(N, 128);
     const int M = B * k0;
     const long ldc = round_up(M, 128);
-    ScopedBuf bg, be, by, bc, bp;
+    DevBuf bg, be, by, bc, bp;
     CRM_TRY(bg.ensure(sizeof(double) * cp * ldg));
     CRM_TRY(be.ensure(sizeof(double) * cp * lde));
     CRM_TRY(by.ensure(sizeof(double) * cp * ldy));
@@ -547,14 +551,14 @@ int crm_test_eigvalsh(crm_ctx* c, int count, int k, const double* F, double* lam
     return crm::guarded_on("crm_test_eigvalsh", c, [&]() -> int {
     if (!c || count <= 0 || k <= 0 || !F || !lambda) return CRM_ERR_ARG;
     CRM_HIP(hipSetDevice(c->device));
-    ScopedBuf bF, bQ, bL, bP;
+    DevBuf bF, bQ, bL, bP;
     CRM_TRY(bF.ensure(sizeof(double) * (size_t)count * k * k));
     CRM_TRY(bQ.ensure(sizeof(double) * count));
     CRM_TRY(bL.ensure(sizeof(double) * (size_t)count * k));
     CRM_TRY(bP.ensure(sizeof(double) * count));
     CRM_HIP(hipMemcpyAsync(bF.ptr, F, sizeof(double) * (size_t)count * k * k, hipMemcpyHostToDevice, c->stream));
     CRM_HIP(hipMemsetAsync(bQ.ptr, 0, sizeof(double) * count, c->stream));
-    ScopedBuf bS;
+    DevBuf bS;
     CRM_TRY(bS.ensure(sizeof(double) * eig_scratch_doubles(count, k)));
     CRM_TRY(launch_eig_davies(c->stream, bF.as<double>(), bQ.as<double>(), count, k, bL.as<double>(),
                               bP.as<double>(), nullptr, nullptr, true, bS.as<double>()));
@@ -569,7 +573,7 @@ int crm_test_davies(crm_ctx* c, int count, int k, const double* Q, const double*
     return crm::guarded_on("crm_test_davies", c, [&]() -> int {
     if (!c || count <= 0 || k <= 0 || !Q || !lambda || !pvalue) return CRM_ERR_ARG;
     CRM_HIP(hipSetDevice(c->device));
-    ScopedBuf bQ, bL, bP, bI, bU;
+    DevBuf bQ, bL, bP, bI, bU;
     CRM_TRY(bQ.ensure(sizeof(double) * count));
     CRM_TRY(bL.ensure(sizeof(double) * (size_t)count * k));
     CRM_TRY(bP.ensure(sizeof(double) * count));
@@ -592,7 +596,7 @@ int crm_test_tail_pvalue(crm_ctx* c, int count, int k, const double* Q, const do
     return crm::guarded_on("crm_test_tail_pvalue", c, [&]() -> int {
     if (!c || count <= 0 || k <= 0 || !Q || !lambda || !pvalue || !logp || !status) return CRM_ERR_ARG;
     CRM_HIP(hipSetDevice(c->device));
-    ScopedBuf bQ, bL, bP, bG, bS;
+    DevBuf bQ, bL, bP, bG, bS;
     CRM_TRY(bQ.ensure(sizeof(double) * count));
     CRM_TRY(bL.ensure(sizeof(double) * (size_t)count * k));
     CRM_TRY(bP.ensure(sizeof(double) * count));

@@ -119,13 +119,6 @@ __global__ void gather_vectors_kernel(const double* __restrict__ V, long ldv, co
     Q0[i * ldq + j] = V[(long)keep[j] * ldv + i];
 }
 
-struct Scratch {
-    DevBuf bufs[13];
-    ~Scratch() {
-        for (auto& b : bufs) b.release();
-    }
-};
-
 int contract(crm_ctx* ctx, const double* X, long ldx, const double* Y, long ldy, double* C, long ldc,
              int M, int N, long cells) {
     GemmProblem p{};
@@ -168,7 +161,7 @@ int gram_upper_then_mirror(crm_ctx* ctx, const double* X, long ldx, double* C, l
         p.M = std::min(n, (j + 1) * 128); p.N = std::min(128, n - j * 128);
         pr[j] = p;
     }
-    ScopedBuf d;
+    DevBuf d;
     CRM_TRY(d.ensure(sizeof(GemmProblem) * pr.size()));
     CRM_HIP(hipMemcpyAsync(d.ptr, pr.data(), sizeof(GemmProblem) * pr.size(), hipMemcpyHostToDevice, ctx->stream));
     CRM_TRY(launch_gemm_tn(ctx, d.as<GemmProblem>(), panels, n, 128, cells, false, 0, 1, 0));
@@ -216,7 +209,7 @@ __global__ void hadamard_halves_kernel(const double* __restrict__ U, int k2, con
 // grid points, the ranks are all-gathered, and Q0 / S0 / Mix of each grid point are broadcast by its owner
 // through crm_background_export / _import (cellregmap_amd/distributed.py).
 struct crm_background_builder {
-    Scratch S;
+    DevBuf scratch[13];
     std::vector<DevBuf> Mbuf;                  // per grid point: mixing matrix (thin) or eigenvectors (eigh)
     std::vector<std::vector<double>> S0_host;  // kept eigenvalues per grid point
     std::vector<int> mine;
@@ -224,10 +217,12 @@ struct crm_background_builder {
     int k1 = 0;
     bool thin = true, completed = false;
     double rel_tol = 1e-12;
-    ~crm_background_builder() {
-        for (auto& b : Mbuf) b.release();
-    }
 };
+
+crm_background::~crm_background() {
+    delete builder;
+    for (crm_donor_tables* t : dt_cache) delete t;
+}
 
 namespace {
 struct SetupTrace {
@@ -266,9 +261,8 @@ static int background_begin(crm_ctx* ctx, long n, const double* E1, int k1, cons
     const long cp = round_up(cols, 128);
     const bool thin = n > cols;  // economic_qs_linear: rows > cols -> SVD branch
 
-    crm_background* bg = new crm_background();
-    crm_background_builder* bb = new crm_background_builder();
-    bg->builder = bb;
+    Owned<crm_background> bg(new crm_background());
+    crm_background_builder* bb = bg->builder = new crm_background_builder();
     bg->ctx = ctx;
     bg->n = n;
     bg->n_pad = np;
@@ -281,47 +275,30 @@ static int background_begin(crm_ctx* ctx, long n, const double* E1, int k1, cons
         bg->r[i] = -1;
         if (!mine_flags || mine_flags[i]) bb->mine.push_back(i);
     }
-    auto fail = [&](int code) {
-        crm_background_destroy(bg);
-        return code;
-    };
-    int rc = CRM_OK;
-#define CRM_BG(call)                              \
-    do {                                          \
-        if ((rc = (call)) != CRM_OK) return fail(rc); \
-    } while (0)
-#define CRM_BG_HIP(call)                                                                    \
-    do {                                                                                    \
-        hipError_t e__ = (call);                                                            \
-        if (e__ != hipSuccess) {                                                            \
-            set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #call, hipGetErrorString(e__)); \
-            return fail(CRM_ERR_HIP);                                                       \
-        }                                                                                   \
-    } while (0)
-    DevBuf &dH = bb->S.bufs[0], &dHt = bb->S.bufs[1], &dC = bb->S.bufs[2], &dMt = bb->S.bufs[9], &dG = bb->S.bufs[10];
+    DevBuf &dH = bb->scratch[0], &dHt = bb->scratch[1], &dC = bb->scratch[2], &dMt = bb->scratch[9], &dG = bb->scratch[10];
     // H = [E1, B] (cells x cols) and its transpose
-    CRM_BG(dH.ensure(sizeof(double) * np * cp));
-    CRM_BG_HIP(hipMemsetAsync(dH.ptr, 0, sizeof(double) * np * cp, st));
-    CRM_BG_HIP(hipMemcpy2DAsync(dH.ptr, cp * sizeof(double), E1, k1 * sizeof(double), k1 * sizeof(double), n,
+    CRM_TRY(dH.ensure(sizeof(double) * np * cp));
+    CRM_HIP(hipMemsetAsync(dH.ptr, 0, sizeof(double) * np * cp, st));
+    CRM_HIP(hipMemcpy2DAsync(dH.ptr, cp * sizeof(double), E1, k1 * sizeof(double), k1 * sizeof(double), n,
                                 hipMemcpyHostToDevice, st));
     if (kb > 0 && B) {
-        CRM_BG_HIP(hipMemcpy2DAsync(dH.as<double>() + k1, cp * sizeof(double), B, kb * sizeof(double),
+        CRM_HIP(hipMemcpy2DAsync(dH.as<double>() + k1, cp * sizeof(double), B, kb * sizeof(double),
                                     kb * sizeof(double), n, hipMemcpyHostToDevice, st));
     } else if (kb > 0) {
-        ScopedBuf dU, dK;
-        CRM_BG(dU.ensure(sizeof(double) * n * k2));
-        CRM_BG(dK.ensure(sizeof(double) * n * m));
-        CRM_BG_HIP(hipMemcpyAsync(dU.ptr, U, sizeof(double) * n * k2, hipMemcpyHostToDevice, st));
-        CRM_BG_HIP(hipMemcpyAsync(dK.ptr, hK, sizeof(double) * n * m, hipMemcpyHostToDevice, st));
+        DevBuf dU, dK;
+        CRM_TRY(dU.ensure(sizeof(double) * n * k2));
+        CRM_TRY(dK.ensure(sizeof(double) * n * m));
+        CRM_HIP(hipMemcpyAsync(dU.ptr, U, sizeof(double) * n * k2, hipMemcpyHostToDevice, st));
+        CRM_HIP(hipMemcpyAsync(dK.ptr, hK, sizeof(double) * n * m, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(hadamard_halves_kernel, dim3((unsigned)n), dim3(256), 0, st, dU.as<double>(), k2,
                            dK.as<double>(), m, n, dH.as<double>(), cp, k1);
-        CRM_BG_HIP(hipGetLastError());
-        CRM_BG_HIP(hipStreamSynchronize(st));
+        CRM_HIP(hipGetLastError());
+        CRM_HIP(hipStreamSynchronize(st));
     }
     trace.lap("  upload of the half factor");
-    CRM_BG(dHt.ensure(sizeof(double) * cp * np));
-    CRM_BG_HIP(hipMemsetAsync(dHt.ptr, 0, sizeof(double) * cp * np, st));
-    CRM_BG(transpose(st, dH.as<double>(), cp, n, cols, dHt.as<double>(), np));
+    CRM_TRY(dHt.ensure(sizeof(double) * cp * np));
+    CRM_HIP(hipMemsetAsync(dHt.ptr, 0, sizeof(double) * cp * np, st));
+    CRM_TRY(transpose(st, dH.as<double>(), cp, n, cols, dHt.as<double>(), np));
     trace.lap("  transpose");
 
     const long dim = thin ? cols : n;       // order of the matrices that get diagonalised
@@ -329,29 +306,29 @@ static int background_begin(crm_ctx* ctx, long n, const double* E1, int k1, cons
     bb->dim = dim; bb->dimp = dimp;
     if (thin) {
         // Gram matrix of the unscaled half factor, once
-        CRM_BG(dC.ensure(sizeof(double) * cp * cp));
-        CRM_BG_HIP(hipMemsetAsync(dC.ptr, 0, sizeof(double) * cp * cp, st));   // (its padding is an operand later)
-        CRM_BG(gram_upper_then_mirror(ctx, dH.as<double>(), cp, dC.as<double>(), cp, (int)cols, np));
+        CRM_TRY(dC.ensure(sizeof(double) * cp * cp));
+        CRM_HIP(hipMemsetAsync(dC.ptr, 0, sizeof(double) * cp * cp, st));   // (its padding is an operand later)
+        CRM_TRY(gram_upper_then_mirror(ctx, dH.as<double>(), cp, dC.as<double>(), cp, (int)cols, np));
     } else {
         // E1 E1' and B B' (n x n), contraction over the column axis = rows of Ht; row blocks are
         // copied into zero-padded scratch so that their counts are multiples of the stage depth
         const long k1p = round_up(k1, GEMM_BK), kbp = round_up(std::max<long>(kb, 1), GEMM_BK);
-        CRM_BG(dG.ensure(sizeof(double) * dimp * dimp * 2));
-        CRM_BG(dMt.ensure(sizeof(double) * (k1p + kbp) * np));
+        CRM_TRY(dG.ensure(sizeof(double) * dimp * dimp * 2));
+        CRM_TRY(dMt.ensure(sizeof(double) * (k1p + kbp) * np));
         double* S1 = dG.as<double>();
         double* S2 = S1 + dimp * dimp;
         double* E1t = dMt.as<double>();
         double* Bt = E1t + k1p * np;
-        CRM_BG_HIP(hipMemsetAsync(dG.ptr, 0, sizeof(double) * dimp * dimp * 2, st));
-        CRM_BG_HIP(hipMemsetAsync(E1t, 0, sizeof(double) * (k1p + kbp) * np, st));
-        CRM_BG_HIP(hipMemcpyAsync(E1t, dHt.ptr, sizeof(double) * k1 * np, hipMemcpyDeviceToDevice, st));
+        CRM_HIP(hipMemsetAsync(dG.ptr, 0, sizeof(double) * dimp * dimp * 2, st));
+        CRM_HIP(hipMemsetAsync(E1t, 0, sizeof(double) * (k1p + kbp) * np, st));
+        CRM_HIP(hipMemcpyAsync(E1t, dHt.ptr, sizeof(double) * k1 * np, hipMemcpyDeviceToDevice, st));
         if (kb > 0)
-            CRM_BG_HIP(hipMemcpyAsync(Bt, dHt.as<double>() + (long)k1 * np, sizeof(double) * kb * np,
+            CRM_HIP(hipMemcpyAsync(Bt, dHt.as<double>() + (long)k1 * np, sizeof(double) * kb * np,
                                       hipMemcpyDeviceToDevice, st));
-        CRM_BG(contract(ctx, E1t, np, E1t, np, S1, dimp, (int)n, (int)n, k1p));
-        if (kb > 0) CRM_BG(contract(ctx, Bt, np, Bt, np, S2, dimp, (int)n, (int)n, kbp));
+        CRM_TRY(contract(ctx, E1t, np, E1t, np, S1, dimp, (int)n, (int)n, k1p));
+        if (kb > 0) CRM_TRY(contract(ctx, Bt, np, Bt, np, S2, dimp, (int)n, (int)n, kbp));
     }
-    CRM_BG_HIP(hipStreamSynchronize(st));
+    CRM_HIP(hipStreamSynchronize(st));
     trace.lap("half factor + Gram");
     // eigen-decompositions of the owned grid points (eigh*.hip), all at once -- except that a grid point whose second
     // weight vanishes (rho = 1 in the thin branch: hS = [E1, 0]) has a scaled Gram matrix that is zero outside its
@@ -425,7 +402,7 @@ static int background_begin(crm_ctx* ctx, long n, const double* E1, int k1, cons
         CRM_TRY(eigh_batched(ctx, ew, lam.data(), &Zt));
         trace.lap("eigen-decompositions");
         }
-        ScopedBuf wKeep, wLam;
+        DevBuf wKeep, wLam;
         CRM_TRY(wKeep.ensure(sizeof(int) * (subp + 128)));
         CRM_TRY(wLam.ensure(sizeof(double) * (subp + 128)));
         for (int q = 0; q < npts; q++) {
@@ -470,10 +447,10 @@ static int background_begin(crm_ctx* ctx, long n, const double* E1, int k1, cons
         }
         return CRM_OK;
     };
-    CRM_BG(decompose(full_pts, dim));
-    CRM_BG(decompose(lead_pts, k1));
+    CRM_TRY(decompose(full_pts, dim));
+    CRM_TRY(decompose(lead_pts, k1));
     trace.lap("  mixing matrices");
-    *out = bg;
+    *out = bg.release();
     return CRM_OK;
 }
 
@@ -504,16 +481,14 @@ static int background_complete(crm_background* bg, const int* r_all) {
     }
     bg->ldq = round_up(rmax, 128);
     const long ldq = bg->ldq;
-    DevBuf &dH = bb->S.bufs[0], &dHt = bb->S.bufs[1], &dC = bb->S.bufs[2], &dMt = bb->S.bufs[9], &dG = bb->S.bufs[10],
-           &dErr = bb->S.bufs[11], &dQt = bb->S.bufs[12], &dT1 = bb->S.bufs[3];
+    DevBuf &dH = bb->scratch[0], &dHt = bb->scratch[1], &dC = bb->scratch[2], &dMt = bb->scratch[9], &dG = bb->scratch[10],
+           &dErr = bb->scratch[11], &dQt = bb->scratch[12], &dT1 = bb->scratch[3];
     dG.release();
     dMt.release();
     if (thin) {
         // keep the half factor: T(rho) = Q0(rho)'G is later taken as Mix(rho)' (H'G), see scan.hip
-        bg->H = dH;
-        dH = DevBuf();
-        bg->Ht = dHt;   // (its transpose: operand of Q0 = H Mix, formed on first use)
-        dHt = DevBuf();
+        bg->H = std::move(dH);
+        bg->Ht = std::move(dHt);   // (its transpose: operand of Q0 = H Mix, formed on first use)
         bg->ldh = cp;
         bg->cols = cols;
     } else {
@@ -694,21 +669,16 @@ static int background_seal(crm_background* bg) {
     }
     return CRM_OK;
 }
-#undef CRM_BG
-#undef CRM_BG_HIP
 
 static int background_create_core(crm_ctx* ctx, long n, const double* E1, int k1, const double* B, long kb,
                                   const double* U, int k2, const double* hK, int m, int nrho,
                                   const double* rho, double rel_tol, crm_background** out) {
-    crm_background* bg = nullptr;
-    CRM_TRY(background_begin(ctx, n, E1, k1, B, kb, U, k2, hK, m, nrho, rho, nullptr, rel_tol, &bg));
-    int rc = background_complete(bg, nullptr);
-    if (rc == CRM_OK) rc = background_seal(bg);
-    if (rc != CRM_OK) {
-        crm_background_destroy(bg);
-        return rc;
-    }
-    *out = bg;
+    crm_background* begun = nullptr;
+    CRM_TRY(background_begin(ctx, n, E1, k1, B, kb, U, k2, hK, m, nrho, rho, nullptr, rel_tol, &begun));
+    Owned<crm_background> bg(begun);
+    CRM_TRY(background_complete(bg.get(), nullptr));
+    CRM_TRY(background_seal(bg.get()));
+    *out = bg.release();
     return CRM_OK;
 }
 
@@ -840,4 +810,79 @@ int crm_background_require_q0(crm_background* bg, int i) {
     return CRM_OK;
 }
 
-void crm_background_builder_free(crm_background_builder* b) { delete b; }
+// ---- a background from given spectra; destruction and read-back ------------------------------------------------
+extern "C" {
+
+int crm_background_create_qs(crm_ctx* ctx, long n, int nrho, const double* rho, const int* r,
+                             const double* const* Q0, const double* const* S0,
+                             crm_background** out) {
+    return crm::guarded_on("crm_background_create_qs", ctx, [&]() -> int {
+    if (!ctx || !out || n <= 0 || nrho < 1 || !rho || !r || !Q0 || !S0) return CRM_ERR_ARG;
+    if (nrho > CRM_MAX_RHO) {
+        set_error("background: %d grid points (supported up to %d)", nrho, CRM_MAX_RHO);
+        return CRM_ERR_UNSUPPORTED;
+    }
+    *out = nullptr;
+    CRM_HIP(hipSetDevice(ctx->device));
+    Owned<crm_background> bg(new crm_background());
+    bg->ctx = ctx;
+    bg->n = n;
+    bg->n_pad = round_up(n, CELL_PAD);
+    bg->nrho = nrho;
+    long rmax = 1;
+    for (int i = 0; i < nrho; i++) {
+        if (r[i] < 0) return CRM_ERR_ARG;
+        bg->rho[i] = rho[i];
+        bg->r[i] = r[i];
+        rmax = std::max<long>(rmax, r[i]);
+    }
+    bg->ldq = round_up(rmax, 128);
+    for (int i = 0; i < nrho; i++) {
+        CRM_TRY(bg->Q0[i].ensure(sizeof(double) * bg->n_pad * bg->ldq));
+        CRM_TRY(bg->S0[i].ensure(sizeof(double) * bg->ldq));
+        CRM_TRY(upload_padded(ctx->stream, bg->Q0[i].as<double>(), bg->ldq, bg->n_pad, Q0[i], r[i], n, r[i]));
+        CRM_TRY(upload_padded(ctx->stream, bg->S0[i].as<double>(), bg->ldq, 1, S0[i], r[i], 1, r[i]));
+        bg->q0_ready[i] = true;
+    }
+    bg->s0_max.assign(nrho, 0.0);   // (as background_seal leaves it for the backgrounds the library decomposes itself)
+    for (int i = 0; i < nrho; i++)
+        for (int j = 0; j < r[i]; j++) bg->s0_max[i] = std::max(bg->s0_max[i], S0[i][j]);
+    CRM_HIP(hipStreamSynchronize(ctx->stream));
+    *out = bg.release();
+    return CRM_OK;
+    });
+}
+
+void crm_background_destroy(crm_background* bg) {
+    try {
+    if (!bg) return;
+    std::lock_guard<std::recursive_mutex> lock(bg->ctx->mu);   // (reachable from a finalizer on any thread)
+    (void)hipSetDevice(bg->ctx->device);
+    (void)hipStreamSynchronize(bg->ctx->stream);
+    delete bg;
+    } catch (...) {  // (nothing may unwind into the caller; a destroy has no status to return)
+    }
+}
+
+int crm_background_rank(const crm_background* bg, int i) {
+    return crm::guarded_on("crm_background_rank", bg ? bg->ctx : nullptr, [&]() -> int {
+    if (!bg || i < 0 || i >= bg->nrho) return -1;
+    return bg->r[i];
+    });
+}
+
+int crm_background_read(const crm_background* bg, int i, double* Q0, double* S0) {
+    return crm::guarded_on("crm_background_read", bg ? bg->ctx : nullptr, [&]() -> int {
+    if (!bg || i < 0 || i >= bg->nrho) return CRM_ERR_ARG;
+    if (Q0) CRM_TRY(crm_background_require_q0(const_cast<crm_background*>(bg), i));
+    CRM_HIP(hipSetDevice(bg->ctx->device));
+    const int r = bg->r[i];
+    if (Q0 && r > 0)
+        CRM_HIP(hipMemcpy2D(Q0, r * sizeof(double), bg->Q0[i].ptr, bg->ldq * sizeof(double),
+                            r * sizeof(double), bg->n, hipMemcpyDeviceToHost));
+    if (S0 && r > 0) CRM_HIP(hipMemcpy(S0, bg->S0[i].ptr, r * sizeof(double), hipMemcpyDeviceToHost));
+    return CRM_OK;
+    });
+}
+
+}  // extern "C"

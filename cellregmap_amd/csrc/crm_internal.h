@@ -3,6 +3,7 @@
 #include <map>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <utility>
 
 #include "crm_common.h"
@@ -20,22 +21,31 @@ constexpr int CRM_MAX_GRAM_ROWS = 288;   // contexts + covariate columns + 2 in 
 constexpr int DT_SUMS_LD = 136;        // columns of the per-donor sums table (1 + 1 + c, c <= CRM_MAX_COV_XWIDE = 128)
 constexpr int BLOCK_SLACK_MAX = 4096;  // groups of a donor-constant panel
 
+// A device allocation and its owner: move-only, released by the destructor, so an object that holds DevBuf members gives
+// its device memory back when it is deleted and a half-built one cannot leak it.  No DevBuf may have static or thread
+// storage duration: its destructor would run after the HIP runtime has been torn down.
 struct DevBuf {
     void* ptr = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            release();
+            ptr = o.ptr; bytes = o.bytes;
+            o.ptr = nullptr; o.bytes = 0;
+        }
+        return *this;
+    }
+    ~DevBuf() { release(); }
     int ensure(size_t need);
-    void release();
+    void release();   // (never reports: hipFree's status is dropped)
     template <class T>
     T* as() const { return static_cast<T*>(ptr); }
 };
-
-// temporary device buffer released on scope exit (error paths included)
-struct ScopedBuf : DevBuf {
-    ScopedBuf() = default;
-    ScopedBuf(const ScopedBuf&) = delete;
-    ScopedBuf& operator=(const ScopedBuf&) = delete;
-    ~ScopedBuf() { release(); }
-};
+static_assert(!std::is_copy_constructible<DevBuf>::value, "DevBuf owns its allocation");
 
 int upload_padded(hipStream_t st, double* dst, long ld_dst, long rows_pad, const double* src,
                   long ld_src, long rows, long cols);
@@ -46,6 +56,8 @@ struct EighWork;
 size_t trim_idle_workspaces();
 // CRM_POISON=1: device buffers whose red zone was found overwritten when they were released
 long overruns_detected();
+// bytes held by the live DevBuf allocations of the process (crm_test_live_device_bytes)
+long live_device_bytes();
 }  // namespace crm
 struct crm_ctx;
 namespace crm {
@@ -118,7 +130,7 @@ struct crm_ctx {
     size_t replay_cursor = 0;
     std::vector<ReplayBlock*> replay_blocks;
     void replay_clear() {
-        for (ReplayBlock* b : replay_blocks) { b->T.release(); delete b; }
+        for (ReplayBlock* b : replay_blocks) delete b;
         replay_blocks.clear();
         replay_cursor = 0;
         replay_mode = 0;

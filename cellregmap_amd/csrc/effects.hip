@@ -60,7 +60,7 @@ extern "C" int crm_lmm_fit(crm_gene* gene, int restricted, double* out_fit, doub
     const long slab = (long)(1 + c) * ldq;
     const long ld_gW = round_up(std::max(c, 8), 8);
 
-    ScopedBuf small;
+    DevBuf small;
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     const size_t o_zero = carve(sizeof(double) * ldq), o_g3 = carve(sizeof(double) * (2 + ld_gW)),
@@ -89,7 +89,7 @@ extern "C" int crm_lmm_fit(crm_gene* gene, int restricted, double* out_fit, doub
     fa.gg = d_g3; fa.gy = d_g3 + 1; fa.gW = d_g3 + 2; fa.ld_gW = ld_gW;
     fa.trial = (NullFitTrial*)(sm + o_trial);
     fa.out = (NullFitOut*)(sm + o_fit);
-    ScopedBuf xwide;
+    DevBuf xwide;
     if (c > CRM_MAX_COV_WIDE) {   // 63 .. 128 columns: the slower kernel with its scratch in global memory
         CRM_TRY(xwide.ensure(sizeof(double) * nullfit_xwide_scratch_doubles(1, nrho, c)));
         fa.xwide = xwide.as<double>();
@@ -160,7 +160,7 @@ extern "C" int crm_cov_solve(crm_background* bg, int rho_index, double v0, doubl
     const long n = bg->n, np = bg->n_pad, ldq = bg->ldq;
     const int r = bg->r[rho_index];
     const long ldr = round_up(m, 128);
-    ScopedBuf d_rhs, d_T, d_out, d_prob;
+    DevBuf d_rhs, d_T, d_out, d_prob;
     CRM_TRY(d_rhs.ensure(sizeof(double) * np * ldr));
     CRM_TRY(d_T.ensure(sizeof(double) * ldr * ldq));
     CRM_TRY(d_out.ensure(sizeof(double) * n * m));

@@ -530,7 +530,7 @@ extern "C" int crm_effects_multi(crm_ctx* ctx, crm_background* bg, long n, const
 
     const long ldxe = round_up(cW + k0, 128), lde = round_up(k0, 32), ldy = round_up(ny, 128);
     const long ldg = round_up(VARIANT_BLOCK, 128) + 128;
-    ScopedBuf d_xe, d_e, d_y, d_g, d_txe, d_ty, d_tg, d_tu, d_probs, d_pv, d_pp, d_cp, d_px, d_trial, d_fit, d_beta, d_u;
+    DevBuf d_xe, d_e, d_y, d_g, d_txe, d_ty, d_tg, d_tu, d_probs, d_pv, d_pp, d_cp, d_px, d_trial, d_fit, d_beta, d_u;
     CRM_TRY(d_xe.ensure(sizeof(double) * n_pad * ldxe));
     CRM_TRY(d_y.ensure(sizeof(double) * n_pad * ldy));
     CRM_TRY(d_g.ensure(sizeof(double) * n_pad * ldg));

@@ -45,7 +45,6 @@ struct EighWork {
 // order and *Zt points at a [batch] x slab device array whose row j (of matrix b) is the eigenvector that
 // belongs to lam[b][j] (i.e. column-major eigenvector matrices with leading dimension w.ld).
 int eigh_alloc(EighWork& w, int batch, long dim);
-void eigh_free(EighWork& w);
 int eigh_batched(crm_ctx* ctx, EighWork& w, double* lam_host, double** Zt);
 
 // phases (also reachable one by one through the test hooks)

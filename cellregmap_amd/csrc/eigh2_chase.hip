@@ -389,7 +389,6 @@ extern "C" int crm_test_eigh2(crm_ctx* ctx, int nq, int dim, const double* C, co
     CRM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     EighWork w;
-    struct Guard { EighWork& w; ~Guard() { eigh_free(w); } } guard{w};
     CRM_TRY(eigh_alloc(w, nq, dim));
     CRM_HIP(hipMemsetAsync(w.A.ptr, 0, sizeof(double) * (size_t)nq * w.slab, st));
     CRM_HIP(hipMemcpy2DAsync(w.A.as<double>(), w.ld * sizeof(double), C, dim * sizeof(double), dim * sizeof(double), dim,

@@ -128,12 +128,6 @@ int eigh_alloc(EighWork& w, int batch, long dim) {
     return CRM_OK;
 }
 
-void eigh_free(EighWork& w) {
-    for (DevBuf* b : {&w.A, &w.Vt, &w.Vc, &w.QA, &w.QB, &w.d, &w.e, &w.tau, &w.lam, &w.small, &w.AB, &w.Vbc, &w.taubc, &w.Tbc, &w.s1,
-                      &w.sync})
-        b->release();
-}
-
 // Qt: rows = eigenvectors of the tridiagonal (sorted); returns *Zt: rows = eigenvectors of A.
 int eigh_rows_to_columns(crm_ctx* ctx, EighWork& w, const double* Qt) {
     hipStream_t st = ctx->stream;
@@ -307,7 +301,6 @@ extern "C" int crm_test_eigh(crm_ctx* ctx, int batch, int dim, const double* A, 
     CRM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     EighWork w;
-    struct Guard { EighWork& w; ~Guard() { eigh_free(w); } } guard{w};
     CRM_TRY(eigh_alloc(w, batch, dim));
     CRM_HIP(hipMemsetAsync(w.A.ptr, 0, sizeof(double) * (size_t)batch * w.slab, st));
     for (int b = 0; b < batch; b++)

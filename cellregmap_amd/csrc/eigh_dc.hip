@@ -432,10 +432,10 @@ int eigh_dc(crm_ctx* ctx, EighWork& w, double* lam_host, double** Qt_out) {
         }
     // ---- device scratch -------------------------------------------------------------------------------
     const int max_nodes = (int)leaves.size();
-    ScopedBuf dDcut, dLeaf, dLamA, dLamB, dZ, dDl, dW, dZhat, dTau, dOrg, dSrc, dRowNode, dNodes, dDesc, dRots, dProbs;
+    DevBuf dDcut, dLeaf, dLamA, dLamB, dZ, dDl, dW, dZhat, dTau, dOrg, dSrc, dRowNode, dNodes, dDesc, dRots, dProbs;
     CRM_TRY(dDcut.ensure(sizeof(double) * (size_t)B * ld));
     CRM_TRY(dLeaf.ensure(sizeof(int) * 2 * leaves.size()));
-    for (ScopedBuf* bf : {&dLamA, &dLamB, &dZ, &dDl, &dW, &dZhat, &dTau}) CRM_TRY(bf->ensure(sizeof(double) * (size_t)B * ld));
+    for (DevBuf* bf : {&dLamA, &dLamB, &dZ, &dDl, &dW, &dZhat, &dTau}) CRM_TRY(bf->ensure(sizeof(double) * (size_t)B * ld));
     CRM_TRY(dOrg.ensure(sizeof(int) * (size_t)B * ld));
     CRM_TRY(dSrc.ensure(sizeof(int) * (size_t)B * ld));
     CRM_TRY(dRowNode.ensure(sizeof(int) * ld));

@@ -1,6 +1,12 @@
 // Device-resident objects behind the opaque handles of include/crm_hip.h.
+//
+// Ownership: an object holds its device memory in DevBuf members, which release themselves, so deleting the object gives
+// all of it back and no list of buffers is kept anywhere.  crm_*_destroy sets the device, takes the context's lock, waits
+// for the stream (kernels may still be reading the buffers) and deletes.  A constructor builds into an Owned<> from `new`
+// to `*out = obj.release()`: whatever return leaves it early destroys the half-built object the same way.
 #pragma once
 #include <cmath>
+#include <memory>
 
 #include "crm_internal.h"
 
@@ -19,14 +25,13 @@ struct crm_donor_tables {
     crm::DevBuf Bd;   // [nrho][(m_pad*k0) x ldq]     KR(Z, E0)' Q0(rho)
     crm::DevBuf Z2;   // [m_pad x ld]  Z'E   (or the m*m-row mixed table under idx_G)
     crm::DevBuf Z3;   // [m_pad x ld]  Z'(E (x) E)
-    void release() { TZ.release(); Bd.release(); Z2.release(); Z3.release(); }
 };
 
 struct crm_background_builder;   // state of a constructor in progress (background.hip)
-void crm_background_builder_free(crm_background_builder*);
 
 // Sigma(rho) = Q0 diag(S0) Q0' for every grid point (cellregmap/_cellregmap.py:95-131).
 struct crm_background {
+    ~crm_background();                            // (background.hip: the builder and the cached donor tables go with it)
     crm_background_builder* builder = nullptr;   // non-null between `begin` and `seal`
     crm_ctx* ctx = nullptr;
     long n = 0, n_pad = 0;
@@ -145,3 +150,27 @@ struct crm_panel {
     crm::DevBuf Z;      // [n_pad x ldz] 0/1 indicator of the groups (operand of the table builds)
     long ldz = 0;
 };
+
+namespace crm {
+// Owner of an object under construction: its deleter is the object's crm_*_destroy (which takes the context's recursive
+// lock, held or not by the constructor that lets go of the object).
+template <class T> struct Destroy;
+template <> struct Destroy<crm_background> { void operator()(crm_background* p) const { crm_background_destroy(p); } };
+template <> struct Destroy<crm_gene> { void operator()(crm_gene* p) const { crm_gene_destroy(p); } };
+template <> struct Destroy<crm_panel> { void operator()(crm_panel* p) const { crm_panel_destroy(p); } };
+template <class T> using Owned = std::unique_ptr<T, Destroy<T>>;
+
+// content hash of a host array: keys of the shared donor tables and of the genes of a multi-gene pass (gene.hip)
+unsigned long content_key(const void* data, size_t bytes, unsigned long seed);
+
+// kinship.hip: one Jacobi rotation of a k x k row-major symmetric A and of the accumulated V (columns p, q)
+void jacobi_rotate(int k, double* A, double* V, int p, int q, double cs, double sn);
+
+// donor_tables.hip: the per-donor tables of the collapsed path for one gene and grouped panel (shared != nullptr: the
+// phenotype-free ones as well), and the two of its kernels the scan launches per call / per block
+int build_donor_tables(crm_gene* gene, const crm_panel* panel, crm_donor_tables* shared, const double* d_Ep, const double* d_EE,
+                       const double* Zt, bool cross);
+int launch_permute_group(hipStream_t st, const int* group, const int* idx, long n, int* out);   // out[i] = group[idx[i]]
+int launch_donor_cross(hipStream_t st, int nb, const double* Gam, long ld_gam, int m, const double* C, long ldc, int k0,
+                       double* Z2, long ldz2);
+}  // namespace crm

@@ -1,10 +1,9 @@
-// Host orchestration of the interaction scan behind the C-ABI: device-resident background,
-// gene and genotype-panel objects, and the per-block kernel pipeline
+// Host orchestration of the interaction scan behind the C-ABI: the scan plan and the per-block kernel pipeline
 //   stats -> T(rho) = G' Q0(rho) -> null fits + rho* -> sort by rho* -> Khatri-Rao contraction
 //   -> side contractions -> assemble (Q, F) -> eigenvalues + Davies.
-// Reference loop being replaced: cellregmap/_cellregmap.py:340-436.
+// Reference loop being replaced: cellregmap/_cellregmap.py:340-436.  The objects it works on are built elsewhere:
+// background.hip, kinship.hip, gene.hip, panel.hip, donor_tables.hip.
 #include <algorithm>
-#include <atomic>
 
 #include "nullfit.h"
 #include "objects.h"
@@ -13,1287 +12,11 @@ using namespace crm;
 
 namespace crm {
 
-static unsigned long next_panel_uid() {
-    static std::atomic<unsigned long> counter{0};
-    return ++counter;
-}
-
-// content hash (64-bit words mixed splitmix-style): keys of the shared donor tables
-static unsigned long content_key(const void* data, size_t bytes, unsigned long seed) {
-    const unsigned char* p = static_cast<const unsigned char*>(data);
-    unsigned long h = seed ^ (0x9E3779B97F4A7C15ul * (bytes + 1));
-    size_t i = 0;
-    for (; i + 8 <= bytes; i += 8) {
-        unsigned long w;
-        memcpy(&w, p + i, 8);
-        h ^= w + 0x9E3779B97F4A7C15ul + (h << 6) + (h >> 2);
-        h *= 0xBF58476D1CE4E5B9ul;
-        h ^= h >> 29;
-    }
-    for (; i < bytes; i++) h = (h ^ p[i]) * 0x100000001B3ul;
-    return h ? h : 1;
-}
-
-static int pick_split(long cells_pad, long blocks_without_split) { return split_for(cells_pad, blocks_without_split); }
-
 static int ctx_cus(const crm_ctx* ctx) {
     int cus = 256;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus < 1) cus = 256;
     return cus;
 }
-
-// flags[0] |= any non-finite entry; flags[1] |= any cell differing from its group's representative
-__global__ void verify_panel_kernel(const double* __restrict__ G, long ld, long p, const int* __restrict__ group,
-                                    const long* __restrict__ rep, int* __restrict__ flags) {
-    const long i = blockIdx.x;
-    const long j = (long)blockIdx.y * blockDim.x + threadIdx.x;
-    if (j >= p) return;
-    const double v = G[i * ld + j];
-    if (!(fabs(v) < INFINITY)) atomicOr(&flags[0], 1);
-    if (group) {
-        const double r = G[rep[group[i]] * ld + j];
-        if (__double_as_longlong(v) != __double_as_longlong(r)) atomicOr(&flags[1], 1);
-    }
-}
-
-// Symmetric eigen-decomposition A = V diag(w) V' of a small k x k matrix (row-major, destroyed) by cyclic Jacobi:
-// rotations until every off-diagonal entry is below eps times the root of its two diagonal entries (the relative
-// accuracy of the eigenvalues of a positive semidefinite Gram matrix).  V: k x k row-major, columns the eigenvectors.
-static void jacobi_eigh(int k, std::vector<double>& A, std::vector<double>& V, std::vector<double>& w) {
-    V.assign((size_t)k * k, 0.0);
-    for (int i = 0; i < k; i++) V[(size_t)i * k + i] = 1.0;
-    for (int sweep = 0; sweep < 60; sweep++) {
-        bool rotated = false;
-        for (int p = 0; p < k - 1; p++)
-            for (int q = p + 1; q < k; q++) {
-                const double apq = A[(size_t)p * k + q], app = A[(size_t)p * k + p], aqq = A[(size_t)q * k + q];
-                if (!(std::fabs(apq) > 2.220446049250313e-16 * std::sqrt(std::fabs(app * aqq))) || apq == 0.0) continue;
-                rotated = true;
-                const double theta = (aqq - app) / (2.0 * apq);
-                const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
-                for (int r = 0; r < k; r++) {   // columns p, q
-                    const double arp = A[(size_t)r * k + p], arq = A[(size_t)r * k + q];
-                    A[(size_t)r * k + p] = cs * arp - sn * arq;
-                    A[(size_t)r * k + q] = sn * arp + cs * arq;
-                }
-                for (int r = 0; r < k; r++) {   // rows p, q
-                    const double apr = A[(size_t)p * k + r], aqr = A[(size_t)q * k + r];
-                    A[(size_t)p * k + r] = cs * apr - sn * aqr;
-                    A[(size_t)q * k + r] = sn * apr + cs * aqr;
-                }
-                A[(size_t)p * k + q] = A[(size_t)q * k + p] = 0.0;
-                for (int r = 0; r < k; r++) {
-                    const double vrp = V[(size_t)r * k + p], vrq = V[(size_t)r * k + q];
-                    V[(size_t)r * k + p] = cs * vrp - sn * vrq;
-                    V[(size_t)r * k + q] = sn * vrp + cs * vrq;
-                }
-            }
-        if (!rotated) break;
-    }
-    w.resize(k);
-    for (int i = 0; i < k; i++) w[i] = A[(size_t)i * k + i];
-}
-
-// Unrelated donors (objects.h: kin_wb): is the donor-level kinship hKd hKd' diagonal to rounding?  Then the per-donor
-// eigen-decompositions of G_d = us_d'us_d and the rows R = Phi'E1, uploaded once per background.  Any off-diagonal entry
-// above 8 m eps sqrt(kappa_d kappa_d') keeps the MixK route; so do k2 > 128, k1 > 64 and donor counts whose test or
-// tables would be large.
-static int seal_unrelated_donors(crm_background* bg, const double* hKd, long m) {
-    bg->kin_wb = false;
-    const long groups = bg->kin_groups;
-    const int k1 = bg->kin_k1, k2 = bg->kin_k2, KK = k1 + k2;
-    if (form("kin_diag", 1) == 0 || k2 > 128 || k1 > 64 || (double)groups * groups * m > 4e9) return CRM_OK;
-    std::vector<double> kappa(groups, 0.0);
-    for (long d = 0; d < groups; d++)
-        for (long q = 0; q < m; q++) kappa[d] += hKd[d * m + q] * hKd[d * m + q];
-    const double tol = 8.0 * (double)m * 2.220446049250313e-16;
-    for (long d = 0; d < groups; d++)
-        for (long e = d + 1; e < groups; e++) {
-            double s = 0.0;
-            for (long q = 0; q < m; q++) s += hKd[d * m + q] * hKd[e * m + q];
-            if (!(std::fabs(s) <= tol * std::sqrt(kappa[d] * kappa[e]))) return CRM_OK;
-        }
-    crm_ctx* ctx = bg->ctx;
-    hipStream_t st = ctx->stream;
-    // [us | E1]'[us | E1] per donor over its own cells: G_d, us_d'E1_d and the donor's share of E1'E1
-    const long ldc = round_up(KK, 128);
-    if (sizeof(double) * (double)groups * KK * ldc > (double)(1ull << 30)) return CRM_OK;
-    ScopedBuf dC, probs_dev;
-    CRM_TRY(dC.ensure(sizeof(double) * (size_t)groups * KK * ldc));
-    std::vector<GemmProblem> pr((size_t)groups);
-    long maxlen = GEMM_BK;
-    for (long d = 0; d < groups; d++) {
-        GemmProblem p{};
-        p.X = bg->kin_Y.as<double>() + bg->kin_row0[d] * bg->kin_ldy; p.ldx = bg->kin_ldy;
-        p.Y = p.X; p.ldy = bg->kin_ldy;
-        p.C = dC.as<double>() + (size_t)d * KK * ldc; p.ldc = ldc;
-        p.M = KK; p.N = KK; p.cells = bg->kin_len[d];
-        maxlen = std::max(maxlen, bg->kin_len[d]);
-        pr[d] = p;
-    }
-    CRM_TRY(probs_dev.ensure(sizeof(GemmProblem) * pr.size()));
-    CRM_HIP(hipMemcpyAsync(probs_dev.ptr, pr.data(), sizeof(GemmProblem) * pr.size(), hipMemcpyHostToDevice, st));
-    CRM_TRY(launch_gemm_tn(ctx, probs_dev.as<GemmProblem>(), (int)groups, KK, KK, maxlen, false, 0, 1, 0));
-    std::vector<double> C((size_t)groups * KK * ldc);
-    CRM_HIP(hipMemcpyAsync(C.data(), dC.ptr, sizeof(double) * C.size(), hipMemcpyDeviceToHost, st));
-    CRM_HIP(hipStreamSynchronize(st));
-    const int k2pad = (int)round_up(k2, GEMM_BK);
-    const long P = groups * k2, ldp = round_up(P, 128);
-    std::vector<double> hU((size_t)groups * k2pad * 128, 0.0), hR((size_t)k1 * ldp, 0.0), hEE((size_t)k1 * k1, 0.0),
-        lam((size_t)P, 0.0);
-    std::vector<double> A((size_t)k2 * k2), V, w;
-    for (long d = 0; d < groups; d++) {
-        const double* Cd = C.data() + (size_t)d * KK * ldc;
-        for (int i = 0; i < k2; i++)
-            for (int j = 0; j < k2; j++) A[(size_t)i * k2 + j] = 0.5 * (Cd[i * ldc + j] + Cd[j * ldc + i]);
-        jacobi_eigh(k2, A, V, w);
-        double wmax = 0.0;
-        for (int j = 0; j < k2; j++) wmax = std::max(wmax, w[j]);
-        double* Ud = hU.data() + (size_t)d * k2pad * 128;
-        for (int j = 0; j < k2; j++) {
-            // (directions of us_d below rounding -- k2 > the donor's cells -- carry no variance: dropped)
-            if (!(w[j] > (double)k2 * 2.220446049250313e-16 * wmax)) continue;
-            const double sc = 1.0 / std::sqrt(w[j]);
-            lam[d * k2 + j] = w[j];
-            for (int q = 0; q < k2; q++) Ud[(size_t)q * 128 + j] = V[(size_t)q * k2 + j] * sc;
-            for (int a = 0; a < k1; a++) {
-                double s = 0.0;
-                for (int q = 0; q < k2; q++) s += Ud[(size_t)q * 128 + j] * Cd[q * ldc + k2 + a];
-                hR[(size_t)a * ldp + d * k2 + j] = s;
-            }
-        }
-        for (int a = 0; a < k1; a++)
-            for (int e = 0; e < k1; e++) hEE[(size_t)a * k1 + e] += Cd[(k2 + a) * ldc + k2 + e];
-    }
-    CRM_TRY(bg->wb_U.ensure(sizeof(double) * hU.size()));
-    CRM_TRY(bg->wb_R.ensure(sizeof(double) * hR.size()));
-    CRM_TRY(bg->wb_EE.ensure(sizeof(double) * hEE.size()));
-    CRM_HIP(hipMemcpyAsync(bg->wb_U.ptr, hU.data(), sizeof(double) * hU.size(), hipMemcpyHostToDevice, st));
-    CRM_HIP(hipMemcpyAsync(bg->wb_R.ptr, hR.data(), sizeof(double) * hR.size(), hipMemcpyHostToDevice, st));
-    CRM_HIP(hipMemcpyAsync(bg->wb_EE.ptr, hEE.data(), sizeof(double) * hEE.size(), hipMemcpyHostToDevice, st));
-    std::vector<std::vector<double>> s0(bg->nrho, std::vector<double>((size_t)ldp, 0.0));
-    for (int i = 0; i < bg->nrho; i++) {
-        for (long p = 0; p < P; p++) s0[i][p] = (1.0 - bg->rho[i]) * kappa[p / k2] * lam[p];
-        CRM_TRY(bg->wb_S0[i].ensure(sizeof(double) * (size_t)ldp));
-        CRM_HIP(hipMemcpyAsync(bg->wb_S0[i].ptr, s0[i].data(), sizeof(double) * (size_t)ldp, hipMemcpyHostToDevice, st));
-    }
-    CRM_HIP(hipStreamSynchronize(st));
-    bg->wb_P = P;
-    bg->wb_ldp = ldp;
-    bg->wb_k2pad = k2pad;
-    static std::atomic<unsigned long> wb_tables_made{0};
-    bg->wb_gen = ++wb_tables_made;
-    bg->kin_wb = true;
-    return CRM_OK;
-}
-
-__global__ void gather_rows_kernel(const double* __restrict__ G, long ld, const long* __restrict__ rep,
-                                   double* __restrict__ Gd) {
-    const long d = blockIdx.x;
-    const long j = (long)blockIdx.y * blockDim.x + threadIdx.x;
-    if (j < ld) Gd[d * ld + j] = G[rep[d] * ld + j];
-}
-
-}  // namespace crm
-
-extern "C" {
-
-// ---- background ---------------------------------------------------------------------------
-int crm_background_create_qs(crm_ctx* ctx, long n, int nrho, const double* rho, const int* r,
-                             const double* const* Q0, const double* const* S0,
-                             crm_background** out) {
-    return crm::guarded_on("crm_background_create_qs", ctx, [&]() -> int {
-    if (!ctx || !out || n <= 0 || nrho < 1 || !rho || !r || !Q0 || !S0) return CRM_ERR_ARG;
-    if (nrho > CRM_MAX_RHO) {
-        set_error("background: %d grid points (supported up to %d)", nrho, CRM_MAX_RHO);
-        return CRM_ERR_UNSUPPORTED;
-    }
-    *out = nullptr;
-    CRM_HIP(hipSetDevice(ctx->device));
-    crm_background* bg = new crm_background();
-    bg->ctx = ctx;
-    bg->n = n;
-    bg->n_pad = round_up(n, CELL_PAD);
-    bg->nrho = nrho;
-    long rmax = 1;
-    for (int i = 0; i < nrho; i++) {
-        if (r[i] < 0) { delete bg; return CRM_ERR_ARG; }
-        bg->rho[i] = rho[i];
-        bg->r[i] = r[i];
-        rmax = std::max<long>(rmax, r[i]);
-    }
-    bg->ldq = round_up(rmax, 128);
-    for (int i = 0; i < nrho; i++) {
-        int rc = bg->Q0[i].ensure(sizeof(double) * bg->n_pad * bg->ldq);
-        if (rc == CRM_OK) rc = bg->S0[i].ensure(sizeof(double) * bg->ldq);
-        if (rc == CRM_OK)
-            rc = upload_padded(ctx->stream, bg->Q0[i].as<double>(), bg->ldq, bg->n_pad, Q0[i], r[i], n, r[i]);
-        if (rc == CRM_OK)
-            rc = upload_padded(ctx->stream, bg->S0[i].as<double>(), bg->ldq, 1, S0[i], r[i], 1, r[i]);
-        if (rc != CRM_OK) { crm_background_destroy(bg); return rc; }
-        bg->q0_ready[i] = true;
-    }
-    bg->s0_max.assign(nrho, 0.0);   // (as background_seal leaves it for the backgrounds the library decomposes itself)
-    for (int i = 0; i < nrho; i++)
-        for (int j = 0; j < r[i]; j++) bg->s0_max[i] = std::max(bg->s0_max[i], S0[i][j]);
-    CRM_HIP(hipStreamSynchronize(ctx->stream));
-    *out = bg;
-    return CRM_OK;
-    });
-}
-
-void crm_background_destroy(crm_background* bg) {
-    try {
-    if (!bg) return;
-    std::lock_guard<std::recursive_mutex> lock(bg->ctx->mu);   // (reachable from a finalizer on any thread)
-    (void)hipSetDevice(bg->ctx->device);
-    (void)hipStreamSynchronize(bg->ctx->stream);
-    for (int i = 0; i < CRM_MAX_RHO; i++) {
-        bg->Q0[i].release();
-        bg->S0[i].release();
-        bg->Mix[i].release();
-    }
-    bg->H.release();
-    bg->Ht.release();
-    bg->kin_map.release();
-    bg->kin_Y.release();
-    bg->kin_hKd.release();
-    for (int i = 0; i < CRM_MAX_RHO; i++) bg->MixK[i].release();
-    for (crm_donor_tables* t : bg->dt_cache) {
-        t->release();
-        delete t;
-    }
-    if (bg->builder) crm_background_builder_free(bg->builder);
-    delete bg;
-    } catch (...) {  // (nothing may unwind into the caller; a destroy has no status to return)
-    }
-}
-
-int crm_background_set_kinship_groups(crm_background* bg, const int* group, long groups, const double* hKd, long m,
-                                      const double* U, int k2) {
-    return crm::guarded_on("crm_background_set_kinship_groups", bg ? bg->ctx : nullptr, [&]() -> int {
-    if (!bg || !group || !hKd || !U || groups < 1 || m < 1 || k2 < 1) return CRM_ERR_ARG;
-    if (bg->builder) {
-        set_error("kinship groups: the background is still under construction");
-        return CRM_ERR_ARG;
-    }
-    const long n = bg->n;
-    const int k1 = (int)(bg->cols - (long)k2 * m);
-    // only backgrounds that kept their half factor H = [E1, L_1 .. L_k2] (thin branch, well-conditioned spectrum) can use it
-    if (!bg->fast_T || !bg->H.ptr || k1 < 1 || k1 + k2 > 2 * CRM_MAX_K0 || groups > 4096) return CRM_OK;   // (kin_operand: one thread per column of [us | E1], <= 1024)
-    for (long i = 0; i < n; i++)
-        if (group[i] < 0 || group[i] >= groups) {
-            set_error("kinship groups: group index %d at cell %ld outside [0, %ld)", group[i], i, groups);
-            return CRM_ERR_ARG;
-        }
-    crm_ctx* ctx = bg->ctx;
-    CRM_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    bg->kin = false;   // (a second announcement that fails must not leave the first one's buffers in use)
-    struct Undo {      // ... nor keep its own: whatever it allocated goes back unless it ends with bg->kin set
-        crm_background* b;
-        ~Undo() {
-            if (b->kin) return;
-            b->kin_fold = false;
-            b->kin_wb = false;
-            for (DevBuf* x : {&b->kin_map, &b->kin_Y, &b->kin_hKd, &b->wb_U, &b->wb_R, &b->wb_EE}) x->release();
-            for (int i = 0; i < b->nrho; i++) b->wb_S0[i].release();
-            for (int i = 0; i < b->nrho; i++) b->MixK[i].release();
-        }
-    } undo{bg};
-    // cells in donor order, every donor's run padded to whole stages of the contraction
-    std::vector<long> count(groups, 0);
-    for (long i = 0; i < n; i++) count[group[i]]++;
-    bg->kin_row0.assign(groups, 0);
-    bg->kin_len.assign(groups, 0);
-    long rows = 0;
-    for (long d = 0; d < groups; d++) {
-        bg->kin_row0[d] = rows;
-        bg->kin_len[d] = round_up(std::max<long>(count[d], 1), GEMM_BK);
-        rows += bg->kin_len[d];
-    }
-    std::vector<int> map(rows, -1);
-    std::vector<long> fill(groups, 0);
-    for (long i = 0; i < n; i++) {
-        const long d = group[i];
-        map[bg->kin_row0[d] + fill[d]++] = (int)i;
-    }
-    bg->kin_rows = rows;
-    bg->kin_groups = groups;
-    bg->kin_groups_pad = round_up(groups, GEMM_BK);
-    bg->kin_cols = m;
-    bg->kin_k1 = k1;
-    bg->kin_k2 = k2;
-    bg->kin_ldh = round_up(m, 128);
-    bg->kin_ldy = round_up(k1 + k2, 128);
-    CRM_TRY(bg->kin_map.ensure(sizeof(int) * rows));
-    CRM_TRY(bg->kin_Y.ensure(sizeof(double) * rows * bg->kin_ldy));
-    CRM_TRY(bg->kin_hKd.ensure(sizeof(double) * bg->kin_groups_pad * bg->kin_ldh));
-    ScopedBuf dU;
-    CRM_TRY(dU.ensure(sizeof(double) * n * k2));
-    CRM_HIP(hipMemcpyAsync(bg->kin_map.ptr, map.data(), sizeof(int) * rows, hipMemcpyHostToDevice, st));
-    CRM_HIP(hipMemcpyAsync(dU.ptr, U, sizeof(double) * n * k2, hipMemcpyHostToDevice, st));
-    CRM_TRY(upload_padded(st, bg->kin_hKd.as<double>(), bg->kin_ldh, bg->kin_groups_pad, hKd, m, groups, m));
-    CRM_TRY(launch_kin_operand(st, dU.as<double>(), k2, bg->H.as<double>(), bg->ldh, k1, bg->kin_map.as<int>(), rows,
-                               bg->kin_Y.as<double>(), bg->kin_ldy));
-    // the route rests on H[c, k1 + j m + d] = U[c, j] hKd[group(c), d] entry by entry: check it here, once, instead of
-    // returning the results of another model when a caller announces a structure its half factor does not have
-    ScopedBuf dgroup, dcheck;
-    CRM_TRY(dgroup.ensure(sizeof(int) * n));
-    CRM_TRY(dcheck.ensure(2 * sizeof(unsigned long long)));
-    unsigned long long check[2] = {0, 0};
-    CRM_HIP(hipMemcpyAsync(dgroup.ptr, group, sizeof(int) * n, hipMemcpyHostToDevice, st));
-    CRM_HIP(hipMemsetAsync(dcheck.ptr, 0, sizeof check, st));
-    CRM_TRY(launch_kin_verify(st, bg->H.as<double>(), bg->ldh, k1, dU.as<double>(), k2, dgroup.as<int>(),
-                              bg->kin_hKd.as<double>(), bg->kin_ldh, m, n, dcheck.as<unsigned long long>()));
-    CRM_HIP(hipMemcpyAsync(check, dcheck.ptr, sizeof check, hipMemcpyDeviceToHost, st));
-    CRM_HIP(hipStreamSynchronize(st));
-    double dmax, hmax;
-    memcpy(&dmax, &check[0], sizeof dmax);
-    memcpy(&hmax, &check[1], sizeof hmax);
-    if (!(dmax <= 1e-12 * hmax)) {
-        set_error("kinship groups: the half factor of this background is not U[c, j] * hKd[group(c), d] (largest difference "
-                  "%.3g against entries up to %.3g)", dmax, hmax);
-        return CRM_ERR_ARG;
-    }
-    // the column of ones behind hKd's m columns (objects.h: kin_hKd): the contraction over the donors on the pair products
-    // then also gives their sum over the donors (scan_pass: ScanPass::unfolded_AH).  Written after the check, which reads
-    // the m columns alone.
-    if (m + 1 <= bg->kin_ldh) {
-        std::vector<double> ones((size_t)groups, 1.0);
-        CRM_HIP(hipMemcpy2DAsync(bg->kin_hKd.as<double>() + m, sizeof(double) * bg->kin_ldh, ones.data(), sizeof(double),
-                                 sizeof(double), groups, hipMemcpyHostToDevice, st));
-        CRM_HIP(hipStreamSynchronize(st));   // (ones lives on this stack frame)
-    }
-    // Fold the donor-level factor into the mixing matrices (objects.h: kin_fold) -- one small product per (grid point, j):
-    // MixK[k1 + d' k2 + j, :] = sum_d hKd[d', d] Mix[k1 + j m + d, :], the contraction over d in stages of 16 rows (the
-    // rows of hKd' beyond m are zero; the rows of Mix they meet belong to the next j or to Mix's own zero padding, which
-    // must exist: cols + padding <= ldh).
-    bg->kin_fold = false;
-    const long kfold = k1 + groups * (long)k2, m_pad = round_up(m, GEMM_BK);
-    const int fold_form = form("kin_fold", 1);   // 0 never, 1 where it pays, 2 also with few columns of us
-    // (k2 >= 32: the folded form launches the per-donor sums for the us columns alone, 64 columns wide -- with few of them,
-    // config 2's 20, one launch over [us | E1] together and the small contraction over the donors per block is the better
-    // form: config 2 463 000 against 451 000 variant-tests/s.  k2 == 1 -- mode B, us a single column -- folds too: its us rows
-    // are per-donor sums of the Khatri-Rao rows themselves, a plain batched product, see ScanPass::folded_S)
-    if ((double)kfold <= 1.25 * (double)bg->cols && bg->cols + (m_pad - m) <= bg->ldh && (k2 >= 32 || k2 == 1 || fold_form > 1) && fold_form != 0) {
-        const long kdim = round_up(kfold, GEMM_BK), ldq = bg->ldq, ld_t = round_up(groups, 128);
-        ScopedBuf hKdT, probs_dev;
-        CRM_TRY(hKdT.ensure(sizeof(double) * m_pad * ld_t));
-        {
-            std::vector<double> t((size_t)m_pad * ld_t, 0.0);
-            for (long dd = 0; dd < groups; dd++)
-                for (long d = 0; d < m; d++) t[(size_t)d * ld_t + dd] = hKd[dd * m + d];
-            CRM_HIP(hipMemcpyAsync(hKdT.ptr, t.data(), sizeof(double) * t.size(), hipMemcpyHostToDevice, st));
-            CRM_HIP(hipStreamSynchronize(st));
-        }
-        std::vector<GemmProblem> pr((size_t)bg->nrho * k2);
-        for (int i = 0; i < bg->nrho; i++) {
-            CRM_TRY(bg->MixK[i].ensure(sizeof(double) * kdim * ldq));
-            CRM_HIP(hipMemsetAsync(bg->MixK[i].ptr, 0, sizeof(double) * kdim * ldq, st));
-            CRM_HIP(hipMemcpyAsync(bg->MixK[i].ptr, bg->Mix[i].ptr, sizeof(double) * (size_t)k1 * ldq, hipMemcpyDeviceToDevice, st));
-            for (int j = 0; j < k2; j++) {
-                GemmProblem p{};
-                p.X = hKdT.as<double>(); p.ldx = ld_t;
-                p.Y = bg->Mix[i].as<double>() + (size_t)(k1 + (long)j * m) * ldq; p.ldy = ldq;
-                p.C = bg->MixK[i].as<double>() + (size_t)(k1 + j) * ldq; p.ldc = (long)k2 * ldq;
-                p.M = (int)groups; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-                pr[(size_t)i * k2 + j] = p;
-            }
-        }
-        CRM_TRY(probs_dev.ensure(sizeof(GemmProblem) * pr.size()));
-        CRM_HIP(hipMemcpyAsync(probs_dev.ptr, pr.data(), sizeof(GemmProblem) * pr.size(), hipMemcpyHostToDevice, st));
-        CRM_TRY(launch_gemm_tn(ctx, probs_dev.as<GemmProblem>(), (int)pr.size(), (int)groups, (int)ldq, m_pad, false, 0, 1, 0));
-        CRM_HIP(hipStreamSynchronize(st));
-        bg->kin_kdim = kdim;
-        bg->kin_fold = true;
-        CRM_TRY(seal_unrelated_donors(bg, hKd, m));
-    }
-    bg->kin = true;
-    return CRM_OK;
-    });
-}
-
-int crm_background_kinship_groups(const crm_background* bg) {
-    if (!bg) return 0;
-    try {
-        std::lock_guard<std::recursive_mutex> lock(bg->ctx->mu);
-        return bg->kin ? (int)bg->kin_groups : 0;
-    } catch (...) {
-        return 0;
-    }
-}
-
-long crm_background_kinship_folded(const crm_background* bg) {
-    if (!bg) return 0;
-    try {
-        std::lock_guard<std::recursive_mutex> lock(bg->ctx->mu);
-        return bg->kin && bg->kin_fold ? bg->kin_kdim : 0;
-    } catch (...) {
-        return 0;
-    }
-}
-
-int crm_background_rank(const crm_background* bg, int i) {
-    return crm::guarded_on("crm_background_rank", bg ? bg->ctx : nullptr, [&]() -> int {
-    if (!bg || i < 0 || i >= bg->nrho) return -1;
-    return bg->r[i];
-    });
-}
-
-int crm_background_read(const crm_background* bg, int i, double* Q0, double* S0) {
-    return crm::guarded_on("crm_background_read", bg ? bg->ctx : nullptr, [&]() -> int {
-    if (!bg || i < 0 || i >= bg->nrho) return CRM_ERR_ARG;
-    if (Q0) CRM_TRY(crm_background_require_q0(const_cast<crm_background*>(bg), i));
-    CRM_HIP(hipSetDevice(bg->ctx->device));
-    const int r = bg->r[i];
-    if (Q0 && r > 0)
-        CRM_HIP(hipMemcpy2D(Q0, r * sizeof(double), bg->Q0[i].ptr, bg->ldq * sizeof(double),
-                            r * sizeof(double), bg->n, hipMemcpyDeviceToHost));
-    if (S0 && r > 0) CRM_HIP(hipMemcpy(S0, bg->S0[i].ptr, r * sizeof(double), hipMemcpyDeviceToHost));
-    return CRM_OK;
-    });
-}
-
-// ---- gene -----------------------------------------------------------------------------------
-extern "C++" {
-// rotations t = Q0(rho)' [y, W] of a gene for every grid point: rows of a [(1+c) x ldq] matrix per grid point
-static int gene_rotations(crm_gene* g) {
-    crm_background* bg = g->bg;
-    crm_ctx* ctx = g->ctx;
-    const int c = g->c;
-    const long np = bg->n_pad, ldyw = g->ld_yw;
-    int rc = CRM_OK;
-    auto fail = [&](int code) { return code; };
-    const int nrho = bg->nrho;
-    const long ldq = bg->ldq;
-    const long slab = (long)(1 + c) * ldq;
-    if (bg->fast_T && ctx->fast_gene_rot) {
-        // Q0(rho) = H Mix(rho):  t = Mix(rho)' (H'[y, W]) -- no Q0 needed
-        ScopedBuf thw;
-        const long ldh = bg->ldh;
-        if ((rc = thw.ensure(sizeof(double) * ldh * 128)) != CRM_OK) return fail(rc);
-        if ((rc = g->rot.ensure(sizeof(double) * slab * nrho)) != CRM_OK) return fail(rc);
-        if ((rc = ctx->ws_probs.ensure(sizeof(GemmProblem) * (CRM_MAX_RHO + 4))) != CRM_OK) return fail(rc);
-        CRM_HIP(hipMemsetAsync(thw.ptr, 0, sizeof(double) * ldh * 128, ctx->stream));
-        CRM_HIP(hipMemsetAsync(g->rot.ptr, 0, sizeof(double) * slab * nrho, ctx->stream));
-        std::vector<GemmProblem> pr(nrho + 1);
-        GemmProblem p0{};
-        p0.X = bg->H.as<double>(); p0.ldx = ldh; p0.Y = g->yW.as<double>(); p0.ldy = ldyw;
-        p0.C = thw.as<double>(); p0.ldc = 128; p0.M = (int)bg->cols; p0.N = 1 + c;
-        pr[0] = p0;
-        for (int i = 0; i < nrho; i++) {
-            GemmProblem p{};
-            p.X = thw.as<double>(); p.ldx = 128; p.Y = bg->Mix[i].as<double>(); p.ldy = ldq;
-            p.C = g->rot.as<double>() + (long)i * slab; p.ldc = ldq;
-            p.M = 1 + c; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-            pr[1 + i] = p;
-        }
-        CRM_HIP(hipMemcpyAsync(ctx->ws_probs.ptr, pr.data(), sizeof(GemmProblem) * (nrho + 1), hipMemcpyHostToDevice, ctx->stream));
-        if ((rc = launch_gemm_tn(ctx, ctx->ws_probs.as<GemmProblem>(), 1, (int)bg->cols, 1 + c, np, false, 0, 1, 0)) != CRM_OK) return fail(rc);
-        if ((rc = launch_gemm_tn(ctx, ctx->ws_probs.as<GemmProblem>() + 1, nrho, 1 + c, (int)ldq, ldh, false, 0, 1, 0)) != CRM_OK) return fail(rc);
-        CRM_HIP(hipStreamSynchronize(ctx->stream));
-        return CRM_OK;
-    }
-    if ((rc = crm_background_require_q0(bg, -1)) != CRM_OK) return fail(rc);
-    const int ks = pick_split(np, (ldq / GEMM_BN) * nrho);
-    if ((rc = g->rot.ensure(sizeof(double) * slab * nrho * ks)) != CRM_OK) return fail(rc);
-    std::vector<GemmProblem> probs(nrho);
-    for (int i = 0; i < nrho; i++) {
-        GemmProblem p{};
-        p.X = g->yW.as<double>(); p.ldx = ldyw;
-        p.Y = bg->Q0[i].as<double>(); p.ldy = ldq;
-        p.C = g->rot.as<double>() + (long)i * slab; p.ldc = ldq;
-        p.M = 1 + c; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-        probs[i] = p;
-    }
-    if ((rc = ctx->ws_probs.ensure(sizeof(GemmProblem) * CRM_MAX_RHO)) != CRM_OK) return fail(rc);
-    CRM_HIP(hipMemcpyAsync(ctx->ws_probs.ptr, probs.data(), sizeof(GemmProblem) * nrho, hipMemcpyHostToDevice, ctx->stream));
-    // splits write slabs nrho*slab apart
-    CRM_HIP(hipMemsetAsync(g->rot.ptr, 0, sizeof(double) * slab * nrho * ks, ctx->stream));
-    if ((rc = launch_gemm_tn(ctx, ctx->ws_probs.as<GemmProblem>(), nrho, 1 + c, (int)ldq, np, false, 0, ks, slab * nrho)) != CRM_OK) return fail(rc);
-    if ((rc = launch_reduce_splits(ctx->stream, g->rot.as<double>(), slab * nrho, ks, slab * nrho)) != CRM_OK) return fail(rc);
-    CRM_HIP(hipStreamSynchronize(ctx->stream));
-    return CRM_OK;
-}
-
-}  // extern "C++"
-
-int crm_gene_create(crm_background* bg, const double* y, const double* W, int c, const double* E0,
-                    int k0, crm_gene** out) {
-    return crm::guarded_on("crm_gene_create", bg ? bg->ctx : nullptr, [&]() -> int {
-    if (!bg || !y || !W || !E0 || !out) return CRM_ERR_ARG;
-    *out = nullptr;
-    if (bg->builder) {
-        set_error("gene: the background is still under construction (crm_background_seal not called)");
-        return CRM_ERR_ARG;
-    }
-    if (c < 1 || c > CRM_MAX_COV_XWIDE) {
-        set_error("gene: %d covariate columns (supported 1..%d; the interaction scan up to %d)", c, CRM_MAX_COV_XWIDE, CRM_MAX_COV_WIDE);
-        return CRM_ERR_UNSUPPORTED;
-    }
-    if (k0 < 1 || k0 > CRM_MAX_K0) {
-        set_error("gene: %d contexts (supported 1..%d)", k0, CRM_MAX_K0);
-        return CRM_ERR_UNSUPPORTED;
-    }
-    crm_ctx* ctx = bg->ctx;
-    CRM_HIP(hipSetDevice(ctx->device));
-    const long n = bg->n, np = bg->n_pad;
-    for (long i = 0; i < n; i++) {
-        bool fin = std::isfinite(y[i]);
-        for (int j = 0; j < c && fin; j++) fin = std::isfinite(W[i * c + j]);
-        if (!fin) {
-            set_error("gene: non-finite values in the outcome or the covariates");
-            return CRM_ERR_NUMERIC;
-        }
-    }
-    crm_gene* g = new crm_gene();
-    g->bg = bg;
-    g->ctx = bg->ctx;
-    g->c = c;
-    g->k0 = k0;
-    g->e0_key = content_key(E0, sizeof(double) * (size_t)bg->n * k0, (unsigned long)k0);
-    g->w_key = content_key(W, sizeof(double) * (size_t)bg->n * c, (unsigned long)c);
-    g->ldw = 16;
-    g->lde = round_up(k0, 16);
-    int rc = CRM_OK;
-    auto fail = [&](int code) { crm_gene_destroy(g); return code; };
-    // host-side inner products
-    std::vector<double> WW((size_t)c * c, 0.0), Wy(c, 0.0);
-    auto inner_products = [&](const double* Wm) {
-        std::fill(WW.begin(), WW.end(), 0.0);
-        std::fill(Wy.begin(), Wy.end(), 0.0);
-        for (long i = 0; i < n; i++)
-            for (int a = 0; a < c; a++) {
-                Wy[a] += Wm[i * c + a] * y[i];
-                for (int b = a; b < c; b++) WW[a * c + b] += Wm[i * c + a] * Wm[i * c + b];
-            }
-        for (int a = 0; a < c; a++)
-            for (int b = 0; b < a; b++) WW[a * c + b] = WW[b * c + a];
-    };
-    auto is_diagonal = [&]() {
-        for (int a = 0; a < c; a++)
-            for (int b = a + 1; b < c; b++)
-                if (std::fabs(WW[a * c + b]) > 1e-13 * std::sqrt(WW[a * c + a] * WW[b * c + b])) return false;
-        return true;
-    };
-    g->yy = 0.0;
-    for (long i = 0; i < n; i++) g->yy += y[i] * y[i];
-    inner_products(W);
-    // The orthogonalisation of the variants against W (blockops.hip: launch_ortho_block) and the null fits work in a basis
-    // of span(W) with mutually orthogonal columns -- U diag(s) of the thin SVD, the basis glimix-core's LMM holds its
-    // covariates in, which is what the Python host passes.  Columns that are not orthogonal are brought there here: the
-    // scans depend on W through its column space only.  W <- W V with V the eigenvectors of W'W by a cyclic Jacobi
-    // iteration, repeated on the result: a pass leaves the columns orthogonal to ~eps cond(W)^2, and on a nearly diagonal
-    // Gram matrix Jacobi resolves the small singular values to high relative accuracy, so two or three passes reach the
-    // 1e-13 the diagonal test asks for up to cond(W) ~ 1e7 -- beyond which the reference's own rank rule
-    // (numpy_sugar.economic_svd: singular values below sqrt(eps)) is what decides.
-    std::vector<double> Wo;
-    std::vector<double> Vtot;   // product of the passes' V (empty: W was orthogonal as passed)
-    const double* Wuse = W;
-    for (int pass = 0; pass < 4 && !is_diagonal(); pass++) {
-        std::vector<double> A(WW), V((size_t)c * c, 0.0);
-        for (int a = 0; a < c; a++) V[a * c + a] = 1.0;
-        for (int sweep = 0; sweep < 60; sweep++) {
-            double offd = 0.0, diag = 0.0;
-            for (int a = 0; a < c; a++)
-                for (int b = 0; b < c; b++) (a == b ? diag : offd) += A[a * c + b] * A[a * c + b];
-            if (offd <= 1e-32 * diag) break;
-            for (int pi = 0; pi < c - 1; pi++)
-                for (int qi = pi + 1; qi < c; qi++) {
-                    const double apq = A[pi * c + qi];
-                    if (apq == 0.0) continue;
-                    const double theta = (A[qi * c + qi] - A[pi * c + pi]) / (2.0 * apq);
-                    const double t = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                    const double cs = 1.0 / std::sqrt(t * t + 1.0), sn = t * cs;
-                    for (int k = 0; k < c; k++) {
-                        const double akp = A[k * c + pi], akq = A[k * c + qi];
-                        A[k * c + pi] = cs * akp - sn * akq;
-                        A[k * c + qi] = sn * akp + cs * akq;
-                    }
-                    for (int k = 0; k < c; k++) {
-                        const double apk = A[pi * c + k], aqk = A[qi * c + k];
-                        A[pi * c + k] = cs * apk - sn * aqk;
-                        A[qi * c + k] = sn * apk + cs * aqk;
-                    }
-                    for (int k = 0; k < c; k++) {
-                        const double vkp = V[k * c + pi], vkq = V[k * c + qi];
-                        V[k * c + pi] = cs * vkp - sn * vkq;
-                        V[k * c + qi] = sn * vkp + cs * vkq;
-                    }
-                }
-        }
-        std::vector<double> Wn((size_t)n * c);
-        std::vector<double> row(c);
-        for (long i = 0; i < n; i++) {
-            for (int a = 0; a < c; a++) row[a] = Wuse[i * c + a];
-            for (int b = 0; b < c; b++) {
-                double acc = 0.0;
-                for (int a = 0; a < c; a++) acc += row[a] * V[a * c + b];
-                Wn[i * c + b] = acc;
-            }
-        }
-        Wo.swap(Wn);
-        Wuse = Wo.data();
-        inner_products(Wuse);
-        if (Vtot.empty()) Vtot = V;
-        else {
-            std::vector<double> T((size_t)c * c, 0.0);
-            for (int a = 0; a < c; a++)
-                for (int k = 0; k < c; k++)
-                    for (int b = 0; b < c; b++) T[a * c + b] += Vtot[a * c + k] * V[k * c + b];
-            Vtot.swap(T);
-        }
-    }
-    if (!is_diagonal()) {
-        set_error("gene: the covariates could not be brought to mutually orthogonal columns (W'W stays coupled beyond 1e-13 "
-                  "after four passes): pass an orthogonal basis of span(W), e.g. U diag(s) of its thin SVD");
-        return fail(CRM_ERR_NUMERIC);
-    }
-    // [y | W] packed as one operand (column 0 = y) for the rotations, plus separate views
-    const long ldyw = 128;
-    if ((rc = g->yW.ensure(sizeof(double) * np * ldyw)) != CRM_OK) return fail(rc);
-    if ((rc = g->E0.ensure(sizeof(double) * np * g->lde)) != CRM_OK) return fail(rc);
-    {
-        std::vector<double> pack((size_t)n * (1 + c));
-        for (long i = 0; i < n; i++) {
-            pack[i * (1 + c)] = y[i];
-            for (int j = 0; j < c; j++) pack[i * (1 + c) + 1 + j] = Wuse[i * c + j];
-        }
-        if ((rc = upload_padded(ctx->stream, g->yW.as<double>(), ldyw, np, pack.data(), 1 + c, n, 1 + c)) != CRM_OK)
-            return fail(rc);
-        CRM_HIP(hipStreamSynchronize(ctx->stream));
-    }
-    g->ld_yw = ldyw;
-    if ((rc = upload_padded(ctx->stream, g->E0.as<double>(), g->lde, np, E0, k0, n, k0)) != CRM_OK) return fail(rc);
-    // What the orthogonalisation of the variants against W needs: (W'W)^-1 = diag(1 / s^2), V = I, d^2 = s^2
-    {
-        constexpr double EPS = 2.220446049250313e-16;
-        std::vector<double> proj((size_t)2 * c * c + c, 0.0);
-        double* inv = proj.data();
-        double* V = inv + (size_t)c * c;
-        double* d2 = V + (size_t)c * c;
-        for (int a = 0; a < c; a++) {
-            if (!(WW[a * c + a] >= EPS)) {
-                set_error("gene: the covariates are rank deficient by the reference's rule (a singular value of %.3g, below "
-                          "sqrt(eps)): pass a basis of span(W)", std::sqrt(std::max(WW[a * c + a], 0.0)));
-                return fail(CRM_ERR_NUMERIC);
-            }
-            V[a * c + a] = 1.0;
-            d2[a] = WW[a * c + a];
-            inv[a * c + a] = 1.0 / WW[a * c + a];
-        }
-        if ((rc = g->Wproj.ensure(sizeof(double) * proj.size())) != CRM_OK) return fail(rc);
-        CRM_HIP(hipMemcpyAsync(g->Wproj.ptr, proj.data(), sizeof(double) * proj.size(), hipMemcpyHostToDevice, ctx->stream));
-        CRM_HIP(hipStreamSynchronize(ctx->stream));   // (proj lives on this stack frame)
-    }
-    if ((rc = g->WW.ensure(sizeof(double) * c * c)) != CRM_OK) return fail(rc);
-    if ((rc = g->Wy.ensure(sizeof(double) * c)) != CRM_OK) return fail(rc);
-    CRM_HIP(hipMemcpyAsync(g->WW.ptr, WW.data(), sizeof(double) * c * c, hipMemcpyHostToDevice, ctx->stream));
-    CRM_HIP(hipMemcpyAsync(g->Wy.ptr, Wy.data(), sizeof(double) * c, hipMemcpyHostToDevice, ctx->stream));
-    CRM_HIP(hipStreamSynchronize(ctx->stream));
-    g->W_host.assign(Wuse, Wuse + (size_t)n * c);
-    g->W_basis = Vtot;
-    if ((rc = gene_rotations(g)) != CRM_OK) return fail(rc);
-    *out = g;
-    return CRM_OK;
-    });
-}
-
-// Another phenotype on the cohort of `like`: same background, covariates and contexts -- only y differs.  What a gene
-// keeps of W and E0 (device copies, W'W, the projection onto span(W), the content keys that let a multi-phenotype pass check
-// that its genes agree) is copied on the device instead of being checked, hashed, orthogonalised and uploaded again: binding
-// a phenotype costs its own upload and rotations only (per-gene run_interaction calls of the reference, _cellregmap.py:547-587,
-// over many genes of one cohort).  The results are bit for bit those of crm_gene_create with the same W and E0.
-int crm_gene_create_like(const crm_gene* like, const double* y, crm_gene** out) {
-    return crm::guarded_on("crm_gene_create_like", like ? like->ctx : nullptr, [&]() -> int {
-    if (!like || !y || !out) return CRM_ERR_ARG;
-    *out = nullptr;
-    crm_background* bg = like->bg;
-    crm_ctx* ctx = like->ctx;
-    CRM_HIP(hipSetDevice(ctx->device));
-    const long n = bg->n;
-    const int c = like->c;
-    if (like->W_host.size() != (size_t)n * c) {
-        set_error("gene: the template gene holds no covariates");
-        return CRM_ERR_ARG;
-    }
-    for (long i = 0; i < n; i++)
-        if (!std::isfinite(y[i])) {
-            set_error("gene: non-finite values in the outcome or the covariates");
-            return CRM_ERR_NUMERIC;
-        }
-    crm_gene* g = new crm_gene();
-    g->bg = bg; g->ctx = ctx; g->c = c; g->k0 = like->k0;
-    g->e0_key = like->e0_key; g->w_key = like->w_key;
-    g->ldw = like->ldw; g->lde = like->lde; g->ld_yw = like->ld_yw;
-    g->W_host = like->W_host;
-    g->W_basis = like->W_basis;
-    int rc = CRM_OK;
-    auto fail = [&](int code) { crm_gene_destroy(g); return code; };
-    hipStream_t st = ctx->stream;
-    const DevBuf* src[] = {&like->yW, &like->E0, &like->WW, &like->Wproj};
-    DevBuf* dst[] = {&g->yW, &g->E0, &g->WW, &g->Wproj};
-    for (int q = 0; q < 4; q++) {
-        if ((rc = dst[q]->ensure(src[q]->bytes)) != CRM_OK) return fail(rc);
-        CRM_HIP(hipMemcpyAsync(dst[q]->ptr, src[q]->ptr, src[q]->bytes, hipMemcpyDeviceToDevice, st));
-    }
-    // column 0 of [y | W]
-    CRM_HIP(hipMemcpy2DAsync(g->yW.ptr, sizeof(double) * g->ld_yw, y, sizeof(double), sizeof(double), n, hipMemcpyHostToDevice, st));
-    g->yy = 0.0;
-    std::vector<double> Wy(c, 0.0);
-    const double* Wm = g->W_host.data();
-    for (long i = 0; i < n; i++) g->yy += y[i] * y[i];
-    for (long i = 0; i < n; i++)
-        for (int a = 0; a < c; a++) Wy[a] += Wm[i * c + a] * y[i];
-    if ((rc = g->Wy.ensure(sizeof(double) * c)) != CRM_OK) return fail(rc);
-    CRM_HIP(hipMemcpyAsync(g->Wy.ptr, Wy.data(), sizeof(double) * c, hipMemcpyHostToDevice, st));
-    CRM_HIP(hipStreamSynchronize(st));
-    if ((rc = gene_rotations(g)) != CRM_OK) return fail(rc);
-    *out = g;
-    return CRM_OK;
-    });
-}
-
-extern "C++" {
-__global__ void scatter_column_kernel(const double* __restrict__ src, long lds, int col, double* __restrict__ dst, long ldd, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i * ldd] = src[i * lds + col];
-}
-}  // extern "C++"
-
-// ngenes phenotypes (the columns of Y: n x ngenes, row-major, leading dimension ldy) on the cohort of `like`, bound in one
-// call: what crm_gene_create_like does per phenotype, with the rotations Q0(rho)'y of all of them as ONE product against the
-// half factor and one against every mixing matrix -- those operands (0.8 GB + 11 x 0.2 GB at BASELINE config 3) are read once
-// per batch instead of once per phenotype.  out: ngenes handles; on failure none is left behind.
-int crm_gene_create_batch(const crm_gene* like, const double* Y, long ldy, int ngenes, crm_gene** out) {
-    return crm::guarded_on("crm_gene_create_batch", like ? like->ctx : nullptr, [&]() -> int {
-    if (!like || !Y || !out || ngenes < 1 || ldy < ngenes) return CRM_ERR_ARG;
-    for (int j = 0; j < ngenes; j++) out[j] = nullptr;
-    crm_background* bg = like->bg;
-    crm_ctx* ctx = like->ctx;
-    CRM_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const long n = bg->n, np = bg->n_pad, ldq = bg->ldq;
-    const int c = like->c, nrho = bg->nrho;
-    if (like->W_host.size() != (size_t)n * c) {
-        set_error("gene: the template gene holds no covariates");
-        return CRM_ERR_ARG;
-    }
-    for (long i = 0; i < n; i++)
-        for (int j = 0; j < ngenes; j++)
-            if (!std::isfinite(Y[i * ldy + j])) {
-                set_error("gene: non-finite values in the outcome or the covariates");
-                return CRM_ERR_NUMERIC;
-            }
-    std::vector<crm_gene*> made;
-    auto fail = [&](int code) {
-        for (crm_gene* g : made) crm_gene_destroy(g);
-        for (int j = 0; j < ngenes; j++) out[j] = nullptr;
-        return code;
-    };
-    int rc = CRM_OK;
-    const long ldY = round_up(ngenes, 128);
-    ScopedBuf dY;
-    if ((rc = dY.ensure(sizeof(double) * np * ldY)) != CRM_OK) return rc;
-    if ((rc = upload_padded(st, dY.as<double>(), ldY, np, Y, ldy, n, ngenes)) != CRM_OK) return rc;
-    const double* Wm = like->W_host.data();
-    for (int j = 0; j < ngenes; j++) {
-        crm_gene* g = new crm_gene();
-        made.push_back(g);
-        g->bg = bg; g->ctx = ctx; g->c = c; g->k0 = like->k0;
-        g->e0_key = like->e0_key; g->w_key = like->w_key;
-        g->ldw = like->ldw; g->lde = like->lde; g->ld_yw = like->ld_yw;
-        g->W_host = like->W_host;
-        g->W_basis = like->W_basis;
-        const DevBuf* src[] = {&like->yW, &like->E0, &like->WW, &like->Wproj, &like->rot};
-        DevBuf* dst[] = {&g->yW, &g->E0, &g->WW, &g->Wproj, &g->rot};
-        for (int q = 0; q < 5; q++) {
-            if ((rc = dst[q]->ensure(src[q]->bytes)) != CRM_OK) return fail(rc);
-            CRM_HIP(hipMemcpyAsync(dst[q]->ptr, src[q]->ptr, src[q]->bytes, hipMemcpyDeviceToDevice, st));
-        }
-        hipLaunchKernelGGL(scatter_column_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dY.as<double>(), ldY, j,
-                           g->yW.as<double>(), g->ld_yw, n);
-        g->yy = 0.0;
-        std::vector<double> Wy(c, 0.0);
-        for (long i = 0; i < n; i++) g->yy += Y[i * ldy + j] * Y[i * ldy + j];
-        for (long i = 0; i < n; i++)
-            for (int a = 0; a < c; a++) Wy[a] += Wm[i * c + a] * Y[i * ldy + j];
-        if ((rc = g->Wy.ensure(sizeof(double) * c)) != CRM_OK) return fail(rc);
-        CRM_HIP(hipMemcpyAsync(g->Wy.ptr, Wy.data(), sizeof(double) * c, hipMemcpyHostToDevice, st));
-        CRM_HIP(hipStreamSynchronize(st));     // (Wy lives on this stack frame)
-    }
-    CRM_HIP(hipGetLastError());
-    const long slab = (long)(1 + c) * ldq;
-    if (bg->fast_T && ctx->fast_gene_rot) {
-        // t_y = Mix(rho)' (H'y) for all phenotypes at once; the rows Q0(rho)'W came over with the copy of `like`'s rotations
-        const long ldh = bg->ldh;
-        ScopedBuf thw, rt;
-        if ((rc = thw.ensure(sizeof(double) * ldh * ldY)) != CRM_OK) return fail(rc);
-        if ((rc = rt.ensure(sizeof(double) * (size_t)nrho * ngenes * ldq)) != CRM_OK) return fail(rc);
-        if ((rc = ctx->ws_probs.ensure(sizeof(GemmProblem) * (CRM_MAX_RHO + 4))) != CRM_OK) return fail(rc);
-        CRM_HIP(hipMemsetAsync(thw.ptr, 0, sizeof(double) * ldh * ldY, st));
-        CRM_HIP(hipMemsetAsync(rt.ptr, 0, sizeof(double) * (size_t)nrho * ngenes * ldq, st));
-        std::vector<GemmProblem> pr(nrho + 1);
-        GemmProblem p0{};
-        p0.X = bg->H.as<double>(); p0.ldx = ldh; p0.Y = dY.as<double>(); p0.ldy = ldY;
-        p0.C = thw.as<double>(); p0.ldc = ldY; p0.M = (int)bg->cols; p0.N = ngenes;
-        pr[0] = p0;
-        for (int i = 0; i < nrho; i++) {
-            GemmProblem p{};
-            p.X = thw.as<double>(); p.ldx = ldY; p.Y = bg->Mix[i].as<double>(); p.ldy = ldq;
-            p.C = rt.as<double>() + (size_t)i * ngenes * ldq; p.ldc = ldq;
-            p.M = ngenes; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-            pr[1 + i] = p;
-        }
-        CRM_HIP(hipMemcpyAsync(ctx->ws_probs.ptr, pr.data(), sizeof(GemmProblem) * (nrho + 1), hipMemcpyHostToDevice, st));
-        if ((rc = launch_gemm_tn(ctx, ctx->ws_probs.as<GemmProblem>(), 1, (int)bg->cols, ngenes, np, false, 0, 1, 0)) != CRM_OK) return fail(rc);
-        if ((rc = launch_gemm_tn(ctx, ctx->ws_probs.as<GemmProblem>() + 1, nrho, ngenes, (int)ldq, ldh, false, 0, 1, 0)) != CRM_OK) return fail(rc);
-        for (int j = 0; j < ngenes; j++)     // row 0 of every grid point's [(1 + c) x ldq] block
-            CRM_HIP(hipMemcpy2DAsync(made[j]->rot.ptr, sizeof(double) * slab, rt.as<double>() + (size_t)j * ldq,
-                                     sizeof(double) * (size_t)ngenes * ldq, sizeof(double) * ldq, nrho, hipMemcpyDeviceToDevice, st));
-        CRM_HIP(hipStreamSynchronize(st));
-    } else {
-        for (crm_gene* g : made)
-            if ((rc = gene_rotations(g)) != CRM_OK) return fail(rc);
-    }
-    for (int j = 0; j < ngenes; j++) out[j] = made[j];
-    return CRM_OK;
-    });
-}
-
-void crm_gene_destroy(crm_gene* g) {
-    try {
-    if (!g) return;
-    std::lock_guard<std::recursive_mutex> lock(g->ctx->mu);   // (reachable from a finalizer on any thread)
-    (void)hipSetDevice(g->ctx->device);
-    (void)hipStreamSynchronize(g->ctx->stream);
-    g->dt_own.release();
-    for (auto* b : {&g->yW, &g->E0, &g->WW, &g->Wy, &g->Wproj, &g->rot, &g->Ep, &g->YE, &g->EE, &g->idx, &g->dt_Z1, &g->dt_sums,
-                    &g->dt_Zt, &g->kinEp, &g->kinP, &g->kinUE, &g->kinEE, &g->wb_yW})
-        b->release();
-    delete g;
-    } catch (...) {  // (nothing may unwind into the caller; a destroy has no status to return)
-    }
-}
-
-// ---- panel ----------------------------------------------------------------------------------
-// (No lock of the context: the upload touches none of its work buffers and runs on a stream of its own, so that a panel
-// can go to the device from one thread while another thread's constructor holds the context -- 8 GB over PCIe beside
-// the eleven decompositions.  The copy is complete when the call returns.)
-int crm_panel_create(crm_ctx* ctx, long n, const double* G, long ldg, long p, crm_panel** out) {
-    return crm::guarded("crm_panel_create", [&]() -> int {
-    if (!ctx || !G || !out || n <= 0 || p <= 0 || ldg < p) return CRM_ERR_ARG;
-    *out = nullptr;
-    CRM_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->upload_stream ? ctx->upload_stream : ctx->stream;
-    crm_panel* P = new crm_panel();
-    P->ctx = ctx;
-    P->uid = next_panel_uid();
-    P->n = n;
-    P->n_pad = round_up(n, CELL_PAD);
-    P->p = p;
-    P->ld = round_up(p, 128);
-    int rc = P->G.ensure(sizeof(double) * P->n_pad * P->ld);
-    if (rc == CRM_OK) rc = upload_padded(st, P->G.as<double>(), P->ld, P->n_pad, G, ldg, n, p);
-    if (rc != CRM_OK) { crm_panel_destroy(P); return rc; }
-    CRM_HIP(hipStreamSynchronize(st));
-    *out = P;
-    return CRM_OK;
-    });
-}
-
-void crm_panel_destroy(crm_panel* P) {
-    try {
-    if (!P) return;
-    std::lock_guard<std::recursive_mutex> lock(P->ctx->mu);   // (reachable from a finalizer on any thread)
-    (void)hipSetDevice(P->ctx->device);
-    (void)hipStreamSynchronize(P->ctx->stream);
-    P->G.release();
-    P->Gd.release();
-    P->group.release();
-    P->Z.release();
-    delete P;
-    } catch (...) {  // (nothing may unwind into the caller; a destroy has no status to return)
-    }
-}
-
-// ---- grouped (donor-constant) panel --------------------------------------------------------------
-int crm_panel_create_grouped(crm_ctx* ctx, long n, const int* group, long m, const double* Gd, long ldg,
-                             long p, crm_panel** out) {
-    return crm::guarded_on("crm_panel_create_grouped", ctx, [&]() -> int {
-    if (!ctx || !group || !Gd || !out || n <= 0 || m <= 0 || p <= 0 || ldg < p) return CRM_ERR_ARG;
-    *out = nullptr;
-    for (long i = 0; i < n; i++) {
-        if (group[i] < 0 || group[i] >= m) {
-            set_error("grouped panel: group index %d at cell %ld outside [0, %ld)", group[i], i, m);
-            return CRM_ERR_ARG;
-        }
-    }
-    CRM_HIP(hipSetDevice(ctx->device));
-    crm_panel* P = new crm_panel();
-    P->ctx = ctx;
-    P->uid = next_panel_uid();
-    P->n = n;
-    P->n_pad = round_up(n, CELL_PAD);
-    P->p = p;
-    P->ld = round_up(p, 128);
-    P->grouped = true;
-    P->m = m;
-    P->m_pad = round_up(m, GEMM_BK);
-    P->ldz = round_up(m, 128) + 128;
-    int rc = P->Gd.ensure(sizeof(double) * P->m_pad * P->ld);
-    if (rc == CRM_OK) rc = upload_padded(ctx->stream, P->Gd.as<double>(), P->ld, P->m_pad, Gd, ldg, m, p);
-    if (rc == CRM_OK) rc = P->group.ensure(sizeof(int) * n);
-    if (rc == CRM_OK) rc = P->Z.ensure(sizeof(double) * P->n_pad * P->ldz);
-    if (rc != CRM_OK) { crm_panel_destroy(P); return rc; }
-    CRM_HIP(hipMemcpyAsync(P->group.ptr, group, sizeof(int) * n, hipMemcpyHostToDevice, ctx->stream));
-    P->group_key = content_key(group, sizeof(int) * n, (unsigned long)m);
-    rc = launch_indicator(ctx->stream, P->group.as<int>(), n, P->n_pad, (int)m, P->Z.as<double>(), P->ldz);
-    if (rc != CRM_OK) { crm_panel_destroy(P); return rc; }
-    CRM_HIP(hipStreamSynchronize(ctx->stream));
-    *out = P;
-    return CRM_OK;
-    });
-}
-
-}  // extern "C"
-
-namespace crm {
-// One workgroup per variant: mean and standard deviation of the EXPANDED column (every donor's dosage weighted by
-// its number of cells; population variance, as numpy's std / the reference simulator's column_normalize,
-// cellregmap/_simulate.py:50-54), then the standardised donor-level column in float64.
-__global__ __launch_bounds__(256) void standardise_dosages_kernel(const signed char* __restrict__ D, long ldd, long m, long p,
-                                                                  const double* __restrict__ cells_of, double n, int standardise,
-                                                                  double* __restrict__ Gd, long ldg, int* __restrict__ flags) {
-    __shared__ double red[2][4];
-    const long j = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double s1 = 0.0, s2 = 0.0;
-    for (long d = tid; d < m; d += blockDim.x) {
-        const double g = (double)D[d * ldd + j], w = cells_of[d];
-        s1 += w * g;
-        s2 += w * g * g;
-    }
-    for (int off = 32; off > 0; off >>= 1) { s1 += __shfl_xor(s1, off, 64); s2 += __shfl_xor(s2, off, 64); }
-    if (lane == 0) { red[0][wave] = s1; red[1][wave] = s2; }
-    __syncthreads();
-    s1 = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    s2 = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    const double mean = s1 / n;
-    double var = 0.0;   // second pass in the centred form (the raw-moment difference cancels for rare alleles)
-    for (long d = tid; d < m; d += blockDim.x) {
-        const double c = (double)D[d * ldd + j] - mean;
-        var += cells_of[d] * c * c;
-    }
-    for (int off = 32; off > 0; off >>= 1) var += __shfl_xor(var, off, 64);
-    __syncthreads();
-    if (lane == 0) red[0][wave] = var;
-    __syncthreads();
-    var = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / n;
-    const double sd = sqrt(var);
-    if (standardise && !(sd > 0.0)) {
-        if (tid == 0) atomicOr(&flags[0], 1);   // monomorphic column: the reference's normalisation divides by zero
-        return;
-    }
-    for (long d = tid; d < m; d += blockDim.x) {
-        const double g = (double)D[d * ldd + j];
-        Gd[d * ldg + j] = standardise ? (g - mean) / sd : g;
-    }
-}
-}  // namespace crm
-
-extern "C" int crm_panel_create_grouped_i8(crm_ctx* ctx, long n, const int* group, long m, const signed char* dosage,
-                                           long ldd, long p, int standardise, crm_panel** out) {
-    return crm::guarded_on("crm_panel_create_grouped_i8", ctx, [&]() -> int {
-    if (!ctx || !group || !dosage || !out || n <= 0 || m <= 0 || p <= 0 || ldd < p) return CRM_ERR_ARG;
-    *out = nullptr;
-    std::vector<double> cells_of(m, 0.0);
-    for (long i = 0; i < n; i++) {
-        if (group[i] < 0 || group[i] >= m) {
-            set_error("grouped panel: group index %d at cell %ld outside [0, %ld)", group[i], i, m);
-            return CRM_ERR_ARG;
-        }
-        cells_of[group[i]] += 1.0;
-    }
-    CRM_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    crm_panel* P = new crm_panel();
-    auto fail = [&](int code) { crm_panel_destroy(P); return code; };
-    P->ctx = ctx;
-    P->uid = next_panel_uid();
-    P->n = n;
-    P->n_pad = round_up(n, CELL_PAD);
-    P->p = p;
-    P->ld = round_up(p, 128);
-    P->grouped = true;
-    P->m = m;
-    P->m_pad = round_up(m, GEMM_BK);
-    P->ldz = round_up(m, 128) + 128;
-    ScopedBuf dD, dCells, dFlags;
-    int rc = P->Gd.ensure(sizeof(double) * P->m_pad * P->ld);
-    if (rc == CRM_OK) rc = P->group.ensure(sizeof(int) * n);
-    if (rc == CRM_OK) rc = P->Z.ensure(sizeof(double) * P->n_pad * P->ldz);
-    if (rc == CRM_OK) rc = dD.ensure((size_t)m * p);
-    if (rc == CRM_OK) rc = dCells.ensure(sizeof(double) * m);
-    if (rc == CRM_OK) rc = dFlags.ensure(sizeof(int));
-    if (rc != CRM_OK) return fail(rc);
-    int h_flag = 0;
-    if (hipMemsetAsync(P->Gd.ptr, 0, sizeof(double) * P->m_pad * P->ld, st) != hipSuccess ||
-        hipMemsetAsync(dFlags.ptr, 0, sizeof(int), st) != hipSuccess ||
-        hipMemcpy2DAsync(dD.ptr, p, dosage, ldd, p, m, hipMemcpyHostToDevice, st) != hipSuccess ||   // 1 byte per dosage over PCIe
-        hipMemcpyAsync(dCells.ptr, cells_of.data(), sizeof(double) * m, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(P->group.ptr, group, sizeof(int) * n, hipMemcpyHostToDevice, st) != hipSuccess)
-        return fail(CRM_ERR_HIP);
-    hipLaunchKernelGGL(standardise_dosages_kernel, dim3((unsigned)p), dim3(256), 0, st, dD.as<signed char>(), p, m, p,
-                       dCells.as<double>(), (double)n, standardise ? 1 : 0, P->Gd.as<double>(), P->ld, dFlags.as<int>());
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(&h_flag, dFlags.ptr, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess)
-        return fail(CRM_ERR_HIP);
-    P->group_key = content_key(group, sizeof(int) * n, (unsigned long)m);
-    rc = launch_indicator(st, P->group.as<int>(), n, P->n_pad, (int)m, P->Z.as<double>(), P->ldz);
-    if (rc != CRM_OK) return fail(rc);
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(CRM_ERR_HIP);
-    if (h_flag) {
-        set_error("panel: a monomorphic variant cannot be standardised (zero variance)");
-        return fail(CRM_ERR_NUMERIC);
-    }
-    *out = P;
-    return CRM_OK;
-    });
-}
-
-extern "C" {
-// Upload an expanded genotype matrix, check it for non-finite entries and -- when a candidate
-// grouping is given (group_hint[i] in [0, m_hint), rep_rows[d] = a row carrying group d) -- verify ON THE
-// DEVICE that every cell equals its group's representative in every variant; if so the panel is stored
-// donor-level (grouped), otherwise dense.  Replaces the host-side isfinite pass and the host-side
-// verification of detect_groups (both O(n p) memory passes that dominated short scans).
-int crm_panel_create_auto(crm_ctx* ctx, long n, const double* G, long ldg, long p, const int* group_hint,
-                          long m_hint, const long* rep_rows, crm_panel** out, int* out_grouped) {
-    return crm::guarded("crm_panel_create_auto", [&]() -> int {   // (no lock of the context, like crm_panel_create)
-    if (!ctx || !G || !out || n <= 0 || p <= 0 || ldg < p) return CRM_ERR_ARG;
-    if (out_grouped) *out_grouped = 0;
-    crm_panel* P = nullptr;
-    CRM_TRY(crm_panel_create(ctx, n, G, ldg, p, &P));
-    hipStream_t st = ctx->upload_stream ? ctx->upload_stream : ctx->stream;
-    auto fail = [&](int code) { crm_panel_destroy(P); return code; };
-    ScopedBuf flags, dgroup, drep;
-    int rc;
-    if ((rc = flags.ensure(sizeof(int) * 2)) != CRM_OK) return fail(rc);
-    const bool hinted = group_hint && rep_rows && m_hint > 0 && m_hint < BLOCK_SLACK_MAX - 1;
-    if (hinted) {
-        for (long i = 0; i < n; i++)
-            if (group_hint[i] < 0 || group_hint[i] >= m_hint) return fail(CRM_ERR_ARG);
-        for (long d = 0; d < m_hint; d++)
-            if (rep_rows[d] < 0 || rep_rows[d] >= n) return fail(CRM_ERR_ARG);
-        if ((rc = dgroup.ensure(sizeof(int) * n)) != CRM_OK) return fail(rc);
-        if ((rc = drep.ensure(sizeof(long) * m_hint)) != CRM_OK) return fail(rc);
-        if (hipMemcpyAsync(dgroup.ptr, group_hint, sizeof(int) * n, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpyAsync(drep.ptr, rep_rows, sizeof(long) * m_hint, hipMemcpyHostToDevice, st) != hipSuccess)
-            return fail(CRM_ERR_HIP);
-    }
-    if (hipMemsetAsync(flags.ptr, 0, sizeof(int) * 2, st) != hipSuccess) return fail(CRM_ERR_HIP);
-    hipLaunchKernelGGL(verify_panel_kernel, dim3((unsigned)n, (unsigned)((p + 255) / 256)), dim3(256), 0, st,
-                       P->G.as<double>(), P->ld, p, hinted ? dgroup.as<int>() : nullptr,
-                       hinted ? drep.as<long>() : nullptr, flags.as<int>());
-    int h_flags[2] = {0, 0};
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(h_flags, flags.ptr, sizeof h_flags, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return fail(CRM_ERR_HIP);
-    if (h_flags[0]) {
-        set_error("panel: non-finite values in the genotype matrix");
-        return fail(CRM_ERR_NUMERIC);
-    }
-    if (hinted && !h_flags[1]) {
-        // collapse: gather the representative rows, drop the dense copy
-        P->grouped = true;
-        P->m = m_hint;
-        P->m_pad = round_up(m_hint, GEMM_BK);
-        P->ldz = round_up(m_hint, 128) + 128;
-        if ((rc = P->Gd.ensure(sizeof(double) * P->m_pad * P->ld)) != CRM_OK) return fail(rc);
-        if (hipMemsetAsync(P->Gd.ptr, 0, sizeof(double) * P->m_pad * P->ld, st) != hipSuccess) return fail(CRM_ERR_HIP);
-        hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)m_hint, (unsigned)((P->ld + 255) / 256)), dim3(256), 0,
-                           st, P->G.as<double>(), P->ld, drep.as<long>(), P->Gd.as<double>());
-        if ((rc = P->group.ensure(sizeof(int) * n)) != CRM_OK) return fail(rc);
-        if ((rc = P->Z.ensure(sizeof(double) * P->n_pad * P->ldz)) != CRM_OK) return fail(rc);
-        if (hipMemcpyAsync(P->group.ptr, dgroup.ptr, sizeof(int) * n, hipMemcpyDeviceToDevice, st) != hipSuccess)
-            return fail(CRM_ERR_HIP);
-        if ((rc = launch_indicator(st, P->group.as<int>(), n, P->n_pad, (int)m_hint, P->Z.as<double>(), P->ldz)) != CRM_OK)
-            return fail(rc);
-        if (hipStreamSynchronize(st) != hipSuccess) return fail(CRM_ERR_HIP);
-        P->G.release();
-        P->group_key = content_key(group_hint, sizeof(int) * n, (unsigned long)m_hint);
-        if (out_grouped) *out_grouped = 1;
-    }
-    *out = P;
-    return CRM_OK;
-    });
-}
-
-int crm_set_donor_collapse(crm_ctx* ctx, int on) {
-    return crm::guarded_on("crm_set_donor_collapse", ctx, [&]() -> int {
-    if (!ctx) return CRM_ERR_ARG;
-    ctx->collapse = on != 0;
-    return CRM_OK;
-    });
-}
-
-}  // extern "C"
-
-namespace crm {
-
-// sums[d][q] over the cells of donor d: q = 0 count, 1 y, 2.. the covariate columns.  One workgroup per (donor, q):
-// its threads stride over the cells and meet in a fixed order (the same bits whatever the launch).
-__global__ __launch_bounds__(256) void donor_sums_kernel(const int* __restrict__ group, long cells, int m,
-                                                         const double* __restrict__ yW, long ldw, int c,
-                                                         double* __restrict__ sums) {
-    __shared__ double part[256];
-    const int d = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
-    double acc = 0.0;
-    for (long i = tid; i < cells; i += 256)
-        if (group[i] == d) acc += q == 0 ? 1.0 : yW[i * ldw + (q - 1)];
-    part[tid] = acc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) part[tid] += part[tid + w];
-        __syncthreads();
-    }
-    if (tid == 0) sums[d * DT_SUMS_LD + q] = part[0];
-}
-
-__global__ void permute_group_kernel(const int* __restrict__ group, const int* __restrict__ idx, long n,
-                                     int* __restrict__ out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = group[idx[i]];
-}
-
-// Z2[b, j] = sum_{d, d'} gamma_{d,b} gamma_{d',b} C[(d, d'), j]  with  C[(d, d'), :] = sum_i z'_d[i] z_d'[i] E[i, :]
-// (test direction carried by the permuted indicators z', fixed effect by the unpermuted ones)
-__global__ __launch_bounds__(128) void donor_cross_kernel(const double* __restrict__ Gam, long ld_gam, int m,
-                                                           const double* __restrict__ C, long ldc, int k0,
-                                                           double* __restrict__ Z2, long ldz2) {
-    __shared__ double gam[BLOCK_SLACK_MAX > 256 ? 256 : BLOCK_SLACK_MAX];
-    const int b = blockIdx.x;
-    for (int d = threadIdx.x; d < m; d += blockDim.x) gam[d] = Gam[(long)d * ld_gam + b];
-    __syncthreads();
-    for (int j = threadIdx.x; j < k0; j += blockDim.x) {
-        double acc = 0.0;
-        for (int d = 0; d < m; d++) {
-            const double gd = gam[d];
-            if (gd == 0.0) continue;
-            double inner = 0.0;
-            const double* row = C + (long)d * m * ldc + j;
-            for (int e = 0; e < m; e++) inner += gam[e] * row[(long)e * ldc];
-            acc += gd * inner;
-        }
-        Z2[(long)b * ldz2 + j] = acc;
-    }
-}
-
-// Per-donor tables of the collapsed path: every n-length contraction of the scan is linear in
-// diag(g) (or diag(g)^2 = sum_d gamma_d^2 diag(z_d) for donor-constant g), so it is taken once per donor
-// indicator z_d with the same kernels and afterwards combined with the donor dosages gamma.
-static int build_donor_tables(crm_gene* gene, const crm_panel* panel, crm_donor_tables* shared, const double* d_Ep,
-                              const double* d_EE, const double* Zt, bool cross) {
-    // shared != nullptr: also (re)build the phenotype-free tables (TZ, Bd, Z2, Z3) into *shared.
-    // Zt: indicators of the test direction (rows permuted by idx_G, else the panel's own);
-    // cross: Z2 becomes the m*m-row table of the mixed products z'_d o z_d'.
-    crm_background* bg = gene->bg;
-    crm_ctx* ctx = bg->ctx;
-    hipStream_t st = ctx->stream;
-    const long n = bg->n, np = bg->n_pad, ldq = bg->ldq;
-    const int nrho = bg->nrho, c = gene->c, k0 = gene->k0;
-    const long m = panel->m, mp = panel->m_pad;
-    const int npair = k0 * (k0 + 1) / 2;
-    const long ldZ1 = gene->ld_ye, ldZ2 = gene->ld_ep, ldZ3 = gene->ld_ee;
-    const bool full = shared != nullptr;
-    CRM_TRY(ctx->ws_probs.ensure(sizeof(GemmProblem) * (CRM_MAX_RHO + 4)));
-    GemmProblem* d_probs = ctx->ws_probs.as<GemmProblem>();
-    std::vector<GemmProblem> probs(CRM_MAX_RHO + 4);
-    const double* Z = panel->Z.as<double>();
-    if (full) CRM_TRY(crm_background_require_q0(bg, -1));   // the tables are contractions against every Q0(rho)
-    if (full) {
-        CRM_TRY(shared->TZ.ensure(sizeof(double) * (size_t)nrho * mp * ldq));
-        CRM_TRY(shared->Bd.ensure(sizeof(double) * (size_t)nrho * mp * k0 * ldq));
-        CRM_HIP(hipMemsetAsync(shared->TZ.ptr, 0, sizeof(double) * (size_t)nrho * mp * ldq, st));
-        CRM_HIP(hipMemsetAsync(shared->Bd.ptr, 0, sizeof(double) * (size_t)nrho * mp * k0 * ldq, st));
-        for (int i = 0; i < nrho; i++) {
-            GemmProblem p{};
-            p.X = Z; p.ldx = panel->ldz; p.Y = bg->Q0[i].as<double>(); p.ldy = ldq;
-            p.C = shared->TZ.as<double>() + (size_t)i * mp * ldq; p.ldc = ldq;
-            p.M = (int)m; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-            probs[i] = p;
-        }
-        CRM_HIP(hipMemcpyAsync(d_probs, probs.data(), sizeof(GemmProblem) * nrho, hipMemcpyHostToDevice, st));
-        CRM_TRY(launch_gemm_tn(ctx, d_probs, nrho, (int)m, (int)ldq, np, false, 0, 1, 0));
-        CRM_HIP(hipStreamSynchronize(st));
-        for (int i = 0; i < nrho; i++) {
-            GemmProblem p{};
-            p.X = Zt; p.ldx = panel->ldz; p.E = d_Ep; p.lde = gene->ld_ep; p.k0 = k0;
-            p.Y = bg->Q0[i].as<double>(); p.ldy = ldq;
-            p.C = shared->Bd.as<double>() + (size_t)i * mp * k0 * ldq; p.ldc = ldq;
-            p.M = (int)m * k0; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-            probs[i] = p;
-        }
-        CRM_HIP(hipMemcpyAsync(d_probs, probs.data(), sizeof(GemmProblem) * nrho, hipMemcpyHostToDevice, st));
-        CRM_TRY(launch_gemm_tn(ctx, d_probs, nrho, (int)m * k0, (int)ldq, np, true, k0, 1, 0));
-        CRM_HIP(hipStreamSynchronize(st));
-    }
-    // side tables (split over the cell axis: only one M tile)
-    DevBuf unused;
-    struct Side { DevBuf* buf; const double* Y; long ldy; int N; long ld; bool needed; } side[3] = {
-        {&gene->dt_Z1, gene->YE.as<double>(), gene->ld_ye, k0 * (1 + c), ldZ1, true},
-        {full ? &shared->Z2 : &unused, d_Ep, gene->ld_ep, k0, ldZ2, full},
-        {full ? &shared->Z3 : &unused, d_EE, gene->ld_ee, npair, ldZ3, full}};
-    if (full && cross) {
-        // C[(d*m + d'), :] = KR(Zt, Z)' Ep : the Khatri-Rao contraction with the indicators as "contexts"
-        side[1].needed = false;
-        const long rows = m * m;
-        CRM_TRY(shared->Z2.ensure(sizeof(double) * (size_t)rows * ldZ2));
-        CRM_HIP(hipMemsetAsync(shared->Z2.ptr, 0, sizeof(double) * (size_t)rows * ldZ2, st));
-        GemmProblem p{};
-        p.X = Zt; p.ldx = panel->ldz; p.E = Z; p.lde = panel->ldz; p.k0 = (int)m;
-        p.Y = d_Ep; p.ldy = gene->ld_ep; p.C = shared->Z2.as<double>(); p.ldc = ldZ2;
-        p.M = (int)rows; p.N = k0;
-        CRM_HIP(hipMemcpyAsync(d_probs, &p, sizeof p, hipMemcpyHostToDevice, st));
-        CRM_TRY(launch_gemm_tn(ctx, d_probs, 1, (int)rows, k0, np, true, (int)m, 1, 0));
-        CRM_HIP(hipStreamSynchronize(st));
-    }
-    for (auto& sd : side) {
-        if (!sd.needed) continue;
-        const int ks = pick_split(np, sd.ld / GEMM_BN);
-        const long sz = mp * sd.ld;
-        CRM_TRY(sd.buf->ensure(sizeof(double) * (size_t)sz * ks));
-        CRM_HIP(hipMemsetAsync(sd.buf->ptr, 0, sizeof(double) * (size_t)sz * ks, st));
-        GemmProblem p{};
-        p.X = Zt; p.ldx = panel->ldz; p.Y = sd.Y; p.ldy = sd.ldy; p.C = sd.buf->as<double>(); p.ldc = sd.ld;
-        p.M = (int)m; p.N = sd.N;
-        CRM_HIP(hipMemcpyAsync(d_probs, &p, sizeof p, hipMemcpyHostToDevice, st));
-        CRM_TRY(launch_gemm_tn(ctx, d_probs, 1, (int)m, sd.N, np, false, 0, ks, sz));
-        CRM_TRY(launch_reduce_splits(st, sd.buf->as<double>(), sz, ks, sz));
-        CRM_HIP(hipStreamSynchronize(st));
-    }
-    CRM_TRY(gene->dt_sums.ensure(sizeof(double) * mp * DT_SUMS_LD));
-    CRM_HIP(hipMemsetAsync(gene->dt_sums.ptr, 0, sizeof(double) * mp * DT_SUMS_LD, st));
-    hipLaunchKernelGGL(donor_sums_kernel, dim3((unsigned)m, c + 2), dim3(256), 0, st,
-                       panel->group.as<int>(), n, (int)m, gene->yW.as<double>(), gene->ld_yw, c,
-                       gene->dt_sums.as<double>());
-    CRM_HIP(hipGetLastError());
-    CRM_HIP(hipStreamSynchronize(st));
-    return CRM_OK;
-}
-
-}  // namespace crm
-
-extern "C" {
-
-// ---- the scan ---------------------------------------------------------------------------------
-}  // extern "C"
-
-namespace crm {
 
 // Collapsed path: a variant that keeps less than this share of its squared norm outside span(W) is repeated on the dense
 // path (the donor-level sums can only form [W, g]'K^-1[W, g] in the raw basis: eps / share instead of eps / sqrt(share))
@@ -1458,9 +181,9 @@ static ScanPlan plan_scan(const std::vector<crm_gene*>& genes, const crm_panel* 
     // Z1 = Gt' [y o E, W o E] of all phenotypes in ONE batched launch per block (a problem per phenotype, each with its own
     // output region) instead of a skinny launch + reduction per phenotype -- at config 4 those 64 pairs of launches were an
     // eighth of the scan.  The slices along the cell axis shrink with the number of problems.
-    P.ks1 = pick_split(np, (long)mt_blk * (P.ldZ1 / GEMM_BN) * ng);
-    P.ks2 = pick_split(np, (long)mt_blk * (P.ldZ2 / GEMM_BN));
-    P.ks3 = pick_split(np, (long)mt_blk * (P.ldZ3 / GEMM_BN));
+    P.ks1 = split_for(np, (long)mt_blk * (P.ldZ1 / GEMM_BN) * ng);
+    P.ks2 = split_for(np, (long)mt_blk * (P.ldZ2 / GEMM_BN));
+    P.ks3 = split_for(np, (long)mt_blk * (P.ldZ3 / GEMM_BN));
     // H'G of step 3: few output tiles (cols x block) against a long contraction (cells) -- slices along the cell axis
     // until the launch fills the chip twice with 128-wide tiles (mode B at config 3: 64 tiles, cfg3 mode C: 320)
     // (rows of the operand of the rotations' Mix products: the half factor's columns, or -- folded kinship structure,
@@ -1887,9 +610,7 @@ struct ScanPass {
         if (P.cross) {
             CRM_TRY(g0->dt_Zt.ensure(sizeof(double) * (size_t)np * panel->ldz + sizeof(int) * n));
             int* gperm = reinterpret_cast<int*>(g0->dt_Zt.as<double>() + (size_t)np * panel->ldz);
-            hipLaunchKernelGGL(permute_group_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
-                               panel->group.as<int>(), d_idxG, n, gperm);
-            CRM_HIP(hipGetLastError());
+            CRM_TRY(launch_permute_group(st, panel->group.as<int>(), d_idxG, n, gperm));
             CRM_TRY(launch_indicator(st, gperm, n, np, (int)panel->m, g0->dt_Zt.as<double>(), panel->ldz));
             Zt = g0->dt_Zt.as<double>();
         }
@@ -2787,9 +1508,7 @@ struct ScanPass {
         probs[2] = p;
         CRM_TRY(upload(SLOT_RHO, probs.data() + 1, 2));
         if (P.cross) {
-            hipLaunchKernelGGL(donor_cross_kernel, dim3(nb), dim3(128), 0, st, B.Gb + R.b0, ldb, (int)panel->m,
-                               tab->Z2.as<double>(), P.ldZ2, k0, dZ2, P.ldZ2);
-            CRM_HIP(hipGetLastError());
+            CRM_TRY(launch_donor_cross(st, nb, B.Gb + R.b0, ldb, (int)panel->m, tab->Z2.as<double>(), P.ldZ2, k0, dZ2, P.ldZ2));
         } else {
             CRM_TRY(launch_gemm_tn(ctx, d_probs + SLOT_RHO, 1, nb, k0, P.xrows, false, 0, s2, z2_sz));
             CRM_TRY(launch_reduce_splits(st, dZ2, z2_sz, s2, z2_sz));
@@ -2829,7 +1548,7 @@ struct ScanPass {
         CRM_HIP(hipMemcpyAsync(lam0.data(), d_lam, sizeof(double) * (size_t)nb * k0, hipMemcpyDeviceToHost, st));
         CRM_HIP(hipMemcpyAsync(q0.data(), d_Q, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
         CRM_HIP(hipMemcpyAsync(p0.data(), d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
-        ScopedBuf probe;
+        DevBuf probe;
         CRM_TRY(probe.ensure(sizeof(NullFitOut) * (size_t)nb + 64));
         flat.assign(nb, 0);
         for (int side = 0; side < 2; side++) {
@@ -3323,3 +2042,4 @@ int crm_scan_interaction_multi_tail(crm_gene* const* genes, int ngenes, crm_pane
 }
 
 }  // extern "C"
+

@@ -45,6 +45,9 @@ long crm_test_sync_fallbacks(const crm_ctx* ctx);
 /* CRM_POISON=1 only (else always 0): number of device buffers of this process whose red zone -- 4 KiB of 0xFF behind every
  * allocation -- was found overwritten when the buffer was released, i.e. kernels that wrote past the end of a buffer. */
 long crm_test_overruns(void);
+/* Bytes held by the live device buffers of the process (red zones not counted): equal before and after a round that
+ * creates and destroys its objects, or something leaked. */
+long crm_test_live_device_bytes(void);
 /* ... and the same inspection, now, of the context's own work buffers (which live as long as the context). */
 int crm_test_check_context(crm_ctx* ctx);
 /* Self-test of that detector: writes eight bytes past the end of a scratch buffer on purpose (CRM_POISON=1 only) and

@@ -112,6 +112,8 @@ struct crm_ctx {
     long tail_launches = 0;   // blocks whose last columns took the 160-column-tile launch (crm_test_tail_launches)
     long spectrum_tail_launches = 0;   // blocks whose last few columns of the spectrum went through the skinny one-pass kernel
     long donor_pair_blocks = 0;   // blocks whose per-donor sums came from the symmetric pair features (crm_test_donor_pair_blocks)
+    long rotation_tail_launches = 0;   // blocks whose rotations sent the last few columns of their spectra through it (crm_test_rotation_tail_launches)
+    long rho0_position_blocks = 0;     // blocks whose null fits at rho = 0 read the position basis (crm_test_rho0_position_blocks)
     long unrelated_donor_blocks = 0;   // blocks served by the unrelated-donor form (crm_test_unrelated_donor_blocks)
     long gram_dma_launches = 0;   // score-statistic Grams that went through a direct-to-LDS kernel (crm_test_gram_dma_launches)
     long tests_without_pair = 0;  // (phenotype, variant) tests whose fit has no kinship term to speak of: no A~ formed for them

@@ -105,6 +105,7 @@ static int seal_unrelated_donors(crm_background* bg, const double* hKd, long m) 
     std::vector<double> hU((size_t)groups * k2pad * 128, 0.0), hR((size_t)k1 * ldp, 0.0), hEE((size_t)k1 * k1, 0.0),
         lam((size_t)P, 0.0);
     std::vector<double> A((size_t)k2 * k2), V, w;
+    long kept = 0;
     for (long d = 0; d < groups; d++) {
         const double* Cd = C.data() + (size_t)d * KK * ldc;
         for (int i = 0; i < k2; i++)
@@ -118,6 +119,7 @@ static int seal_unrelated_donors(crm_background* bg, const double* hKd, long m) 
             if (!(w[j] > (double)k2 * 2.220446049250313e-16 * wmax)) continue;
             const double sc = 1.0 / std::sqrt(w[j]);
             lam[d * k2 + j] = w[j];
+            kept++;
             for (int q = 0; q < k2; q++) Ud[(size_t)q * 128 + j] = V[(size_t)q * k2 + j] * sc;
             for (int a = 0; a < k1; a++) {
                 double s = 0.0;
@@ -142,6 +144,7 @@ static int seal_unrelated_donors(crm_background* bg, const double* hKd, long m) 
     }
     CRM_HIP(hipStreamSynchronize(st));
     bg->wb_P = P;
+    bg->wb_kept = kept;
     bg->wb_ldp = ldp;
     bg->wb_k2pad = k2pad;
     static std::atomic<unsigned long> wb_tables_made{0};

@@ -83,6 +83,7 @@ struct crm_background {
     // Woodbury (a k1 x k1 capacitance per variant): no product with MixK(rho*) at all.
     bool kin_wb = false;
     long wb_P = 0, wb_ldp = 0;                  // positions donors k2, padded to 128
+    long wb_kept = 0;                           // positions with a direction of us_d above rounding (the others: zero columns of Phi)
     int wb_k2pad = 0;                           // k2 padded to whole stages of the contraction
     crm::DevBuf wb_U;                           // [donors][k2pad x 128]: U_d Lambda_d^-1/2, zero padded
     crm::DevBuf wb_R;                           // [k1 x wb_ldp]: R[a, d k2 + j] = (Phi_d' E1_d)[j, a]

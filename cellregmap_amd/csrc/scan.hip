@@ -109,8 +109,9 @@ enum class Route {
 };
 
 // Slots of the pass's problem records (ctx->ws_probs): [0] a single product -- in step 6 the A~ groups, then their tails;
-// [1, 1 + nrho) the rotations of step 3 (the side contractions at 1 and 2); from 1 + nrho the rotations' cut problems; from
-// SLOT_KIN the records of the kinship-structure routes (ScanPlan::kin_probs); after those, the Z1 problems
+// from 1 the rotations of step 3 (the side contractions at 1 and 2): the batched launch's problems, behind them the cut ones,
+// behind those the spectrum tails -- each a part of one of the nrho products, so at most 2 nrho records; from SLOT_KIN
+// the records of the kinship-structure routes (ScanPlan::kin_probs); after those, the Z1 problems
 constexpr int SLOT_ONE = 0, SLOT_RHO = 1, SLOT_KIN = 2 * CRM_MAX_RHO + 4;
 
 // What a pass does: sizes, leading dimensions, splits and the route, fixed before anything is launched (plan_scan).
@@ -406,6 +407,9 @@ struct ScanPass {
     std::vector<int> h_pos = std::vector<int>((size_t)P.BLK * ng), h_ord = std::vector<int>(P.pair_cap);
     std::vector<GemmProblem> probs = std::vector<GemmProblem>(CRM_MAX_RHO + 4);
     std::vector<int> pair_of = std::vector<int>((size_t)nrho * P.BLK), h_near = std::vector<int>(P.BLK);
+    bool rho0_pos[CRM_MAX_RHO] = {false};   // grid points whose null fits of this block read the position basis (plan_rotations)
+    std::vector<GemmProblem> rot_tails;     // the rotations' spectrum tails of the block (plan_rotations)
+    std::vector<GemmProblem> phi_recs;      // the donors' records of Phi'gx of the block (woodbury_phi)
 
     ScanPass(const std::vector<crm_gene*>& genes_, crm_panel* panel_, long first_, long count_, const int* idx_E_,
              const int* idx_G_, const std::vector<ScanOut>& outs_, bool allow_collapse, std::vector<long>* near_out_)
@@ -872,29 +876,41 @@ struct ScanPass {
     // The eleven products run as one launch of equally long tiles, i.e. in rounds of as many tiles as the chip holds
     // workgroups (two per CU): at config 3, 12 832 tiles are 25.06 rounds of 512 and the last 0.06 costs a whole one.
     // The smallest problems that make up that remainder (there: rho = 1, r = 50, 32 tiles) are taken out and run cut
-    // along the contraction axis instead -- a sixteenth of a round plus a reduction.  Returns the problems left in probs.
-    int cut_rotations(const Block& B, int& n_main) {
-        const int nb = B.nb, BLK = P.BLK;
-        n_main = nrho;
+    // along the contraction axis instead -- a sixteenth of a round plus a reduction.  cut_rotations works on probs[0, n_list)
+    // and returns the problems left in probs.  cut_choice is the choice itself, for problems of N[0 .. cnt) columns: which
+    // ones are cut, how many tiles they are, and the rounds the batched launch takes after it -- plan_rotations asks it
+    // too, to see what saves a round.
+    bool cut_choice(int nb, int cnt, const int* N, bool* is_cut, long& acc, long& rounds) const {
         const long slots = 2L * ctx_cus(ctx), mtl = (nb + GEMM_BM - 1) / GEMM_BM;
         long tiles[CRM_MAX_RHO], total = 0;
         int order[CRM_MAX_RHO];
-        for (int i = 0; i < nrho; i++) { tiles[i] = mtl * ((probs[i].N + 127) / 128); total += tiles[i]; order[i] = i; }
-        std::sort(order, order + nrho, [&](int a, int b) { return tiles[a] < tiles[b]; });
+        for (int i = 0; i < cnt; i++) { tiles[i] = mtl * ((N[i] + 127) / 128); total += tiles[i]; order[i] = i; }
+        std::sort(order, order + cnt, [&](int a, int b) { return tiles[a] < tiles[b]; });
         const long need = total % slots;
-        long acc = 0;
+        acc = 0;
         int take = 0;
-        while (take < nrho - 1 && acc < need) acc += tiles[order[take++]];
-        if (!(total > slots && need > 0 && acc >= need && acc <= slots / 4)) return CRM_OK;
+        while (take < cnt - 1 && acc < need) acc += tiles[order[take++]];
+        const bool cut = total > slots && need > 0 && acc >= need && acc <= slots / 4;
+        rounds = ((cut ? total - acc : total) + slots - 1) / slots;
+        for (int q = 0; q < take && cut; q++) is_cut[order[q]] = true;
+        return cut;
+    }
+    int cut_rotations(const Block& B, int n_list, int& n_main) {
+        const int nb = B.nb, BLK = P.BLK;
+        n_main = n_list;
+        const long slots = 2L * ctx_cus(ctx);
+        int widths[CRM_MAX_RHO];
+        bool is_cut[CRM_MAX_RHO] = {false};
+        long acc = 0, rounds = 0;
+        for (int i = 0; i < n_list; i++) widths[i] = probs[i].N;
+        if (!cut_choice(nb, n_list, widths, is_cut, acc, rounds)) return CRM_OK;
         int n_cut = 0, cut_ks = 1;
         GemmProblem cut_probs[CRM_MAX_RHO];
         double* cut_dst[CRM_MAX_RHO];
-        bool is_cut[CRM_MAX_RHO] = {false};
         long cut_doubles = 0;
-        for (int q = 0; q < take; q++) is_cut[order[q]] = true;
         while ((long)(cut_ks + 1) * acc <= slots && cut_ks < 16 && P.kdim / GEMM_BK / (cut_ks + 1) >= 8) cut_ks++;
         n_main = 0;
-        for (int i = 0; i < nrho; i++) {
+        for (int i = 0; i < n_list; i++) {
             if (!is_cut[i]) { probs[n_main++] = probs[i]; continue; }
             GemmProblem c = probs[i];
             cut_dst[n_cut] = c.C;
@@ -908,7 +924,7 @@ struct ScanPass {
             cut_probs[q].C = ctx->ws_Tcut.as<double>() + at;
             at += (long)BLK * cut_probs[q].ldc;
         }
-        const int slot = SLOT_RHO + nrho;
+        const int slot = SLOT_RHO + n_main;
         CRM_TRY(upload(slot, cut_probs, n_cut));
         int cut_maxn = 1;
         for (int q = 0; q < n_cut; q++) cut_maxn = std::max(cut_maxn, cut_probs[q].N);
@@ -928,6 +944,9 @@ struct ScanPass {
         if (P.folded()) CRM_TRY(fold_TH(B));
         else if (P.kin()) CRM_TRY(unfolded_TH(B));
         else if (P.fastT) CRM_TRY(plain_TH(B));
+        // (unrelated-donor form: Phi'gx of the block, which the null fits at rho = 0 read -- H'Gx is all it needs)
+        if (P.wb()) CRM_TRY(woodbury_phi(B));
+        GemmProblem all[CRM_MAX_RHO];
         for (int i = 0; i < nrho; i++) {
             GemmProblem p{};
             if (P.fastT) {
@@ -939,10 +958,12 @@ struct ScanPass {
             }
             p.C = ctx->ws_T.as<double>() + (size_t)i * P.BLK * P.ldT; p.ldc = P.ldT;
             p.M = nb; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
-            probs[i] = p;
+            all[i] = p;
         }
-        int n_main = nrho;
-        if (P.fastT) CRM_TRY(cut_rotations(B, n_main));
+        const int n_list = plan_rotations(B, all);   // (probs[0, n_list), rot_tails, rho0_pos)
+        if (n_list == 0) return CRM_OK;
+        int n_main = n_list;
+        if (P.fastT) CRM_TRY(cut_rotations(B, n_list, n_main));
         CRM_TRY(upload(SLOT_RHO, probs.data(), n_main));
         // (unrelated-donor form: the kernel timer brackets this launch, the rotations MixK(rho)'(H'Gx) -- the step's largest)
         const bool timing_T = P.wb() && ctx->timing && ctx->timed_used < 65536;
@@ -952,7 +973,84 @@ struct ScanPass {
             CRM_TRY(timer_close());
             for (int q = 0; q < n_main; q++) ctx->kr_flops += 2.0 * (double)P.kdim * (double)nb * (double)probs[q].N;
         }
+        if (!rot_tails.empty()) {   // (records behind the batched launch's and the cut ones; rot_tails lives as long as the pass)
+            CRM_TRY(upload(SLOT_RHO + n_list, rot_tails.data(), rot_tails.size()));
+            CRM_TRY(launch_skinny_tn(st, d_probs + SLOT_RHO + n_list, (int)rot_tails.size(), nb, P.kdim));
+            ctx->rotation_tail_launches++;
+        }
         return CRM_OK;
+    }
+
+    // What the rotations of a block leave out of the batched launch, decided together because the launch runs in rounds:
+    //
+    // rho = 0 from the positions (unrelated-donor form).  Sigma(0) = blockdiag_d kappa_d us_d us_d' has the positions
+    // Phi_d = us_d U_d Lambda_d^-1/2 as orthonormal eigenvectors and wb_S0 at rho = 0 as eigenvalues, and the null fit is
+    // a sum over the spectrum that asks for no order and no particular basis of an eigenspace: Phi'gx (woodbury_phi),
+    // Phi'[y, W] (prepare_woodbury) and wb_S0 serve it as they serve the assembly, and the dense product MixK(0)'(H'Gx)
+    // -- a tenth of the step's largest launch at config 3 -- is not formed.  Dropped positions (zero columns of Phi,
+    // s = 0) stay in: each adds nothing to a quadratic form and log delta to the log-determinant, as a direction of the
+    // complement does.  Guard: the positions seal_unrelated_donors kept must be as many as the grid point's rank
+    // -- else the two rank rules disagree about a direction and the dense product stays.
+    //
+    // The spectrum tails.  A spectrum a little longer than a multiple of the 128-column tile (config 3: r = 5000 = 39
+    // tiles + 8 columns) pays a whole column of tiles for those few columns, at every grid point; one pass over H'Gx per
+    // grid point forms them instead (launch_skinny_tn; eligibility as in a_records).
+    //
+    // Either changes the last bits of the null fits it touches (another summation order, another kernel), so each is
+    // taken only where the batched launch then runs fewer rounds (cut_choice).  Config 3, rounds of 512 tiles: all ten
+    // problems 10 x 32 x 40 + 32 = 12 832 tiles, 25 rounds once rho = 1 is cut out; the tails alone 12 512, still 25;
+    // rho = 0 alone 11 552, 23; both 9 x 32 x 39 + 32 = 11 264 = 22 rounds exactly.  A block of a few variants is a
+    // fraction of one round either way and keeps the dense products.  form("rho0_positions") / form("rotation_tails"): 0
+    // never, 1 by this rule, 2 wherever the guard / the eligibility allows (tests).
+    int plan_rotations(const Block& B, const GemmProblem* all) {
+        // (both only where the rotations start from H'Gx, P.fastT: the launch cut_rotations then shapes, whose rounds
+        // cut_choice models -- the unrelated-donor form is planned on the folded route alone, which has it)
+        const int mode0 = P.fastT && P.wb() ? form("rho0_positions", 1) : 0;
+        const int modeT = P.fastT && P.kin() && !form("kr_no_tail", 0) ? form("rotation_tails", 1) : 0;
+        bool cand[CRM_MAX_RHO] = {false};
+        int rem[CRM_MAX_RHO] = {0}, n_cand = 0, n_rem = 0;
+        for (int i = 0; i < nrho; i++) {
+            const GemmProblem& p = all[i];
+            cand[i] = mode0 > 0 && bg->rho[i] == 0.0 && bg->r[i] > 0 && bg->wb_kept == bg->r[i];
+            const int m = p.N % 128;
+            if (modeT > 0 && p.N >= 1024 && m > 0 && m <= 16 && p.ldx % 2 == 0 && (reinterpret_cast<uintptr_t>(p.X) & 15) == 0) rem[i] = m;
+            n_cand += cand[i] ? 1 : 0;
+        }
+        for (int i = 0; i < nrho; i++) n_rem += rem[i] > 0 ? 1 : 0;
+        auto rounds = [&](bool drop, bool tails) {
+            int widths[CRM_MAX_RHO], cnt = 0;
+            bool is_cut[CRM_MAX_RHO] = {false};
+            long acc = 0, r = 0;
+            for (int i = 0; i < nrho; i++)
+                if (!(drop && cand[i])) widths[cnt++] = all[i].N - (tails ? rem[i] : 0);
+            if (cnt > 0) cut_choice(B.nb, cnt, widths, is_cut, acc, r);
+            return r;
+        };
+        // try {neither, drop rho = 0, tails, both} and keep the fewest rounds; a tie keeps the earlier one, the dense
+        // products first.  A forced form (value 2) is on in all four.
+        const bool can0 = n_cand > 0, canT = n_rem > 0, force0 = mode0 >= 2 && can0, forceT = modeT >= 2 && canT;
+        bool drop = force0, tails = forceT;
+        long best = rounds(drop, tails);
+        for (int pick = 1; pick < 4; pick++) {
+            const bool d = force0 || (can0 && (pick & 1)), t = forceT || (canT && (pick & 2));
+            const long r = rounds(d, t);
+            if (r < best) { best = r; drop = d; tails = t; }
+        }
+        rot_tails.clear();
+        int n_list = 0;
+        for (int i = 0; i < nrho; i++) {
+            rho0_pos[i] = drop && cand[i];
+            if (rho0_pos[i]) continue;
+            GemmProblem p = all[i];
+            if (tails && rem[i] > 0) {
+                GemmProblem t = p;
+                p.N -= rem[i];
+                t.Y = p.Y + p.N; t.C = p.C + p.N; t.N = rem[i];
+                rot_tails.push_back(t);
+            }
+            probs[n_list++] = p;
+        }
+        return n_list;
     }
 
     // 4. null fits + rho* per gene; the probe hook (ctx->probe_on) keeps the (variant, grid point) records of this block --
@@ -971,6 +1069,13 @@ struct ScanPass {
                 R.tW = R.ty + ldq; R.ldW = ldq;
                 R.S0 = bg->S0[i].as<double>();
                 R.r = bg->r[i];
+                if (rho0_pos[i]) {   // (the operands of the assembly: gene_results, the P.wb() branch)
+                    R.T = wb_g; R.ldT = P.ldwb;
+                    R.ty = wb_yW + (size_t)gi * (1 + c) * P.ldwb;
+                    R.tW = R.ty + P.ldwb; R.ldW = P.ldwb;
+                    R.S0 = bg->wb_S0[i].as<double>();
+                    R.r = (int)bg->wb_P;
+                }
             }
             fa.WW = g->WW.as<double>(); fa.Wy = g->Wy.as<double>(); fa.yy = g->yy;
             fa.gg = d_gg; fa.gy = d_gy + (size_t)gi * BLK; fa.gW = d_gW; fa.ld_gW = P.ld_gW;
@@ -981,6 +1086,7 @@ struct ScanPass {
             CRM_TRY(launch_nullfit(st, fa, nb, false, d_queue));
         }
         trace_pop();
+        if (std::find(rho0_pos, rho0_pos + nrho, true) != rho0_pos + nrho) ctx->rho0_position_blocks++;
         if (ctx->probe_on) {
             std::vector<NullFitTrial> h_trial((size_t)nb * nrho);
             CRM_HIP(hipMemcpyAsync(h_trial.data(), d_trial, sizeof(NullFitTrial) * h_trial.size(), hipMemcpyDeviceToHost, st));
@@ -1008,7 +1114,8 @@ struct ScanPass {
         }
         CRM_HIP(hipMemcpyAsync(d_fit, rb->fit.data(), rb->fit.size(), hipMemcpyHostToDevice, st));
         // (unrelated-donor form: the assembly reads Phi'gx and E1'gx of the block from H'Gx -- formed again, same bits)
-        if (P.wb()) CRM_TRY(fold_TH(B));
+        // (and nothing after the null fits reads the rotations on that route: no rows recorded, none to put back)
+        if (P.wb()) return fold_TH(B);
         hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((P.ldT + 255) / 256), B.nb), dim3(256), 0, st, ctx->ws_T.as<double>(),
                            (long)P.BLK, P.ldT, d_fit, B.nb, (int)P.ldT, rb->T.as<double>(), 1);
         CRM_HIP(hipGetLastError());
@@ -1018,15 +1125,14 @@ struct ScanPass {
     // Phi'gx of the block: per donor U_d Lambda_d^-1/2 applied to its rows of H'Gx (stored transposed)
     int woodbury_phi(const Block& B) {
         const long groups = bg->kin_groups;
-        std::vector<GemmProblem> kp((size_t)groups);
+        phi_recs.resize((size_t)groups);
         GemmProblem p{};
         p.X = ctx->ws_TH.as<double>() + (size_t)bg->kin_k1 * P.ldb; p.ldx = P.ldb; p.C = wb_g; p.ldc = P.ldwb; p.M = B.nb;
-        woodbury_records(bg, p, (long)bg->kin_k2 * P.ldb, kp.data());
-        CRM_TRY(with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) {
-            return launch_gemm_tn(ctx, d_kp, (int)groups, B.nb, bg->kin_k2, bg->wb_k2pad, false, 0, 1, 0);
-        }));
-        ctx->unrelated_donor_blocks++;
-        return CRM_OK;
+        woodbury_records(bg, p, (long)bg->kin_k2 * P.ldb, phi_recs.data());
+        // (no with_records: the host is not to wait here, ahead of the step's largest launch -- phi_recs lives as long as
+        // the pass and is written again only in the next block, after collect_fits has synchronised the stream)
+        CRM_TRY(upload(SLOT_KIN, phi_recs.data(), phi_recs.size()));
+        return launch_gemm_tn(ctx, d_probs + SLOT_KIN, (int)groups, B.nb, bg->kin_k2, bg->wb_k2pad, false, 0, 1, 0);
     }
 
     // 5. the fits of the block on the host (nb*ng*48 bytes cross PCIe): the collapsed path's near flags, the permutation
@@ -1057,10 +1163,12 @@ struct ScanPass {
             rb->col0 = B.col0; rb->nb = nb; rb->collapsed = P.collapsed();
             rb->fit.resize(sizeof(NullFitOut) * (size_t)nb);
             memcpy(rb->fit.data(), h_fit.data(), rb->fit.size());
-            CRM_TRY(rb->T.ensure(sizeof(double) * (size_t)nb * P.ldT));
-            hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((P.ldT + 255) / 256), nb), dim3(256), 0, st, ctx->ws_T.as<double>(),
-                               (long)BLK, P.ldT, d_fit, nb, (int)P.ldT, rb->T.as<double>(), 0);
-            CRM_HIP(hipGetLastError());
+            if (!P.wb()) {   // (replay_block: the unrelated-donor form replays no rows)
+                CRM_TRY(rb->T.ensure(sizeof(double) * (size_t)nb * P.ldT));
+                hipLaunchKernelGGL(replay_rows_kernel, dim3((unsigned)((P.ldT + 255) / 256), nb), dim3(256), 0, st, ctx->ws_T.as<double>(),
+                                   (long)BLK, P.ldT, d_fit, nb, (int)P.ldT, rb->T.as<double>(), 0);
+                CRM_HIP(hipGetLastError());
+            }
         }
         // Flat-optimum flag, first half (info calls only; include/crm_hip.h: CRM_MODEL_FLAT_OPTIMUM): how far the search of the
         // selected fit was from taking another path -- the smallest margin of the decisions on objective values that steered
@@ -1773,12 +1881,13 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
         if (!P.fastT && !P.collapsed()) CRM_TRY(crm_background_require_q0(bg, -1));
         if (ctx->replay_mode == 2) {
             CRM_TRY(S.replay_block(B));
+            if (P.wb()) CRM_TRY(S.woodbury_phi(B));
         } else {
-            CRM_TRY(S.rotations(B));
+            CRM_TRY(S.rotations(B));   // (unrelated-donor form: with Phi'gx, woodbury_phi)
             CRM_TRY(S.null_fits(B));
             if (ctx->probe_on) return CRM_OK;   // (test hook: the pass ends with this block's records)
         }
-        if (P.wb()) CRM_TRY(S.woodbury_phi(B));
+        if (P.wb()) ctx->unrelated_donor_blocks++;
         CRM_TRY(S.collect_fits(B));
         for (int b0 = 0; b0 < B.nb;) {
             const SubRange R = S.sub_range(B, b0);
@@ -1988,6 +2097,21 @@ int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks) {
     return crm::guarded("crm_test_unrelated_donor_blocks", [&]() -> int {
     if (!ctx || !blocks) return CRM_ERR_ARG;
     *blocks = ctx->unrelated_donor_blocks;
+    return CRM_OK;
+    });
+}
+
+int crm_test_rho0_position_blocks(const crm_ctx* ctx, long* blocks) {
+    return crm::guarded("crm_test_rho0_position_blocks", [&]() -> int {
+    if (!ctx || !blocks) return CRM_ERR_ARG;
+    *blocks = ctx->rho0_position_blocks;
+    return CRM_OK;
+    });
+}
+int crm_test_rotation_tail_launches(const crm_ctx* ctx, long* launches) {
+    return crm::guarded("crm_test_rotation_tail_launches", [&]() -> int {
+    if (!ctx || !launches) return CRM_ERR_ARG;
+    *launches = ctx->rotation_tail_launches;
     return CRM_OK;
     });
 }

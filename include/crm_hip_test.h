@@ -29,6 +29,11 @@ extern "C" {
  *   "chase_abort" 1       the bulge chase of the two-stage eigen-solver gives up at its first inter-workgroup wait (what a
  *                         device shared with another process does to it after 2 s): the constructor must come out through
  *                         the one-stage solver with the same spectra
+ *   "rho0_positions" 0 / 2   unrelated-donor form: the null fits at rho = 0 never / wherever the background allows it from the
+ *                         position basis instead of the rotation MixK(0)'(H'Gx) (default 1: where the batched launch of the
+ *                         rotations then runs fewer rounds)
+ *   "rotation_tails" 0 / 2   the last r mod 128 <= 16 spectrum columns of the rotations never / wherever eligible through the
+ *                         skinny one-pass kernel (default 1: where that saves a round; "kr_no_tail" 1 switches them off too)
  *   "flat_kappa_milli" v  factor (in thousandths) on the noise bound of CRM_MODEL_FLAT_OPTIMUM / CRM_MODEL_RHO_TIE (study tool)
  * These replace the environment switches of earlier versions; the GPU suite flips every one of them. */
 int crm_test_set_form(const char* name, int value, int reset);
@@ -85,6 +90,15 @@ long crm_test_donor_pair_blocks(const crm_ctx* ctx);
  * (scan.hip: kin_wb; form "kin_diag": 0 never, 1 where the background allows it and the cost model says it pays, 2 wherever
  * the background and the shapes allow it -- k0 + c + 2 + k1 <= 144).  *blocks: the count so far. */
 int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks);
+/* Blocks of this context's scans on the unrelated-donor form whose null fits at rho = 0 read the position basis -- Phi'gx,
+ * Phi'[y, W] and s_p(0), the assembly's own operands -- so that the rotation MixK(0)'(H'Gx) was not formed (scan.hip:
+ * plan_rotations; taken where the kept positions are as many as the grid point's rank; form "rho0_positions" = 0: never).
+ * *blocks: the count so far. */
+int crm_test_rho0_position_blocks(const crm_ctx* ctx, long* blocks);
+/* Blocks whose rotations MixK(rho)'(H'Gx) sent the last few columns of their spectra (r mod 128 <= 16, kinship-structure
+ * routes) through the skinny one-pass kernel (scan.hip: plan_rotations; form "rotation_tails": 0 never, 1 where the
+ * batched launch then takes fewer rounds, 2 wherever a problem is eligible).  *launches: the count so far. */
+int crm_test_rotation_tail_launches(const crm_ctx* ctx, long* launches);
 /* Score-statistic Grams of this context's scans that went through a direct-to-LDS kernel (assemble.hip: up to 144 rows
  * with 16-byte-aligned operands, form "gram_staged" = 0) and not through the register-staged one.  *launches: the count so far. */
 int crm_test_gram_dma_launches(const crm_ctx* ctx, long* launches);

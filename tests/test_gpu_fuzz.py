@@ -10,6 +10,7 @@ permutation hooks (tests/fuzz_cases.py).  Two tiers:
     (``scan_interaction_info``: bound_Q, bound_p -- how far two faithful runs may differ, include/crm_hip.h:
     crm_scan_interaction_bounds), i.e. the north-star tolerances (Q 1e-6, p 1e-5) outright wherever the library does not
     raise the corresponding flag; the flagged share and the share of scans beyond the tolerances are bounded as well.
+    Beside the library's own bounds every variant, flagged or not, stays inside the oracle-vs-oracle envelope (Q 2e-5, p 5e-5).
     rho* may differ only where the two best grid points tie in lml.
 
 The summary (worst / median differences, share beyond the north-star bar, lml agreement) goes to
@@ -152,6 +153,10 @@ def test_fuzz_verbatim_procedure():
     # ... and every scan, flagged or not, stays within its own bounds (p: plus what two roundings of Davies' integration to
     # acc = 1e-6 differ by)
     assert s["beyond_own_bound_on_Q"] == 0 and s["beyond_own_bound_on_p"] == 0, s
+    # ... and, independently of what the library reports about itself (its bounds rest on an empirical constant), inside the
+    # envelope two faithful runs of the ORACLE span among themselves (tests/test_oracle_spread.py, test_oracle_brackets.py)
+    assert np.all(a[same, 0] <= 2e-5), (s, float(a[same, 0].max()))
+    assert np.all(a[same, 2] <= 5e-5 * a[same, 5] + P_ATOL), (s, float(a[same, 1].max()))
     # the flags mean something: few p-values are at risk (measured 1.6 - 2.0 % of a stream), the statistic -- which moves by
     # ~1e-6 per stopping tolerance -- on about a third; and few scans are actually beyond (measured 0.4 - 0.6 % / 0.02 %)
     assert s["share_flat_optimum"] < 0.05, s

@@ -3,7 +3,11 @@ rows of 16 x 16 tiles dealt to the four wavefronts) against the register-staged 
 tolerances of test_gpu_edges.py::test_gram_kernel_forms_agree: Q within 1e-11 max(|Q|, tr F), F within 1e-11 max|F|, p
 within 1e-6 relative + 1e-13.  The null fits do not read the Gram: rho* and the other outputs are the same bits.  Every
 case asserts through crm_test_gram_dma_launches that the direct-to-LDS form served the default scan and not the staged
-one."""
+one.
+
+This file holds the two forms against each other only; what both share (the orthogonalisation against W, the mixing
+matrices, the finalisation) is held against an independent extended-precision reference, at the same parameter rows and both
+forms, by tests/test_gpu_pinned.py::test_gram_forms."""
 import ctypes
 
 import numpy as np

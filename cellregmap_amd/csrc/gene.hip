@@ -43,19 +43,20 @@ static int gene_rotations(crm_gene* g) {
         // Q0(rho) = H Mix(rho):  t = Mix(rho)' (H'[y, W]) -- no Q0 needed
         DevBuf thw;
         const long ldh = bg->ldh;
-        CRM_TRY(thw.ensure(sizeof(double) * ldh * 128));
+        const long ldt = round_up(1 + c, 128);   // (129 columns at c = CRM_MAX_COV_XWIDE)
+        CRM_TRY(thw.ensure(sizeof(double) * ldh * ldt));
         CRM_TRY(g->rot.ensure(sizeof(double) * slab * nrho));
         CRM_TRY(ctx->ws_probs.ensure(sizeof(GemmProblem) * (CRM_MAX_RHO + 4)));
-        CRM_HIP(hipMemsetAsync(thw.ptr, 0, sizeof(double) * ldh * 128, ctx->stream));
+        CRM_HIP(hipMemsetAsync(thw.ptr, 0, sizeof(double) * ldh * ldt, ctx->stream));
         CRM_HIP(hipMemsetAsync(g->rot.ptr, 0, sizeof(double) * slab * nrho, ctx->stream));
         std::vector<GemmProblem> pr(nrho + 1);
         GemmProblem p0{};
         p0.X = bg->H.as<double>(); p0.ldx = ldh; p0.Y = g->yW.as<double>(); p0.ldy = ldyw;
-        p0.C = thw.as<double>(); p0.ldc = 128; p0.M = (int)bg->cols; p0.N = 1 + c;
+        p0.C = thw.as<double>(); p0.ldc = ldt; p0.M = (int)bg->cols; p0.N = 1 + c;
         pr[0] = p0;
         for (int i = 0; i < nrho; i++) {
             GemmProblem p{};
-            p.X = thw.as<double>(); p.ldx = 128; p.Y = bg->Mix[i].as<double>(); p.ldy = ldq;
+            p.X = thw.as<double>(); p.ldx = ldt; p.Y = bg->Mix[i].as<double>(); p.ldy = ldq;
             p.C = g->rot.as<double>() + (long)i * slab; p.ldc = ldq;
             p.M = 1 + c; p.N = bg->r[i] > 0 ? bg->r[i] : 1;
             pr[1 + i] = p;
@@ -250,8 +251,9 @@ int crm_gene_create(crm_background* bg, const double* y, const double* W, int c,
     std::vector<double> WW, Wy;
     CRM_TRY(orthogonal_covariates(n, c, y, W, g->W_host, g->W_basis, WW, Wy));
     const double* Wuse = g->W_host.data();
-    // [y | W] packed as one operand (column 0 = y) for the rotations, plus separate views
-    const long ldyw = 128;
+    // [y | W] packed as one operand (column 0 = y) for the rotations, plus separate views; 1 + c = 129 columns at
+    // c = CRM_MAX_COV_XWIDE
+    const long ldyw = round_up(1 + c, 128);
     CRM_TRY(g->yW.ensure(sizeof(double) * np * ldyw));
     CRM_TRY(g->E0.ensure(sizeof(double) * np * g->lde));
     {

@@ -235,7 +235,9 @@ static ScanPlan plan_scan(const std::vector<crm_gene*>& genes, const crm_panel* 
     // where the Gram over the donors k2 positions with k1 more rows costs less than the MixK product it replaces.
     const int wb_k1 = bg->kin ? bg->kin_k1 : 0;
     bool wb = false;
-    // (k0 + c + 2 + k1 <= 144: the single-workgroup Gram forms; wider shapes keep the MixK route)
+    // (k0 + c + 2 + k1 <= 144: the single-workgroup Gram forms; wider shapes keep the MixK route.  c + 1 <= 128: this
+    // route keeps [y | W] and its products in tables of 128 columns (prepare_woodbury: yWk, Bk, E1'[y, W]), so
+    // c = CRM_MAX_COV_XWIDE = 128, whose [y | W] has 129, stays on the MixK route)
     constexpr int WB_MAX_ROWS = 144;
     if (kfold && bg->kin_wb && !P.slow_forms && c + 1 <= 128 && P.KT + wb_k1 <= WB_MAX_ROWS &&
         woodbury_lds_bytes(P.KT, wb_k1) <= 150 * 1024) {

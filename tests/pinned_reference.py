@@ -19,11 +19,24 @@ achieve on a problem and the yardstick of tests/test_gpu_pinned.py (``limits``).
 
 A problem whose reference cannot be evaluated -- Sigma not positive definite in longdouble, X without full column rank --
 raises: nothing is left out silently.
+
+The effect sizes and the association likelihood-ratio tests are closed forms at a point the device reports as well:
+
+    K = v0 (rho U U' + (1 - rho) L L') + v1 I     beta = (M' K^-1 M)^-1 M' K^-1 y     u = U' K^-1 (y - M beta)
+    ML:  s = y' P y / n                           lml = -1/2 (n log 2 pi + n + n log s + log|Sigma|)
+
+(``pinned_effects``, ``pinned_ml``; U = g o E0, M = [W, g, E0]).  Where the device reports no point -- the association
+scan that refits delta per variant -- ``pinned_ml_max`` maximises the reference itself over x = logit(delta) by three-point
+parabolas, which also gives the curvature that turns the search's tolerance on x into one on the likelihood (it is
+``pinned_max`` with ``restricted=False``; ``grid_lmls`` uses the restricted one for the effect sizes' grid).  Their
+float64 yardsticks are ``oracle_effects_at`` and ``oracle_ml_at``; ``effects_errors`` / ``ml_errors`` are the records
+``limits`` reads.
 """
 import numpy as np
 
-from oracle.lmm import LMM
-from oracle.scoretest import LowRankCov, Projection, score_F, score_Q
+from oracle.lmm import LMM, FastScanner
+from oracle.scoretest import LowRankCov, Projection, cov_solve, score_F, score_Q
+from oracle.sugar import economic_qs_linear
 
 LD = np.longdouble
 if np.finfo(LD).eps > 1e-18:
@@ -34,6 +47,11 @@ LOG2PI = np.log(8 * np.arctan(LD(1)))      # (numpy.pi is a double)
 FLOOR_PER_CELL = 2.2e-16      # an n-length float64 sum in the worst order
 CEILING = 1e-11               # the tightest figure the suite asserts between two forms of the library
 PATHS = 32                    # device stages rounded independently, against the oracle's three products with Q0
+# ``grid_lmls`` maximises the reference itself at the two best grid values whenever they are this close (relative).  It is
+# 100 x CEILING on purpose: ``argmax_or_tie`` is only ever asked with a limit that ``limits`` returned, which is at most
+# CEILING, so every pair it can call tied -- or just not tied -- has been maximised in longdouble, not read at a float64
+# optimum; pairs further apart than this are separated by far more than that read can be off.
+REFINE_WITHIN = 100 * CEILING
 
 
 def _cholesky(A, block=32):
@@ -117,6 +135,116 @@ def pinned(y, X, half_S, half_dK, delta, gram=None):
     return Q, F, lml, s
 
 
+def _sigma(half_S, delta, gram, n):
+    """(1 - delta) hS hS' + delta I in longdouble."""
+    if gram is None:
+        hS = np.asarray(half_S, LD)
+        gram = hS @ hS.T
+    Sigma = (1 - LD(delta)) * np.asarray(gram, LD)
+    Sigma[np.diag_indices(n)] += LD(delta)
+    return Sigma
+
+
+def _off(basis, v):
+    """v projected off an orthonormal basis, twice."""
+    v = v - basis @ (basis.T @ v)
+    return v - basis @ (basis.T @ v)
+
+
+def pinned_ml(y, X, half_S, delta, gram=None):
+    """(lml, scale) of the ML likelihood in longdouble at ``delta``: s = y'Py / n, lml = -1/2 (n log 2 pi + n + n log s +
+    log|Sigma|) -- what the association scan's null fit (X = W) and its alternatives (X = [W, g]) return."""
+    y = np.asarray(y, LD).ravel()
+    X = np.asarray(X, LD)
+    n = y.size
+    L = _cholesky(_sigma(half_S, delta, gram, n))
+    white = _forward(L, np.column_stack([y, X]))
+    basis, _ = _orthonormal(white[:, 1:])
+    ry = _off(basis, white[:, 0])
+    s = (ry @ ry) / n
+    lml = -(n * LOG2PI + n + n * np.log(s) + 2 * np.sum(np.log(np.diag(L)))) / 2
+    return lml, s
+
+
+def _logistic(x):
+    return 1 / (1 + np.exp(-LD(x)))
+
+
+def pinned_max(y, X, half_S, x0, restricted=False, gram=None):
+    """(L*, x*, curvature): the maximum over x = logit(delta) of ``pinned_ml`` (``restricted``: of ``pinned``'s lml), the
+    x where it is taken and -L'' there, by three-point parabolas in longdouble: from x0 (the float64 oracle's optimum)
+    with h = 1e-3 until the vertex stays within h, then once with h = 1e-4 around it.  A stencil that is not concave has
+    no vertex: raised."""
+    y = np.asarray(y, LD).ravel()
+    if gram is None:
+        hS = np.asarray(half_S, LD)
+        gram = hS @ hS.T
+    none = np.zeros((y.size, 0))
+
+    def f(x):
+        if restricted:
+            return pinned(y, X, None, none, _logistic(x), gram=gram)[2]
+        return pinned_ml(y, X, None, _logistic(x), gram=gram)[0]
+
+    def vertex(x, h):
+        lo, mid, hi = f(x - h), f(x), f(x + h)
+        second = (hi - 2 * mid + lo) / (h * h)
+        if not second < 0:
+            raise ValueError("the likelihood is not concave around x = %.6g (second difference %.3g)" % (float(x), float(second)))
+        return x - (hi - lo) / (2 * h) / second, -second
+
+    x, h = LD(x0), LD(10) ** -3
+    for _ in range(4):
+        new, _ = vertex(x, h)
+        moved, x = abs(new - x), new
+        if moved <= h:
+            break
+    else:
+        raise ValueError("no maximum within 4e-3 of x0 = %.6g" % float(x0))
+    x, curvature = vertex(x, LD(10) ** -4)
+    return f(x), x, curvature
+
+
+def pinned_ml_max(y, X, half_S, x0, gram=None):
+    """``pinned_max`` of the ML likelihood: the reference of a scan that refits delta per variant."""
+    return pinned_max(y, X, half_S, x0, restricted=False, gram=gram)
+
+
+def refit_allowance(x, curvature):
+    """What a search with rtol = atol = 1e-6 on x may leave of the likelihood: half the curvature times the square of three
+    tolerances (brent_search.h and oracle/brent.py stop when the bracket is within 2 tol of the best point)."""
+    return float(curvature) / 2 * (3 * (1e-6 * abs(float(x)) + 1e-6)) ** 2
+
+
+def pinned_effects(y, M, U, half_L, rho, v0, v1, beta=None):
+    """(beta, u) in longdouble at (rho, v0, v1): K = v0 (rho U U' + (1 - rho) L L') + v1 I is formed and factorised, [y, M, U]
+    whitened, the whitened M orthonormalised (Gram-Schmidt twice; R = basis' Z) and beta back-substituted from
+    R beta = basis' y; u = U' K^-1 (y - M beta).  M = [W, g, E0], U = g o E0; ``half_L = None``: no L (mode A).
+    ``beta`` given: u for that beta (estimate_aggregate_environment takes it from a fit under another covariance)."""
+    y = np.asarray(y, LD).ravel()
+    M, U = np.asarray(M, LD), np.asarray(U, LD)
+    n, m = M.shape
+    rho, v0, v1 = LD(rho), LD(v0), LD(v1)
+    K = (v0 * rho) * (U @ U.T)
+    if half_L is not None:
+        hL = np.asarray(half_L, LD)
+        K += (v0 * (1 - rho)) * (hL @ hL.T)
+    K[np.diag_indices(n)] += v1
+    white = _forward(_cholesky(K), np.column_stack([y, M, U]))
+    wy, Z, wU = white[:, 0], white[:, 1:1 + m], white[:, 1 + m:]
+    if beta is not None:
+        beta = np.asarray(beta, LD)
+        return beta, wU.T @ (wy - Z @ beta)
+    basis, _ = _orthonormal(Z)                  # (raises where M is not of full column rank)
+    R = basis.T @ Z
+    t = basis.T @ wy
+    t += basis.T @ (wy - basis @ t)
+    beta = np.zeros(m, LD)
+    for j in range(m - 1, -1, -1):
+        beta[j] = (t[j] - R[j, j + 1:] @ beta[j + 1:]) / R[j, j]
+    return beta, wU.T @ (wy - Z @ beta)
+
+
 class _LMMAt(LMM):
     """The oracle's LMM with delta given as a number instead of through logistic(logit(delta)), which returns a
     neighbouring double: the two evaluations are to meet at the same point exactly."""
@@ -139,6 +267,83 @@ def oracle_at(y, X, Q0, S0, half_dK, delta, projection=Projection):
     P = projection(LowRankCov(Q0, np.asarray(S0, float), lmm.v0, lmm.v1), np.asarray(X, float))
     y = np.asarray(y, float).ravel()
     return score_Q(P, half_dK, y), score_F(P, half_dK), lml, lmm.scale
+
+
+def pinned_solve(half_S, v0, v1, rhs):
+    """(v0 hS hS' + v1 I)^-1 rhs in longdouble: K = C C', the inverse of C by forward substitution on the identity."""
+    hS, rhs = np.asarray(half_S, LD), np.asarray(rhs, LD)
+    n = hS.shape[0]
+    K = LD(v0) * (hS @ hS.T)
+    K[np.diag_indices(n)] += LD(v1)
+    Ci = _forward(_cholesky(K), np.eye(n))
+    return Ci.T @ (Ci @ rhs)
+
+
+def effects_half(U, half_L, rho):
+    """The per-SNP covariance half [sqrt(rho) U, sqrt(1 - rho) L] (oracle/crm.py: predict_interaction)."""
+    if half_L is None:
+        return np.sqrt(rho) * np.asarray(U, float)
+    return np.concatenate([np.sqrt(rho) * np.asarray(U, float), np.sqrt(1 - rho) * np.asarray(half_L, float)], axis=1)
+
+
+def oracle_effects_at(y, M, U, half_L, rho, v0, v1, fit=None, beta=None):
+    """The float64 oracle's (beta, u, lml, scale) at the same point: its ``LMM`` (restricted) pinned at
+    delta = v1 / (v0 + v1), then ``LowRankCov`` / ``cov_solve`` on y - M beta as oracle/crm.py: predict_interaction strings
+    them together.  ``fit``: called on the pinned LMM and the decomposition, returns (beta, u) -- the CPU test passes
+    imitated kernel slips.  ``beta`` given: u on y - M beta, as ``pinned_effects``."""
+    y = np.asarray(y, float).ravel()
+    U = np.asarray(U, float)
+    delta = float(v1) / (float(v0) + float(v1))
+    (Q0,), S0 = economic_qs_linear(effects_half(U, half_L, float(rho)), return_q1=False)
+    lmm = _LMMAt(y, M, ((Q0,), S0), restricted=True)
+    lmm._at = delta
+    lml = -lmm._neg_lml_at(np.log(delta) - np.log1p(-delta))
+    if fit is not None:
+        beta, u = fit(lmm, Q0, S0)
+    elif beta is not None:
+        u = U.T @ cov_solve(LowRankCov(Q0, S0, float(v0), float(v1)), y - np.asarray(M, float) @ beta)
+    else:
+        beta = lmm.beta
+        u = U.T @ cov_solve(LowRankCov(Q0, S0, float(v0), float(v1)), y - lmm.mean())
+    return beta, u, lml, lmm.scale
+
+
+def oracle_ml_at(y, X, Q0, S0, delta, G=None):
+    """The float64 oracle's ML (lml, scale) at ``delta`` (``LMM._neg_lml_at``, restricted=False) and, with ``G``, its
+    ``FastScanner``'s alternative lmls of the columns of G at that frozen delta."""
+    delta = float(delta)
+    lmm = _LMMAt(y, X, ((Q0,), np.asarray(S0, float)), restricted=False)
+    lmm._at = delta
+    lml = -lmm._neg_lml_at(np.log(delta) - np.log1p(-delta))
+    alt = None if G is None else FastScanner(lmm).fast_scan(np.asarray(G, float))["lml"]
+    return lml, lmm.scale, alt
+
+
+def grid_lmls(y, X, half_of, grid, restricted):
+    """The reference's maximised lml per grid value: the float64 oracle's polished fit gives x = logit(delta), the
+    reference is evaluated there (a lower bound of its maximum, short by half the curvature times the square of the
+    polish's 1e-12); where the best two come within ``REFINE_WITHIN`` of each other both are maximised by ``pinned_max``."""
+    y = np.asarray(y, float).ravel()
+    none = np.zeros((y.size, 0))
+    xs, out = [], []
+    for rho in grid:
+        hS = half_of(float(rho))
+        lmm = LMM(y, X, economic_qs_linear(hS, return_q1=False), restricted=restricted)
+        lmm.fit(verbose=False, polish=True)
+        xs.append(lmm._x)
+        out.append(pinned(y, X, hS, none, lmm.delta)[2] if restricted else pinned_ml(y, X, hS, lmm.delta)[0])
+    order = np.argsort(np.asarray(out, float))[::-1]
+    if len(out) > 1 and abs(out[order[0]] - out[order[1]]) <= REFINE_WITHIN * abs(out[order[0]]):
+        for i in order[:2]:
+            out[i] = pinned_max(y, X, half_of(float(grid[i])), xs[i], restricted=restricted)[0]
+    return out
+
+
+def argmax_or_tie(lmls, limit):
+    """(index of the largest, whether the two largest are within ``limit`` x |largest| of each other)."""
+    order = np.argsort(np.asarray(lmls, float))[::-1]
+    tie = len(lmls) > 1 and abs(lmls[order[0]] - lmls[order[1]]) <= limit * abs(lmls[order[0]])
+    return int(order[0]), bool(tie)
 
 
 def half_factor(rho, E1, hK=None, Ls=None):
@@ -166,6 +371,38 @@ def errors(got, ref):
             "F": float(np.abs(np.asarray(gF, LD) - F).max() / np.abs(F).max()),
             "lml": float(abs(LD(glml) - lml) / abs(lml)),
             "scale": float(abs(LD(gs) - s) / s)}
+
+
+def relative(got, ref):
+    return float(abs(LD(got) - ref) / abs(ref))
+
+
+def vector_error(got, ref):
+    """max|got - ref| relative to the largest magnitude of the reference vector.  A reference that is zero throughout
+    (beta_gxe at rho = 0) is met by zeros only."""
+    ref = np.asarray(ref, LD)
+    gap, top = np.abs(np.asarray(got, LD) - ref).max(), np.abs(ref).max()
+    if top == 0:
+        return 0.0 if gap == 0 else float("inf")
+    return float(gap / top)
+
+
+def effects_errors(got, ref):
+    """``got`` and ``ref``: dicts with some of beta, u, beta_gxe (vectors: ``vector_error``), lml, scale (relative)."""
+    return {k: (relative if k in ("lml", "scale") else vector_error)(got[k], ref[k]) for k in got}
+
+
+def ml_errors(got, ref):
+    """``got`` and ``ref``: dicts with lml and some of scale (relative) and lrs -- the pair (alt lml, null lml), the
+    statistic 2 (alt - null) held absolutely, relative to |null lml| of the reference."""
+    out = {}
+    for k in got:
+        if k == "lrs":
+            (ga, gn), (ra, rn) = got[k], ref[k]
+            out[k] = float(abs(2 * (LD(ga) - LD(gn)) - 2 * (ra - rn)) / abs(rn))
+        else:
+            out[k] = relative(got[k], ref[k])
+    return out
 
 
 def worst(rows):

@@ -620,10 +620,113 @@ __global__ __launch_bounds__(256) void woodbury_kernel(AssembleArgs a, const dou
     }
 }
 
+// The same correction without the backward substitution: M_uE C^-1 M_Ev = Y'Y with Y = L^-1 M_E. (k1 x KT), C = L L'.
+// Y is what a Cholesky factorisation of the augmented matrix [C ; M_.E] (k1 + KT rows, k1 columns) leaves below L, so the
+// factor and the forward substitution are one right-looking sweep: at column j every entry (R, q > j) takes
+// -= A[R][j] A[q][j], for the rows of C below the diagonal (R >= q) and for every row of M_.E alike.  The matrix is held
+// by columns, AT [k1][LD] with LD odd: a wavefront owns whole columns q = j + 1 + wave, + 4, ..., its lanes the rows R, so
+// column j is only read and every other column is touched by one wavefront alone -- one barrier per column.  The
+// wavefront that updates column j + 1 also finishes it (square root of the pivot, division of the rest): it works the
+// pivot out before it stores anything, and the column is ready when the barrier opens.  Y'Y is then a Gram over
+// the k1 rows of Y: 16 x 16 tiles of the upper triangle on the FP64 MFMA (k1 padded with zeros to a multiple of 4),
+// mirrored.  LDS: k1 (k1 + KT + 1) doubles at the most, inside woodbury_lds_bytes.
+__global__ __launch_bounds__(256) void woodbury_yty_kernel(AssembleArgs a, const double* __restrict__ Gw, int KT,
+                                                           double* __restrict__ Gext) {
+    extern __shared__ double wsm[];
+    const int k1 = a.wb_k1, KW = KT + k1, k0 = a.k0, c = a.c;
+    const int NR = k1 + KT, LD = NR | 1;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const NullFitOut fit = a.fit[b];
+    const double g = fit.v0 * a.rho[fit.rho_index].rho;
+    const double inv = 1.0 / fit.v1;
+    const double* __restrict__ G = Gw + (long)b * KW * KW;
+    double* __restrict__ out = Gext + (long)b * KT * KT;
+    if (!(g > 0.0)) {
+        for (int e = tid; e < KT * KT; e += 256) out[e] = G[(long)(e / KT) * KW + e % KT];
+        return;
+    }
+    double* AT = wsm;   // [k1][LD]: column q holds C[R][q] at R in [q, k1) and M_uE[u][q] at R = k1 + u
+    const long pos = a.sorted_pos[b];
+    for (int e = tid; e < KT * k1; e += 256) {
+        const int u = e / k1, f = e - u * k1;
+        double plain;
+        if (u < k0) plain = pos >= 0 ? a.wb_E1X[(long)f * a.wb_ldE1X + pos * k0 + u] : 0.0;
+        else if (u < k0 + c) plain = a.wb_E1yW[(long)f * a.wb_ldE1yW + 1 + (u - k0)];
+        else if (u == k0 + c) plain = a.wb_E1g[(long)f * a.wb_ldE1g + b];
+        else plain = a.wb_E1yW[(long)f * a.wb_ldE1yW];
+        AT[f * LD + k1 + u] = (u < k0 && pos < 0) ? 0.0 : (plain - G[(long)u * KW + KT + f]) * inv;
+    }
+    for (int e = tid; e < k1 * k1; e += 256) {
+        const int i = e / k1, j = e - i * k1;
+        if (j <= i) AT[j * LD + i] = (i == j ? 1.0 : 0.0) + g * (a.wb_EE[e] - G[(long)(KT + i) * KW + KT + j]) * inv;
+    }
+    __syncthreads();
+    if (wave == 0) {   // column 0
+        const double l = sqrt(AT[0]);
+        for (int R = lane; R < NR; R += 64) AT[R] = R == 0 ? l : AT[R] / l;
+    }
+    __syncthreads();
+    for (int j = 0; j + 1 < k1; j++) {
+        const double* colj = AT + j * LD;
+        // the next pivot, worked out by every lane from the same two numbers before any store of this step: the lane
+        // of the diagonal arrives at the same value through its own update
+        const double lnext = wave == 0 ? sqrt(fma(-colj[j + 1], colj[j + 1], AT[(j + 1) * LD + j + 1])) : 0.0;
+        for (int R = ((j + 1) & ~63) + lane; R < NR; R += 64) {   // (rows up to j have nothing left to take)
+            const double aR = R > j ? colj[R] : 0.0;
+            for (int q0 = j + 1 + wave; q0 < k1; q0 += 16) {
+                double lq[4], cv[4];
+#pragma unroll
+                for (int m = 0; m < 4; m++) {
+                    const int q = q0 + 4 * m;
+                    const bool on = q < k1 && R >= q;
+                    lq[m] = on ? colj[q] : 0.0;
+                    cv[m] = on ? AT[q * LD + R] : 0.0;
+                }
+#pragma unroll
+                for (int m = 0; m < 4; m++) {
+                    const int q = q0 + 4 * m;
+                    if (!(q < k1 && R >= q)) continue;
+                    double v = fma(-aR, lq[m], cv[m]);
+                    if (q == j + 1) v = R == q ? lnext : v / lnext;   // (wavefront 0: the next pivot column, finished)
+                    AT[q * LD + R] = v;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    // out = Gw + v1 g Y'Y on the upper triangle of 16 x 16 tiles, dealt to the wavefronts, mirrored
+    const int ts = (KT + 15) / 16, l15 = lane & 15, l4 = lane >> 4;
+    const double scale = fit.v1 * g;
+    const double* __restrict__ Y = AT + k1;
+    int t = 0;
+    for (int ti = 0; ti < ts; ti++)
+        for (int tj = ti; tj < ts; tj++, t++) {
+            if ((t & 3) != wave) continue;
+            const int u = 16 * ti + l15, v = 16 * tj + l15;
+            v4d acc = (v4d){0.0, 0.0, 0.0, 0.0};
+            for (int f0 = 0; f0 < k1; f0 += 4) {
+                const int f = f0 + l4;
+                const double fa = (f < k1 && u < KT) ? Y[f * LD + u] : 0.0;
+                const double fb = (f < k1 && v < KT) ? Y[f * LD + v] : 0.0;
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(fa, fb, acc, 0, 0, 0);
+            }
+#pragma unroll
+            for (int reg = 0; reg < 4; reg++) {
+                const int row = 16 * ti + l4 + 4 * reg;
+                if (row < KT && v < KT && v >= row) {
+                    const double s = scale * acc[reg];
+                    out[(long)row * KT + v] = G[(long)row * KW + v] + s;
+                    if (v != row) out[(long)v * KT + row] = G[(long)v * KW + row] + s;
+                }
+            }
+        }
+}
+
 constexpr int PMAX = CRM_MAX_COV_XWIDE + 1;
 
 __global__ __launch_bounds__(128) void finalize_kernel(AssembleArgs a, const double* __restrict__ Gext,
-                                                        int KT, double* __restrict__ rows) {
+                                                        int KT, double* __restrict__ rows, int sym) {
     // per variant: everything below is k0- or (c+1)-sized; LDS carved from the dynamic segment:
     // L [P][P] (Cholesky factor of X'K^-1X), xky [P], uvec [k0], vv, ww [P] each, then dkx [k0][P] (D'K^-1X) and
     // sol [k0][P] -- or, when those two do not fit (many contexts x many covariates), in `rows` (global memory,
@@ -814,8 +917,14 @@ __global__ __launch_bounds__(128) void finalize_kernel(AssembleArgs a, const dou
         const int lo = j < jp ? j : jp, hi = j < jp ? jp : j;
         // pair index of (lo, hi) in the row-major upper triangle
         const long pidx = (long)lo * k0 - (long)lo * (lo - 1) / 2 + (hi - lo);
-        double v = (a.Z3[(long)b * a.ldZ3 + pidx] - Ge[(long)j * KT + jp]) * inv;
-        for (int i = 0; i < P; i++) v -= dkx(j, i) * sol(jp, i);
+        // sym (the Y'Y form of the unrelated-donor correction, whose Ge is mirrored): the lower triangle of F repeats the
+        // upper one's arithmetic -- entry (j, j') and entry (j', j) both from Ge(lo, hi), dkx(lo, .) and sol(hi, .) in the same
+        // order -- so F comes out exactly symmetric, and its lower triangle rounds differently from what it did.  Otherwise
+        // the projection term is taken against the solved rows of j' as it always was, which rounds differently for the
+        // two entries (1e-16 of max|F|).
+        const int ja = sym ? lo : j, jb = sym ? hi : jp;
+        double v = (a.Z3[(long)b * a.ldZ3 + pidx] - Ge[(long)ja * KT + jb]) * inv;
+        for (int i = 0; i < P; i++) v -= dkx(ja, i) * sol(jb, i);
         F[e] = ok ? 0.5 * v * rescale : NAN;
     }
 }
@@ -916,18 +1025,21 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
 #undef CRM_GRAM_GROUPS
     CRM_HIP(hipGetLastError());
     if (dma && dma_launches) ++*dma_launches;
+    const bool yty = a.wb_k1 > 0 && form("woodbury_ytY", 1) != 0;
     if (a.wb_k1 > 0) {
-        const size_t lds = woodbury_lds_bytes(KT0, a.wb_k1);
-        if (lds > 60 * 1024)
-            CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&woodbury_kernel),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(woodbury_kernel, dim3(variants), dim3(256), lds, st, a, a.wb_Gw, KT0, Gfin);
+        // form("woodbury_ytY", 0): the factor, then both substitutions, one column of C^-1 M_Ev per thread
+        const size_t lds = yty ? sizeof(double) * a.wb_k1 * (size_t)((KT0 + a.wb_k1) | 1) : woodbury_lds_bytes(KT0, a.wb_k1);
+        const void* fn = yty ? reinterpret_cast<const void*>(&woodbury_yty_kernel) : reinterpret_cast<const void*>(&woodbury_kernel);
+        if (lds > 60 * 1024) CRM_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (yty) hipLaunchKernelGGL(woodbury_yty_kernel, dim3(variants), dim3(256), lds, st, a, a.wb_Gw, KT0, Gfin);
+        else hipLaunchKernelGGL(woodbury_kernel, dim3(variants), dim3(256), lds, st, a, a.wb_Gw, KT0, Gfin);
         CRM_HIP(hipGetLastError());
     }
     if (fin_lds > 60 * 1024)
         CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&finalize_kernel),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_lds));
-    hipLaunchKernelGGL(finalize_kernel, dim3(variants), dim3(128), fin_lds, st, a, Gfin, KT0, rows_global ? fin_rows : nullptr);
+    hipLaunchKernelGGL(finalize_kernel, dim3(variants), dim3(128), fin_lds, st, a, Gfin, KT0, rows_global ? fin_rows : nullptr,
+                       yty ? 1 : 0);
     CRM_HIP(hipGetLastError());
     return CRM_OK;
 }

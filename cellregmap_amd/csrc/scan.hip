@@ -123,6 +123,7 @@ struct ScanPlan {
     // skip_pairs: ScanPass::no_kinship_term; cross: the collapsed path under the genotype permutation hook
     bool fastT = false, slow_forms = false, skip_pairs = true, cross = false;
     bool e1_pairs = false, e1_sym = false, donor_pairs = false, wb_rotate = false, pairs_unfolded = false;
+    bool wb_block = false;   // unrelated-donor form: the pair stage in block order (always so with several phenotypes)
     int ng = 1, BLK = 0, pair_cap = 0;
     long ldb = 0, ldp = 0, ldA = 0, ldAw = 0, ldT = 0, ldZ1 = 0, ldZ2 = 0, ldZ3 = 0, ld_ah = 0, ld_xg = 0, ldP = 0, ldPd = 0,
          pd_slab = 0, ldwb = 0, ld_gW = 0, th_slab = 0, s_rows = 0;
@@ -294,6 +295,9 @@ static ScanPlan plan_scan(const std::vector<crm_gene*>& genes, const crm_panel* 
     // in one pass (blockops.hip: donor_pairs_rotate_kernel) instead of the rows of S and a per-donor product over them --
     // bit for bit the same ws_A; form("donor_pairs_rotate", 0) keeps the two launches
     P.wb_rotate = wb && P.donor_pairs && donor_pairs_rotate_serves(k0) && form("donor_pairs_rotate", 1) != 0;
+    // Unrelated-donor form: nothing reads the block in rho*-sorted pair order (no MixK(rho*) product), so the pair stage runs
+    // in block order for one phenotype as it does for several; form("wb_block_order", 0) keeps the sorted copy
+    P.wb_block = wb && (ng > 1 || form("wb_block_order", 1) != 0);
     // The same idea on the UNFOLDED kinship-structure route (few contexts: BASELINE config 2's 20): with E1 = E2 = E the
     // per-donor blocks [us | E1]'(g o E0) are one symmetric matrix S_d = sum_c g_c e_c e_c' twice over -- one batched plain
     // product per donor against E (x) E in donor order (P_d), the contraction over the donors with the kinship factor ON THE
@@ -1244,6 +1248,13 @@ struct ScanPass {
                 const NullFitOut& f = fit[(size_t)gi * BLK + b];
                 h_pos[(size_t)gi * BLK + b] = no_kinship_term(f) ? -1 : pair_of[(size_t)f.rho_index * BLK + b];
             }
+        if (P.wb_block && ng == 1) {
+            // (the position of a test is its variant's place in the block; the sorted copy Gs is not formed: donor_columns)
+            for (int b = 0; b < nb; b++)
+                if (h_pos[b] >= 0) h_pos[b] = b;
+            CRM_HIP(hipMemcpyAsync(d_pos, h_pos.data(), sizeof(int) * (size_t)BLK, hipMemcpyHostToDevice, st));
+            return CRM_OK;
+        }
         CRM_HIP(hipMemcpyAsync(d_pos, h_pos.data(), sizeof(int) * (size_t)BLK * ng, hipMemcpyHostToDevice, st));
         if (P.wb() && ng > 1) {   // (S in block order: a variant's rows of the rotated S sit at its own position)
             std::vector<int> h_posw((size_t)BLK * ng, -1);
@@ -1351,10 +1362,10 @@ struct ScanPass {
 
     // The kinship routes' operand columns in donor order (Gk): one phenotype takes them in the rho*-sorted pair order (Gs)
     // straight away, so that the result is the operand of the Mix products as it stands; several phenotypes share a
-    // variant between pairs: block order, then the pair gather
+    // variant between pairs: block order, then the pair gather.  The unrelated-donor form has no Mix product: block order
     struct DonorCols { bool in_pair_order; const double* G; long ldg; int ncol; };
     int donor_columns(const Block& B, const SubRange& R, const Pairs& Q, DonorCols& D) {
-        D.in_pair_order = ng == 1;
+        D.in_pair_order = ng == 1 && !P.wb_block;
         D.G = D.in_pair_order ? ctx->ws_Gs.as<double>() : B.Gt + R.b0;
         D.ldg = D.in_pair_order ? P.ldp : P.ldb;
         D.ncol = D.in_pair_order ? Q.npairs : R.nb;
@@ -1520,7 +1531,7 @@ struct ScanPass {
     // (U_d Lambda_d^-1/2)' S_d, stored transposed into ws_A; col = the pair (one phenotype) or the block position
     int woodbury_S(const SubRange& R, const Pairs& Q) {
         const long groups = bg->kin_groups;
-        const int ncol = ng == 1 ? Q.npairs : R.nb;
+        const int ncol = P.wb_block ? R.nb : Q.npairs;
         std::vector<GemmProblem> kp((size_t)groups);
         GemmProblem p{};
         p.X = ctx->ws_S.as<double>() + (size_t)bg->kin_k1 * P.ld_ah; p.ldx = P.ld_ah;

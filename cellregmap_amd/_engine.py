@@ -65,7 +65,7 @@ class HadamardHalves(Sequence):
         # so [diag(E[:, i]) hK for i] is the same covariance sum_i L_i L_i' = K o EE' in another basis of the same column
         # space (H -> H blockdiag(I, V (x) I): same Gram spectrum, same Q0 S0 Q0').  In that basis the per-donor sums of the
         # kinship-structure route against the kinship term's contexts are sums against the scan's own contexts -- symmetric
-        # when E2 = E, the reference's default -- which halves their product (csrc/scan.hip: donor pairs).
+        # when E2 = E, the reference's default -- which halves their product (csrc/scan_plan.hip: donor pairs).
         self._device_us = None
         if contexts is not None:
             E = np.ascontiguousarray(contexts, dtype=float)

@@ -338,6 +338,54 @@ int crm_test_set_form(const char* name, int value, int reset) {
     });
 }
 
+long crm_test_tail_launches(const crm_ctx* ctx) { return ctx ? ctx->tail_launches : -1; }
+
+long crm_test_spectrum_tail_launches(const crm_ctx* ctx) { return ctx ? ctx->spectrum_tail_launches : -1; }
+
+long crm_test_dense_repeats(const crm_ctx* ctx) { return ctx ? ctx->dense_repeats : -1; }
+
+long crm_test_donor_pair_blocks(const crm_ctx* ctx) { return ctx ? ctx->donor_pair_blocks : -1; }
+
+int crm_test_gram_dma_launches(const crm_ctx* ctx, long* launches) {
+    return crm::guarded("crm_test_gram_dma_launches", [&]() -> int {
+    if (!ctx || !launches) return CRM_ERR_ARG;
+    *launches = ctx->gram_dma_launches;
+    return CRM_OK;
+    });
+}
+int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks) {
+    return crm::guarded("crm_test_unrelated_donor_blocks", [&]() -> int {
+    if (!ctx || !blocks) return CRM_ERR_ARG;
+    *blocks = ctx->unrelated_donor_blocks;
+    return CRM_OK;
+    });
+}
+
+int crm_test_rho0_position_blocks(const crm_ctx* ctx, long* blocks) {
+    return crm::guarded("crm_test_rho0_position_blocks", [&]() -> int {
+    if (!ctx || !blocks) return CRM_ERR_ARG;
+    *blocks = ctx->rho0_position_blocks;
+    return CRM_OK;
+    });
+}
+int crm_test_rotation_tail_launches(const crm_ctx* ctx, long* launches) {
+    return crm::guarded("crm_test_rotation_tail_launches", [&]() -> int {
+    if (!ctx || !launches) return CRM_ERR_ARG;
+    *launches = ctx->rotation_tail_launches;
+    return CRM_OK;
+    });
+}
+
+long crm_test_tests_without_pair(const crm_ctx* ctx) { return ctx ? ctx->tests_without_pair : -1; }
+
+int crm_test_set_shared_h(crm_ctx* ctx, int mode) {
+    return crm::guarded_on("crm_test_set_shared_h", ctx, [&]() -> int {
+    if (!ctx) return CRM_ERR_ARG;
+    ctx->tune.shared_h = mode < 0 ? -1 : (mode > 0 ? 1 : 0);
+    return CRM_OK;
+    });
+}
+
 int crm_kernel_timer_reset(crm_ctx* c) {
     return crm::guarded_on("crm_kernel_timer_reset", c, [&]() -> int {
     if (!c) return CRM_ERR_ARG;

@@ -543,13 +543,13 @@ __global__ __launch_bounds__(256, NTL <= 8 ? 2 : 1) void gram_ext_dma_wide_kerne
     }
 }
 
-// Unrelated-donor form (scan.hip: kin_wb).  The Gram Gw of the KT + k1 rows [X ; W ; gx ; y ; E1] was taken over the
+// Unrelated-donor form (scan_plan.hip: kin_wb).  The Gram Gw of the KT + k1 rows [X ; W ; gx ; y ; E1] was taken over the
 // donors k2 positions with the weights of N = v1 I + v0 sum_p s_p(rho) phi_p phi_p' alone, so that
 //     M_uv = u'N^-1 v = (u'v - Gw_uv) / v1 ;
 // K0 = N + v0 rho E1 E1' then gives, with the k1 x k1 capacitance C = I + v0 rho M_EE (positive definite, >= I),
 //     u'K0^-1 v = M_uv - v0 rho M_uE C^-1 M_Ev .
 // finalize_kernel reads K0^-1 as (plain - Ge) / v1, so Ge = Gw + v1 v0 rho M_uE C^-1 M_Ev on the leading KT x KT block.
-// A variant without a kinship term to speak of (sorted_pos < 0: its X rows of Gw are zero, scan.hip: no_kinship_term)
+// A variant without a kinship term to speak of (sorted_pos < 0: its X rows of Gw are zero, scan_pass.h: no_kinship_term)
 // drops the X part of the correction the same way.  v0 rho = 0 (rho* = 0, or no kinship variance) leaves Gw as it is.
 // One workgroup per variant; LDS: M_uE [KT][k1], C [k1][k1], C^-1 M_Ev [k1][KT].
 __global__ __launch_bounds__(256) void woodbury_kernel(AssembleArgs a, const double* __restrict__ Gw, int KT,
@@ -857,7 +857,7 @@ __global__ __launch_bounds__(128) void finalize_kernel(AssembleArgs a, const dou
                 xky[i] = s / L(i, i);
             }
             if (fit.scale < 0.0) {
-                // A record of (v0, v1) = (1 - delta, delta) without its scale (scan.hip: the probes of the flat-optimum flag):
+                // A record of (v0, v1) = (1 - delta, delta) without its scale (scan_results.hip: the probes of the flat-optimum flag):
                 // the REML scale at that delta is y'Py / df with P of the unit-scale covariance, from what is at hand --
                 // y'K^-1y and the forward-substituted X'K^-1y (glimix-core: LMM.scale; nullfit.hip evaluates the same).
                 double r = (a.yy - Ge[(long)(k0 + c + 1) * KT + (k0 + c + 1)]) * inv;

@@ -30,7 +30,6 @@ extern "C" int crm_scan_association(crm_gene* gene, crm_panel* panel, long first
     hipStream_t st = ctx->stream;
     const long n = bg->n, np = bg->n_pad, ldq = bg->ldq;
     const int nrho = bg->nrho, c = gene->c;
-    const long slab = (long)(1 + c) * ldq;
     const int BLK = (int)std::min<long>(ctx->block_variants > 0 ? ctx->block_variants : CRM_DEFAULT_BLOCK,
                                         round_up(std::max<long>(count, 1), 128));
     const long ldb = BLK + 128, ldT = ldq;
@@ -77,16 +76,8 @@ extern "C" int crm_scan_association(crm_gene* gene, crm_panel* panel, long first
     CRM_HIP(hipMemsetAsync(d_gy, 0, sizeof(double), st));
     CRM_HIP(hipMemsetAsync(d_gW, 0, sizeof(double) * ld_gW, st));
     NullFitArgs fa{};
-    fa.nrho = nrho; fa.c = c; fa.restricted = 0; fa.polish = (ctx->polish && c <= CRM_MAX_COV) ? 1 : 0; fa.exact = (ctx->nullfit_exact || form("nullfit_exact", 0)) ? 1 : 0; fa.n = n;
-    for (int i = 0; i < nrho; i++) {
-        NullFitRho& R = fa.rho[i];
-        R.T = d_zero; R.ldT = 0;
-        R.ty = gene->rot.as<double>() + (long)i * slab;
-        R.tW = R.ty + ldq; R.ldW = ldq;
-        R.S0 = bg->S0[i].as<double>();
-        R.r = bg->r[i];
-    }
-    fa.WW = gene->WW.as<double>(); fa.Wy = gene->Wy.as<double>(); fa.yy = gene->yy;
+    nullfit_gene_args(fa, gene, 0);
+    for (int i = 0; i < nrho; i++) { fa.rho[i].T = d_zero; fa.rho[i].ldT = 0; }
     fa.gg = d_gg; fa.gy = d_gy; fa.gW = d_gW; fa.ld_gW = ld_gW;
     fa.trial = d_trial; fa.out = d_fit;
     DevBuf xwide;

@@ -172,27 +172,13 @@ __global__ void multi_lrt_kernel(const double* __restrict__ alt_lml, const doubl
 // The null model of crm_scan_association (ML, X = W, over the rho grid) with the same arguments, into *out.
 int association_null_fit(crm_gene* gene, double* d_zero, double* d_gg, double* d_gy, double* d_gW, long ld_gW,
                          NullFitTrial* d_trial, NullFitOut* d_fit, double* xwide) {
-    crm_background* bg = gene->bg;
-    crm_ctx* ctx = bg->ctx;
-    const long ldq = bg->ldq;
-    const int nrho = bg->nrho, c = gene->c;
-    const long slab = (long)(1 + c) * ldq;
     NullFitArgs fa{};
-    fa.nrho = nrho; fa.c = c; fa.restricted = 0; fa.polish = (ctx->polish && c <= CRM_MAX_COV) ? 1 : 0;
-    fa.exact = (ctx->nullfit_exact || form("nullfit_exact", 0)) ? 1 : 0; fa.n = bg->n;
-    for (int i = 0; i < nrho; i++) {
-        NullFitRho& R = fa.rho[i];
-        R.T = d_zero; R.ldT = 0;
-        R.ty = gene->rot.as<double>() + (long)i * slab;
-        R.tW = R.ty + ldq; R.ldW = ldq;
-        R.S0 = bg->S0[i].as<double>();
-        R.r = bg->r[i];
-    }
-    fa.WW = gene->WW.as<double>(); fa.Wy = gene->Wy.as<double>(); fa.yy = gene->yy;
+    nullfit_gene_args(fa, gene, 0);
+    for (int i = 0; i < fa.nrho; i++) { fa.rho[i].T = d_zero; fa.rho[i].ldT = 0; }
     fa.gg = d_gg; fa.gy = d_gy; fa.gW = d_gW; fa.ld_gW = ld_gW;
     fa.trial = d_trial; fa.out = d_fit;
     fa.xwide = xwide;
-    return launch_nullfit(ctx->stream, fa, 1);
+    return launch_nullfit(gene->ctx->stream, fa, 1);
 }
 
 int check_genes(crm_gene* const* genes, int ngenes, const char* what) {

@@ -486,7 +486,7 @@ static int background_complete(crm_background* bg, const int* r_all) {
     dG.release();
     dMt.release();
     if (thin) {
-        // keep the half factor: T(rho) = Q0(rho)'G is later taken as Mix(rho)' (H'G), see scan.hip
+        // keep the half factor: T(rho) = Q0(rho)'G is later taken as Mix(rho)' (H'G), see scan_block.hip: rotations
         bg->H = std::move(dH);
         bg->Ht = std::move(dHt);   // (its transpose: operand of Q0 = H Mix, formed on first use)
         bg->ldh = cp;
@@ -639,7 +639,7 @@ static int background_seal(crm_background* bg) {
     // the mixing-matrix route amplifies rounding by sqrt(S_max / S_min): use it only for spectra
     // whose kept part is well conditioned
     bg->fast_T = bb->thin;
-    // (also kept: the largest entry of every spectrum -- scan.hip decides from it which fits have no kinship term to speak
+    // (also kept: the largest entry of every spectrum -- scan_pass.h: no_kinship_term decides from it which fits have no kinship term to speak
     // of; filled here, once, before the background is shared between genes and threads)
     std::vector<double> s0;
     bg->s0_max.assign(bg->nrho, 0.0);

@@ -481,7 +481,7 @@ int launch_collinear_flag(hipStream_t st, const double* gg, const double* gW, lo
     return CRM_OK;
 }
 
-// ---- E1 rows of the folded kinship-structure form through pair products (scan.hip, ScanPass::folded_S) -------------
+// ---- E1 rows of the folded kinship-structure form through pair products (scan_pairs.hip, ScanPass::folded_S) -------------
 // P[c, a k0 + i] = H[c, a] * Ep[c, i]  (a < k1: the E1 columns of the half factor; Ep: the scan's (permuted) contexts)
 __global__ void pair_features_kernel(const double* __restrict__ H, long ldh, int k1, const double* __restrict__ Ep,
                                      long ld_ep, int k0, double* __restrict__ P, long ldp) {
@@ -541,7 +541,7 @@ int launch_pair_rows_sym(hipStream_t st, const double* C, long ldc, int variants
     return CRM_OK;
 }
 
-// ---- per-donor sums of the folded kinship-structure form from the symmetric pair features (scan.hip, ScanPass::folded_S)
+// ---- per-donor sums of the folded kinship-structure form from the symmetric pair features (scan_pairs.hip, ScanPass::folded_S)
 // P[d][b][pair(j, i)] = sum over the cells of donor d of g_b E_j E_i (j <= i; one batched product against E (x) E in donor
 // order) holds everything of S_d = sum_c g_c e_c e_c' when the contexts of the kinship term are the scan's own (the
 // reference's default E2 = E).  A workgroup takes four variants and a range of donors and walks them:
@@ -630,7 +630,7 @@ int launch_donor_pairs_expand(hipStream_t st, const double* P, long p_slab, long
     return CRM_OK;
 }
 
-// ---- the unrelated-donor form's rotated S straight from the pair products (scan.hip, ScanPass::folded_S) ----------------
+// ---- the unrelated-donor form's rotated S straight from the pair products (scan_pairs.hip, ScanPass::folded_S) ----------------
 //     A[(b k0 + i), d k2 + j] = sum_k S_d[k, i] Psi_d[k, j],   S_d[k, i] = P[d][b][pair(min(k, i), max(k, i))]
 // with Psi_d = U_d Lambda_d^-1/2 (wb_U: k2pad x 128 per donor, zero beyond k2 rows and columns) and k2 = k0: the product of the
 // per-donor rotation launch without the rows of S in between.  Every output is accumulated as that launch does it: one

@@ -81,7 +81,7 @@ struct crm_ctx {
     int block_variants = 0;  // 0 = automatic
     bool fast_T = true;    // T(rho) through the mixing matrices when the background offers them
     int kin_route = 1;          // H'(g o E0) donor by donor when the background knows its kinship structure: 0 never
-                                // (CRM_KIN_ROUTE=0), 1 when its flop count pays (scan.hip), 2 always
+                                // (CRM_KIN_ROUTE=0), 1 when its flop count pays (scan_plan.hip), 2 always
     bool fast_gene_rot = true;  // Q0(rho)'[y, W] of a gene through the mixing matrices as well (else against Q0 itself)
     bool collapse = true;  // use the donor-collapsed path for grouped panels
     // Progress callbacks, one per calling thread (crm_set_progress_callback installs it for the thread that calls it; a

@@ -57,7 +57,6 @@ extern "C" int crm_lmm_fit(crm_gene* gene, int restricted, double* out_fit, doub
     hipStream_t st = ctx->stream;
     const long n = bg->n, ldq = bg->ldq;
     const int nrho = bg->nrho, c = gene->c;
-    const long slab = (long)(1 + c) * ldq;
     const long ld_gW = round_up(std::max(c, 8), 8);
 
     DevBuf small;
@@ -74,18 +73,8 @@ extern "C" int crm_lmm_fit(crm_gene* gene, int restricted, double* out_fit, doub
 
     // a zero "variant" is dropped by the fit kernels (rank-deficient [M, 0]): exactly LMM(y, M)
     NullFitArgs fa{};
-    fa.nrho = nrho; fa.c = c; fa.restricted = restricted ? 1 : 0;
-    fa.polish = (ctx->polish && c <= CRM_MAX_COV) ? 1 : 0; fa.exact = (ctx->nullfit_exact || form("nullfit_exact", 0)) ? 1 : 0;
-    fa.n = n;
-    for (int i = 0; i < nrho; i++) {
-        NullFitRho& R = fa.rho[i];
-        R.T = d_zero; R.ldT = 0;
-        R.ty = gene->rot.as<double>() + (long)i * slab;
-        R.tW = R.ty + ldq; R.ldW = ldq;
-        R.S0 = bg->S0[i].as<double>();
-        R.r = bg->r[i];
-    }
-    fa.WW = gene->WW.as<double>(); fa.Wy = gene->Wy.as<double>(); fa.yy = gene->yy;
+    nullfit_gene_args(fa, gene, restricted ? 1 : 0);
+    for (int i = 0; i < nrho; i++) { fa.rho[i].T = d_zero; fa.rho[i].ldT = 0; }
     fa.gg = d_g3; fa.gy = d_g3 + 1; fa.gW = d_g3 + 2; fa.ld_gW = ld_gW;
     fa.trial = (NullFitTrial*)(sm + o_trial);
     fa.out = (NullFitOut*)(sm + o_fit);

@@ -423,7 +423,7 @@ int launch_gemm_tn(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int max_m
 }
 
 // ---- C = X'Y for a narrow Y (N <= 16 columns) -------------------------------------------------------------------------
-// The last few columns of a product whose width is a little more than a multiple of the 128-column tile (scan.hip: the
+// The last few columns of a product whose width is a little more than a multiple of the 128-column tile (scan_block.hip, scan_pairs.hip: the
 // spectrum's 5 000 = 39 tiles + 8) would cost a whole column of tiles -- 1/40 of the launch -- in the tiled kernels.  Here
 // they are one pass over X: a wavefront takes 32 columns of X (16-byte loads: columns m, m + 1 per lane, four rows per
 // instruction) as the A operands of two v_mfma_f64_16x16x4_f64 per k-step against the same four rows of Y; bound by the

@@ -23,6 +23,23 @@ unsigned long content_key(const void* data, size_t bytes, unsigned long seed) {
     for (; i < bytes; i++) h = (h ^ p[i]) * 0x100000001B3ul;
     return h ? h : 1;
 }
+
+void nullfit_gene_args(NullFitArgs& a, const crm_gene* gene, int restricted) {
+    const crm_background* bg = gene->bg;
+    const crm_ctx* ctx = bg->ctx;
+    const long ldq = bg->ldq, slab = (long)(1 + gene->c) * ldq;
+    a.nrho = bg->nrho; a.c = gene->c; a.restricted = restricted; a.n = bg->n;
+    a.polish = (ctx->polish && gene->c <= CRM_MAX_COV) ? 1 : 0;
+    a.exact = (ctx->nullfit_exact || form("nullfit_exact", 0)) ? 1 : 0;
+    for (int i = 0; i < bg->nrho; i++) {
+        NullFitRho& R = a.rho[i];
+        R.ty = gene->rot.as<double>() + (long)i * slab;
+        R.tW = R.ty + ldq; R.ldW = ldq;
+        R.S0 = bg->S0[i].as<double>();
+        R.r = bg->r[i];
+    }
+    a.WW = gene->WW.as<double>(); a.Wy = gene->Wy.as<double>(); a.yy = gene->yy;
+}
 }  // namespace crm
 
 __global__ void scatter_column_kernel(const double* __restrict__ src, long lds, int col, double* __restrict__ dst, long ldd, long n) {

@@ -245,7 +245,7 @@ int crm_background_set_kinship_groups(crm_background* bg, const int* group, long
         return CRM_ERR_ARG;
     }
     // the column of ones behind hKd's m columns (objects.h: kin_hKd): the contraction over the donors on the pair products
-    // then also gives their sum over the donors (scan_pass: ScanPass::unfolded_AH).  Written after the check, which reads
+    // then also gives their sum over the donors (scan_pairs.hip: ScanPass::unfolded_AH).  Written after the check, which reads
     // the m columns alone.
     if (m + 1 <= bg->kin_ldh) {
         std::vector<double> ones((size_t)groups, 1.0);

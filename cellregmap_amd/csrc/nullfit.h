@@ -59,6 +59,8 @@ struct NullFitArgs {
     NullFitTrial* trial;  // [variants x nrho]
     NullFitOut* out;      // [variants]
 };
+// nrho, c, n, polish, exact, the grid's rotations of [y, W] and spectra, W'W, W'y, y'y of `gene` on its background
+void nullfit_gene_args(NullFitArgs& a, const crm_gene* gene, int restricted);
 
 // c <= CRM_MAX_COV: register kernel (nullfit.hip); larger c (or force_wide): LDS kernel
 // (nullfit_wide.hip).  Both end with the rho* selection into a.out.
@@ -182,7 +184,7 @@ struct AssembleArgs {
     const int* sorted_pos;    // [variants] position of variant b inside the rho*-sorted A~ buffer; < 0: none was formed
     const double* A;          // [variants*k0 x ldA]  rows (pos*k0 + j) = Q0(rho*)' (gtest o E_j)
     long ldA;
-    const double* A_none;     // ldA zeros: the rows of a variant without a position (scan.hip: no kinship term in its fit)
+    const double* A_none;     // ldA zeros: the rows of a variant without a position (scan_pass.h: no_kinship_term)
     int k0, c;
     long n;
     // n-length reductions, block order
@@ -195,7 +197,7 @@ struct AssembleArgs {
                                         // (launch_ortho_block; null where the block was not orthogonalised)
     double* Q;   // [variants]
     double* F;   // [variants x k0 x k0]
-    // Unrelated-donor form (scan.hip: kin_wb, assemble.hip: woodbury_kernel), wb_k1 > 0: the Gram runs over donors k2
+    // Unrelated-donor form (scan_plan.hip: kin_wb, assemble.hip: woodbury_kernel), wb_k1 > 0: the Gram runs over donors k2
     // positions with k1 more rows R = Phi'E1 behind the k0 + c + 2 of the spectral form, and the E1 term is added back by
     // a k1 x k1 capacitance solve before the finalize.  Plain E1 products: E1'X (rows of the folded S), E1'[y, W] (gene),
     // E1'gx (block), E1'E1.

@@ -73,30 +73,30 @@ int crm_test_set_shared_h(crm_ctx* ctx, int mode);
  * flop count is below the direct contraction's; 2: always (environment: CRM_KIN_ROUTE=0 / 1 / 2). */
 int crm_test_set_kinship_route(crm_ctx* ctx, int on);
 /* Number of Khatri-Rao blocks of this context's scans whose last columns went through the 160-column-tile launch
- * (scan.hip: spectra with r mod 128 <= 32); tests use it to know which form they exercised. */
+ * (scan_pairs.hip: spectra with r mod 128 <= 32); tests use it to know which form they exercised. */
 long crm_test_tail_launches(const crm_ctx* ctx);
 /* ... and whose last few columns of the spectrum (r mod 128 <= 16 on the kinship-structure route) went through the skinny
  * one-pass kernel instead of another 128-column tile of the product with the mixing matrix. */
 long crm_test_spectrum_tail_launches(const crm_ctx* ctx);
 /* Variants that scans on the donor-collapsed path repeated on the dense path because they were nearly collinear with the
- * covariates (scan.hip: COLLINEAR_TAU; the dense path orthogonalises the block against W in the cell axis). */
+ * covariates (scan_pass.h: COLLINEAR_TAU; the dense path orthogonalises the block against W in the cell axis). */
 long crm_test_dense_repeats(const crm_ctx* ctx);
 /* Blocks of this context's scans whose per-donor sums H'(g o E0) came from one batched product against the symmetric pair
- * features E (x) E (scan.hip: donor pairs -- the kinship term's contexts are the scan's own; form "donor_pairs": 0 never,
+ * features E (x) E (scan_plan.hip: donor pairs -- the kinship term's contexts are the scan's own; form "donor_pairs": 0 never,
  * 1 where its estimated time is the smaller one, 2 always). */
 long crm_test_donor_pair_blocks(const crm_ctx* ctx);
 /* Blocks of this context's scans served by the unrelated-donor form: a folded kinship structure whose donor-level kinship
  * hKd hKd' is diagonal takes Q and F through a per-donor Woodbury inverse instead of the product A~ = MixK(rho*)'S
- * (scan.hip: kin_wb; form "kin_diag": 0 never, 1 where the background allows it and the cost model says it pays, 2 wherever
+ * (scan_plan.hip: kin_wb; form "kin_diag": 0 never, 1 where the background allows it and the cost model says it pays, 2 wherever
  * the background and the shapes allow it -- k0 + c + 2 + k1 <= 144).  *blocks: the count so far. */
 int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks);
 /* Blocks of this context's scans on the unrelated-donor form whose null fits at rho = 0 read the position basis -- Phi'gx,
- * Phi'[y, W] and s_p(0), the assembly's own operands -- so that the rotation MixK(0)'(H'Gx) was not formed (scan.hip:
+ * Phi'[y, W] and s_p(0), the assembly's own operands -- so that the rotation MixK(0)'(H'Gx) was not formed (scan_block.hip:
  * plan_rotations; taken where the kept positions are as many as the grid point's rank; form "rho0_positions" = 0: never).
  * *blocks: the count so far. */
 int crm_test_rho0_position_blocks(const crm_ctx* ctx, long* blocks);
 /* Blocks whose rotations MixK(rho)'(H'Gx) sent the last few columns of their spectra (r mod 128 <= 16, kinship-structure
- * routes) through the skinny one-pass kernel (scan.hip: plan_rotations; form "rotation_tails": 0 never, 1 where the
+ * routes) through the skinny one-pass kernel (scan_block.hip: plan_rotations; form "rotation_tails": 0 never, 1 where the
  * batched launch then takes fewer rounds, 2 wherever a problem is eligible).  *launches: the count so far. */
 int crm_test_rotation_tail_launches(const crm_ctx* ctx, long* launches);
 /* Score-statistic Grams of this context's scans that went through a direct-to-LDS kernel (assemble.hip: up to 144 rows
@@ -104,7 +104,7 @@ int crm_test_rotation_tail_launches(const crm_ctx* ctx, long* launches);
 int crm_test_gram_dma_launches(const crm_ctx* ctx, long* launches);
 /* (phenotype, variant) tests of this context's scans whose selected fit has no kinship term to speak of --
  * (v0 / v1) max S0(rho*) <= 1e-10: delta at its upper clamp -- and for which no rotated test direction A~ was formed
- * (scan.hip; form "pairs_without_kinship_term" = 0 forms it for every test). */
+ * (scan_pass.h: no_kinship_term; form "pairs_without_kinship_term" = 0 forms it for every test). */
 long crm_test_tests_without_pair(const crm_ctx* ctx);
 /* The same product stored transposed: CT (N x (B*k0)). */
 int crm_test_contract_kr_t(crm_ctx* ctx, long cells, int B, int k0, int N, const double* G,

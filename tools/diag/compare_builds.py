@@ -1,9 +1,16 @@
-"""Are the null fits of this build the ones of another build of the library, bit for bit?  Runs the verbatim scans of a fuzz
-stream under the library given by CRM_OTHER_LIB (default tools/_r05/libcrm_hip_r05.so: round 5's HEAD, built by
-`git worktree add /tmp/r05 d67abc4 && python -m cellregmap_amd.build` there) and under the current one, each in its own
-process, and compares delta, lml, scale, rho*, Q and the p-values entry by entry.
-    python tools/diag/compare_builds.py [count 150] [seed 2026]         (parent)
-    python tools/diag/compare_builds.py --child <lib or ''> <count> <seed> <out.npz>"""
+"""Does this build compute what another build of the library computes, bit for bit?  Runs the verbatim scans of a fuzz
+stream under the other library (a path, or CRM_OTHER_LIB: e.g. the parent commit built in a `git worktree` of it) and
+under the current one, each in its own fresh process, and compares p, rho*, Q, lml, delta and scale entry by entry and
+the context's route counters after the last scan.  --forms switches kernel forms (crm_test_set_form) in both processes,
+so that the routes the cost models leave to large cohorts are compared too (with CRM_KIN_ROUTE=2 in the environment the
+kinship-structure route is taken wherever a background knows its donors); the counters say whether they were reached.
+Behind the stream come a few cohorts whose kinship term carries the scan's own contexts, Ls = get_L_values(hK, E): the
+stream's mode C hands its Ls over as dense matrices, so nothing in it can reach the pair-product forms.
+Exit status 0: every array and every counter identical.
+    python tools/diag/compare_builds.py <other library> [count 150] [seed 2026] [--forms name=value[,name=value...]]
+    python tools/diag/compare_builds.py --child <lib or ''> <count> <seed> <out.npz> <forms or ''>"""
+import argparse
+import ctypes
 import json
 import os
 import subprocess
@@ -15,59 +22,102 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+ARRAYS = ("pv", "rho1", "Q", "lml", "delta", "scale")
+COUNTERS = ("crm_test_unrelated_donor_blocks", "crm_test_donor_pair_blocks", "crm_test_gram_dma_launches",
+            "crm_test_tail_launches", "crm_test_spectrum_tail_launches", "crm_test_rotation_tail_launches",
+            "crm_test_rho0_position_blocks", "crm_test_tests_without_pair", "crm_test_dense_repeats")
+STRUCTURED = ((6, 120, 7, 37), (12, 90, 20, 130), (7, 60, 5, 37))   # donors, cells per donor, contexts, variants
 
-def child(lib_path, count, seed, out):
+
+def parse_forms(text):
+    return [(name, int(value)) for name, value in (item.split("=") for item in text.split(",") if item)]
+
+
+def child(lib_path, count, seed, out, forms):
     from cellregmap_amd import _lib
 
     if lib_path:
-        import ctypes
-
         _lib.LIB_PATH = lib_path
         probe = ctypes.CDLL(lib_path)     # (an older build lacks the entry points added since: bind what it has)
         for name in [k for k in _lib.SIGNATURES if not hasattr(probe, k)]:
             del _lib.SIGNATURES[name]
+    lib = _lib.load()
+    # before any CellRegMap exists: some forms are read when the kinship structure is announced
+    applied = [name for name, value in parse_forms(forms) if lib.crm_test_set_form(name.encode(), value, 0) == 0]
     from fuzz_cases import build_case, fuzz_cases
 
-    from cellregmap_amd import CellRegMap, GenotypePanel
+    from cellregmap_amd import CellRegMap, GenotypePanel, _engine, get_L_values
+    from cellregmap_amd.synth import make_cohort
 
-    keep = {k: [] for k in ("pv", "rho1", "Q", "lml", "delta", "scale")}
+    keep = {k: [] for k in ARRAYS}
+
+    def scan(crm, G, groups, **hooks):
+        pv, info, st = crm.scan_interaction(GenotypePanel(G, groups=groups), return_stats=True, **hooks)
+        keep["pv"].append(pv)
+        keep["rho1"].append(info["rho1"])
+        for k in ("Q", "lml", "delta", "scale"):
+            keep[k].append(st[k])
+
     for case in fuzz_cases(count, seed=seed, wide_covariates=True):
         y, E, W, G, kw, hooks = build_case(case)
         crm = CellRegMap(y, E, W=W, **kw)
         for groups in (None, "auto"):
-            pv, info, st = crm.scan_interaction(GenotypePanel(G, groups=groups), return_stats=True, **hooks)
-            keep["pv"].append(pv)
-            keep["rho1"].append(info["rho1"])
-            for k in ("Q", "lml", "delta", "scale"):
-                keep[k].append(st[k])
-    np.savez(out, **{k: np.concatenate(v) for k, v in keep.items()})
+            scan(crm, G, groups, **hooks)
+    for donors, cells, k0, variants in STRUCTURED:
+        c = make_cohort(donors, cells, k0, variants, seed=300 + k0)
+        G = c.G + 0.05 * np.random.default_rng(k0).normal(size=c.G.shape)     # (general genotypes: the dense path)
+        scan(CellRegMap(c.y, c.E, W=c.W, Ls=get_L_values(c.hK, c.E)), G, None)
+    ctx, counters = _engine._context(0), {}
+    for name in COUNTERS:
+        if name not in _lib.SIGNATURES:
+            counters[name] = None             # (this library does not export it)
+        elif _lib.SIGNATURES[name][0] is ctypes.c_long:
+            counters[name] = int(getattr(lib, name)(ctx))
+        else:
+            value = ctypes.c_long(-1)
+            _lib.check(getattr(lib, name)(ctx, ctypes.byref(value)))
+            counters[name] = value.value
+    np.savez(out, notes=np.array(json.dumps({"counters": counters, "forms": applied})),
+             **{k: np.concatenate(v) for k, v in keep.items()})
 
 
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
-        return child(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), sys.argv[5])
-    count = int(sys.argv[1]) if len(sys.argv) > 1 else 150
-    seed = int(sys.argv[2]) if len(sys.argv) > 2 else 2026
-    other = os.environ.get("CRM_OTHER_LIB", os.path.join(ROOT, "tools", "_r05", "libcrm_hip_r05.so"))
+        return child(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), sys.argv[5], sys.argv[6])
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("other", nargs="?", default=os.environ.get("CRM_OTHER_LIB"), help="the other build's libcrm_hip.so (or CRM_OTHER_LIB)")
+    ap.add_argument("count", nargs="?", type=int, default=150)
+    ap.add_argument("seed", nargs="?", type=int, default=2026)
+    ap.add_argument("--forms", default="", help="kernel forms for both processes: name=value[,name=value...]")
+    args = ap.parse_args()
+    if not args.other or not os.path.exists(args.other):
+        ap.error("the other library: give its path or set CRM_OTHER_LIB (got %r)" % (args.other,))
+    parse_forms(args.forms)     # (a malformed list fails here, not in the children)
+    other, this = os.path.abspath(args.other), os.environ.get("CRM_THIS_LIB", "")     # (this: a diagnostic build instead of the package's own library)
     outs = []
-    this = os.environ.get("CRM_THIS_LIB", "")     # (a diagnostic build instead of the package's own library)
     for tag, lib in (("other", other), ("this", this)):
         out = os.path.join("/tmp", "compare_builds_%s_%d.npz" % (tag, os.getpid()))
-        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", lib, str(count), str(seed), out])
+        subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", lib, str(args.count), str(args.seed), out, args.forms])
         outs.append(np.load(out))
     a, b = outs
-    rep = {"other_library": other, "this_library": this or "cellregmap_amd/libcrm_hip.so", "problems": count, "seed": seed, "variant_scans": int(a["pv"].size)}
-    for k in a.files:
+    na, nb = json.loads(str(a["notes"])), json.loads(str(b["notes"]))
+    rep = {"other_library": args.other, "this_library": this or "cellregmap_amd/libcrm_hip.so", "problems": args.count, "seed": args.seed, "structured_cohorts": len(STRUCTURED),
+           "CRM_KIN_ROUTE": os.environ.get("CRM_KIN_ROUTE"), "forms": args.forms, "forms_applied": {"other": na["forms"], "this": nb["forms"]}, "variant_scans": int(a["pv"].size)}
+    for k in ARRAYS:
         same = (a[k] == b[k]) | (np.isnan(a[k]) & np.isnan(b[k]))
         rep[k] = {"identical": int(same.sum()), "different": int((~same).sum()),
                   "worst_rel_difference": float(np.nanmax(np.abs(a[k] - b[k]) / np.maximum(np.abs(a[k]), 1e-300))) if (~same).any() else 0.0}
+    rep["counters"] = {name[len("crm_test_"):]: {"other": na["counters"][name], "this": nb["counters"][name]} for name in COUNTERS}
+    rep["counters_identical"] = all(v["other"] is not None and v["other"] == v["this"] for v in rep["counters"].values())
     print(json.dumps(rep, indent=1))
     dest = os.path.join(ROOT, "gpurun_out")
     os.makedirs(dest, exist_ok=True)
     tag = os.path.basename(this).replace("libcrm_hip_", "").replace(".so", "") if this else "package"
-    with open(os.path.join(dest, "compare_builds_seed%d_%s.json" % (seed, tag)), "w") as fh:
+    if args.forms:
+        tag += "_" + args.forms.replace("=", "-").replace(",", "_")
+    with open(os.path.join(dest, "compare_builds_seed%d_%s.json" % (args.seed, tag)), "w") as fh:
         json.dump(rep, fh, indent=1)
-    return 0 if all(rep[k]["different"] == 0 for k in ("delta", "lml", "scale", "rho1")) else 1
+    return 0 if rep["counters_identical"] and all(rep[k]["different"] == 0 for k in ARRAYS) else 1
 
 
 if __name__ == "__main__":

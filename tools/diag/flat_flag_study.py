@@ -21,7 +21,7 @@ from fuzz_cases import build_case, fuzz_cases  # noqa: E402
 from cellregmap_amd import CellRegMap, GenotypePanel, _engine, _lib  # noqa: E402
 from oracle.crm import OracleCellRegMap  # noqa: E402
 
-REC = 10   # scan.hip: FLAT_REC
+REC = 10   # scan_pass.h: FLAT_REC
 COLUMNS = ("decision", "Q_move_one_tol", "p_move_one_tol", "margin", "noise_bound_roundings", "rho_decision", "rho_gap", "lml",
            "curvature", "delta",
            "actual_rel_dQ", "actual_rel_dp", "covariates", "actual_rel_dlml", "same_rho", "flag", "rho_tie_flag", "mode",

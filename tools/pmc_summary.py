@@ -63,7 +63,7 @@ def main():
     if kin:
         # operands of one launch at config 3: the per-donor sums S (5050 = k1 + donors k2 rows x 204 800 doubles) read once,
         # MixK(rho*) 5050 x 4992 per selected grid point, A~ 204 800 x 4992 written (the spectrum's 5 000 columns less the
-        # last 8, which go through skinny_tn_kernel: scan.hip, spectrum tail)
+        # last 8, which go through skinny_tn_kernel: scan_pairs.hip, spectrum tail)
         alg = 8.0 * (5050 * 204800 + 5050 * 4992 + 204800 * 4992)
         shape = {"config": "cfg3", "cells": 20000, "contexts": 50, "variants_per_launch": 4096,
                  "flops_per_launch": 2.0 * 5050 * 4992 * 50 * 4096}

@@ -1,4 +1,4 @@
-"""Numpy statement of the unrelated-donor form of the score test (scan.hip: kin_wb; assemble.hip: woodbury_kernel).
+"""Numpy statement of the unrelated-donor form of the score test (scan_plan.hip: kin_wb; assemble.hip: woodbury_kernel).
 
 With a diagonal donor-level kinship hKd hKd' = diag(kappa_d), the covariance of the null model
 

@@ -480,7 +480,9 @@ int crm_test_check_context(crm_ctx* c) {
 int crm_test_null_fit_probe(crm_ctx* c, int on, double x) {
     return crm::guarded_on("crm_test_null_fit_probe", c, [&]() -> int {
     if (!c) return CRM_ERR_ARG;
+    if (on < 0 || on > 2) return CRM_ERR_ARG;
     c->probe_on = on != 0;
+    c->probe_mode = on;
     c->probe_x = x;
     return CRM_OK;
     });

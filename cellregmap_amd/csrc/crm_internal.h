@@ -97,8 +97,11 @@ struct crm_ctx {
     bool in_scan = false;  // a scan is running on this context (its work buffers are in use: no second one from a callback)
     bool polish = false;  // opt-in: refine the null-fit optimum beyond Brent's 1e-6 (nullfit.hip)
     bool probe_on = false;       // crm_test_null_fit_probe: scans stop after the null-fit kernels and keep the trial records
+    int probe_mode = 0;          // 1: the objective at probe_x instead of the search; 2: the searches as in any scan (include/crm_hip_test.h)
     double probe_x = 0.0;
-    std::vector<double> probe_out;   // [variants x nrho x 2]: lml, scale at probe_x (last scanned block)
+    // mode 1: [variants x nrho x 2]: lml, scale at probe_x; mode 2: [variants x nrho x 5]: lml, delta, scale, nfev, use_g of
+    // the searches, then [variants]: the grid index select_rho_kernel chose (first block of the pass)
+    std::vector<double> probe_out;
     bool nullfit_exact = false;  // null-fit likelihood in the reference's own operations (IEEE division, one log per entry)
     crm::GemmTune tune;   // contraction kernel variant (test hooks only change it)
     crm::DevBuf sync_counters;  // per-XCD generation counters of the persistent contraction form ([8]: waits that ran out)

@@ -322,6 +322,10 @@ int ScanPass::plan_rotations(const Block& B, const GemmProblem* all) {
 //    the pass stops after it
 int ScanPass::null_fits(const Block& B) {
     const int nb = B.nb, BLK = P.BLK;
+    if (ctx->probe_mode == 2 && ng != 1) {   // (d_trial is written again per phenotype: the records of one only)
+        set_error("null-fit records (crm_test_null_fit_probe, on = 2): one phenotype per pass, not %d", ng);
+        return CRM_ERR_ARG;
+    }
     trace_push("crm null fits");
     for (int gi = 0; gi < ng; gi++) {
         crm_gene* g = genes[gi];
@@ -341,7 +345,7 @@ int ScanPass::null_fits(const Block& B) {
         fa.gg = d_gg; fa.gy = d_gy + (size_t)gi * BLK; fa.gW = d_gW; fa.ld_gW = P.ld_gW;
         fa.g_drop = P.collapsed() ? nullptr : d_drop;
         if (c > CRM_MAX_COV_WIDE) fa.xwide = ctx->ws_xwide.as<double>();
-        fa.trial = d_trial; fa.out = d_fit + (size_t)gi * BLK; fa.probe = ctx->probe_on ? 1 : 0; fa.probe_x = ctx->probe_x;
+        fa.trial = d_trial; fa.out = d_fit + (size_t)gi * BLK; fa.probe = ctx->probe_mode == 1 ? 1 : 0; fa.probe_x = ctx->probe_x;
         fa.track = outs[gi].flags ? 1 : 0;
         CRM_TRY(launch_nullfit(st, fa, nb, false, d_queue));
     }
@@ -350,7 +354,19 @@ int ScanPass::null_fits(const Block& B) {
     if (ctx->probe_on) {
         std::vector<NullFitTrial> h_trial((size_t)nb * nrho);
         CRM_HIP(hipMemcpyAsync(h_trial.data(), d_trial, sizeof(NullFitTrial) * h_trial.size(), hipMemcpyDeviceToHost, st));
+        std::vector<NullFitOut> h_out(ctx->probe_mode == 2 ? (size_t)nb : 0);
+        if (!h_out.empty()) CRM_HIP(hipMemcpyAsync(h_out.data(), d_fit, sizeof(NullFitOut) * h_out.size(), hipMemcpyDeviceToHost, st));
         CRM_HIP(hipStreamSynchronize(st));
+        if (ctx->probe_mode == 2) {   // (the records of the searches themselves, then the selection's choice per variant)
+            ctx->probe_out.assign(5 * h_trial.size() + h_out.size(), 0.0);
+            for (size_t q = 0; q < h_trial.size(); q++) {
+                double* rec = &ctx->probe_out[5 * q];
+                rec[0] = h_trial[q].lml; rec[1] = h_trial[q].delta; rec[2] = h_trial[q].scale;
+                rec[3] = (double)h_trial[q].nfev; rec[4] = (double)h_trial[q].use_g;
+            }
+            for (size_t b = 0; b < h_out.size(); b++) ctx->probe_out[5 * h_trial.size() + b] = (double)h_out[b].rho_index;
+            return CRM_OK;
+        }
         ctx->probe_out.assign(2 * h_trial.size(), 0.0);
         for (size_t q = 0; q < h_trial.size(); q++) {
             ctx->probe_out[2 * q] = h_trial[q].lml;

@@ -113,7 +113,14 @@ int crm_test_contract_kr_t(crm_ctx* ctx, long cells, int B, int k0, int N, const
  * stops after the null-fit kernels of its first block (outputs untouched) and keeps, per (variant, grid point), the
  * log-likelihood and the scale at x = logit(delta); crm_test_null_fit_probe_read copies them out as
  * [variants][grid points][2] doubles and returns their number (> capacity: CRM_ERR_ARG).  Lets a test compare the
- * likelihood itself with the oracle's at the same point, apart from where the two searches stop. */
+ * likelihood itself with the oracle's at the same point, apart from where the two searches stop.
+ * on = 2: the searches run as in any scan (every kernel, every launch form, any covariate count; x is not read) and the
+ * pass ends at the same place; crm_test_null_fit_probe_read then copies out [variants][grid points][5] doubles -- lml,
+ * delta, scale, the number of objective evaluations and use_g of each search, as the kernels left them in the trial table
+ * that the selection of rho* reads -- followed by [variants] doubles: the grid index that selection wrote per variant
+ * (variants x (5 grid points + 1) numbers in all, which is the count returned).  One phenotype per pass: the trial table is
+ * written again per phenotype, so a pass over several returns CRM_ERR_ARG.  on = 0 switches the hook off; any other value
+ * is CRM_ERR_ARG. */
 int crm_test_null_fit_probe(crm_ctx* ctx, int on, double x);
 int crm_test_null_fit_probe_read(crm_ctx* ctx, double* out, long capacity);
 /* Eigenvalues (ascending) of `count` symmetric k x k matrices (lower triangle read). */

@@ -1,7 +1,8 @@
-"""The cohorts of tests/test_gpu_pinned_effects.py and tests/test_gpu_pinned_association.py (plain helper module, not a
-test): built here so that tests/test_pinned_reference_cpu.py can hold every one of them to the condition the GPU tests
-rely on -- at the float64 oracle's own optimum, 32 x the oracle's error against the longdouble reference stays below the
-1e-11 ceiling, so that the ceiling never sets a limit.  A cohort that fails that check is replaced here.
+"""The cohorts of tests/test_gpu_pinned_effects.py, tests/test_gpu_pinned_association.py and
+tests/test_gpu_pinned_null_model.py (plain helper module, not a test): built here so that
+tests/test_pinned_reference_cpu.py can hold every one of them to the condition the GPU tests rely on -- at the float64 oracle's own optimum, 32 x the oracle's error against the longdouble reference stays below the
+1e-11 ceiling, so that the ceiling never sets a limit.  A cohort that fails that check is replaced here.  The null-model
+cohorts (NULL_MODEL) are held to more: the oracle's own Brent search passes every check the device's is put to.
 
 All cohorts stay at or below 320 cells: one longdouble evaluation of the reference is then well under a second.
 """
@@ -142,3 +143,161 @@ def oracle_null(y, W, half_of, grid):
         if best is None or lmm.lml() > best[1].lml():
             best = (float(rho), lmm, (Q0, S0))
     return best
+
+
+# ---- null fits of the interaction scan, every grid point ------------------------------------------------------------------
+# name -> donors, cells per donor, contexts k0, covariate columns c, mode, seed, variants, and optionally
+#   path: "dense" (default; the donor-constant genotypes get cell-level noise) or "collapsed" (kept donor-constant),
+#   y: "cohort" (default; the simulator's phenotype), "noise" (no random effect at all) or "kinship" (a strong one),
+#   ragged: unequal donor sizes (test_gpu_unrelated_donors._ragged; the unrelated-donor route of mode C asks for them),
+#   per_wave: fits that the form under test packs into a wavefront (the last `variants mod per_wave` ones are held too)
+# Mode B: hS = [sqrt(rho) E, sqrt(1 - rho) hK] with hK cells x donors, so the spectrum has `donors` entries at rho = 0, k0
+# at rho = 1 and r = k0 + donors in between.  Mode C: k0 + donors x k0.  60 to 130 cells, except where 127 / 128 covariate
+# columns need more cells than columns (160 and about 170).
+NULL_MODEL = {
+    # the register kernel, one fit per wavefront: the lane loop over a spectrum of 63, 64, 65 and of 5 entries
+    "c 1, r 63, dense": dict(donors=10, cells=12, k0=53, c=1, mode="B", seed=101, variants=7),
+    "c 1, r 63, collapsed": dict(donors=10, cells=12, k0=53, c=1, mode="B", seed=101, variants=7, path="collapsed"),
+    "c 3, r 64, dense": dict(donors=10, cells=12, k0=54, c=3, mode="B", seed=102, variants=7),
+    "c 3, r 64, collapsed": dict(donors=10, cells=12, k0=54, c=3, mode="B", seed=102, variants=7, path="collapsed"),
+    "c 8, r 65, dense": dict(donors=10, cells=12, k0=55, c=8, mode="B", seed=103, variants=7),
+    "c 8, r 65, collapsed": dict(donors=10, cells=12, k0=55, c=8, mode="B", seed=103, variants=7, path="collapsed"),
+    "c 2, r 5": dict(donors=3, cells=30, k0=2, c=2, mode="B", seed=104, variants=7),
+    # the LDS-shared queue form: one covariate column and 1027 variants (1024 at least; a last wavefront of three fits)
+    "queue, r 16": dict(donors=6, cells=15, k0=10, c=1, mode="B", seed=105, variants=1027, per_wave=4),
+    "queue, r 17": dict(donors=6, cells=15, k0=11, c=1, mode="B", seed=106, variants=1027, per_wave=4),
+    # nullfit_wide.hip at its first and last covariate count, nullfit_xwide.hip at its first and last
+    "c 9": dict(donors=10, cells=12, k0=4, c=9, mode="B", seed=107, variants=5),
+    # (one longdouble evaluation costs 30 ms at 62 columns and 60 ms at 128, eight of them per trial: two variants, both
+    # held, at 62 / 63 columns and one at 127 / 128 keep a case at a few seconds)
+    "c 62": dict(donors=10, cells=13, k0=4, c=62, mode="B", seed=108, variants=2),
+    "c 63": dict(donors=10, cells=13, k0=4, c=63, mode="B", seed=109, variants=2),
+    "c 128": dict(donors=8, cells=20, k0=4, c=128, mode="B", seed=110, variants=1),
+    "c 127, mode C": dict(donors=5, cells=40, k0=3, c=127, mode="C", seed=111, variants=1, ragged=True),
+    "mode A, k0 17": dict(donors=8, cells=10, k0=17, c=2, mode="A", seed=112, variants=7),
+    "mode C": dict(donors=5, cells=24, k0=3, c=1, mode="C", seed=113, variants=12, ragged=True),
+    "no kinship term": dict(donors=9, cells=10, k0=4, c=1, mode="B", seed=114, variants=7, y="noise"),
+    "strong kinship term": dict(donors=9, cells=10, k0=4, c=1, mode="B", seed=115, variants=7, y="kinship"),
+    # as many spectrum entries as cells at the interior grid points (50 + 10 = 60): n - r = 0, the complement terms vanish
+    "saturated": dict(donors=10, cells=6, k0=50, c=1, mode="B", seed=120, variants=7),
+}
+
+
+class NullModelCase:
+    def __init__(self, name):
+        spec = dict(path="dense", y="cohort", ragged=False, per_wave=1)
+        spec.update(NULL_MODEL[name])
+        donors, cells, k0, c, seed, variants = (spec[k] for k in ("donors", "cells", "k0", "c", "seed", "variants"))
+        rng = np.random.default_rng(seed + 500)
+        if spec["ragged"]:
+            from test_gpu_unrelated_donors import _ragged
+
+            co, keep, G = _ragged(donors, cells, k0, variants, seed)
+            y, E, hK = co.y[keep], co.E[keep], co.hK[keep]
+        else:
+            co = make_cohort(donors, cells, k0, variants, seed=seed)
+            y, E, hK = co.y, co.E, co.hK
+            G = co.G if spec["path"] == "collapsed" else co.G + 0.05 * rng.normal(size=co.G.shape)
+        n = y.size
+        if spec["y"] == "noise":
+            y = rng.normal(size=n)
+        elif spec["y"] == "kinship":
+            y = 3.0 * (hK @ rng.normal(size=hK.shape[1])) + 0.5 * rng.normal(size=n)
+        self.name, self.n, self.c, self.mode, self.path, self.donors = name, n, c, spec["mode"], spec["path"], donors
+        self.per_wave = spec["per_wave"]
+        self.y, self.E, self.hK, self.G = y, E, hK, np.ascontiguousarray(G)
+        self.W = np.column_stack([np.ones(n)] + [rng.normal(size=n) for _ in range(c - 1)])
+        self.grid = [1.0] if self.mode == "A" else list(ocrm.RHO_GRID)
+        self.Ls = ocrm.khatri_rao_halves(hK, E) if self.mode == "C" else None
+        self._half, self._qs, self._gram, self._trial, self._logdet, self._at, self._fit = {}, {}, {}, {}, {}, {}, {}
+
+    def picks(self):
+        """The variants held: ``pinned_reference.pick``'s three, and for a form that packs ``per_wave`` fits into a
+        wavefront the last ``variants mod per_wave`` ones."""
+        p = self.G.shape[1]
+        return sorted(set(pr.pick(p)) | set(range(p - p % self.per_wave, p)))
+
+    def half(self, i):
+        if i not in self._half:
+            rho = float(self.grid[i])
+            kw = {"A": {}, "B": {"hK": self.hK}, "C": {"Ls": self.Ls}}[self.mode]
+            self._half[i] = pr.half_factor(rho, self.E, **kw)
+        return self._half[i]
+
+    def qs(self, i):
+        if i not in self._qs:
+            (Q0,), S0 = economic_qs_linear(self.half(i), return_q1=False)
+            self._qs[i] = (Q0, S0)
+        return self._qs[i]
+
+    def gram(self, i):
+        if i not in self._gram:
+            hS = np.asarray(self.half(i), pr.LD)
+            self._gram[i] = hS @ hS.T
+        return self._gram[i]
+
+    def X(self, j):
+        return np.column_stack([self.W, self.G[:, j]])
+
+    def logdet_XX(self, j):
+        if j not in self._logdet:
+            self._logdet[j] = pr.log_gram(self.X(j))
+        return self._logdet[j]
+
+    def oracle_fit(self, j, i):
+        """Of variant j at grid point i, computed once: the float64 oracle's fit as the reference procedure leaves it (Brent
+        alone: lml, delta, scale), and the x of the polished one."""
+        if (j, i) not in self._fit:
+            Q0, S0 = self.qs(i)
+            lmm = LMM(self.y, self.X(j), ((Q0,), S0), restricted=True)
+            lmm.fit(verbose=False)
+            brent = (lmm.lml(), lmm.delta, lmm.scale)
+            self._fit[(j, i)] = (brent, lmm._polish(lmm._x, -brent[0]))   # (what fit(polish=True) does after the same search)
+        return self._fit[(j, i)]
+
+    def trial(self, j, i):
+        """(the oracle's Brent record, ``pinned_reference.null_trial_reference`` started from its polished fit), once."""
+        if (j, i) not in self._trial:
+            brent, x0 = self.oracle_fit(j, i)
+            self._trial[(j, i)] = (brent, pr.null_trial_reference(self.y, self.X(j), None, x0, gram=self.gram(i)))
+        return self._trial[(j, i)]
+
+    def reference_lml(self, j, i, x):
+        """The reference's restricted lml of variant j at grid point i and x = logit(delta)."""
+        none = np.zeros((self.n, 0))
+        return pr.pinned(self.y, self.X(j), None, none, pr._logistic(x), gram=self.gram(i), logdet_XX=self.logdet_XX(j))[2]
+
+    def at(self, j, i, delta):
+        """((lml, scale) of the reference, of the float64 oracle) of variant j at grid point i and ``delta``."""
+        key = (j, i, float(delta))
+        if key not in self._at:
+            none = np.zeros((self.n, 0))
+            ref = pr.pinned(self.y, self.X(j), None, none, delta, gram=self.gram(i), logdet_XX=self.logdet_XX(j))
+            self._at[key] = ((ref[2], ref[3]), pr.oracle_null_at(self.y, self.X(j), *self.qs(i), delta))
+        return self._at[key]
+
+
+_null_model_cases = {}
+
+
+def null_model_case(name):
+    """One object per cohort and process: the references of its trials are computed once and shared."""
+    if name not in _null_model_cases:
+        _null_model_cases[name] = NullModelCase(name)
+    return _null_model_cases[name]
+
+
+def hold_trials(cs, records, variants):
+    """Checks b, c and d of tests/test_gpu_pinned_null_model.py on ``records[j][i] = (lml, delta, scale, ...)`` for the
+    variants given: (the limits, the float64 oracle's errors at the same points, {(j, i): shares of every bound}).  The
+    limits are ``pinned_reference.limits`` of the oracle's own error at the same points, the largest over the trials held."""
+    rows, ora = {}, []
+    for j in variants:
+        for i in range(len(cs.grid)):
+            ref_at, own = cs.at(j, i, records[j][i][1])
+            ora.append({"lml": pr.relative(own[0], ref_at[0]), "scale": pr.relative(own[1], ref_at[1])})
+            rows[(j, i)] = ref_at
+    ora = pr.worst(ora)
+    lim = pr.limits(ora, cs.n)
+    shares = {key: pr.trial_shares(records[key[0]][key[1]], ref_at, cs.trial(*key)[1], lim) for key, ref_at in rows.items()}
+    return lim, ora, shares

@@ -31,6 +31,12 @@ parabolas, which also gives the curvature that turns the search's tolerance on x
 ``pinned_max`` with ``restricted=False``; ``grid_lmls`` uses the restricted one for the effect sizes' grid).  Their
 float64 yardsticks are ``oracle_effects_at`` and ``oracle_ml_at``; ``effects_errors`` / ``ml_errors`` are the records
 ``limits`` reads.
+
+The null fits of the interaction scan at every grid point (tests/test_gpu_pinned_null_model.py) are held the same way from
+both sides: ``null_trial_reference`` is ``pinned_max`` of the restricted likelihood per (variant, grid point) -- or the
+value at the clamp of the logistic where the maximum sits there --, ``stop_allowance`` how far in x a faithful search may
+stop from it, ``trial_shares`` the checks on one trial record as shares of their bounds, ``selection_from_records`` /
+``selection_against_reference`` the two checks on the choice of rho*; ``oracle_null_at`` is the yardstick.
 """
 import numpy as np
 
@@ -103,10 +109,11 @@ def _orthonormal(Z):
     return Q, logdet
 
 
-def pinned(y, X, half_S, half_dK, delta, gram=None):
+def pinned(y, X, half_S, half_dK, delta, gram=None, logdet_XX=None):
     """(Q, F, lml, scale) in longdouble at the background half factor ``half_S`` (= hS at rho*) and ``delta``;
     X = [W, g], half_dK = g[idx_G] o E0[idx_E].  ``gram``: hS hS' in longdouble where the caller can form it in fewer
-    operations than the product of an n x 1000 factor (``kronecker_gram``); ``half_S`` is then not read."""
+    operations than the product of an n x 1000 factor (``kronecker_gram``); ``half_S`` is then not read.  ``logdet_XX``:
+    log|X'X| as ``log_gram(X)`` returns it, for a caller that evaluates many points on one X."""
     y = np.asarray(y, LD).ravel()
     X, D = np.asarray(X, LD), np.asarray(half_dK, LD)
     n, c = X.shape
@@ -130,9 +137,15 @@ def pinned(y, X, half_S, half_dK, delta, gram=None):
     Q = (u @ u) / (2 * s * s)
     F = (rD.T @ rD) / (2 * s)
     logdet_Sigma = 2 * np.sum(np.log(np.diag(L)))
-    logdet_XX = _orthonormal(X)[1]
+    if logdet_XX is None:
+        logdet_XX = _orthonormal(X)[1]
     lml = -(df * LOG2PI + df + df * np.log(s) + logdet_Sigma + logdet_XSX - logdet_XX) / 2
     return Q, F, lml, s
+
+
+def log_gram(X):
+    """log|X'X| in longdouble, as ``pinned`` forms it."""
+    return _orthonormal(np.asarray(X, LD))[1]
 
 
 def _sigma(half_S, delta, gram, n):
@@ -180,10 +193,11 @@ def pinned_max(y, X, half_S, x0, restricted=False, gram=None):
         hS = np.asarray(half_S, LD)
         gram = hS @ hS.T
     none = np.zeros((y.size, 0))
+    logdet_XX = log_gram(X) if restricted else None
 
     def f(x):
         if restricted:
-            return pinned(y, X, None, none, _logistic(x), gram=gram)[2]
+            return pinned(y, X, None, none, _logistic(x), gram=gram, logdet_XX=logdet_XX)[2]
         return pinned_ml(y, X, None, _logistic(x), gram=gram)[0]
 
     def vertex(x, h):
@@ -214,6 +228,78 @@ def refit_allowance(x, curvature):
     """What a search with rtol = atol = 1e-6 on x may leave of the likelihood: half the curvature times the square of three
     tolerances (brent_search.h and oracle/brent.py stop when the bracket is within 2 tol of the best point)."""
     return float(curvature) / 2 * (3 * (1e-6 * abs(float(x)) + 1e-6)) ** 2
+
+
+CLAMP = 2.220446049250313e-16     # delta is held to [CLAMP, 1 - CLAMP]: oracle/lmm.py (epsilon.tiny) and nullfit.hip (EPS_TINY) alike
+
+
+def _logit(delta):
+    d = LD(delta)
+    return np.log(d) - np.log1p(-d)
+
+
+def null_trial_reference(y, X, half_S, x0, gram=None):
+    """(L*, x*, curvature, clamp) of one null fit -- one variant at one grid value -- from the reference alone:
+    ``pinned_max(restricted=True)`` started from ``x0``, the x of the float64 oracle's polished fit there (as ``grid_lmls``
+    does).  Where that fit sits at a clamp of the logistic (delta = CLAMP or 1 - CLAMP: the likelihood is monotone up to
+    it, so no stencil around x0 has a vertex) the reference's value at the clamp is returned with x* = logit of the
+    clamp's delta, curvature None and the clamp's delta as the mark (None: an interior maximum).  Anything else that has no maximum near x0 raises (``pinned_max``)."""
+    x0 = float(x0)
+    delta0 = 1 / (1 + np.exp(-x0)) if x0 > 0 else np.exp(x0) / (np.exp(x0) + 1)
+    for clamp in (CLAMP, 1 - CLAMP):
+        if (delta0 <= clamp) if clamp < 0.5 else (delta0 >= clamp):
+            none = np.zeros((np.asarray(y).size, 0))
+            return pinned(y, X, half_S, none, clamp, gram=gram)[2], _logit(clamp), None, clamp
+    return pinned_max(y, X, half_S, x0, restricted=True, gram=gram) + (None,)
+
+
+def stop_allowance(x, curvature, top, lim):
+    """How far in x = logit(delta) a faithful search may stop from the maximum x*: three tolerances 1e-6 |x*| + 1e-6 (the
+    same three as ``refit_allowance``: brent_search.h and oracle/brent.py stop when the bracket is within 2 tol of the best
+    point, and the best point is at most one more from the bracket's middle), plus the radius inside which the search
+    cannot tell points apart at all.  Around x* the likelihood is L* - curvature / 2 (x - x*)^2; the objective the search
+    compares carries rounding noise of up to ``lim`` |L*| (the lml limit of ``limits``), so two points whose true values
+    differ by less than that may be ordered either way: every x with curvature / 2 (x - x*)^2 <= lim |L*|, that is
+    |x - x*| <= sqrt(2 lim |L*| / curvature), can be taken for the best one."""
+    x, curvature = float(x), float(curvature)
+    return 3 * (1e-6 * abs(x) + 1e-6) + float(np.sqrt(2 * lim * abs(float(top)) / curvature))
+
+
+def trial_shares(rec, ref_at, trial, lim):
+    """The checks b, c and d of tests/test_gpu_pinned_null_model.py on one trial record, as shares of their bounds (a share
+    above 1 is a failure; the caller asserts).  ``rec``: (lml, delta, scale) of the search under test; ``ref_at``: the
+    reference's (lml, scale) at that delta; ``trial``: ``null_trial_reference``; ``lim``: {"lml", "scale"} of ``limits``."""
+    lml, delta, scale = (LD(v) for v in rec[:3])
+    top, x, curvature, clamped = trial
+    noise = lim["lml"] * abs(top)
+    out = {"lml": float(abs(lml - ref_at[0]) / abs(ref_at[0])) / lim["lml"],
+           "scale": float(abs(scale - ref_at[1]) / ref_at[1]) / lim["scale"]}
+    if clamped is not None:
+        # d: the reference at the search's delta is not below the reference at the clamp by more than the noise; and the
+        # delta is the clamp's own double (one memoised point on both sides)
+        out["clamp value"] = float((top - ref_at[0]) / noise)
+        out["clamp delta"] = 0.0 if float(delta) == clamped else float("inf")
+    else:
+        out["short of L*"] = float((top - lml) / (refit_allowance(x, curvature) + noise))
+        out["above L*"] = float((lml - top) / noise)
+        out["stop"] = float(abs(_logit(delta) - x)) / stop_allowance(x, curvature, top, lim["lml"])
+    return out
+
+
+def selection_from_records(lmls, rho_index):
+    """e: is ``rho_index`` the first index of the maximum of the trial lmls (the reference's ``>`` in its loop over the grid)?"""
+    lmls = np.asarray(lmls, float)
+    return bool(np.all(np.isfinite(lmls))) and int(rho_index) == int(np.argmax(lmls))
+
+
+def selection_against_reference(tops, rho_index, limit):
+    """f: (accepted, tie) -- without a tie the index is the reference's; with one it is among the grid points within
+    ``limit`` x |largest| of the largest."""
+    best, tie = argmax_or_tie(tops, limit)
+    if not tie:
+        return int(rho_index) == best, False
+    tied = [i for i, v in enumerate(tops) if abs(tops[best] - v) <= limit * abs(tops[best])]
+    return int(rho_index) in tied, True
 
 
 def pinned_effects(y, M, U, half_L, rho, v0, v1, beta=None):
@@ -267,6 +353,14 @@ def oracle_at(y, X, Q0, S0, half_dK, delta, projection=Projection):
     P = projection(LowRankCov(Q0, np.asarray(S0, float), lmm.v0, lmm.v1), np.asarray(X, float))
     y = np.asarray(y, float).ravel()
     return score_Q(P, half_dK, y), score_F(P, half_dK), lml, lmm.scale
+
+
+def oracle_null_at(y, X, Q0, S0, delta):
+    """The float64 oracle's restricted (lml, scale) at ``delta``: the null-fit half of ``oracle_at``."""
+    lmm = _LMMAt(y, X, ((Q0,), np.asarray(S0, float)), restricted=True)
+    lmm._at = float(delta)
+    lml = -lmm._neg_lml_at(np.log(lmm._at) - np.log1p(-lmm._at))
+    return lml, lmm.scale
 
 
 def pinned_solve(half_S, v0, v1, rhs):

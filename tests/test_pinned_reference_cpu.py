@@ -540,3 +540,179 @@ def test_an_effects_reference_that_cannot_be_evaluated_raises():
         pr.pinned_effects(y, np.column_stack([M, M[:, 1] - 2 * M[:, 3]]), U, half_L, rho, v0, v1)
     with pytest.raises(np.linalg.LinAlgError):
         pr.pinned_effects(y, M, U, half_L, rho, v0, 0.0)             # K singular: 3 + 24 columns for 120 cells
+
+
+# =========================================================================================================================
+# the null fits of the interaction scan at every grid point (tests/test_gpu_pinned_null_model.py)
+# =========================================================================================================================
+def _mp_restricted(y, X, hS, delta):
+    """The restricted lml at 40 digits; ``delta`` an mpf."""
+    import mpmath as mp
+
+    my, mX, mS = _mp_matrix(np.asarray(y, float).reshape(-1, 1)), _mp_matrix(X), _mp_matrix(hS)
+    n, c = mX.rows, mX.cols
+    Sigma = (1 - delta) * (mS * mS.T) + delta * mp.eye(n)
+    Si = mp.inverse(Sigma)
+    SiX = Si * mX
+    A = mX.T * SiX
+    P = Si - SiX * mp.inverse(A) * SiX.T
+    df = n - c
+    s = (my.T * P * my)[0] / df
+    return -(df * mp.log(2 * mp.pi) + df + df * mp.log(s) + mp.log(mp.det(Sigma)) + mp.log(mp.det(A))
+             - mp.log(mp.det(mX.T * mX))) / 2
+
+
+def test_the_restricted_maximum_agrees_with_mpmath_at_forty_digits():
+    import mpmath as mp
+
+    mp.mp.dps = 40
+    y, W, E, G, kw = _problem("B", 3, 12, 2, 4, 2, seed=5)
+    hS = pr.half_factor(0.3, E, **kw)
+    X = np.column_stack([W, G[:, 1]])
+    o = ocrm.LMM(y, X, ocrm.economic_qs_linear(hS, return_q1=False), restricted=True)
+    o.fit(verbose=False, polish=True)
+    top, x, curvature, clamp = pr.null_trial_reference(y, X, hS, o._x)
+    assert clamp is None
+    mx = _mp_exact(x)
+    at = lambda t: _mp_restricted(y, X, hS, 1 / (1 + mp.exp(-t)))  # noqa: E731
+    mtop = at(mx)
+    h = mp.mpf("1e-5")
+    lo, hi = at(mx - h), at(mx + h)
+    assert lo < mtop and hi < mtop
+    gaps = {"maximum": _mp_gap(top, mtop),
+            "curvature": float(abs(-(hi - 2 * mtop + lo) / (h * h) - _mp_exact(curvature)) / _mp_exact(curvature)),
+            "x*": float(abs(-h * (hi - lo) / (2 * (hi - 2 * mtop + lo))))}
+    print("pinned_max(restricted=True) against mpmath: %s" % ", ".join("%s %.2e" % kv for kv in gaps.items()))
+    assert gaps["maximum"] <= 1e-18 and gaps["curvature"] <= 1e-6 and gaps["x*"] <= 1e-9, gaps
+
+
+def test_a_trial_at_the_clamp_is_marked_not_raised():
+    """No random effect at all: the oracle's polished fit sits at delta = 1 - 2^-52, where no stencil has a vertex."""
+    cs = pc.null_model_case("no kinship term")
+    top, x, curvature, clamp = cs.trial(0, 3)[1]
+    assert clamp == 1 - pr.CLAMP and curvature is None and abs(float(x) - 36.04365338911715) < 1e-9
+    assert float(top) == float(pr.pinned(cs.y, cs.X(0), cs.half(3), np.zeros((cs.n, 0)), clamp)[2])
+    with pytest.raises(ValueError):                    # (started anywhere else on that likelihood it has no maximum nearby)
+        pr.pinned_max(cs.y, cs.X(0), cs.half(3), 5.0, restricted=True)
+
+
+LADDER = (-12, -8, -4, -2, -1, 0, 1, 2, 4, 8, 12)
+
+
+def _oracle_records(cs, variants):
+    """[variant][grid] -> (lml, delta, scale) of the float64 oracle's own Brent search: what stands in for the device."""
+    return {j: [cs.oracle_fit(j, i)[0] for i in range(len(cs.grid))] for j in variants}
+
+
+def null_model_oracle_shares(name):
+    """(case, held variants, the oracle's Brent records, limits, {(variant, grid): shares}, the largest share per bound) of
+    a cohort with the float64 oracle's own unpolished search in the device's place."""
+    cs = pc.null_model_case(name)
+    sel = cs.picks()
+    rec = _oracle_records(cs, sel)
+    lim, ora, shares = pc.hold_trials(cs, rec, sel)              # (a reference that cannot be evaluated raises here)
+    worst = {}
+    for sh in shares.values():
+        for k, v in sh.items():
+            worst[k] = max(worst.get(k, -np.inf), v)
+    return cs, sel, rec, lim, shares, worst
+
+
+@pytest.mark.parametrize("name", list(pc.NULL_MODEL))
+def test_the_null_model_cohorts_meet_their_conditions(name):
+    """What tests/test_gpu_pinned_null_model.py relies on, for every cohort it names and every trial it holds, from the
+    reference and the float64 oracle alone: ``pinned`` raises nowhere; the oracle's own unpolished Brent stop passes b, c
+    and d within the same limits; the maximum found from the oracle's basin is the global one on a ladder of x; and the
+    oracle's own choice of rho* passes e and f.  (With the oracle in the device's place its lml and scale shares are 1/32
+    at most by construction -- the limit is 32 x its own error; the stopping point and the two sides of L* are what this
+    run decides.)"""
+    cs, sel, rec, lim, shares, worst = null_model_oracle_shares(name)
+    assert max(lim.values()) <= pr.CEILING, (name, lim)
+    for key, sh in shares.items():
+        for k, v in sh.items():
+            assert v <= 1, (name, key, k, v)
+    for j in sel:
+        tops = []
+        for i in range(len(cs.grid)):
+            top = cs.trial(j, i)[1][0]
+            tops.append(top)
+            for x in LADDER:
+                assert cs.reference_lml(j, i, x) <= top + lim["lml"] * abs(top), (name, j, i, x)
+        index = int(np.argmax([r[0] for r in rec[j]]))
+        assert pr.selection_from_records([r[0] for r in rec[j]], index)
+        assert pr.selection_against_reference(tops, index, lim["lml"])[0], (name, j, index)
+    print("%s (%d cells, variants %s): limits %s; the oracle's own search, largest shares: %s"
+          % (name, cs.n, sel, " ".join("%s %.2e" % kv for kv in lim.items()), ", ".join("%s %.3g" % kv for kv in worst.items())))
+
+
+def test_the_clamped_and_the_tied_cohorts_are_what_they_are_named():
+    cs = pc.null_model_case("no kinship term")
+    lim = pc.hold_trials(cs, _oracle_records(cs, cs.picks()), cs.picks())[0]
+    for j in cs.picks():
+        trials = [cs.trial(j, i)[1] for i in range(len(cs.grid))]
+        assert all(t[3] == 1 - pr.CLAMP for t in trials)
+        assert pr.argmax_or_tie([t[0] for t in trials], lim["lml"])[1]
+    cs = pc.null_model_case("strong kinship term")
+    for j in cs.picks():
+        assert all(cs.trial(j, i)[1][3] is None and cs.oracle_fit(j, i)[0][1] < 0.2 for i in range(len(cs.grid) - 1))
+
+
+def slip_report_null_model():
+    """[(slip, factor over the bound that rejects it)] on the cohort "c 3, r 64, dense": the float64 oracle's own records --
+    which pass -- with one imitated mistake each, through the checks of tests/test_gpu_pinned_null_model.py."""
+    cs = pc.null_model_case("c 3, r 64, dense")
+    p, nrho = cs.G.shape[1], len(cs.grid)
+    sel = cs.picks()
+    good = _oracle_records(cs, range(p))
+    j, i = sel[1], 5                                              # an interior trial of an interior grid point
+    (top, x, curvature, clamp), won = cs.trial(j, i)[1], int(np.argmax([r[0] for r in good[j]]))
+    assert clamp is None and i != won
+
+    def at_x(xx, delta=None):
+        delta = float(pr._logistic(xx)) if delta is None else delta
+        lml, scale = pr.oracle_null_at(cs.y, cs.X(j), *cs.qs(i), delta)
+        return lml, delta, scale
+
+    def worst_share(rec_ji, keys=None):
+        rec = {v: list(good[v]) for v in sel}
+        rec[j][i] = rec_ji
+        _, _, shares = pc.hold_trials(cs, rec, sel)
+        return max(v for k, v in shares[(j, i)].items() if keys is None or k in keys)
+
+    tol = 1e-6 * abs(float(x)) + 1e-6
+    lml, delta, scale = good[j][i]
+    out = [("a stop ten tolerances from x*", worst_share(at_x(float(x) + 10 * tol), ("stop",))),
+           ("a clamp reported for an interior optimum", worst_share(at_x(None, 1 - pr.CLAMP), ("short of L*", "stop"))),
+           ("the wrong side of the bracket (x* - 4)", worst_share(at_x(float(x) - 4.0), ("short of L*",))),
+           ("a non-winning grid point's lml off by 1e-9 relative", worst_share((lml * (1 + 1e-9), delta, scale), ("lml",))),
+           ("the ML scale (/ n) where the restricted one belongs",
+            worst_share((lml, delta, scale * (cs.n - cs.c - 1) / cs.n), ("scale",)))]
+    # the table read as [grid][variant]
+    flat = [good[v][g] for v in range(p) for g in range(nrho)]
+    swapped = {v: [flat[g * p + v] for g in range(nrho)] for v in range(p)}
+    _, _, shares = pc.hold_trials(cs, swapped, sel)
+    out.append(("the trial table read as [grid][variant]", max(max(sh.values()) for sh in shares.values())))
+    # selection
+    lim = pc.hold_trials(cs, good, sel)[0]
+    tops = [cs.trial(j, g)[1][0] for g in range(nrho)]
+    lmls = [r[0] for r in good[j]]
+    assert pr.selection_from_records(lmls, won) and pr.selection_against_reference(tops, won, lim["lml"]) == (True, False)
+    tied = list(lmls)
+    tied[nrho - 1] = tied[won]
+    assert pr.selection_from_records(tied, won)
+    inf = float("inf")
+    off = won + 1 if won + 1 < nrho else won - 1
+    out.append(("the last instead of the first of equal maxima", 1.0 if pr.selection_from_records(tied, nrho - 1) else inf))
+    out.append(("a rho index off by one without a tie (from the records)", 1.0 if pr.selection_from_records(lmls, off) else inf))
+    out.append(("a rho index off by one without a tie (against the reference)",
+                1.0 if pr.selection_against_reference(tops, off, lim["lml"])[0] else inf))
+    return out
+
+
+def test_every_injected_slip_of_the_null_model_is_rejected():
+    report = slip_report_null_model()
+    for slip, factor in report:
+        print("%-62s %9.3g x the bound" % (slip + ":", factor))
+    assert len(report) == 9
+    for slip, factor in report:
+        assert factor > 1, (slip, factor)

@@ -5,7 +5,10 @@
     python tools/pinned_record.py <dir>/pinned_effects.json <dir>/pinned_association.json \
         > profiles/pinned_effects_association_errors.json
 
-The two GPU test files write their per-case errors beside the file $CRM_PINNED_JSON names; this merges them under
+    CRM_PINNED_JSON=<dir>/pinned.json pytest tests/test_gpu_pinned_null_model.py -m gpu
+    python tools/pinned_record.py --null-model <dir>/pinned_null_model.json > profiles/pinned_null_model_errors.json
+
+The GPU test files write their per-case errors beside the file $CRM_PINNED_JSON names; this merges them under
 ``device_cases``, adds a ``summary`` (per quantity the worst device error, its limit and its share of it; the refitting
 scan's largest shortfall and overshoot) and computes the ``cpu`` section, which needs no GPU: the float64 oracle against
 the reference at its own optimum on every cohort of tests/pinned_cases.py, the oracle's Brent result against the refit
@@ -70,11 +73,52 @@ def summary(cases):
     return worst
 
 
+def null_model_cpu_section():
+    """No GPU: every cohort of pinned_cases.NULL_MODEL with the float64 oracle's own Brent search in the device's place,
+    and the injected slips."""
+    own = {}
+    for name in pc.NULL_MODEL:
+        cs, sel, _, lim, shares, worst = cpu.null_model_oracle_shares(name)
+        own[name] = {"cells": cs.n, "variants": [int(j) for j in sel], "trials": len(shares), "limit": _floats(lim),
+                     "largest_shares": _floats(worst)}
+    slips = [{"slip": s, "times_the_bound": None if f == float("inf") else float("%.4g" % f),
+              "rejected_outright": f == float("inf")} for s, f in cpu.slip_report_null_model()]
+    return {"the_oracles_own_search_through_the_same_checks": own, "injected_slips": slips}
+
+
+def null_model_summary(cases):
+    """Per bound the case with the largest share of it; the numbers of trials, of trials at a clamp and of ties."""
+    worst = {}
+    for case, rec in cases.items():
+        for k, v in rec["shares"].items():
+            if k not in worst or v["share"] > worst[k]["share"]:
+                worst[k] = dict(v, case=case)
+    return {"largest_share_per_bound": worst, "cases": len(cases), "trials": sum(r["trials"] for r in cases.values()),
+            "trials_at_a_clamp": sum(r["at_a_clamp"] for r in cases.values()),
+            "held_variants_with_a_tie": sum(r["ties"] for r in cases.values()),
+            "nfev": [min(r["nfev"][0] for r in cases.values()), max(r["nfev"][1] for r in cases.values())]}
+
+
 def main(paths):
+    null_model = paths[:1] == ["--null-model"]
     cases = {}
-    for p in paths:
+    for p in paths[1:] if null_model else paths:
         with open(p) as fh:
             cases.update(json.load(fh))
+    if null_model:
+        out = {"cpu": null_model_cpu_section(), "device_cases": cases, "summary": null_model_summary(cases),
+               "what": "tests/test_gpu_pinned_null_model.py on an MI355X, merged by tools/pinned_record.py --null-model: per case "
+                       "the trial records of a real scan (crm_test_null_fit_probe, on = 2) of the held variants at every grid "
+                       "point against the longdouble reference -- shares: the largest share of each bound and where (lml, "
+                       "scale: |device - reference at the trial's delta| over the limit, 32 x oracle, floor cells x 2.2e-16, "
+                       "ceiling 1e-11; short of L* / above L*: the trial's lml against the reference's own maximum, over "
+                       "refit_allowance + limit |L*| and over limit |L*|; stop: |logit(delta) - x*| over stop_allowance; clamp "
+                       "value / clamp delta: trials whose maximum sits at delta = 1 - 2^-52).  A share above 1 fails the test.  "
+                       "cpu: the float64 oracle's own Brent search through the same checks on every cohort, and the injected "
+                       "slips of tests/test_pinned_reference_cpu.py (no GPU)."}
+        json.dump(out, sys.stdout, indent=1, sort_keys=True)
+        sys.stdout.write("\n")
+        return
     out = {"cpu": cpu_section(), "device_cases": cases, "summary": summary(cases),
            "what": "tests/test_gpu_pinned_effects.py and tests/test_gpu_pinned_association.py on an MI355X, merged by "
                    "tools/pinned_record.py: per case the largest error of the device and of the float64 oracle against the "

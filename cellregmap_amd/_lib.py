@@ -115,6 +115,7 @@ SIGNATURES = {
                                         c_int_p, vp]),
     "crm_test_eigvalsh": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp]),
     "crm_test_davies": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
+    "crm_test_davies_trace": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "crm_test_tail_pvalue": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
 }
 

@@ -620,12 +620,13 @@ int crm_test_eigvalsh(crm_ctx* c, int count, int k, const double* F, double* lam
     });
 }
 
-int crm_test_davies(crm_ctx* c, int count, int k, const double* Q, const double* lambda, double* pvalue,
-                    int* ifault, double* liu) {
-    return crm::guarded_on("crm_test_davies", c, [&]() -> int {
+// (the body of both Davies hooks; trace may be null)
+static int davies_hook(crm_ctx* c, int count, int k, const double* Q, const double* lambda, double* pvalue, int* ifault,
+                       double* liu, int* trace) {
     if (!c || count <= 0 || k <= 0 || !Q || !lambda || !pvalue) return CRM_ERR_ARG;
     CRM_HIP(hipSetDevice(c->device));
-    DevBuf bQ, bL, bP, bI, bU;
+    DevBuf bQ, bL, bP, bI, bU, bT;
+    if (trace) CRM_TRY(bT.ensure(sizeof(int) * 3 * (size_t)count));
     CRM_TRY(bQ.ensure(sizeof(double) * count));
     CRM_TRY(bL.ensure(sizeof(double) * (size_t)count * k));
     CRM_TRY(bP.ensure(sizeof(double) * count));
@@ -634,12 +635,27 @@ int crm_test_davies(crm_ctx* c, int count, int k, const double* Q, const double*
     CRM_HIP(hipMemcpyAsync(bQ.ptr, Q, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
     CRM_HIP(hipMemcpyAsync(bL.ptr, lambda, sizeof(double) * (size_t)count * k, hipMemcpyHostToDevice, c->stream));
     CRM_TRY(launch_eig_davies(c->stream, nullptr, bQ.as<double>(), count, k, bL.as<double>(), bP.as<double>(),
-                              bI.as<int>(), bU.as<double>(), false));
+                              bI.as<int>(), bU.as<double>(), false, nullptr, trace ? bT.as<int>() : nullptr));
     CRM_HIP(hipMemcpyAsync(pvalue, bP.ptr, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
     if (ifault) CRM_HIP(hipMemcpyAsync(ifault, bI.ptr, sizeof(int) * count, hipMemcpyDeviceToHost, c->stream));
     if (liu) CRM_HIP(hipMemcpyAsync(liu, bU.ptr, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    if (trace) CRM_HIP(hipMemcpyAsync(trace, bT.ptr, sizeof(int) * 3 * (size_t)count, hipMemcpyDeviceToHost, c->stream));
     CRM_HIP(hipStreamSynchronize(c->stream));
     return CRM_OK;
+}
+
+int crm_test_davies(crm_ctx* c, int count, int k, const double* Q, const double* lambda, double* pvalue,
+                    int* ifault, double* liu) {
+    return crm::guarded_on("crm_test_davies", c, [&]() -> int {
+    return davies_hook(c, count, k, Q, lambda, pvalue, ifault, liu, nullptr);
+    });
+}
+
+int crm_test_davies_trace(crm_ctx* c, int count, int k, const double* Q, const double* lambda, double* pvalue,
+                          int* ifault, double* liu, int* trace) {
+    return crm::guarded_on("crm_test_davies_trace", c, [&]() -> int {
+    if (!trace) return CRM_ERR_ARG;
+    return davies_hook(c, count, k, Q, lambda, pvalue, ifault, liu, trace);
     });
 }
 

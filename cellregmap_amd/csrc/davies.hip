@@ -107,6 +107,7 @@ struct Qf {
     double sigsq, lmax, lmin, mean, c;
     double intl, ersm;
     int count, lim;
+    int terms, nint;   // abscissas summed and integrations done: read by the test hook's trace only
     bool fail, overflow;
 };
 
@@ -269,6 +270,8 @@ __device__ void integrate(Qf& q, int nterm, double interv, double tausq, bool ma
     }
     q.intl += wsum(a1);
     q.ersm += wsum(a2);
+    q.terms += nterm + 1;   // (dead, and removed, where no trace is asked for)
+    q.nint += 1;
 }
 
 // AS 155 cfe.  Weights are positive and ascending, so the |lb|-descending order th[]
@@ -301,11 +304,23 @@ __device__ double conv_coef(Qf& q, double x) {
     return pow(2.0, sum1 / 4.0) / (PI * axl * axl);
 }
 
-// P[ sum lb_j chi2_1 < c ];  returns the cdf (or -1 when the search gave up)
-__device__ double qfc_wave(const double* lb, int r, double c, int lane, int& ifault) {
+// P[ sum lb_j chi2_1 < c ];  returns the cdf (or -1 when the search gave up).  TRACE (crm_test_davies_trace only): path[3]
+// receives the evaluation counter, the abscissas summed and the integrations done.  The kernel sits at the register limit
+// (three more live counters are 16 bytes of scratch per lane), so the scans' instantiation does not carry them.
+template <bool TRACE>
+__device__ double qfc_wave(const double* lb, int r, double c, int lane, int& ifault, int* path) {
     Qf q;
+    auto done = [&](double v) {
+        if constexpr (TRACE) {
+            path[0] = q.count;
+            path[1] = q.terms;
+            path[2] = q.nint;
+        }
+        return v;
+    };
     q.lb = lb; q.r = r; q.lane = lane; q.c = c;
     q.sigsq = 0.0; q.intl = 0.0; q.ersm = 0.0; q.count = 0; q.lim = DAVIES_LIM;
+    q.terms = 0; q.nint = 0;
     q.fail = false; q.overflow = false;
     ifault = 0;
     double acc1 = DAVIES_ACC, xlim = (double)DAVIES_LIM;
@@ -318,16 +333,16 @@ __device__ double qfc_wave(const double* lb, int r, double c, int lane, int& ifa
     q.mean = wsum(mean);
     q.lmax = lb[r - 1] > 0.0 ? lb[r - 1] : 0.0;  // ascending order
     q.lmin = lb[0] < 0.0 ? lb[0] : 0.0;
-    if (sd == 0.0) return (c > 0.0) ? 1.0 : 0.0;
+    if (sd == 0.0) return done((c > 0.0) ? 1.0 : 0.0);
     if (q.lmin == 0.0 && q.lmax == 0.0) {
         ifault = 3;
-        return -1.0;
+        return done(-1.0);
     }
     sd = sqrt(sd);
     const double almx = (q.lmax < -q.lmin) ? -q.lmin : q.lmax;
     double utx = 16.0 / sd, up = 4.5 / sd, un = -up, tausq, intv = 0.0, xnt = 0.0, xntm;
     find_trunc_point(q, utx, 0.5 * acc1);
-    if (q.overflow) { ifault = 4; return -1.0; }
+    if (q.overflow) { ifault = 4; return done(-1.0); }
     if (c != 0.0 && almx > 0.07 * sd) {
         tausq = 0.25 * acc1 / conv_coef(q, c);
         if (q.fail) {
@@ -336,37 +351,37 @@ __device__ double qfc_wave(const double* lb, int r, double c, int lane, int& ifa
             q.sigsq += tausq;
             find_trunc_point(q, utx, 0.25 * acc1);
         }
-        if (q.overflow) { ifault = 4; return -1.0; }
+        if (q.overflow) { ifault = 4; return done(-1.0); }
     }
     acc1 *= 0.5;
     for (;;) {
         const double d1 = cutoff(q, acc1, up) - c;
-        if (q.overflow) { ifault = 4; return -1.0; }
-        if (d1 < 0.0) return 1.0;
+        if (q.overflow) { ifault = 4; return done(-1.0); }
+        if (d1 < 0.0) return done(1.0);
         const double d2 = c - cutoff(q, acc1, un);
-        if (q.overflow) { ifault = 4; return -1.0; }
-        if (d2 < 0.0) return 0.0;
+        if (q.overflow) { ifault = 4; return done(-1.0); }
+        if (d2 < 0.0) return done(0.0);
         intv = 2.0 * PI / ((d1 > d2) ? d1 : d2);
         xnt = utx / intv;
         xntm = 3.0 / sqrt(acc1);
         if (xnt <= xntm * 1.5) break;
-        if (xntm > xlim) { ifault = 1; return -1.0; }
+        if (xntm > xlim) { ifault = 1; return done(-1.0); }
         const int ntm = (int)floor(xntm + 0.5);
         const double intv1 = utx / ntm;
         const double x = 2.0 * PI / intv1;
         if (x <= fabs(c)) break;
         tausq = 0.33 * acc1 / (1.1 * (conv_coef(q, c - x) + conv_coef(q, c + x)));
-        if (q.overflow) { ifault = 4; return -1.0; }
+        if (q.overflow) { ifault = 4; return done(-1.0); }
         if (q.fail) break;
         acc1 *= 0.67;
         integrate(q, ntm, intv1, tausq, false);
         xlim -= xntm;
         q.sigsq += tausq;
         find_trunc_point(q, utx, 0.25 * acc1);
-        if (q.overflow) { ifault = 4; return -1.0; }
+        if (q.overflow) { ifault = 4; return done(-1.0); }
         acc1 *= 0.75;
     }
-    if (xnt > xlim) { ifault = 1; return -1.0; }
+    if (xnt > xlim) { ifault = 1; return done(-1.0); }
     const int nt = (int)floor(xnt + 0.5);
     integrate(q, nt, intv, 0.0, true);
     const double qfval = 0.5 - q.intl;
@@ -375,7 +390,7 @@ __device__ double qfc_wave(const double* lb, int r, double c, int lane, int& ifa
 #pragma unroll
     for (int j = 0; j < 4; j++)
         if (rats[j] * x == rats[j] * upv) ifault = 2;
-    return qfval;
+    return done(qfval);
 }
 
 // modified Liu (Lee, Wu & Lin 2012) survival at t for weights lb (dof 1, nc 0)
@@ -674,14 +689,15 @@ __device__ void tridiagonalise_wide(double* A, int k, int ks, int lane, double* 
 // LDS, NARROW (k <= 64, and every launch without the eigenvalue step): A [k][ks] (ks = k | 1), over which -- the matrix is
 // dead once reduced -- ev [k], kept [k], the tridiagonal's dd [k], ee [k] are laid.  Otherwise (k > 64): A [k][ks] (in
 // global memory past 128 contexts), ev [k], kept [k] (doubles as dd), k + 2 doubles for ee, 2k for the Householder vectors.
-template <bool NARROW>
+template <bool NARROW, bool TRACE>
 __global__ __launch_bounds__(64) void eig_davies_kernel(const double* __restrict__ Fall,
                                                          const double* __restrict__ Qall, int k,
                                                          double* __restrict__ lambda_out,
                                                          double* __restrict__ pv_out,
                                                          int* __restrict__ ifault_out,
                                                          double* __restrict__ liu_out, int do_eig,
-                                                         double* __restrict__ scratch) {
+                                                         double* __restrict__ scratch,
+                                                         int* __restrict__ trace_out) {
     extern __shared__ double sm[];
     const int lane = threadIdx.x;
     const int b = blockIdx.x;
@@ -780,6 +796,7 @@ __global__ __launch_bounds__(64) void eig_davies_kernel(const double* __restrict
             pv_out[b] = NAN;
             if (ifault_out) ifault_out[b] = -1;
             if (liu_out) liu_out[b] = NAN;
+            if constexpr (TRACE) trace_out[3 * b] = trace_out[3 * b + 1] = trace_out[3 * b + 2] = 0;
         }
         return;
     }
@@ -803,12 +820,14 @@ __global__ __launch_bounds__(64) void eig_davies_kernel(const double* __restrict
             pv_out[b] = NAN;
             if (ifault_out) ifault_out[b] = -2;
             if (liu_out) liu_out[b] = NAN;
+            if constexpr (TRACE) trace_out[3 * b] = trace_out[3 * b + 1] = trace_out[3 * b + 2] = 0;
         }
         return;
     }
     const double p_liu = liu_mod_sf(kept, r, Q, lane);
     int ifault = 0;
-    const double cdf = qfc_wave(kept, r, Q, lane, ifault);
+    int path[3] = {0, 0, 0};
+    const double cdf = qfc_wave<TRACE>(kept, r, Q, lane, ifault, path);
     double p = 1.0 - cdf;
     if (r == 1) p = p_liu;
     if (p > 1.0 || p <= 0.0) p = p_liu;
@@ -816,6 +835,11 @@ __global__ __launch_bounds__(64) void eig_davies_kernel(const double* __restrict
         pv_out[b] = p;
         if (ifault_out) ifault_out[b] = ifault;
         if (liu_out) liu_out[b] = p_liu;
+        if constexpr (TRACE) {   // (the test hook's launch only)
+            trace_out[3 * b] = path[0];
+            trace_out[3 * b + 1] = path[1];
+            trace_out[3 * b + 2] = path[2];
+        }
 #ifdef CRM_DAVIES_STAMPS
         st3 = wall_clock64();
         if (k >= 4) {
@@ -834,7 +858,7 @@ __global__ __launch_bounds__(64) void eig_davies_kernel(const double* __restrict
 size_t eig_scratch_doubles(int count, int k) { return k > 128 ? (size_t)count * k * (k | 1) : 0; }
 
 int launch_eig_davies(hipStream_t st, const double* F, const double* Q, int count, int k,
-                      double* lambda, double* pvalue, int* ifault, double* liu, bool do_eig, double* scratch) {
+                      double* lambda, double* pvalue, int* ifault, double* liu, bool do_eig, double* scratch, int* trace) {
     if (count <= 0) return CRM_OK;
     if (k < 1 || k > CRM_MAX_K0) {
         set_error("eigen/Davies: k0=%d (supported 1..%d)", k, CRM_MAX_K0);
@@ -851,15 +875,17 @@ int launch_eig_davies(hipStream_t st, const double* F, const double* Q, int coun
     if (narrow) {
         lds = sizeof(double) * (do_eig ? (size_t)std::max(k * ks, 4 * k) : (size_t)2 * k);
         lds = (lds + 15) / 16 * 16;
-        hipLaunchKernelGGL(eig_davies_kernel<true>, dim3(count), dim3(64), lds, st, F, Q, k, lambda, pvalue,
-                           ifault, liu, do_eig ? 1 : 0, nullptr);
+        auto kern = trace ? eig_davies_kernel<true, true> : eig_davies_kernel<true, false>;
+        hipLaunchKernelGGL(kern, dim3(count), dim3(64), lds, st, F, Q, k, lambda, pvalue,
+                           ifault, liu, do_eig ? 1 : 0, nullptr, trace);
     } else {
         // A [k x ks], ev [k], kept [k] (doubles as the tridiagonal's diagonal), k + 2 doubles (its sub-diagonal), then 2k
         // doubles for the Householder vectors
         lds = sizeof(double) * ((global_copy ? 0 : (size_t)k * ks) + 2 * k + 2 * (k / 2 + 1) + 2 * k);
         lds = (lds + 15) / 16 * 16;
-        hipLaunchKernelGGL(eig_davies_kernel<false>, dim3(count), dim3(64), lds, st, F, Q, k, lambda, pvalue,
-                           ifault, liu, 1, global_copy ? scratch : nullptr);
+        auto kern = trace ? eig_davies_kernel<false, true> : eig_davies_kernel<false, false>;
+        hipLaunchKernelGGL(kern, dim3(count), dim3(64), lds, st, F, Q, k, lambda, pvalue,
+                           ifault, liu, 1, global_copy ? scratch : nullptr, trace);
     }
     CRM_HIP(hipGetLastError());
     return CRM_OK;

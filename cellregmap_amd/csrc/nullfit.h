@@ -222,8 +222,10 @@ size_t woodbury_lds_bytes(int KT, int k1);
 // ---- eigenvalues + Davies / Liu (davies.hip) -----------------------------------------------------
 // lambda: ascending eigenvalues of the lower triangle of F (count x k x k); pvalue per SKAT rule.
 // scratch: eig_scratch_doubles(count, k) doubles (0: F fits LDS, k <= 128)
+// trace (test hook only; null in every scan): count x 3 ints -- evaluation counter, abscissas summed, integrations of AS 155
 int launch_eig_davies(hipStream_t st, const double* F, const double* Q, int count, int k,
-                      double* lambda, double* pvalue, int* ifault, double* liu, bool do_eig, double* scratch = nullptr);
+                      double* lambda, double* pvalue, int* ifault, double* liu, bool do_eig, double* scratch = nullptr,
+                      int* trace = nullptr);
 size_t eig_scratch_doubles(int count, int k);
 
 // ---- exact tail p-values (tail_pvalue.hip) ------------------------------------------------------

@@ -128,6 +128,12 @@ int crm_test_eigvalsh(crm_ctx* ctx, int count, int k, const double* F, double* l
 /* Davies/Liu p-values for `count` (Q, lambda[k]) pairs after the eigenvalue filter. */
 int crm_test_davies(crm_ctx* ctx, int count, int k, const double* Q, const double* lambda,
                     double* pvalue, int* ifault, double* liu);
+/* The same launch, which also reports the path AS 155 took per pair: trace [count][3] = (evaluation counter, abscissas summed
+ * over all integrations, number of integrations), written by lane 0 of each wavefront.  Every other launch of the kernel passes
+ * a null trace and runs the instantiation that keeps no such counters; pvalue, ifault and liu have the bits crm_test_davies
+ * gives. */
+int crm_test_davies_trace(crm_ctx* ctx, int count, int k, const double* Q, const double* lambda,
+                          double* pvalue, int* ifault, double* liu, int* trace);
 /* Exact tail p-values (crm_scan_interaction_tail's method) for `count` (Q, lambda[k]) pairs, lambda as the scan's
  * eigenvalues (the filter is applied here): p, log p (natural) and CRM_TAIL_* status per pair. */
 int crm_test_tail_pvalue(crm_ctx* ctx, int count, int k, const double* Q, const double* lambda, double* pvalue,

@@ -38,7 +38,10 @@ PARITY STATUS
   Davies p-value, so for these pieces: **parity unpinned** -- they are written
   from the published algorithms and checked against independent mathematics
   (dense REML likelihood, numerical Imhof integral, scipy distributions) and,
-  for ``qfc.c``, against the published table of AS 155 (Davies 1980, Table 1);
+  for ``qfc.c``, against the published table of AS 155 (Davies 1980, Table 1),
+  and at 2 to 256 weights against its own long-double build, the exact tail
+  probability and Imhof's integral at 30 digits
+  (tests/test_oracle_davies_widths_cpu.py);
   ``oracle.lmm`` also reproduces the worked examples of glimix-core's own
   documentation (lml to 13 digits; values quoted from memory, no network).
   Only the Liu branch is pinned by the reference (test_math.py:76-83).  The

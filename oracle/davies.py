@@ -13,8 +13,13 @@ procedure is what is restated here:
 
 A non-zero ``ifault`` only clears ``Is_Converged`` (as in SKAT); the p-value
 is replaced by the modified-Liu value only when it is outside (0, 1] or when a
-single eigenvalue survives the filter.  **Parity unpinned** for the Davies
-branch; the Liu branch is pinned by cellregmap/test/test_math.py:76-83.
+single eigenvalue survives the filter.  The Liu branch is pinned by
+cellregmap/test/test_math.py:76-83.  The reference holds no Davies p-value; that
+branch is pinned by ``qfc_ld`` -- ``qfc.c`` built a second time with every
+variable in long double -- which takes the same path as ``qfc`` at 2 to 256
+weights and lies within acc = 1e-6 of the exact tail value and of Imhof's
+integral at 30 digits wherever ``ifault`` is 0
+(tests/test_oracle_davies_widths_cpu.py).
 """
 import ctypes
 import os
@@ -43,6 +48,8 @@ def _lib():
             ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_double,
             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ]
+        lib.crm_oracle_qfc_ld.restype = ctypes.c_int
+        lib.crm_oracle_qfc_ld.argtypes = lib.crm_oracle_qfc.argtypes + [ctypes.c_void_p]
         _LIB = lib
     return _LIB
 
@@ -63,6 +70,25 @@ def qfc(lam, q, dof=None, nc=None, sigma=0.0, lim=DAVIES_LIM, acc=DAVIES_ACC):
         int(lim), float(acc), trace.ctypes.data, ctypes.byref(ifault), ctypes.byref(res),
     )
     return res.value, ifault.value, trace
+
+
+def qfc_ld(lam, q, lim=DAVIES_LIM, acc=DAVIES_ACC):
+    """P[sum lam_j chi2_1 > q] by the same algorithm with every variable in long double (doubles in and out).
+
+    Returns (sf, ifault, trace[7]); sf = 1 - cdf is formed in long double (2 where the search gave up)."""
+    lam = np.ascontiguousarray(lam, dtype=np.float64)
+    r = lam.shape[0]
+    dof = np.ones(r, np.int32)
+    nc = np.zeros(r)
+    trace = np.zeros(7)
+    ifault = ctypes.c_int(0)
+    res = ctypes.c_double(0.0)
+    sf = ctypes.c_double(0.0)
+    _lib().crm_oracle_qfc_ld(
+        lam.ctypes.data, nc.ctypes.data, dof.ctypes.data, r, 0.0, float(q),
+        int(lim), float(acc), trace.ctypes.data, ctypes.byref(ifault), ctypes.byref(res), ctypes.byref(sf),
+    )
+    return sf.value, ifault.value, trace
 
 
 def liu_sf(t, lambs, dofs, deltas, kurtosis=False):

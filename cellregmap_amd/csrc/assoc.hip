@@ -5,15 +5,13 @@
 //   lrt_pvalues            cellregmap/_cellregmap.py:443-469  (chi2_1 survival with the clips)
 // The null fit and the per-SNP refits reuse the null-fit kernels (ML mode); this file holds the
 // FastScanner closed form and the LRT.
-#include "nullfit.h"
+#include "delta_search.h"
 #include "objects.h"
 
 namespace crm {
 
 namespace {
 
-constexpr double LOG2PI = 1.8378770664093453;
-constexpr double EPS_SMALL = 1.4901161193847656e-08;
 constexpr double DBL_TINY = 2.2250738585072014e-308;   // numpy_sugar.epsilon.super_tiny
 constexpr double DBL_EPS = 2.220446049250313e-16;      // numpy_sugar.epsilon.tiny
 constexpr int CMAX = CRM_MAX_COV_XWIDE;   // layout constant of the prep record (effects.hip reads it too)

@@ -20,15 +20,13 @@
 // the shared T(rho*) with that gene's y quantities.
 #include <algorithm>
 
-#include "nullfit.h"
+#include "delta_search.h"
 #include "objects.h"
 
 namespace crm {
 
 namespace {
 
-constexpr double LOG2PI = 1.8378770664093453;
-constexpr double EPS_SMALL = 1.4901161193847656e-08;
 constexpr double DBL_TINY = 2.2250738585072014e-308;
 constexpr double DBL_EPS = 2.220446049250313e-16;
 constexpr int CMAX = CRM_MAX_COV_XWIDE;   // layout constant of the fastscan_prep record

@@ -1,7 +1,8 @@
-// The scalar search of the reference's null fits, shared by the three null-fit kernels (nullfit.hip, nullfit_wide.hip,
-// nullfit_xwide.hip): glimix-core's LMM.fit -> brent-search minimize(rtol = atol = 1e-6) over x = logit(delta)
-// (cellregmap/_cellregmap.py:351-352), statement for statement as oracle/brent.py restates it -- a downhill bracketing
-// phase with growth factor 2 from (0, 1), then Brent's localmin.
+// The scalar search of the reference's fits over delta.  nullfit_wide.hip, nullfit_xwide.hip and effects_multi.hip feed it
+// delta_search.h's ClampedObjective, built around their own evaluation of the likelihood; the register kernels of
+// nullfit.hip feed it their own memoised objective.  It is glimix-core's LMM.fit -> brent-search minimize(rtol = atol =
+// 1e-6) over x = logit(delta) (cellregmap/_cellregmap.py:351-352), statement for statement as oracle/brent.py restates
+// it -- a downhill bracketing phase with growth factor 2 from (0, 1), then Brent's localmin.
 //
 // Besides the minimiser the search leaves behind how close it came to taking ANOTHER path (BrentTrace): the search is a
 // sequence of decisions on objective VALUES -- f(x2) > f(x1) in the bracketing phase; f(u) <= f(x0), f(u) <= f(x1),

@@ -12,25 +12,23 @@
 // No per-SNP eigen-solve and no per-SNP rotation against an 11-point grid: the n-length work is Q_L'[W, E0] per call,
 // Q_L'y per phenotype, Q_L'g and Q_L'(g o E0) per variant (the scan's contraction kernels, gemm_tn.hip), and the complement
 // numerators of Z = [W, g, E0, y, U] per pair.  Then one 256-thread workgroup per (pair, grid point) runs the reference's
-// search (bracket + Brent, rtol = atol = 1e-6, brent_search.h) on the REML objective of oracle/lmm.py evaluated through
-// the form above, with nullfit_xwide.hip's layout: sqrt(w)-scaled spectrum rows staged in LDS, TS x TS register tiles per
-// thread, the complement numerators in global memory and the packed systems in LDS.  A last kernel takes the strict `>`
-// over the grid and forms beta and the BLUP coefficients u = U'K^-1 (y - M beta) at the chosen point.
+// search (brent_search.h on delta_search.h's memoised objective, the noise bound never asked for) on the REML objective of
+// oracle/lmm.py evaluated through the form above: Grams by tile_gram.h's gram_tiles, 32 positions per staging step, the
+// complement numerators in global memory and the packed systems (tile_gram.h: packed_cholesky) in LDS.  A last kernel takes
+// the strict `>` over the grid and forms beta and the BLUP coefficients u = U'K^-1 (y - M beta) at the chosen point.
 #include <algorithm>
 #include <cmath>
 #include <numeric>
 #include <vector>
 
-#include "brent_search.h"
+#include "delta_search.h"
 #include "objects.h"
+#include "tile_gram.h"
 
 using namespace crm;
 
 namespace {
 
-constexpr double LOG2PI = 1.8378770664093453;
-constexpr double EPS_TINY = 2.220446049250313e-16;
-constexpr double EPS_SMALL = 1.4901161193847656e-08;
 constexpr int CHX = 32;          // spectrum entries (or cells) per staging step
 constexpr int EKT_MAX = 130;     // columns of Z = [W, g, E0, y, U]: c_W + 2 k0 + 2 <= 130
 constexpr int VARIANT_BLOCK = 64;    // distinct variants per rotation block (bounds the Q_L'(g o E0) workspace)
@@ -68,46 +66,6 @@ struct EffArgs {
     double* u;       // [pairs x k0]
 };
 
-__device__ inline double logistic_clamped_x(double x) {
-    double v;
-    if (x > 0.0) {
-        v = 1.0 / (1.0 + exp(-x));
-    } else {
-        v = exp(x);
-        v = v / (v + 1.0);
-    }
-    return fmin(fmax(v, EPS_TINY), 1.0 - EPS_TINY);
-}
-
-__device__ inline int tri(int i, int k) { return i * (i + 1) / 2 + k; }   // k <= i
-
-// In-place Cholesky of the leading P x P block in packed lower storage, all threads.  false on a non-positive pivot.
-__device__ bool packed_cholesky(double* H, int P, double* scal, double& logdet) {
-    const int tid = threadIdx.x;
-    logdet = 0.0;
-    for (int j = 0; j < P; j++) {
-        __syncthreads();
-        if (tid == 0) {
-            double d = H[tri(j, j)];
-            for (int k = 0; k < j; k++) d -= H[tri(j, k)] * H[tri(j, k)];
-            scal[0] = d;
-        }
-        __syncthreads();
-        const double d = scal[0];
-        if (!(d > 0.0)) return false;
-        const double l = sqrt(d);
-        logdet += 2.0 * log(l);
-        for (int i = j + 1 + tid; i < P; i += blockDim.x) {
-            double s = H[tri(i, j)];
-            for (int k = 0; k < j; k++) s -= H[tri(i, k)] * H[tri(j, k)];
-            H[tri(i, j)] = s / l;
-        }
-        if (tid == 0) H[tri(j, j)] = l;
-        __syncthreads();
-    }
-    return true;
-}
-
 // Column z of Z = [W (cW), g, E0 (k0), y, U (k0)] for the pair (v, p): its spectrum row and its entry at cell i.
 struct ZCols {
     const EffArgs& a;
@@ -128,58 +86,6 @@ struct ZCols {
     }
 };
 
-// KT x KT Gram of scaled rows in TS x TS register tiles (16 x 16 threads).  Staging step of CHX positions: `scale(q)` (called
-// by the threads q < CHX, q = position - start) gives the factor of position start + q, `value(row, q)` the unscaled entry.
-// by_row: consecutive threads stage consecutive positions of one row (spectrum rows are contiguous); else consecutive rows of
-// one position (the cell-axis operands are row-major).  `sink(row, col, v)` gets every entry from the thread that holds it.
-template <int TS, class Scale, class Value, class Sink>
-__device__ inline void gram_tiles(double* S, double* sd, int KT, long len, bool by_row, Scale&& scale, Value&& value,
-                                  Sink&& sink) {
-    const int tid = threadIdx.x;
-    const int ti = tid >> 4, tj = tid & 15;
-    double acc[TS][TS];
-#pragma unroll
-    for (int i = 0; i < TS; i++)
-#pragma unroll
-        for (int j = 0; j < TS; j++) acc[i][j] = 0.0;
-    for (long c0 = 0; c0 < len; c0 += CHX) {
-        if (tid < CHX) sd[tid] = c0 + tid < len ? scale(c0, tid) : 0.0;
-        __syncthreads();
-        for (int e = tid; e < 16 * TS * CHX; e += 256) {
-            int row, q;
-            if (by_row) { row = e / CHX; q = e - row * CHX; }
-            else { q = e / (16 * TS); row = e - q * (16 * TS); }
-            double v = 0.0;
-            if (row < KT && c0 + q < len && sd[q] != 0.0) v = value(row, c0 + q) * sd[q];
-            S[row * (CHX + 1) + q] = v;
-        }
-        __syncthreads();
-#pragma unroll 2
-        for (int q = 0; q < CHX; q++) {
-            double x[TS], y[TS];
-#pragma unroll
-            for (int i = 0; i < TS; i++) {
-                x[i] = S[(ti + 16 * i) * (CHX + 1) + q];
-                y[i] = S[(tj + 16 * i) * (CHX + 1) + q];
-            }
-#pragma unroll
-            for (int i = 0; i < TS; i++)
-#pragma unroll
-                for (int j = 0; j < TS; j++) acc[i][j] += x[i] * y[j];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < TS; i++) {
-        const int row = ti + 16 * i;
-#pragma unroll
-        for (int j = 0; j < TS; j++) {
-            const int col = tj + 16 * j;
-            if (row < KT && col < KT) sink(row, col, acc[i][j]);
-        }
-    }
-}
-
 // Complement numerators c(u, v) = u'v - t_u't_v of Z and the plain X'X, once per pair (they depend on neither delta nor rho).
 template <int TS>
 __global__ __launch_bounds__(256) void effects_numerators_kernel(EffArgs a) {
@@ -191,8 +97,8 @@ __global__ __launch_bounds__(256) void effects_numerators_kernel(EffArgs a) {
     double* const sd = S + 16 * TS * (CHX + 1);
     double* const Cp = a.Cp + (size_t)b * KT * KT;
     double* const PX = a.PX + (size_t)b * P * P;
-    auto one = [&](long, int) -> double { return 1.0; };
-    gram_tiles<TS>(S, sd, KT, a.n, false, one, [&](int row, long i) { return z.cell(row, i); },
+    auto one = [&](long, int, double&) -> double { return 1.0; };
+    gram_tiles<TS, CHX>(S, sd, nullptr, nullptr, KT, a.n, false, one, [&](int row, long i) { return z.cell(row, i); },
                    [&](int row, int col, double v) {
                        Cp[(size_t)row * KT + col] = v;
                        if (row < P && col < P) PX[(size_t)row * P + col] = v;
@@ -200,7 +106,7 @@ __global__ __launch_bounds__(256) void effects_numerators_kernel(EffArgs a) {
     __threadfence();
     __syncthreads();
     // (entries written above by this thread only: each (row, col) has one owner in both passes)
-    gram_tiles<TS>(S, sd, KT, a.r, true, one, [&](int row, long j) { return z.trow(row)[j]; },
+    gram_tiles<TS, CHX>(S, sd, nullptr, nullptr, KT, (long)a.r, true, one, [&](int row, long j) { return z.trow(row)[j]; },
                    [&](int row, int col, double v) { Cp[(size_t)row * KT + col] -= v; });
 }
 
@@ -256,9 +162,7 @@ __global__ __launch_bounds__(256) void effects_fit_kernel(EffArgs a) {
     // against the same change of log|X'K^-1X|)
     const double* PX = a.PX + (size_t)b * P * P;
     for (int e = tid; e < P * (P + 1) / 2; e += 256) {
-        int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-        while (tri(i + 1, 0) <= e) i++;
-        while (tri(i, 0) > e) i--;
+        const int i = tri_row(e);
         Hp[e] = PX[(size_t)i * P + (e - tri(i, 0))];
     }
     double logdetXX;
@@ -266,43 +170,35 @@ __global__ __launch_bounds__(256) void effects_fit_kernel(EffArgs a) {
     __syncthreads();
     const double df = n - (double)P;
 
-    double cur_scale = NAN, cur_lml = -INFINITY;
     // evaluation at delta: lml and scale; with want_blup also beta (vec[0..P)) and U'D^-1 r (vec[P..P + k0))
-    auto evaluate = [&](double delta, bool want_blup) -> bool {
+    auto evaluate = [&](double delta, bool want_blup) -> DeltaValue {
+        DeltaValue out{false, NAN, NAN, NAN};
         const double omd = 1.0 - delta;
         const double aa = omd * (1.0 - rho);
         const double inv_d = 1.0 / delta;
         const double cdiag = woodbury ? 1.0 / (omd * rho) : 0.0;
-        double lpart = 0.0;
-        gram_tiles<TS>(S, sd, KT, r, true,
-                       [&](long c0, int q) {
-                           const double D = delta + aa * a.S[c0 + q];
-                           lpart += log(D);
-                           return sqrt(1.0 / D);
-                       },
-                       [&](int row, long j) { return z.trow(row)[j]; },
-                       [&](int row, int col, double v) {
-                           const double k = v + Cp[(size_t)row * KT + col] * inv_d;   // u'N^-1 v
-                           if (row < P1) {
-                               if (col <= row) Hp[tri(row, col)] = k;
-                           } else if (col < P1) {
-                               if (woodbury || want_blup) Bm[(row - P1) * P1 + col] = k;
-                           } else if (woodbury && col <= row) {
-                               Cc[tri(row - P1, col - P1)] = k + (row == col ? cdiag : 0.0);
-                           }
-                       });
-        red[tid] = lpart;
-        __syncthreads();
-        if (tid == 0) {
-            double s = 0.0;
-            for (int i = 0; i < CHX; i++) s += red[i];
-            scal[1] = s;
-        }
-        __syncthreads();
-        double logdetD = scal[1] + (n - (double)r) * log(delta);
+        const double lsum = gram_tiles<TS, CHX>(
+            S, sd, red, scal, KT, (long)r, true,
+            [&](long c0, int q, double& lpart) {
+                const double D = delta + aa * a.S[c0 + q];
+                lpart += log(D);
+                return sqrt(1.0 / D);
+            },
+            [&](int row, long j) { return z.trow(row)[j]; },
+            [&](int row, int col, double v) {
+                const double k = v + Cp[(size_t)row * KT + col] * inv_d;   // u'N^-1 v
+                if (row < P1) {
+                    if (col <= row) Hp[tri(row, col)] = k;
+                } else if (col < P1) {
+                    if (woodbury || want_blup) Bm[(row - P1) * P1 + col] = k;
+                } else if (woodbury && col <= row) {
+                    Cc[tri(row - P1, col - P1)] = k + (row == col ? cdiag : 0.0);
+                }
+            });
+        double logdetD = lsum + (n - (double)r) * log(delta);
         if (woodbury) {
             double logdetC;
-            if (!packed_cholesky(Cc, k0, scal, logdetC)) return false;
+            if (!packed_cholesky(Cc, k0, scal, logdetC)) return out;
             logdetD += logdetC + (double)k0 * log(omd * rho);
             // Z = Lc^-1 U'N^-1 [X, y], column by column
             for (int col = tid; col < P1; col += 256) {
@@ -315,9 +211,7 @@ __global__ __launch_bounds__(256) void effects_fit_kernel(EffArgs a) {
             __syncthreads();
             // [X, y]'D^-1[X, y] = [X, y]'N^-1[X, y] - Z'Z
             for (int e = tid; e < P1 * (P1 + 1) / 2; e += 256) {
-                int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-                while (tri(i + 1, 0) <= e) i++;
-                while (tri(i, 0) > e) i--;
+                const int i = tri_row(e);
                 const int k = e - tri(i, 0);
                 double s = 0.0;
                 for (int q = 0; q < k0; q++) s += Bm[q * P1 + i] * Bm[q * P1 + k];
@@ -326,7 +220,7 @@ __global__ __launch_bounds__(256) void effects_fit_kernel(EffArgs a) {
             __syncthreads();
         }
         double logdetH;
-        if (!packed_cholesky(Hp, P, scal, logdetH)) return false;
+        if (!packed_cholesky(Hp, P, scal, logdetH)) return out;
         if (tid == 0) {
             // rss = y'D^-1y - z'z with L z = X'D^-1y (forward substitution)
             double rss = Hp[tri(P, P)];
@@ -367,15 +261,16 @@ __global__ __launch_bounds__(256) void effects_fit_kernel(EffArgs a) {
         const double s = fmax(rss / df, EPS_SMALL);
         double val = -0.5 * (df * LOG2PI + df + n * log(s) + logdetD);
         val += 0.5 * (logdetXX - (logdetH - (double)P * log(s)));
-        cur_scale = s;
-        cur_lml = val;
+        out.ok = true;
+        out.scale = s;
+        out.lml = val;
         __syncthreads();
-        return true;
+        return out;
     };
 
     if constexpr (BLUP) {
         const EffTrial t = a.trial[(size_t)b * a.nrho + w];
-        evaluate(t.delta, true);
+        (void)evaluate(t.delta, true);
         if (tid == 0) {
             double* f = a.fit + (size_t)b * 6;
             f[0] = rho;
@@ -388,49 +283,18 @@ __global__ __launch_bounds__(256) void effects_fit_kernel(EffArgs a) {
             for (int i = 0; i < k0; i++) a.u[(size_t)b * k0 + i] = vec[P + i] / t.scale;
         }
     } else {
-        int nfev = 0;
-        double cur_delta = 0.5;
-        double memo_f[2] = {0.0, 0.0}, memo_scale[2] = {0.0, 0.0}, memo_lml[2] = {0.0, 0.0};
-        bool memo_set[2] = {false, false};
-        bool last_clamped = false;
-        auto f = [&](double x) -> double {
-            nfev++;
-            const double delta = logistic_clamped_x(x);
-            const int clamp = delta == 1.0 - EPS_TINY ? 1 : (delta == EPS_TINY ? 0 : -1);
-            last_clamped = clamp >= 0;
-            cur_delta = delta;
-            if (clamp >= 0 && memo_set[clamp]) {
-                cur_scale = memo_scale[clamp]; cur_lml = memo_lml[clamp];
-                return memo_f[clamp];
-            }
-            double value;
-            if (evaluate(delta, false)) {
-                value = -cur_lml;
-            } else {
-                cur_scale = NAN; cur_lml = NAN;
-                value = INFINITY;
-            }
-            if (clamp >= 0) {
-                memo_set[clamp] = true; memo_f[clamp] = value; memo_scale[clamp] = cur_scale; memo_lml[clamp] = cur_lml;
-            }
-            return value;
-        };
-        struct Objective {
-            decltype(f)& fn;
-            const bool& at_clamp;
-            __device__ inline double operator()(double x) { return fn(x); }
-            __device__ inline bool clamped() const { return at_clamp; }
-        } objective{f, last_clamped};
+        auto eval = [&](double delta, bool) -> DeltaValue { return evaluate(delta, false); };
+        OutOfLineObjective<decltype(eval)> f(eval, false);
         BrentTrace trace;
         double bf0;
-        const double bx0 = brent_search<false>(objective, trace, bf0);
+        const double bx0 = brent_search<false>(f, trace, bf0);
         f(bx0);   // (the record at the stopping point, as the null fits leave it)
         if (tid == 0) {
             EffTrial t;
-            t.lml = cur_lml;
-            t.delta = cur_delta;
-            t.scale = cur_scale;
-            t.nfev = nfev;
+            t.lml = f.lml;
+            t.delta = f.delta;
+            t.scale = f.scale;
+            t.nfev = f.nfev;
             t.pad = 0;
             a.trial[(size_t)b * a.nrho + w] = t;
         }

@@ -11,11 +11,17 @@
 // sum_j log((1-d) S0[j] + d), followed by a 64-lane butterfly so that every lane holds
 // bitwise identical totals.  The scalar logic on top of the totals -- closed-form beta
 // and scale, REML log-likelihood, and the bracket + Brent search over x = logit(d) with
-// rtol = atol = 1e-6 -- is executed redundantly by all lanes (wave-uniform control flow)
-// and follows oracle/brent.py statement by statement.
+// rtol = atol = 1e-6 (brent_search.h) -- is executed redundantly by all lanes (wave-uniform
+// control flow).
+//
+// The shell around the search -- the memo of the two clamped points, the adaptor brent_search is given, the probes to
+// either side of the stopping point and the trial record -- is this file's own and not delta_search.h's, which the
+// other three searching kernels share: these kernels sit at their register limits, and with the shared objective (two
+// scalar memo slots where the arrays here are indexed by the clamp, which the compiler keeps in LDS or scratch) spills
+// rose at 5..8 covariate columns and nullfit_kernel<7, false, true> ran 2.3 % slower.  The constants and the clamped
+// logistic do come from delta_search.h.
 #include "crm_internal.h"
-#include "nullfit.h"
-#include "brent_search.h"
+#include "delta_search.h"
 #include "wave_ops.h"
 #include <type_traits>
 
@@ -23,20 +29,9 @@ namespace crm {
 
 namespace {
 
-constexpr double LOG2PI = 1.8378770664093453;
-constexpr double EPS_TINY = 2.220446049250313e-16;    // numpy_sugar.epsilon.tiny
-constexpr double EPS_SMALL = 1.4901161193847656e-08;  // numpy_sugar.epsilon.small
-
 // FROM = 32: all six levels (one fit per wavefront); FROM = 8: levels 8 .. 1 (a row of sixteen lanes)
 template <int N, int FROM>
 __device__ inline void butterfly_sums(double (&v)[N]) {
-#ifdef CRM_NF_BUTTERFLY_SUM   // (diagnostic builds, tools/diag/compare_builds.py: the round-5 form, value by value)
-#pragma unroll
-    for (int i = 0; i < N; i++)
-#pragma unroll
-        for (int off = FROM; off > 0; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
-    return;
-#endif
     double t[N];
     if constexpr (FROM >= 32) {
 #pragma unroll
@@ -91,17 +86,6 @@ struct LogProduct {
     }
     __device__ inline double log_value() const { return log(mant) + (double)expo * 0.6931471805599453; }
 };
-
-__device__ inline double logistic_clamped(double x) {
-    double v;
-    if (x > 0.0) {
-        v = 1.0 / (1.0 + exp(-x));
-    } else {
-        v = exp(x);
-        v = v / (v + 1.0);
-    }
-    return fmin(fmax(v, EPS_TINY), 1.0 - EPS_TINY);
-}
 
 __host__ __device__ constexpr int pair_index(int u, int v, int U) {
     // u <= v, row-major upper triangle
@@ -188,7 +172,6 @@ template <int U>
 __device__ __noinline__ double objective_noise_bound(const double (&bb)[U], const double (&sd)[U], const double (&pl)[U * (U + 1) / 2],
                                                      double inv_d, double rss, double df, double lsum, double n_minus_r, double log_delta,
                                                      double n, double log_s, double logdetXX, double logdetH, double p_eff) {
-    constexpr double LOG2PI_ = 1.8378770664093453;
     double mag = 0.0;
 #pragma unroll
     for (int u = 0; u < U; u++)
@@ -198,7 +181,7 @@ __device__ __noinline__ double objective_noise_bound(const double (&bb)[U], cons
             const double m_uv = spec + pl[pair_index(u, v, U)] * inv_d;
             mag += (u == v ? 1.0 : 2.0) * bb[u] * bb[v] * m_uv;
         }
-    const double logs = fabs(lsum) + fabs(n_minus_r) * fabs(log_delta) + n * fabs(log_s) + df * (LOG2PI_ + 1.0) + fabs(logdetXX) +
+    const double logs = fabs(lsum) + fabs(n_minus_r) * fabs(log_delta) + n * fabs(log_s) + df * (LOG2PI + 1.0) + fabs(logdetXX) +
                         fabs(logdetH) + p_eff * fabs(log_s);
     return 0.5 * (df * mag / fabs(rss) + logs);
 }
@@ -526,13 +509,6 @@ __device__ __forceinline__ void nullfit_fit(const NullFitArgs& a, const int b, c
 #pragma unroll
         for (int j = 0; j < P; j++) larg = sub == 1 + j ? piv[j] : larg;
         larg = sub == P + 1 ? s : larg;
-#ifdef CRM_NF_SERIAL_LOGS      // (diagnostic builds: the round-5 form, one logarithm after the other)
-        const double log_delta = log(delta), log_s = log(s);
-        double logdetH = 0.0;
-#pragma unroll
-        for (int j = 0; j < P; j++) logdetH += 2.0 * log(piv[j]);
-        (void)larg;
-#else
         const double lres = log(larg);
         // (one fit per wavefront: scalar reads; four: a shuffle inside the row of the fit)
         auto from_sub = [&](int k) -> double {
@@ -543,7 +519,6 @@ __device__ __forceinline__ void nullfit_fit(const NullFitArgs& a, const int b, c
         double logdetH = 0.0;
 #pragma unroll
         for (int j = 0; j < P; j++) logdetH += 2.0 * from_sub(1 + j);
-#endif
         const double logdetK = lsum + (n - (double)r) * log_delta;
         val = -0.5 * (df * LOG2PI + df + n * log_s + logdetK);
         if (a.restricted) val += 0.5 * (logdetXX - (logdetH - p_eff * log_s));

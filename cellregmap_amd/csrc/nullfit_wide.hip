@@ -5,34 +5,19 @@
 //
 // Each likelihood evaluation is a weighted Gram matrix over the spectrum,
 //     G(d) = sum_j  w_j(d) t_j t_j',   t_j = (Q0'W_1 .. Q0'W_c, Q0'g, Q0'y)_j,  w_j = 1/((1-d) S0_j + d),
-// accumulated by 16 x 16 threads in TS x TS register tiles from sqrt(w)-scaled rows staged in LDS
-// (the same structure as assemble.hip's gram_ext), followed by a workgroup-parallel Cholesky of the
-// (c+1) x (c+1) block and the closed-form beta / scale / log-likelihood.  The scalar search on top
-// (bracket + Brent, rtol = atol = 1e-6) is the same statement sequence as nullfit.hip and
-// oracle/brent.py, executed uniformly by all threads.
-#include "nullfit.h"
-#include "brent_search.h"
+// accumulated by tile_gram.h's gram_tiles, 64 spectrum entries per staging step, followed by a
+// workgroup-parallel Cholesky of the (c+1) x (c+1) block (dense, with a soft last pivot for the rank
+// test on g) and the closed-form beta / scale / log-likelihood.  The search on top is brent_search.h's
+// on delta_search.h's memoised objective, executed uniformly by all threads.
+#include "delta_search.h"
+#include "tile_gram.h"
 
 namespace crm {
 
 namespace {
 
-constexpr double LOG2PI = 1.8378770664093453;
-constexpr double EPS_TINY = 2.220446049250313e-16;
-constexpr double EPS_SMALL = 1.4901161193847656e-08;
 constexpr int CHW = 64;        // spectrum entries per staging step
 constexpr int KT_MAX = 64;     // c + 2 <= 64
-
-__device__ inline double logistic_clamped(double x) {
-    double v;
-    if (x > 0.0) {
-        v = 1.0 / (1.0 + exp(-x));
-    } else {
-        v = exp(x);
-        v = v / (v + 1.0);
-    }
-    return fmin(fmax(v, EPS_TINY), 1.0 - EPS_TINY);
-}
 
 struct WideShared {
     double S[KT_MAX][CHW + 1];   // sqrt(w)-scaled rows of the current chunk
@@ -98,7 +83,7 @@ __device__ void chol_solve_serial(const double* L, int P, double* x) {
 }
 
 template <int TS>
-__global__ __launch_bounds__(256) void nullfit_wide_kernel(NullFitArgs a, int rho_base) {
+__global__ __launch_bounds__(256) void nullfit_wide_kernel(NullFitArgs a) {
     extern __shared__ __align__(16) unsigned char smem_raw[];
     WideShared& sh = *reinterpret_cast<WideShared*>(smem_raw);
     const int b = blockIdx.x;
@@ -109,7 +94,6 @@ __global__ __launch_bounds__(256) void nullfit_wide_kernel(NullFitArgs a, int rh
     const int r = R.r;
     const double n = (double)a.n;
     const int tid = threadIdx.x;
-    const int ti = tid >> 4, tj = tid & 15;
     const double* __restrict__ tg = R.T + (long)b * R.ldT;
 
     auto row_value = [&](int row, int j) -> double {
@@ -117,72 +101,17 @@ __global__ __launch_bounds__(256) void nullfit_wide_kernel(NullFitArgs a, int rh
         if (row == c) return tg[j];
         return R.ty[j];
     };
-    // weighted Gram into sh.Gm; returns sum_j log D_j (weighted) in lsum
-    auto gram_pass = [&](double delta, bool weighted, double& lsum) {
-        double acc[TS][TS];
-#pragma unroll
-        for (int i = 0; i < TS; i++)
-#pragma unroll
-            for (int j = 0; j < TS; j++) acc[i][j] = 0.0;
-        double lpart = 0.0;
+    // weighted Gram into sh.Gm; returns sum_j log D_j (weighted)
+    auto gram_pass = [&](double delta, bool weighted) -> double {
         const double omd = 1.0 - delta;
-        for (int c0 = 0; c0 < r; c0 += CHW) {
-            if (tid < CHW) {
-                const int j = c0 + tid;
-                double v = 0.0;
-                if (j < r) {
-                    if (weighted) {
-                        const double D = omd * R.S0[j] + delta;
-                        lpart += log(D);
-                        v = sqrt(1.0 / D);
-                    } else {
-                        v = 1.0;
-                    }
-                }
-                sh.sd[tid] = v;
-            }
-            __syncthreads();
-            for (int e = tid; e < 16 * TS * CHW; e += 256) {
-                const int row = e / CHW, cc = e - row * CHW;
-                const int j = c0 + cc;
-                double v = 0.0;
-                if (row < KT && j < r) v = row_value(row, j) * sh.sd[cc];
-                sh.S[row][cc] = v;
-            }
-            __syncthreads();
-#pragma unroll 4
-            for (int cc = 0; cc < CHW; cc++) {
-                double x[TS], y[TS];
-#pragma unroll
-                for (int i = 0; i < TS; i++) {
-                    x[i] = sh.S[ti + 16 * i][cc];
-                    y[i] = sh.S[tj + 16 * i][cc];
-                }
-#pragma unroll
-                for (int i = 0; i < TS; i++)
-#pragma unroll
-                    for (int j = 0; j < TS; j++) acc[i][j] += x[i] * y[j];
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int i = 0; i < TS; i++) {
-            const int row = ti + 16 * i;
-#pragma unroll
-            for (int j = 0; j < TS; j++) {
-                const int col = tj + 16 * j;
-                if (row < KT && col < KT) sh.Gm[row * KT_MAX + col] = acc[i][j];
-            }
-        }
-        sh.red[tid] = lpart;
-        __syncthreads();
-        if (tid == 0) {
-            double s = 0.0;
-            for (int i = 0; i < CHW; i++) s += sh.red[i];
-            sh.scal[1] = s;
-        }
-        __syncthreads();
-        lsum = sh.scal[1];
+        return gram_tiles<TS, CHW>(&sh.S[0][0], sh.sd, sh.red, sh.scal, KT, r, true,
+                                   [&](int c0, int q, double& lpart) -> double {
+                                       if (!weighted) return 1.0;
+                                       const double D = omd * R.S0[c0 + q] + delta;
+                                       lpart += log(D);
+                                       return sqrt(1.0 / D);
+                                   },
+                                   row_value, [&](int row, int col, double v) { sh.Gm[row * KT_MAX + col] = v; });
     };
 
     // plain inner products u'v (u, v in {W.., g, y}) -> sh.Cp, then subtract the unweighted Gram
@@ -216,8 +145,7 @@ __global__ __launch_bounds__(256) void nullfit_wide_kernel(NullFitArgs a, int rh
         __syncthreads();
     }
     {
-        double dummy;
-        gram_pass(1.0, false, dummy);
+        (void)gram_pass(1.0, false);
         for (int e = tid; e < KT * KT; e += 256) {
             const int i = e / KT, j = e - i * KT;
             sh.Cp[i * KT_MAX + j] -= sh.Gm[i * KT_MAX + j];
@@ -227,31 +155,11 @@ __global__ __launch_bounds__(256) void nullfit_wide_kernel(NullFitArgs a, int rh
     const double p_eff = use_g ? (double)P : (double)c;
     const double df = a.restricted ? n - p_eff : n;
 
-    double cur_delta = 0.5, cur_scale = 1.0, cur_lml = -INFINITY;
-    int nfev = 0;
-    // (the two clamped points delta = eps, 1 - eps are evaluated once and remembered: see nullfit.hip)
-    double memo_f[2] = {0.0, 0.0}, memo_scale[2] = {0.0, 0.0}, memo_lml[2] = {0.0, 0.0}, memo_noise[2] = {NAN, NAN};
-    bool memo_set[2] = {false, false};
-    bool last_clamped = false, want_noise = false;   // (as in nullfit.hip)
-    double cur_noise = NAN;
-    auto f = [&](double x) -> double {
-        nfev++;
-        const double delta = logistic_clamped(x);
-        const int clamp = delta == 1.0 - EPS_TINY ? 1 : (delta == EPS_TINY ? 0 : -1);
-        last_clamped = clamp >= 0;
-        if (clamp >= 0 && memo_set[clamp]) {
-            cur_delta = delta; cur_scale = memo_scale[clamp]; cur_lml = memo_lml[clamp]; cur_noise = memo_noise[clamp];
-            return memo_f[clamp];
-        }
-        auto remember = [&](double value) -> double {
-            if (clamp >= 0) {
-                memo_set[clamp] = true; memo_f[clamp] = value; memo_scale[clamp] = cur_scale; memo_lml[clamp] = cur_lml;
-                memo_noise[clamp] = cur_noise;
-            }
-            return value;
-        };
-        double lsum;
-        gram_pass(delta, true, lsum);
+    // (out of line, one copy for every call of the search; the objective around it stays inline, its few scalars in
+    // registers: this kernel has them to spare, and its register count stays where three waves per SIMD fit)
+    auto eval = [&](double delta, bool noise_now) __attribute__((noinline)) -> DeltaValue {
+        DeltaValue out{false, NAN, NAN, NAN};
+        const double lsum = gram_pass(delta, true);
         const double inv_d = 1.0 / delta;
         const double logdetK = lsum + (n - (double)r) * log(delta);
         for (int e = tid; e < P * P; e += 256) {
@@ -270,9 +178,8 @@ __global__ __launch_bounds__(256) void nullfit_wide_kernel(NullFitArgs a, int rh
         bool dropped;
         const bool ok = block_cholesky(sh.H, P, sh.scal, logdetH, 0.0, dropped);
         if (!ok) {
-            cur_delta = delta; cur_scale = NAN; cur_lml = NAN;
             __syncthreads();
-            return remember(INFINITY);
+            return out;
         }
         if (tid == 0) {
             // rss = y'Ky - b' H^-1 b
@@ -282,8 +189,8 @@ __global__ __launch_bounds__(256) void nullfit_wide_kernel(NullFitArgs a, int rh
             double rss = sh.Gm[(c + 1) * KT_MAX + (c + 1)] + sh.Cp[(c + 1) * KT_MAX + (c + 1)] * inv_d;
             for (int i = 0; i < P; i++) rss -= sh.rhs[i] * xk[i];
             sh.scal[2] = rss;
-            if (a.track && (want_noise || clamp >= 0)) {
-                // the noise bound of nullfit.hip: magnitudes of the terms of rss = b' K b, b = (-beta, 1)
+            if (noise_now) {
+                // the noise bound of nullfit.hip's objective_noise_bound: magnitudes of the terms of rss = b' K b, b = (-beta, 1)
                 // (Gm: spectrum sums, Cp: complements u'v - t_u't_v, whose two parts are each at most sqrt(u'u v'v))
                 xk[P] = 1.0;
                 const int yi = c + 1;
@@ -308,44 +215,21 @@ __global__ __launch_bounds__(256) void nullfit_wide_kernel(NullFitArgs a, int rh
         const double s = fmax(rss / df, EPS_SMALL);
         double val = -0.5 * (df * LOG2PI + df + n * log(s) + logdetK);
         if (a.restricted) val += 0.5 * (logdetXX - (logdetH - p_eff * log(s)));
-        cur_delta = delta; cur_scale = s; cur_lml = val;
-        if (a.track && (want_noise || clamp >= 0))
-            cur_noise = 0.5 * (df * sh.scal[3] / fabs(rss) + fabs(lsum) + fabs((n - (double)r) * log(delta)) + n * fabs(log(s))
+        out.ok = true;
+        out.scale = s;
+        out.lml = val;
+        if (noise_now)
+            out.noise = 0.5 * (df * sh.scal[3] / fabs(rss) + fabs(lsum) + fabs((n - (double)r) * log(delta)) + n * fabs(log(s))
                                + df * (LOG2PI + 1.0) + fabs(logdetXX) + fabs(logdetH) + p_eff * fabs(log(s)));
         __syncthreads();
-        return remember(-val);
+        return out;
     };
-
-    // ---- bracket + Brent localmin: the search shared with nullfit.hip (brent_search.h) ---------------------------
-    struct Objective {
-        decltype(f)& fn;
-        const bool& at_clamp;
-        __device__ inline double operator()(double x) { return fn(x); }
-        __device__ inline bool clamped() const { return at_clamp; }
-    } objective{f, last_clamped};
+    ClampedObjective<decltype(eval)> f(eval, a.track != 0);
     BrentTrace trace;
     double bf0;
-    const double bx0 = a.track ? brent_search<true>(objective, trace, bf0) : brent_search<false>(objective, trace, bf0);
-    double f_up = NAN, f_dn = NAN;   // (as in nullfit.hip: the objective one stopping tolerance to either side)
-    if (a.track) {
-        const double tolx = 1e-6 * fabs(bx0) + 1e-6;
-        f_up = f(bx0 + tolx);
-        f_dn = f(bx0 - tolx);
-    }
-    want_noise = true;
-    const double f_stop = f(bx0);
-    if (tid == 0) {
-        NullFitTrial t;
-        t.lml = cur_lml;
-        t.delta = cur_delta;
-        t.scale = cur_scale;
-        t.use_g = use_g ? 1 : 0;
-        t.nfev = nfev;
-        t.margin = a.track ? fmin(trace.cmp, trace.sign) : NAN;
-        t.curv = a.track ? 0.5 * (f_up + f_dn) - f_stop : NAN;
-        t.noise = a.track ? cur_noise : NAN;
-        a.trial[(long)b * a.nrho + w] = t;
-    }
+    const double bx0 = a.track ? brent_search<true>(f, trace, bf0) : brent_search<false>(f, trace, bf0);
+    const NullFitTrial t = finish_fit(f, bx0, trace, use_g);
+    if (tid == 0) a.trial[(long)b * a.nrho + w] = t;
 }
 
 }  // namespace
@@ -367,7 +251,7 @@ int launch_nullfit_wide(hipStream_t st, const NullFitArgs& a, int variants) {
     do {                                                                                             \
         CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&nullfit_wide_kernel<T>),          \
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));          \
-        hipLaunchKernelGGL(nullfit_wide_kernel<T>, grid, dim3(256), lds, st, a, 0);                  \
+        hipLaunchKernelGGL(nullfit_wide_kernel<T>, grid, dim3(256), lds, st, a);                     \
     } while (0)
     if (ts <= 1) CRM_WIDE(1);
     else if (ts == 2) CRM_WIDE(2);

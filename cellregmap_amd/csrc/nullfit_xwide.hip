@@ -5,67 +5,25 @@
 // cohort with 100 contexts fits LMMs with 100 covariate columns there; the effect-size estimators fit [W, g, E0]
 // (:175, :223).  The reference accepts any width.
 //
-// Same model, same search (bracket + Brent, rtol = atol = 1e-6, statement for statement as nullfit.hip / oracle/brent.py),
-// same weighted-Gram evaluation as nullfit_wide.hip -- one 256-thread workgroup per (variant, rho), 16 x 16 threads with
-// TS x TS register tiles over sqrt(w)-scaled rows staged in LDS -- but with what no longer fits LDS kept elsewhere:
-//   * the (c+1) x (c+1) system / Cholesky factor in PACKED lower-triangular storage (129 * 130 / 2 doubles = 67 KB),
+// Same model and same search (brent_search.h on delta_search.h's memoised objective) as the other null-fit kernels, and a
+// weighted-Gram evaluation by one 256-thread workgroup per (variant, rho) through tile_gram.h's gram_tiles, but with what no
+// longer fits LDS kept elsewhere:
+//   * the (c+1) x (c+1) system / Cholesky factor in PACKED lower-triangular storage (129 * 130 / 2 doubles = 67 KB;
+//     tile_gram.h: tri, packed_cholesky),
 //   * the complement numerators u'v - t_u't_v (KT x KT, constant over the search) in global memory (NullFitArgs::xwide,
 //     KT * KT doubles per workgroup; they stay in L2),
 //   * the weighted Gram itself nowhere: every thread adds its tile to the packed system (and to the right-hand side /
 //     y'K^-1y) straight from its accumulators,
 //   * 32 spectrum entries per staging step instead of 64.
-#include "nullfit.h"
-#include "brent_search.h"
+#include "delta_search.h"
+#include "tile_gram.h"
 
 namespace crm {
 
 namespace {
 
-constexpr double LOG2PI = 1.8378770664093453;
-constexpr double EPS_TINY = 2.220446049250313e-16;
-constexpr double EPS_SMALL = 1.4901161193847656e-08;
 constexpr int CHX = 32;         // spectrum entries per staging step
 constexpr int XKT_MAX = 130;    // c + 2 <= 130
-
-__device__ inline double logistic_clamped_x(double x) {
-    double v;
-    if (x > 0.0) {
-        v = 1.0 / (1.0 + exp(-x));
-    } else {
-        v = exp(x);
-        v = v / (v + 1.0);
-    }
-    return fmin(fmax(v, EPS_TINY), 1.0 - EPS_TINY);
-}
-
-__device__ inline int tri(int i, int k) { return i * (i + 1) / 2 + k; }   // k <= i
-
-// In-place Cholesky of the leading P x P block in packed lower storage, all threads.  false on a non-positive pivot.
-__device__ bool packed_cholesky(double* H, int P, double* scal, double& logdet) {
-    const int tid = threadIdx.x;
-    logdet = 0.0;
-    for (int j = 0; j < P; j++) {
-        __syncthreads();
-        if (tid == 0) {
-            double d = H[tri(j, j)];
-            for (int k = 0; k < j; k++) d -= H[tri(j, k)] * H[tri(j, k)];
-            scal[0] = d;
-        }
-        __syncthreads();
-        const double d = scal[0];
-        if (!(d > 0.0)) return false;
-        const double l = sqrt(d);
-        logdet += 2.0 * log(l);
-        for (int i = j + 1 + tid; i < P; i += blockDim.x) {
-            double s = H[tri(i, j)];
-            for (int k = 0; k < j; k++) s -= H[tri(i, k)] * H[tri(j, k)];
-            H[tri(i, j)] = s / l;
-        }
-        if (tid == 0) H[tri(j, j)] = l;
-        __syncthreads();
-    }
-    return true;
-}
 
 template <int TS>
 __global__ __launch_bounds__(256) void nullfit_xwide_kernel(NullFitArgs a) {
@@ -78,7 +36,6 @@ __global__ __launch_bounds__(256) void nullfit_xwide_kernel(NullFitArgs a) {
     const int r = R.r;
     const double n = (double)a.n;
     const int tid = threadIdx.x;
-    const int ti = tid >> 4, tj = tid & 15;
     const double* __restrict__ tg = R.T + (long)b * R.ldT;
     // LDS: S [16 TS][CHX + 1], sd [CHX], Hp [P (P + 1) / 2], rhs [KT], red [256], scal [8]
     double* const S = xsm;
@@ -94,73 +51,18 @@ __global__ __launch_bounds__(256) void nullfit_xwide_kernel(NullFitArgs a) {
         if (row == c) return tg[j];
         return R.ty[j];
     };
-    // weighted Gram over the spectrum in register tiles; `sink(row, col, value)` receives every entry of the KT x KT
-    // result (row, col < KT) from the thread that holds it; returns sum_j log D_j in lsum
-    auto gram_pass = [&](double delta, bool weighted, double& lsum, auto&& sink) {
-        double acc[TS][TS];
-#pragma unroll
-        for (int i = 0; i < TS; i++)
-#pragma unroll
-            for (int j = 0; j < TS; j++) acc[i][j] = 0.0;
-        double lpart = 0.0;
+    // weighted Gram over the spectrum; `sink(row, col, value)` receives every entry of the KT x KT result; returns
+    // sum_j log D_j (weighted)
+    auto gram_pass = [&](double delta, bool weighted, auto&& sink) -> double {
         const double omd = 1.0 - delta;
-        for (int c0 = 0; c0 < r; c0 += CHX) {
-            if (tid < CHX) {
-                const int j = c0 + tid;
-                double v = 0.0;
-                if (j < r) {
-                    if (weighted) {
-                        const double D = omd * R.S0[j] + delta;
-                        lpart += log(D);
-                        v = sqrt(1.0 / D);
-                    } else {
-                        v = 1.0;
-                    }
-                }
-                sd[tid] = v;
-            }
-            __syncthreads();
-            for (int e = tid; e < 16 * TS * CHX; e += 256) {
-                const int row = e / CHX, cc = e - row * CHX;
-                const int j = c0 + cc;
-                double v = 0.0;
-                if (row < KT && j < r) v = row_value(row, j) * sd[cc];
-                S[row * (CHX + 1) + cc] = v;
-            }
-            __syncthreads();
-#pragma unroll 2
-            for (int cc = 0; cc < CHX; cc++) {
-                double x[TS], y[TS];
-#pragma unroll
-                for (int i = 0; i < TS; i++) {
-                    x[i] = S[(ti + 16 * i) * (CHX + 1) + cc];
-                    y[i] = S[(tj + 16 * i) * (CHX + 1) + cc];
-                }
-#pragma unroll
-                for (int i = 0; i < TS; i++)
-#pragma unroll
-                    for (int j = 0; j < TS; j++) acc[i][j] += x[i] * y[j];
-            }
-            __syncthreads();
-        }
-#pragma unroll
-        for (int i = 0; i < TS; i++) {
-            const int row = ti + 16 * i;
-#pragma unroll
-            for (int j = 0; j < TS; j++) {
-                const int col = tj + 16 * j;
-                if (row < KT && col < KT) sink(row, col, acc[i][j]);
-            }
-        }
-        red[tid] = lpart;
-        __syncthreads();
-        if (tid == 0) {
-            double s = 0.0;
-            for (int i = 0; i < CHX; i++) s += red[i];
-            scal[1] = s;
-        }
-        __syncthreads();
-        lsum = scal[1];
+        return gram_tiles<TS, CHX>(S, sd, red, scal, KT, r, true,
+                                   [&](int c0, int q, double& lpart) -> double {
+                                       if (!weighted) return 1.0;
+                                       const double D = omd * R.S0[c0 + q] + delta;
+                                       lpart += log(D);
+                                       return sqrt(1.0 / D);
+                                   },
+                                   row_value, sink);
     };
     // (written by this workgroup's threads, read by others of it: past the CU's vector L1)
     auto cp_at = [&](size_t e) -> double { return __hip_atomic_load(Cp + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
@@ -173,9 +75,7 @@ __global__ __launch_bounds__(256) void nullfit_xwide_kernel(NullFitArgs a) {
 
     // rank of [W, g] and log|X'X| from the Cholesky of the plain Gram
     for (int e = tid; e < P * (P + 1) / 2; e += 256) {
-        int i = (int)((sqrt(8.0 * e + 1.0) - 1.0) * 0.5);
-        while (tri(i + 1, 0) <= e) i++;
-        while (tri(i, 0) > e) i--;
+        const int i = tri_row(e);
         Hp[e] = plain(i, e - tri(i, 0));
     }
     __syncthreads();
@@ -214,41 +114,18 @@ __global__ __launch_bounds__(256) void nullfit_xwide_kernel(NullFitArgs a) {
     }
     // complement numerators: plain inner products minus the unweighted Gram, into global memory
     {
-        double dummy;
-        gram_pass(1.0, false, dummy, [&](int row, int col, double v) { Cp[(size_t)row * KT + col] = plain(row, col) - v; });
+        (void)gram_pass(1.0, false, [&](int row, int col, double v) { Cp[(size_t)row * KT + col] = plain(row, col) - v; });
         __threadfence();
         __syncthreads();
     }
     const double p_eff = use_g ? (double)P : (double)c;
     const double df = a.restricted ? n - p_eff : n;
 
-    double cur_delta = 0.5, cur_scale = 1.0, cur_lml = -INFINITY;
-    int nfev = 0;
-    double memo_f[2] = {0.0, 0.0}, memo_scale[2] = {0.0, 0.0}, memo_lml[2] = {0.0, 0.0}, memo_noise[2] = {NAN, NAN};
-    bool memo_set[2] = {false, false};
-    bool last_clamped = false, want_noise = false;   // (as in nullfit.hip)
-    double cur_noise = NAN;
     double* const diagS = S;          // (the tile buffer is free between two passes: diagonal of the spectrum Gram, KT)
-    auto f = [&](double x) -> double {
-        nfev++;
-        const double delta = logistic_clamped_x(x);
-        const int clamp = delta == 1.0 - EPS_TINY ? 1 : (delta == EPS_TINY ? 0 : -1);
-        last_clamped = clamp >= 0;
-        if (clamp >= 0 && memo_set[clamp]) {
-            cur_delta = delta; cur_scale = memo_scale[clamp]; cur_lml = memo_lml[clamp]; cur_noise = memo_noise[clamp];
-            return memo_f[clamp];
-        }
-        auto remember = [&](double value) -> double {
-            if (clamp >= 0) {
-                memo_set[clamp] = true; memo_f[clamp] = value; memo_scale[clamp] = cur_scale; memo_lml[clamp] = cur_lml;
-                memo_noise[clamp] = cur_noise;
-            }
-            return value;
-        };
-        const bool noise_now = a.track && (want_noise || clamp >= 0);
+    auto eval = [&](double delta, bool noise_now) -> DeltaValue {
+        DeltaValue out{false, NAN, NAN, NAN};
         const double inv_d = 1.0 / delta;
-        double lsum;
-        gram_pass(delta, true, lsum, [&](int row, int col, double v) {
+        const double lsum = gram_pass(delta, true, [&](int row, int col, double v) {
             const double k = v + cp_at((size_t)row * KT + col) * inv_d;   // u' Kt^-1 v
             if (row < P && col <= row) {
                 double h = k;
@@ -264,9 +141,8 @@ __global__ __launch_bounds__(256) void nullfit_xwide_kernel(NullFitArgs a) {
         double logdetH;
         const bool ok = packed_cholesky(Hp, P, scal, logdetH);
         if (!ok) {
-            cur_delta = delta; cur_scale = NAN; cur_lml = NAN;
             __syncthreads();
-            return remember(INFINITY);
+            return out;
         }
         if (tid == 0) {
             // rss = y'Ky - z'z with L z = b  (one forward substitution)
@@ -280,8 +156,9 @@ __global__ __launch_bounds__(256) void nullfit_xwide_kernel(NullFitArgs a) {
             }
             scal[2] = rss;
             if (noise_now) {
-                // the noise bound of nullfit.hip: beta by the backward substitution, then the magnitudes of the terms of
-                // rss = b' K b, b = (-beta, 1), by Cauchy-Schwarz on both parts of every entry: (sum_u |b_u| sqrt(m_u))^2
+                // the noise bound of nullfit.hip's objective_noise_bound: beta by the backward substitution, then the magnitudes
+                // of the terms of rss = b' K b, b = (-beta, 1), by Cauchy-Schwarz on both parts of every entry:
+                // (sum_u |b_u| sqrt(m_u))^2
                 double* const beta = diagS + KT;
                 for (int i = P - 1; i >= 0; i--) {
                     double t = red[i];
@@ -303,44 +180,21 @@ __global__ __launch_bounds__(256) void nullfit_xwide_kernel(NullFitArgs a) {
         const double s = fmax(rss / df, EPS_SMALL);
         double val = -0.5 * (df * LOG2PI + df + n * log(s) + logdetK);
         if (a.restricted) val += 0.5 * (logdetXX - (logdetH - p_eff * log(s)));
-        cur_delta = delta; cur_scale = s; cur_lml = val;
+        out.ok = true;
+        out.scale = s;
+        out.lml = val;
         if (noise_now)
-            cur_noise = 0.5 * (df * scal[3] / fabs(rss) + fabs(lsum) + fabs((n - (double)r) * log(delta)) + n * fabs(log(s))
+            out.noise = 0.5 * (df * scal[3] / fabs(rss) + fabs(lsum) + fabs((n - (double)r) * log(delta)) + n * fabs(log(s))
                                + df * (LOG2PI + 1.0) + fabs(logdetXX) + fabs(logdetH) + p_eff * fabs(log(s)));
         __syncthreads();
-        return remember(-val);
+        return out;
     };
-
-    // ---- bracket + Brent localmin: the search shared with nullfit.hip (brent_search.h) ---------------------------
-    struct Objective {
-        decltype(f)& fn;
-        const bool& at_clamp;
-        __device__ inline double operator()(double x) { return fn(x); }
-        __device__ inline bool clamped() const { return at_clamp; }
-    } objective{f, last_clamped};
+    OutOfLineObjective<decltype(eval)> f(eval, a.track != 0);
     BrentTrace trace;
     double bf0;
-    const double bx0 = a.track ? brent_search<true>(objective, trace, bf0) : brent_search<false>(objective, trace, bf0);
-    double f_up = NAN, f_dn = NAN;   // (as in nullfit.hip: the objective one stopping tolerance to either side)
-    if (a.track) {
-        const double tolx = 1e-6 * fabs(bx0) + 1e-6;
-        f_up = f(bx0 + tolx);
-        f_dn = f(bx0 - tolx);
-    }
-    want_noise = true;
-    const double f_stop = f(bx0);
-    if (tid == 0) {
-        NullFitTrial t;
-        t.lml = cur_lml;
-        t.delta = cur_delta;
-        t.scale = cur_scale;
-        t.use_g = use_g ? 1 : 0;
-        t.nfev = nfev;
-        t.margin = a.track ? fmin(trace.cmp, trace.sign) : NAN;
-        t.curv = a.track ? 0.5 * (f_up + f_dn) - f_stop : NAN;
-        t.noise = a.track ? cur_noise : NAN;
-        a.trial[(long)b * a.nrho + w] = t;
-    }
+    const double bx0 = a.track ? brent_search<true>(f, trace, bf0) : brent_search<false>(f, trace, bf0);
+    const NullFitTrial t = finish_fit(f, bx0, trace, use_g);
+    if (tid == 0) a.trial[(long)b * a.nrho + w] = t;
 }
 
 }  // namespace

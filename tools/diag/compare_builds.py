@@ -6,6 +6,11 @@ so that the routes the cost models leave to large cohorts are compared too (with
 kinship-structure route is taken wherever a background knows its donors); the counters say whether they were reached.
 Behind the stream come a few cohorts whose kinship term carries the scan's own contexts, Ls = get_L_values(hK, E): the
 stream's mode C hands its Ls over as dense matrices, so nothing in it can reach the pair-product forms.
+Last come the cohorts of tests/pinned_cases.py, which sit on the boundaries between the null-fit kernels that the stream
+never leaves the first of: the whole trial table of crm_test_null_fit_probe(on = 2) -- lml, delta, scale, nfev and use_g
+of every (variant, grid point), and the selected index -- of every null-model cohort, once from the plain scan and once
+from the call that asks for model flags, and what estimate_betas_many returns on the pairs held of every effects cohort.
+These are compared as 64-bit patterns.
 Exit status 0: every array and every counter identical.
     python tools/diag/compare_builds.py <other library> [count 150] [seed 2026] [--forms name=value[,name=value...]]
     python tools/diag/compare_builds.py --child <lib or ''> <count> <seed> <out.npz> <forms or ''>"""
@@ -67,6 +72,7 @@ def child(lib_path, count, seed, out, forms):
         c = make_cohort(donors, cells, k0, variants, seed=300 + k0)
         G = c.G + 0.05 * np.random.default_rng(k0).normal(size=c.G.shape)     # (general genotypes: the dense path)
         scan(CellRegMap(c.y, c.E, W=c.W, Ls=get_L_values(c.hK, c.E)), G, None)
+    pinned = pinned_tables(lib, _engine._context(0))
     ctx, counters = _engine._context(0), {}
     for name in COUNTERS:
         if name not in _lib.SIGNATURES:
@@ -78,7 +84,45 @@ def child(lib_path, count, seed, out, forms):
             _lib.check(getattr(lib, name)(ctx, ctypes.byref(value)))
             counters[name] = value.value
     np.savez(out, notes=np.array(json.dumps({"counters": counters, "forms": applied})),
-             **{k: np.concatenate(v) for k, v in keep.items()})
+             **{k: np.concatenate(v) for k, v in keep.items()}, **pinned)
+
+
+def pinned_tables(lib, ctx):
+    """{"pinned <cohort>, <what>": float64 array} over the cohorts of tests/pinned_cases.py."""
+    import pinned_cases as pc
+
+    import cellregmap_amd as crm
+    from cellregmap_amd import _lib
+
+    out = {}
+    for name in pc.NULL_MODEL:
+        cs = pc.NullModelCase(name)
+        kw = {"A": {}, "B": {"hK": cs.hK}, "C": {"Ls": crm.get_L_values(cs.hK, cs.E)}}[cs.mode]
+        obj = crm.CellRegMap(cs.y, cs.E, W=cs.W, **kw)
+        panel = crm.GenotypePanel(cs.G, groups="auto" if cs.path == "collapsed" else None)
+        for what in ("plain", "model flags"):
+            buf = np.full(cs.G.shape[1] * (5 * len(cs.grid) + 1), np.nan)
+            _lib.check(lib.crm_test_null_fit_probe(ctx, 2, 0.0))
+            try:
+                if what == "plain":
+                    obj.scan_interaction(panel, progress=False)
+                else:
+                    obj.scan_interaction_info(panel)
+                got = lib.crm_test_null_fit_probe_read(ctx, _lib.ptr(buf), buf.size)
+            finally:
+                _lib.check(lib.crm_test_null_fit_probe(ctx, 0, 0.0))
+            assert got == buf.size, (name, what, got, buf.size)
+            out["pinned %s, %s" % (name, what)] = buf
+    for name, pairs in pc.EFFECTS_HELD.items():
+        cs = pc.EffectsCase(name)
+        bg, bgxe, info = crm.estimate_betas_many(cs.Y, cs.W, cs.E0, cs.G, maf=cs.maf, E2=cs.E2, hK=None if cs.E2 is None else cs.hK,
+                                                 pairs=np.asarray(pairs), return_info=True)
+        out["pinned effects %s, beta_g" % name], out["pinned effects %s, beta_gxe" % name] = np.asarray(bg, float), np.asarray(bgxe, float)
+        for key in sorted(info):
+            value = np.asarray(info[key])
+            if value.dtype.kind in "fiu":
+                out["pinned effects %s, %s" % (name, key)] = value.astype(float)
+    return out
 
 
 def main():
@@ -107,6 +151,10 @@ def main():
         same = (a[k] == b[k]) | (np.isnan(a[k]) & np.isnan(b[k]))
         rep[k] = {"identical": int(same.sum()), "different": int((~same).sum()),
                   "worst_rel_difference": float(np.nanmax(np.abs(a[k] - b[k]) / np.maximum(np.abs(a[k]), 1e-300))) if (~same).any() else 0.0}
+    names = sorted(k for k in a.files if k.startswith("pinned "))
+    same = {k: k in b.files and a[k].shape == b[k].shape and np.array_equal(a[k].view(np.uint64), b[k].view(np.uint64)) for k in names}
+    rep["pinned"] = {"tables": len(names), "values": int(sum(a[k].size for k in names)), "identical_tables": int(sum(same.values())),
+                     "different": [k for k in names if not same[k]], "tables_match": names == sorted(k for k in b.files if k.startswith("pinned "))}
     rep["counters"] = {name[len("crm_test_"):]: {"other": na["counters"][name], "this": nb["counters"][name]} for name in COUNTERS}
     rep["counters_identical"] = all(v["other"] is not None and v["other"] == v["this"] for v in rep["counters"].values())
     print(json.dumps(rep, indent=1))
@@ -117,7 +165,8 @@ def main():
         tag += "_" + args.forms.replace("=", "-").replace(",", "_")
     with open(os.path.join(dest, "compare_builds_seed%d_%s.json" % (args.seed, tag)), "w") as fh:
         json.dump(rep, fh, indent=1)
-    return 0 if rep["counters_identical"] and all(rep[k]["different"] == 0 for k in ARRAYS) else 1
+    pinned_ok = names and not rep["pinned"]["different"] and rep["pinned"]["tables_match"]
+    return 0 if rep["counters_identical"] and pinned_ok and all(rep[k]["different"] == 0 for k in ARRAYS) else 1
 
 
 if __name__ == "__main__":

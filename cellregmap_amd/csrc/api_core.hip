@@ -126,6 +126,8 @@ int DevBuf::ensure(size_t need) {
         return CRM_ERR_HIP;
     }
     bytes = need;
+    static std::atomic<unsigned long> allocations{0};
+    serial = ++allocations;
     g_live_bytes += (long)need;
     // Fresh allocations never carry the previous tenant's bytes into a kernel: they are zero-filled (poison mode: 0xFF,
     // above).  The fill runs on the null stream and is waited for here: the contexts' streams are non-blocking and would
@@ -171,6 +173,7 @@ void DevBuf::release() {
     g_live_bytes -= (long)bytes;
     ptr = nullptr;
     bytes = 0;
+    serial = 0;
 }
 
 // Upload a row-major host matrix [rows x cols] (leading dimension ld_src) into a zero-padded
@@ -311,7 +314,7 @@ FormSlot g_forms[] = {{"gram_staged", 0, false}, {"kr_no_tail", 0, false}, {"nul
                       {"pairs_without_kinship_term", 0, false}, {"flat_kappa_milli", 0, false}, {"chase_abort", 0, false}, {"nullfit_one_per_wave", 0, false},
                       {"kin_diag", 0, false}, {"donor_pairs_rotate", 0, false}, {"rho0_positions", 0, false},
                       {"rotation_tails", 0, false}, {"woodbury_ytY", 0, false},
-                      {"wb_block_order", 0, false}};
+                      {"wb_block_order", 0, false}, {"block_fused", 0, false}};
 std::mutex g_forms_mu;
 }  // namespace
 int form(const char* name, int otherwise) {
@@ -357,6 +360,14 @@ int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks) {
     return crm::guarded("crm_test_unrelated_donor_blocks", [&]() -> int {
     if (!ctx || !blocks) return CRM_ERR_ARG;
     *blocks = ctx->unrelated_donor_blocks;
+    return CRM_OK;
+    });
+}
+
+int crm_test_fused_blocks(const crm_ctx* ctx, long* blocks) {
+    return crm::guarded("crm_test_fused_blocks", [&]() -> int {
+    if (!ctx || !blocks) return CRM_ERR_ARG;
+    *blocks = ctx->fused_blocks;
     return CRM_OK;
     });
 }

@@ -427,6 +427,45 @@ __global__ __launch_bounds__(256) void ortho_apply_kernel(const double* __restri
     Gx[i * ldx + b] = v;
 }
 
+// One pass over a block that is read in place in the panel (scan_block.hip: ScanPass::copy_block, the fused form), after
+// ortho_coef_kernel: per element the arithmetic of ortho_apply_kernel and square_block_kernel as they stand -- g as
+// gather_block_kernel would have copied it (zero beyond the cells and the block's variants), gx by the same fma chain,
+// g * g and g * gx -- written to Gx, G2 and GG in cell order and, on the kinship routes, to the donor-order copies of Gx
+// (Gkx) and of the test direction (Gkt, where the pair stage reads it in block order) through the inverse of kin_map (inv:
+// cell -> donor-order row, -1 for the padding cells).  The workgroups behind the cells' rows write the zeros of the
+// donor-order padding rows (pad_rows), so that every row of every output is written by this launch.
+__global__ __launch_bounds__(256) void block_pass_kernel(const double* __restrict__ G, long ldg, long cells, long cells_pad,
+                                                        int variants, const double* __restrict__ W, long ldw, int c,
+                                                        const double* __restrict__ coef, long ld_coef, int cols,
+                                                        double* __restrict__ Gx, double* __restrict__ G2, double* __restrict__ GG,
+                                                        long ld_out, const int* __restrict__ inv, const int* __restrict__ pad_rows,
+                                                        double* __restrict__ Gkx, double* __restrict__ Gkt, int chunks) {
+    long i;
+    int chunk;
+    row_and_chunk(chunks, i, chunk);
+    const int b = chunk * blockDim.x + threadIdx.x;
+    if (b >= cols) return;
+    if (i >= cells_pad) {
+        const long k = pad_rows[i - cells_pad];
+        Gkx[k * ld_out + b] = 0.0;
+        if (Gkt) Gkt[k * ld_out + b] = 0.0;
+        return;
+    }
+    const double g = i < cells && b < variants ? G[i * ldg + b] : 0.0;
+    double v = g;
+    for (int j = 0; j < c; j++) v = fma(-W[i * ldw + j], coef[(long)j * ld_coef + b], v);
+    Gx[i * ld_out + b] = v;
+    G2[i * ld_out + b] = g * g;
+    GG[i * ld_out + b] = g * v;
+    if (inv) {
+        const long k = inv[i];
+        if (k >= 0) {
+            Gkx[k * ld_out + b] = v;
+            if (Gkt) Gkt[k * ld_out + b] = g;
+        }
+    }
+}
+
 // drop[b] = 1 when the variant's own direction falls under the reference's rank rule (gg: |gx|^2 of the block)
 __global__ void ortho_rank_kernel(const double* __restrict__ gg, const double* __restrict__ thr, int variants,
                                   int* __restrict__ drop) {
@@ -461,6 +500,23 @@ int launch_ortho_block(hipStream_t st, const double* G, long ldg, long cells_pad
     const int chunks = (cols + 255) / 256;
     hipLaunchKernelGGL(ortho_apply_kernel, row_chunk_grid(cells_pad, chunks), dim3(256), 0, st, G, ldg, W,
                        ldw, c, coef, ld_coef, cols, Gx, ldx, chunks);
+    CRM_HIP(hipGetLastError());
+    return CRM_OK;
+}
+
+// the fused form of a block's elementwise passes: the projection coefficients, then block_pass_kernel (inv == nullptr: no
+// donor-order outputs; Gkt == nullptr: the donor-order Gx alone)
+int launch_block_pass(hipStream_t st, const double* G, long ldg, long cells, long cells_pad, int variants, int cols,
+                      const double* W, long ldw, int c, const double* proj, const double* gW, long ld_gW, double* coef,
+                      long ld_coef, double* thr, double* Gx, double* G2, double* GG, long ld_out, const int* inv,
+                      const int* pad_rows, long pads, double* Gkx, double* Gkt) {
+    if (cols <= 0) return CRM_OK;
+    hipLaunchKernelGGL(ortho_coef_kernel, dim3((cols + 255) / 256), dim3(256), 0, st, gW, ld_gW, proj, c, variants, cols,
+                       coef, ld_coef, thr);
+    CRM_HIP(hipGetLastError());
+    const int chunks = (cols + 255) / 256;
+    hipLaunchKernelGGL(block_pass_kernel, row_chunk_grid(cells_pad + (inv ? pads : 0), chunks), dim3(256), 0, st, G, ldg, cells,
+                       cells_pad, variants, W, ldw, c, coef, ld_coef, cols, Gx, G2, GG, ld_out, inv, pad_rows, Gkx, Gkt, chunks);
     CRM_HIP(hipGetLastError());
     return CRM_OK;
 }

@@ -27,15 +27,16 @@ constexpr int BLOCK_SLACK_MAX = 4096;  // groups of a donor-constant panel
 struct DevBuf {
     void* ptr = nullptr;
     size_t bytes = 0;
+    unsigned long serial = 0;   // process-unique number of this allocation (0: none): tells a fresh buffer at a recycled address
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    DevBuf(DevBuf&& o) noexcept : ptr(o.ptr), bytes(o.bytes) { o.ptr = nullptr; o.bytes = 0; }
+    DevBuf(DevBuf&& o) noexcept : ptr(o.ptr), bytes(o.bytes), serial(o.serial) { o.ptr = nullptr; o.bytes = 0; o.serial = 0; }
     DevBuf& operator=(DevBuf&& o) noexcept {
         if (this != &o) {
             release();
-            ptr = o.ptr; bytes = o.bytes;
-            o.ptr = nullptr; o.bytes = 0;
+            ptr = o.ptr; bytes = o.bytes; serial = o.serial;
+            o.ptr = nullptr; o.bytes = 0; o.serial = 0;
         }
         return *this;
     }
@@ -117,6 +118,7 @@ struct crm_ctx {
     long donor_pair_blocks = 0;   // blocks whose per-donor sums came from the symmetric pair features (crm_test_donor_pair_blocks)
     long rotation_tail_launches = 0;   // blocks whose rotations sent the last few columns of their spectra through it (crm_test_rotation_tail_launches)
     long rho0_position_blocks = 0;     // blocks whose null fits at rho = 0 read the position basis (crm_test_rho0_position_blocks)
+    long fused_blocks = 0;             // blocks read in place in the panel and prepared by the fused pass (crm_test_fused_blocks)
     long unrelated_donor_blocks = 0;   // blocks served by the unrelated-donor form (crm_test_unrelated_donor_blocks)
     long gram_dma_launches = 0;   // score-statistic Grams that went through a direct-to-LDS kernel (crm_test_gram_dma_launches)
     long tests_without_pair = 0;  // (phenotype, variant) tests whose fit has no kinship term to speak of: no A~ formed for them
@@ -153,12 +155,22 @@ struct crm_ctx {
     crm::DevBuf ws_Tcut;   // rotations: the few small products taken out of the batched launch (cut along the contraction axis)
     crm::DevBuf ws_Gk, ws_S, ws_S2;   // kinship-structure route: the block in donor order, the per-donor sums (ScanPass::folded_S,
                                       // unfolded_AH / fold_TH, unfolded_TH)
+    // what ws_TH was last cleared for (ScanPass::workspaces): its allocation, the background's stamp, the route and the shapes
+    struct ThKey {
+        unsigned long serial = 0, stamp = 0;
+        int route = -1, ks_h = 0;
+        long ldb = 0, th_slab = 0;
+        bool operator==(const ThKey& o) const {
+            return serial == o.serial && stamp == o.stamp && route == o.route && ks_h == o.ks_h && ldb == o.ldb && th_slab == o.th_slab;
+        }
+    } th_key;
+    crm::DevBuf ws_Gkt;               // ... the test direction of a fused block in donor order, alive beside ws_Gk's Gx
     crm::DevBuf ws_WB;                // unrelated-donor form: Phi'gx of the block, Phi'[y, W] and E1'[y, W] of the genes, scratch
     crm::DevBuf ws_Pd;                // ... the per-donor products against the symmetric pair features (ScanPass::folded_S,
                                       // unfolded_AH)
     crm::DevBuf ws_Anone;             // a row of zeros: A~ of the tests whose fit has no kinship term (AssembleArgs::A_none)
     std::vector<crm::DevBuf*> all_bufs() {
-        return {&sync_counters, &ws_xwide, &ws_Tcut, &ws_S, &ws_S2, &ws_Gk, &ws_Pd, &ws_WB, &ws_Anone, &ws_AH, &ws_XG, &ws_TH, &ws_T, &ws_A, &ws_Gb, &ws_Gx, &ws_Gs, &ws_G2, &ws_GG, &ws_Gt, &ws_Z, &ws_small, &ws_probs, &ws_F, &ws_Gext};
+        return {&sync_counters, &ws_xwide, &ws_Tcut, &ws_S, &ws_S2, &ws_Gk, &ws_Gkt, &ws_Pd, &ws_WB, &ws_Anone, &ws_AH, &ws_XG, &ws_TH, &ws_T, &ws_A, &ws_Gb, &ws_Gx, &ws_Gs, &ws_G2, &ws_GG, &ws_Gt, &ws_Z, &ws_small, &ws_probs, &ws_F, &ws_Gext};
     }
 };
 

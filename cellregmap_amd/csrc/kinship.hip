@@ -177,6 +177,7 @@ int crm_background_set_kinship_groups(crm_background* bg, const int* group, long
     crm_ctx* ctx = bg->ctx;
     CRM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
+    bg->kin_gen = next_stamp();   // (what the genes keep of the previous structure is rebuilt: crm_gene::tab_key)
     bg->kin = false;   // (a second announcement that fails must not leave the first one's buffers in use)
     struct Undo {      // ... nor keep its own: whatever it allocated goes back unless it ends with bg->kin set
         crm_background* b;
@@ -184,7 +185,7 @@ int crm_background_set_kinship_groups(crm_background* bg, const int* group, long
             if (b->kin) return;
             b->kin_fold = false;
             b->kin_wb = false;
-            for (DevBuf* x : {&b->kin_map, &b->kin_Y, &b->kin_hKd, &b->wb_U, &b->wb_R, &b->wb_EE}) x->release();
+            for (DevBuf* x : {&b->kin_map, &b->kin_inv, &b->kin_Y, &b->kin_hKd, &b->wb_U, &b->wb_R, &b->wb_EE}) x->release();
             for (int i = 0; i < b->nrho; i++) b->wb_S0[i].release();
             for (int i = 0; i < b->nrho; i++) b->MixK[i].release();
         }
@@ -206,6 +207,14 @@ int crm_background_set_kinship_groups(crm_background* bg, const int* group, long
         const long d = group[i];
         map[bg->kin_row0[d] + fill[d]++] = (int)i;
     }
+    // the inverse of the map and the padding rows, behind one another (the fused block pass scatters by the first and clears
+    // the second)
+    std::vector<int> inv((size_t)bg->n_pad + (size_t)(rows - n), -1);
+    for (long k = 0, pads = 0; k < rows; k++) {
+        if (map[k] >= 0) inv[map[k]] = (int)k;
+        else inv[(size_t)bg->n_pad + pads++] = (int)k;
+    }
+    bg->kin_pads = rows - n;
     bg->kin_rows = rows;
     bg->kin_groups = groups;
     bg->kin_groups_pad = round_up(groups, GEMM_BK);
@@ -219,7 +228,9 @@ int crm_background_set_kinship_groups(crm_background* bg, const int* group, long
     CRM_TRY(bg->kin_hKd.ensure(sizeof(double) * bg->kin_groups_pad * bg->kin_ldh));
     DevBuf dU;
     CRM_TRY(dU.ensure(sizeof(double) * n * k2));
+    CRM_TRY(bg->kin_inv.ensure(sizeof(int) * inv.size()));
     CRM_HIP(hipMemcpyAsync(bg->kin_map.ptr, map.data(), sizeof(int) * rows, hipMemcpyHostToDevice, st));
+    CRM_HIP(hipMemcpyAsync(bg->kin_inv.ptr, inv.data(), sizeof(int) * inv.size(), hipMemcpyHostToDevice, st));
     CRM_HIP(hipMemcpyAsync(dU.ptr, U, sizeof(double) * n * k2, hipMemcpyHostToDevice, st));
     CRM_TRY(upload_padded(st, bg->kin_hKd.as<double>(), bg->kin_ldh, bg->kin_groups_pad, hKd, m, groups, m));
     CRM_TRY(launch_kin_operand(st, dU.as<double>(), k2, bg->H.as<double>(), bg->ldh, k1, bg->kin_map.as<int>(), rows,

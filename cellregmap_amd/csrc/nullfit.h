@@ -106,6 +106,12 @@ size_t variant_stats_workspace(int variants, int c);
 int launch_ortho_block(hipStream_t st, const double* G, long ldg, long cells_pad, int variants, int cols,
                        const double* W, long ldw, int c, const double* proj, const double* gW, long ld_gW,
                        double* coef, long ld_coef, double* thr, double* Gx, long ldx);
+// The same for a block read in place in the panel, in one pass with the products of launch_square_block and the donor-order
+// copies of the kinship routes (blockops.hip: block_pass_kernel); Gx, G2, GG: [cells_pad x ld_out], Gkx, Gkt: donor order
+int launch_block_pass(hipStream_t st, const double* G, long ldg, long cells, long cells_pad, int variants, int cols,
+                      const double* W, long ldw, int c, const double* proj, const double* gW, long ld_gW, double* coef,
+                      long ld_coef, double* thr, double* Gx, double* G2, double* GG, long ld_out, const int* inv,
+                      const int* pad_rows, long pads, double* Gkx, double* Gkt);
 int launch_ortho_rank(hipStream_t st, const double* gg, const double* thr, int variants, int* drop);
 // near[b] = 1 when gg - gW'(W'W)^-1 gW <= tau gg (donor-level sums: the collapsed path's guard)
 int launch_collinear_flag(hipStream_t st, const double* gg, const double* gW, long ld_gW, const double* proj, int c,

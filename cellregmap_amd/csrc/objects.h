@@ -5,6 +5,7 @@
 // for the stream (kernels may still be reading the buffers) and deletes.  A constructor builds into an Owned<> from `new`
 // to `*out = obj.release()`: whatever return leaves it early destroys the half-built object the same way.
 #pragma once
+#include <atomic>
 #include <cmath>
 #include <memory>
 
@@ -12,6 +13,11 @@
 
 namespace crm {
 constexpr long CELL_PAD = 128;  // cell axis padded (zero rows) to a multiple of this
+// process-unique stamps of a background and of its kinship structure (crm_background::kin_gen)
+inline unsigned long next_stamp() {
+    static std::atomic<unsigned long> made{0};
+    return ++made;
+}
 }
 
 // Phenotype-free per-donor tables of the collapsed path.  They depend on the background, on the
@@ -63,6 +69,9 @@ struct crm_background {
     long kin_rows = 0;                          // cells in donor order, every donor's run padded to a multiple of 16 rows
     std::vector<long> kin_row0, kin_len;        // first row / padded length of each donor's run
     crm::DevBuf kin_map;                        // int[kin_rows]: cell of a sorted row, -1 for padding
+    crm::DevBuf kin_inv;                        // int[n_pad + kin_pads]: the sorted row of every cell (-1: a padding cell), then the padding rows
+    long kin_pads = 0;                          // number of padding rows of the donor order (kin_rows - n)
+    unsigned long kin_gen = crm::next_stamp();  // stamp of this background and its kinship structure: new whenever it is announced again
     crm::DevBuf kin_Y;                          // [kin_rows x kin_ldy]: columns 0..k2-1 us, k2..k2+k1-1 E1, donor order
     long kin_ldy = 128;
     crm::DevBuf kin_hKd;                        // [kin_groups_pad x kin_ldh]: hKd, column m ones (when m < kin_ldh), else 0
@@ -127,6 +136,20 @@ struct crm_gene {
     crm::DevBuf wb_yW;
     unsigned long wb_gen = 0;   // crm_background::wb_gen of the tables they were formed from (0: not formed)
     long ld_ep = 0, ld_ye = 0, ld_ee = 0;
+    // The tables above depend on (E0, y, W, background) alone, so they live from call to call: a scan without idx_E whose key
+    // matches reuses what is marked built; a call with idx_E, another kinship generation or other leading dimensions
+    // rebuilds into the same buffers (scan_prepare.hip: ScanPass::keep_tables).  The probes keep what the data says (-1: not
+    // asked yet); which form then runs is decided by the plan and the forms on every call.
+    struct TableKey {
+        unsigned long stamp = 0;   // crm_background::kin_gen (0: nothing kept)
+        int k0 = 0;
+        long ld_ep = 0, ld_ye = 0, ld_ee = 0;
+        bool operator==(const TableKey& o) const {
+            return stamp == o.stamp && k0 == o.k0 && ld_ep == o.ld_ep && ld_ye == o.ld_ye && ld_ee == o.ld_ee;
+        }
+    } tab_key;
+    bool tab_YE = false, tab_E = false, tab_kinEp = false, tab_kinUE = false, tab_kinP = false, tab_kinEE = false;
+    int tab_e1_is_E = -1, tab_us_is_E = -1;
     // donor tables of the collapsed path (valid for one grouped panel and the identity permutation)
     unsigned long e0_key = 0;    // content hash of E0 (key of the background's shared donor tables)
     unsigned long w_key = 0;     // content hash of W (genes of one multi-gene pass must agree on it)

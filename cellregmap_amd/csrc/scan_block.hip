@@ -26,9 +26,41 @@ __global__ void replay_rows_kernel(double* __restrict__ T, long blk, long ldT, c
 // ---- block stages ---------------------------------------------------------------------------------------------------
 // 1. aligned copy of the block (and its row-permuted twin for the test direction); in
 //    collapsed mode the "block" is the donor dosage slab (m_pad rows)
+//
+// The fused form (form("block_fused"), default): a block of a dense panel is not copied.  Its statistics read the panel
+// slab in place and one pass after the projection coefficients (blockops.hip: block_pass_kernel) writes Gx, G2 = Gt o Gt,
+// GG = Gt o Gx and, on the kinship routes, Gx and Gt in donor order -- what ortho_apply, the two donor-order gathers and
+// square_block wrote, from the same instructions.  Gt is then the panel itself, leading dimension panel->ld, and what the
+// copy left as zeros past the block's nb columns are the panel's next variants.  Who reads them:
+//   - the plain products with Gt as the row operand (Z1, the E1 rows) fetch whole 128-column tiles and store rows < nb alone:
+//     any finite value serves, but the tile must stay inside the panel's row -- the block starts at a multiple of 128;
+//   - the Khatri-Rao products with Gt as the row operand (several phenotypes through H on the direct route; the E1 rows of the
+//     folded form without pair features) fetch up to 128 columns past the block's last tile: a block without that many
+//     columns of the panel's row behind it keeps the copy;
+//   - a pair stage over sub-ranges (several phenotypes with more pairs than the pair-ordered buffers hold) offsets Gt by
+//     b0, off the 128-column grid, and relied on the copy's slack columns: such a pass keeps the copy;
+//   - everything else (the pair-order gather, the statistics) reads the block's own columns.
+// The donor-order and cell-order outputs keep their zeros beyond nb: the pass writes them from g = 0 as the copy did.
+bool ScanPass::fused_pass() const {
+    const bool sub_ranges = ng > 1 && P.pair_cap < (long)std::min(nrho, ng) * P.BLK;
+    return form("block_fused", 1) != 0 && !P.collapsed() && !panel->grouped && !idx_G && panel->n_pad == np && !sub_ranges;
+}
+bool ScanPass::fused_block(long col0, int nb) const {
+    const bool kr_reads_Gt = (P.route == Route::direct && ng > 1) || (P.folded() && !P.e1_pairs);
+    return fused_pass() && col0 % 128 == 0 && col0 + round_up(nb, 128) + (kr_reads_Gt ? 128 : 0) <= panel->ld;
+}
+
 int ScanPass::copy_block(Block& B) {
     const long ldb = P.ldb;
     const int nb = B.nb;
+    B.ldt = ldb;
+    if (fused_block(B.col0, nb)) {
+        B.Gb = B.Gt = panel->G.as<double>() + B.col0;
+        B.ldt = panel->ld;
+        B.fused = true;
+        ctx->fused_blocks++;
+        return CRM_OK;
+    }
     B.Gb = B.Gt = B.Gx = ctx->ws_Gb.as<double>();
     if (P.collapsed()) {
         CRM_TRY(launch_gather_block(st, panel->Gd.as<double>() + B.col0, panel->ld, P.mp, panel->m, nullptr, nullptr, nb, B.Gb, ldb, (int)ldb));
@@ -57,9 +89,18 @@ int ScanPass::block_stats(Block& B) {
     const int nb = B.nb, BLK = P.BLK;
     if (!P.collapsed()) {
         B.Gx = ctx->ws_Gx.as<double>();
-        CRM_TRY(launch_variant_stats(st, B.Gb, ldb, np, nb, g0->yW.as<double>(), g0->yW.as<double>() + 1, g0->ld_yw, c, d_part, d_gg, d_gy, d_gW, ld_gW));
-        CRM_TRY(launch_ortho_block(st, B.Gb, ldb, np, nb, (int)ldb, g0->yW.as<double>() + 1, g0->ld_yw, c, g0->Wproj.as<double>(),
-                                   d_gW, ld_gW, d_coef, ldb, d_thr, B.Gx, ldb));
+        CRM_TRY(launch_variant_stats(st, B.Gb, B.ldt, np, nb, g0->yW.as<double>(), g0->yW.as<double>() + 1, g0->ld_yw, c, d_part, d_gg, d_gy, d_gW, ld_gW));
+        if (B.fused) {
+            // (the donor-order test direction where the pair stage reads it in block order: donor_columns)
+            const bool kin_t = P.kin() && (ng > 1 || P.wb_block);
+            CRM_TRY(launch_block_pass(st, B.Gb, B.ldt, n, np, nb, (int)ldb, g0->yW.as<double>() + 1, g0->ld_yw, c,
+                                      g0->Wproj.as<double>(), d_gW, ld_gW, d_coef, ldb, d_thr, B.Gx, ctx->ws_G2.as<double>(),
+                                      ctx->ws_GG.as<double>(), ldb, P.kin() ? bg->kin_inv.as<int>() : nullptr,
+                                      P.kin() ? bg->kin_inv.as<int>() + np : nullptr, P.kin() ? bg->kin_pads : 0,
+                                      P.kin() ? ctx->ws_Gk.as<double>() : nullptr, kin_t ? ctx->ws_Gkt.as<double>() : nullptr));
+        } else
+            CRM_TRY(launch_ortho_block(st, B.Gb, ldb, np, nb, (int)ldb, g0->yW.as<double>() + 1, g0->ld_yw, c, g0->Wproj.as<double>(),
+                                       d_gW, ld_gW, d_coef, ldb, d_thr, B.Gx, ldb));
     }
     for (int gi = 0; gi < ng; gi++) {
         crm_gene* g = genes[gi];
@@ -83,7 +124,7 @@ int ScanPass::fold_TH(const Block& B) {
     const long groups = bg->kin_groups;
     double* Gk = ctx->ws_Gk.as<double>();
     double* TH = ctx->ws_TH.as<double>();
-    CRM_TRY(launch_gather_rows(st, B.Gx, ldb, bg->kin_map.as<int>(), bg->kin_rows, (int)ldb, Gk, ldb));
+    if (!B.fused) CRM_TRY(launch_gather_rows(st, B.Gx, ldb, bg->kin_map.as<int>(), bg->kin_rows, (int)ldb, Gk, ldb));
     std::vector<GemmProblem> kp((size_t)groups + 1);
     GemmProblem p{};
     p.X = bg->kin_Y.as<double>(); p.ldx = bg->kin_ldy; p.Y = Gk; p.ldy = ldb; p.C = TH + (size_t)k1 * ldb; p.ldc = ldb;
@@ -110,7 +151,7 @@ int ScanPass::unfolded_TH(const Block& B) {
     const long groups = bg->kin_groups, mk = bg->kin_cols;
     double* Gk = ctx->ws_Gk.as<double>();
     double* S2 = ctx->ws_S2.as<double>();
-    CRM_TRY(launch_gather_rows(st, B.Gx, ldb, bg->kin_map.as<int>(), bg->kin_rows, (int)ldb, Gk, ldb));
+    if (!B.fused) CRM_TRY(launch_gather_rows(st, B.Gx, ldb, bg->kin_map.as<int>(), bg->kin_rows, (int)ldb, Gk, ldb));
     std::vector<GemmProblem> kp((size_t)groups + k2);
     GemmProblem p{};
     p.X = bg->kin_Y.as<double>(); p.ldx = bg->kin_ldy; p.Y = Gk; p.ldy = ldb; p.C = S2; p.ldc = ldb;

@@ -78,7 +78,7 @@ int ScanPass::select_pairs(const Block& B, const SubRange& R, Pairs& Q) {
         CRM_HIP(hipStreamSynchronize(st));   // (h_posw lives on this scope)
     }
     CRM_HIP(hipMemcpyAsync(d_ord, h_ord.data(), sizeof(int) * Q.npairs, hipMemcpyHostToDevice, st));
-    return launch_gather_block(st, B.Gt + R.b0, P.ldb, P.xrows, P.xrows, nullptr, d_ord, Q.npairs, ctx->ws_Gs.as<double>(),
+    return launch_gather_block(st, B.Gt + R.b0, B.ldt, P.xrows, P.xrows, nullptr, d_ord, Q.npairs, ctx->ws_Gs.as<double>(),
                                P.ldp, (int)P.ldp);
 }
 
@@ -179,11 +179,17 @@ void ScanPass::a_records(const Pairs& Q, bool via_H, const bool* tail_of, AGroup
 int ScanPass::donor_columns(const Block& B, const SubRange& R, const Pairs& Q, DonorCols& D) {
     D.in_pair_order = ng == 1 && !P.wb_block;
     D.G = D.in_pair_order ? ctx->ws_Gs.as<double>() : B.Gt + R.b0;
-    D.ldg = D.in_pair_order ? P.ldp : P.ldb;
+    D.ldg = D.in_pair_order ? P.ldp : B.ldt;
+    D.Gk = ctx->ws_Gk.as<double>();
+    D.ldk = D.in_pair_order ? P.ldp : P.ldb;
     D.ncol = D.in_pair_order ? Q.npairs : R.nb;
+    if (B.fused && !D.in_pair_order) {   // (block_stats' fused pass has written it; a fused block has one sub-range: fused_pass)
+        D.Gk = ctx->ws_Gkt.as<double>();
+        return CRM_OK;
+    }
     const int blk_cols = (int)(P.ldb - R.b0);   // (columns of the block buffers from the sub-range's first one on)
     return launch_gather_rows(st, D.G, D.ldg, bg->kin_map.as<int>(), bg->kin_rows, D.in_pair_order ? (int)D.ldg : blk_cols,
-                              ctx->ws_Gk.as<double>(), D.ldg);
+                              ctx->ws_Gk.as<double>(), D.ldk);
 }
 int ScanPass::gather_pairs(const double* src, long rows, const Pairs& Q) {   // (several phenotypes: the operand in pair order, XG)
     const int xg_cols = (int)std::min<long>(P.ld_xg, round_up((long)Q.npairs * k0, 128) + 128);
@@ -199,12 +205,11 @@ int ScanPass::folded_S(const Block& B, const SubRange& R, const Pairs& Q) {
     DonorCols D;
     CRM_TRY(donor_columns(B, R, Q, D));
     double* S = ctx->ws_S.as<double>();
-    double* Gk = ctx->ws_Gk.as<double>();
     const int k1 = bg->kin_k1, k2 = bg->kin_k2, ncol = D.ncol, npair = P.npair;
     const long groups = bg->kin_groups, ld_ah = P.ld_ah;
     std::vector<GemmProblem> kp((size_t)groups + P.fold_split6);
     GemmProblem p{};
-    p.X = Gk; p.ldx = D.ldg;
+    p.X = D.Gk; p.ldx = D.ldk;
     if (probed.donor_pairs) {   // per donor G_d' (E (x) E)_d, then the rows of S and the E1 rows from it
         p.Y = g0->kinEE.as<double>(); p.ldy = g0->ld_ee; p.C = ctx->ws_Pd.as<double>(); p.ldc = P.ldPd;
         p.M = ncol; p.N = npair;
@@ -286,7 +291,7 @@ int ScanPass::unfolded_AH(const Block& B, const SubRange& R, const Pairs& Q) {
     const int k1 = bg->kin_k1, k2 = bg->kin_k2, ncol = D.ncol, npair = P.npair;
     const long groups = bg->kin_groups, mk = bg->kin_cols, KK = P.KK, ld_ah = P.ld_ah;
     GemmProblem p{};
-    p.X = ctx->ws_Gk.as<double>(); p.ldx = D.ldg;
+    p.X = D.Gk; p.ldx = D.ldk;
     if (probed.pairs_unfolded) {
         // P_d = G_d'(E (x) E)_d per donor; Z = [hKd | 1]' P over the donors (in ws_S: the per-donor blocks are not formed);
         // rows k1 + j m + c of AH from Z_c, rows [0, k1) from the sums over the donors Z_m
@@ -331,7 +336,7 @@ int ScanPass::unfolded_AH(const Block& B, const SubRange& R, const Pairs& Q) {
 // several phenotypes on the direct route through H: AH = H'(g o E0) over all cells, then the pair gather
 int ScanPass::direct_AH(const Block& B, const SubRange& R, const Pairs& Q, AGroups& A) {
     GemmProblem p{};
-    p.X = B.Gt + R.b0; p.ldx = P.ldb; p.E = d_Ep; p.lde = g0->ld_ep; p.k0 = k0; p.Y = bg->H.as<double>(); p.ldy = bg->ldh;
+    p.X = B.Gt + R.b0; p.ldx = B.ldt; p.E = d_Ep; p.lde = g0->ld_ep; p.k0 = k0; p.Y = bg->H.as<double>(); p.ldy = bg->ldh;
     p.C = ctx->ws_AH.as<double>(); p.ldc = P.ld_ah; p.M = R.nb * k0; p.N = (int)bg->cols;
     CRM_TRY(upload(SLOT_ONE, &p, 1));
     CRM_TRY(launch_kr_transposed(ctx, d_probs + SLOT_ONE, 1, p.M, p.N, np, k0));
@@ -430,7 +435,8 @@ int ScanPass::side_contractions(const Block& B, const SubRange& R) {
     double* const Gt = B.Gt + R.b0;
     double* G2 = ctx->ws_G2.as<double>();
     double* GG = !P.collapsed() ? ctx->ws_GG.as<double>() : nullptr;   // (test direction) o (fixed-effect role)
-    CRM_TRY(launch_square_block(st, Gt, B.Gx + R.b0, ldb, ldb, P.xrows, (int)(ldb - R.b0), G2, GG, ldb));
+    // (a fused block: block_stats' pass has written both, from the same products)
+    if (!B.fused) CRM_TRY(launch_square_block(st, Gt, B.Gx + R.b0, ldb, ldb, P.xrows, (int)(ldb - R.b0), G2, GG, ldb));
     if (!GG) GG = G2;
     const int s2 = P.collapsed() ? 1 : P.ks2, s3 = P.collapsed() ? 1 : P.ks3;
     GemmProblem p{};
@@ -457,7 +463,7 @@ int ScanPass::z1_products(const Block& B, const SubRange& R) {
     for (int gi = 0; gi < ng; gi++) {
         crm_gene* g = genes[gi];
         GemmProblem& p = zp[(size_t)gi];
-        p.X = B.Gt + R.b0; p.ldx = P.ldb; p.Y = P.collapsed() ? g->dt_Z1.as<double>() : g->YE.as<double>(); p.ldy = g->ld_ye;
+        p.X = B.Gt + R.b0; p.ldx = B.ldt; p.Y = P.collapsed() ? g->dt_Z1.as<double>() : g->YE.as<double>(); p.ldy = g->ld_ye;
         p.C = dZ1 + (size_t)gi * z1_sz * P.ks1; p.ldc = P.ldZ1; p.M = R.nb; p.N = k0 * (1 + c);
     }
     CRM_TRY(upload(P.z1_slot(), zp.data(), zp.size()));

@@ -101,6 +101,8 @@ struct Block {      // variants [col0, col0 + nb) of the panel, `done` into the 
     double* Gb = nullptr;   // the aligned copy (collapsed path: the group dosage slab)
     double* Gt = nullptr;   // the test direction's role (rows permuted under the genotype hook)
     double* Gx = nullptr;   // the fixed effects' role (orthogonalised against W)
+    long ldt = 0;           // leading dimension of Gb and Gt: the block buffers', or the panel's where the block is read in place
+    bool fused = false;     // read in place; block_stats' fused pass has written G2, GG and the donor-order copies as well
     std::vector<double> flat_obj;   // (info calls) the selected fits' decision margins, [ng][BLK]
 };
 struct SubRange {   // the pair stage's part of a block: its positions [b0, b0 + nb), `done` into the call
@@ -116,7 +118,12 @@ struct AGroups {    // step 6's problems: [0, nz) in probs, their tails, the spl
     size_t a_slab = 0;
     std::vector<GemmProblem> tails, spectrum_tails;
 };
-struct DonorCols { bool in_pair_order; const double* G; long ldg; int ncol; };   // (ScanPass::donor_columns)
+struct DonorCols {  // (ScanPass::donor_columns) the operand columns in cell order (G) and in donor order (Gk)
+    bool in_pair_order;
+    const double* G; long ldg;
+    const double* Gk; long ldk;
+    int ncol;
+};
 
 // One pass: its inputs, plan, workspaces and host scratch, and a member function per stage
 struct ScanPass {
@@ -207,11 +214,14 @@ struct ScanPass {
 
     // ---- scan_prepare.hip -------------------------------------------------------------------------------------------
     int workspaces();
+    bool keep_tables() const { return !idx_E; }
     int context_features(bool shared_too);
     int prepare_contexts();
     int prepare_kinship();
     int prepare_woodbury();
     // ---- scan_block.hip ---------------------------------------------------------------------------------------------
+    bool fused_pass() const;
+    bool fused_block(long col0, int nb) const;
     int copy_block(Block& B);
     int block_stats(Block& B);
     int fold_TH(const Block& B);

@@ -50,7 +50,13 @@ int ScanPass::workspaces() {
     CRM_TRY(ctx->ws_A.ensure(sizeof(double) * (size_t)(P.wb() ? std::max(max_pairs, BLK) : max_pairs) * k0 * P.ldAw));
     CRM_TRY(ctx->ws_Anone.ensure(sizeof(double) * (size_t)P.ldAw));
     CRM_HIP(hipMemsetAsync(ctx->ws_Anone.ptr, 0, sizeof(double) * (size_t)P.ldAw, st));
-    CRM_TRY(ctx->ws_Gb.ensure(sizeof(double) * (size_t)np * ldb));
+    // (the aligned copy: not where every block of the pass is read in place, scan_block.hip: copy_block)
+    bool copies = false, fused = false;
+    for (long done = 0; done < count; done += BLK)
+        (fused_block(first + done, (int)std::min<long>(BLK, count - done)) ? fused : copies) = true;
+    if (copies) CRM_TRY(ctx->ws_Gb.ensure(sizeof(double) * (size_t)np * ldb));
+    if (fused && P.kin() && (ng > 1 || P.wb_block))   // (the fused pass's donor-order test direction, beside ws_Gk's Gx)
+        CRM_TRY(ctx->ws_Gkt.ensure(sizeof(double) * (size_t)bg->kin_rows * ldb));
     CRM_TRY(ctx->ws_Gs.ensure(sizeof(double) * (size_t)np * P.ldp));
     CRM_TRY(ctx->ws_G2.ensure(sizeof(double) * (size_t)np * ldb));
     if (idx_G)   // (unused when the scan ends up on the collapsed path)
@@ -63,7 +69,16 @@ int ScanPass::workspaces() {
     dZ3 = dZ2 + z2_sz * P.ks2;
     if (bg->fast_T) {
         CRM_TRY(ctx->ws_TH.ensure(sizeof(double) * (size_t)P.th_slab * P.ks_h));
-        CRM_HIP(hipMemsetAsync(ctx->ws_TH.ptr, 0, sizeof(double) * (size_t)P.th_slab, st));
+        // The rows of the first slab that no launch of the route writes meet zero rows of the mixing matrices (the padding of
+        // the contraction length; the unrelated-donor form's stage past the last donor) and must be zeros.  Every launch
+        // that writes ws_TH (fold_TH, unfolded_TH, plain_TH) writes the same rows for every block of every call with the same
+        // background, route and shapes, so those rows stay as the clear left them: it runs when the buffer is new and when
+        // any of these changes, not on every call.
+        const crm_ctx::ThKey th_key{ctx->ws_TH.serial, bg->kin_gen, (int)P.route, P.ks_h, P.ldb, P.th_slab};
+        if (!(ctx->th_key == th_key)) {
+            CRM_HIP(hipMemsetAsync(ctx->ws_TH.ptr, 0, sizeof(double) * (size_t)P.th_slab, st));
+            ctx->th_key = th_key;
+        }
     }
     CRM_TRY(ctx->ws_F.ensure(sizeof(double) * (size_t)BLK * k0 * k0));
     CRM_TRY(ctx->ws_Gext.ensure(sizeof(double) * (size_t)BLK * P.KT * P.KT));
@@ -159,6 +174,7 @@ int ScanPass::context_features(bool shared_too) {
     for (int gi = 0; gi < ng; gi++) {
         crm_gene* g = genes[gi];
         const bool both = gi == 0 && shared_too;
+        if (g->tab_YE && (!both || g->tab_E)) continue;   // (kept from an earlier call: prepare_contexts has checked the key)
         CRM_TRY(g->YE.ensure(sizeof(double) * np * g->ld_ye));
         if (both) {
             CRM_TRY(g->Ep.ensure(sizeof(double) * np * g->ld_ep));
@@ -168,6 +184,8 @@ int ScanPass::context_features(bool shared_too) {
                                         g->yW.as<double>() + 1, g->ld_yw, c,
                                         both ? g->Ep.as<double>() : nullptr, g->ld_ep, g->YE.as<double>(),
                                         g->ld_ye, both ? g->EE.as<double>() : nullptr, g->ld_ee));
+        g->tab_YE = keep_tables();
+        if (both) g->tab_E = keep_tables();
     }
     if (shared_too) {
         d_Ep = g0->Ep.as<double>();
@@ -191,6 +209,13 @@ int ScanPass::prepare_contexts() {
         g->ld_ep = round_up(k0, 128);
         g->ld_ye = P.ldZ1;
         g->ld_ee = P.ldZ3;
+        // what the gene keeps of an earlier call holds for this one when no context permutation is in use and the key matches
+        const crm_gene::TableKey key{bg->kin_gen, k0, g->ld_ep, g->ld_ye, g->ld_ee};
+        if (!keep_tables() || !(g->tab_key == key)) {
+            g->tab_YE = g->tab_E = g->tab_kinEp = g->tab_kinUE = g->tab_kinP = g->tab_kinEE = false;
+            g->tab_e1_is_E = g->tab_us_is_E = -1;
+            g->tab_key = keep_tables() ? key : crm_gene::TableKey{};
+        }
     }
     if (!P.collapsed()) return context_features(true);
     const double* Zt = panel->Z.as<double>();
@@ -248,34 +273,51 @@ int ScanPass::prepare_contexts() {
 int ScanPass::prepare_kinship() {
     const long ldh = bg->ldh;
     const double* H = bg->H.as<double>();
-    if (P.kin()) {   // the (permuted) contexts in donor order
+    if (P.kin() && !g0->tab_kinEp) {   // the (permuted) contexts in donor order
         CRM_TRY(g0->kinEp.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ep));
         CRM_TRY(launch_gather_rows(st, d_Ep, g0->ld_ep, bg->kin_map.as<int>(), bg->kin_rows, (int)g0->ld_ep,
                                    g0->kinEp.as<double>(), g0->ld_ep));
+        g0->tab_kinEp = keep_tables();
     }
-    if (P.folded() && bg->kin_k2 == 1) {
+    if (P.folded() && bg->kin_k2 == 1 && !g0->tab_kinUE) {
         // one column of us: S[(k1 + d'), (b, i)] = sum over the cells of donor d' of us(c) g_b(c) E0(c, i) is the plain product
         // G_d'' (us o E0)_d' of the donor's own cells -- its (b, i) layout is the row of S as it stands.  kinUE = us o E0 in
         // donor order.
         CRM_TRY(g0->kinUE.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ep));
         CRM_TRY(launch_scale_rows(st, g0->kinEp.as<double>(), g0->ld_ep, bg->kin_Y.as<double>(), bg->kin_ldy, bg->kin_rows,
                                   (int)g0->ld_ep, g0->kinUE.as<double>(), g0->ld_ep));
+        g0->tab_kinUE = keep_tables();
     }
+    // The probes: what the data says is kept on the gene (a probe ends in a wait for the host); the plan and the forms decide
+    // on every call which of them are asked and what follows from them
     const SameColumns e1_is_E{H, ldh, d_Ep, g0->ld_ep, n};   // E1 = E
     const SameColumns us_is_E{bg->kin_Y.as<double>(), bg->kin_ldy, g0->kinEp.as<double>(), g0->ld_ep, bg->kin_rows};   // E2 = E
-    if (probed.e1_sym) CRM_TRY(same_columns(st, d_near, k0, {e1_is_E}, probed.e1_sym));
-    if (P.e1_pairs && !probed.e1_sym) {
+    auto asked = [&](const SameColumns& pair, int& kept, bool& same) -> int {
+        if (kept < 0) {
+            CRM_TRY(same_columns(st, d_near, k0, {pair}, same));
+            if (keep_tables()) kept = same ? 1 : 0;
+        } else
+            same = kept == 1;
+        return CRM_OK;
+    };
+    if (probed.e1_sym) CRM_TRY(asked(e1_is_E, g0->tab_e1_is_E, probed.e1_sym));
+    if (P.e1_pairs && !probed.e1_sym && !g0->tab_kinP) {
         CRM_TRY(g0->kinP.ensure(sizeof(double) * (size_t)np * P.ldP));
         CRM_TRY(launch_pair_features(st, H, ldh, bg->kin_k1, d_Ep, g0->ld_ep, k0, np, g0->kinP.as<double>(), P.ldP));
+        g0->tab_kinP = keep_tables();
     }
     probed.donor_pairs = probed.donor_pairs && probed.e1_sym;
-    if (probed.donor_pairs) CRM_TRY(same_columns(st, d_near, k0, {us_is_E}, probed.donor_pairs));
-    if (probed.pairs_unfolded) CRM_TRY(same_columns(st, d_near, k0, {e1_is_E, us_is_E}, probed.pairs_unfolded));
+    if (probed.donor_pairs) CRM_TRY(asked(us_is_E, g0->tab_us_is_E, probed.donor_pairs));
+    if (probed.pairs_unfolded) CRM_TRY(asked(e1_is_E, g0->tab_e1_is_E, probed.pairs_unfolded));
+    if (probed.pairs_unfolded) CRM_TRY(asked(us_is_E, g0->tab_us_is_E, probed.pairs_unfolded));
     probed.wb_rotate = probed.wb_rotate && probed.donor_pairs;
     if (probed.donor_pairs || probed.pairs_unfolded) {   // (the folded and the unfolded form respectively)
-        CRM_TRY(g0->kinEE.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ee));
-        CRM_TRY(launch_gather_rows(st, d_EE, g0->ld_ee, bg->kin_map.as<int>(), bg->kin_rows, (int)g0->ld_ee, g0->kinEE.as<double>(),
-                                   g0->ld_ee));
+        if (!g0->tab_kinEE) {
+            CRM_TRY(g0->kinEE.ensure(sizeof(double) * (size_t)bg->kin_rows * g0->ld_ee));
+            CRM_TRY(launch_gather_rows(st, d_EE, g0->ld_ee, bg->kin_map.as<int>(), bg->kin_rows, (int)g0->ld_ee,
+                                       g0->kinEE.as<double>(), g0->ld_ee));
+            g0->tab_kinEE = keep_tables();
+        }
         CRM_TRY(ctx->ws_Pd.ensure(sizeof(double) * (size_t)(probed.donor_pairs ? bg->kin_groups : bg->kin_groups_pad) * P.pd_slab));
     }
     if (probed.donor_pairs)   // (ws_AH, the folded form's scratch, also holds the sliced pair products of the expansion pass)

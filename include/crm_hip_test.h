@@ -34,6 +34,8 @@ extern "C" {
  *                         rotations then runs fewer rounds)
  *   "rotation_tails" 0 / 2   the last r mod 128 <= 16 spectrum columns of the rotations never / wherever eligible through the
  *                         skinny one-pass kernel (default 1: where that saves a round; "kr_no_tail" 1 switches them off too)
+ *   "block_fused" 0       a block of a dense panel goes through the copy and the elementwise launches after it, not read in
+ *                         place and prepared by the fused pass (default 1; crm_test_fused_blocks)
  *   "flat_kappa_milli" v  factor (in thousandths) on the noise bound of CRM_MODEL_FLAT_OPTIMUM / CRM_MODEL_RHO_TIE (study tool)
  * These replace the environment switches of earlier versions; the GPU suite flips every one of them. */
 int crm_test_set_form(const char* name, int value, int reset);
@@ -90,6 +92,11 @@ long crm_test_donor_pair_blocks(const crm_ctx* ctx);
  * (scan_plan.hip: kin_wb; form "kin_diag": 0 never, 1 where the background allows it and the cost model says it pays, 2 wherever
  * the background and the shapes allow it -- k0 + c + 2 + k1 <= 144).  *blocks: the count so far. */
 int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks);
+/* Blocks of this context's interaction scans that were read in place in the panel and prepared by the fused pass (scan_block.hip:
+ * copy_block; blockops.hip: block_pass_kernel) instead of the copy and the elementwise launches after it.  Form "block_fused":
+ * 0 keeps those launches, 1 (default) fuses every block of a dense panel that starts at a multiple of 128 variants; a block
+ * that kept the copy does not count.  *blocks: the count so far. */
+int crm_test_fused_blocks(const crm_ctx* ctx, long* blocks);
 /* Blocks of this context's scans on the unrelated-donor form whose null fits at rho = 0 read the position basis -- Phi'gx,
  * Phi'[y, W] and s_p(0), the assembly's own operands -- so that the rotation MixK(0)'(H'Gx) was not formed (scan_block.hip:
  * plan_rotations; taken where the kept positions are as many as the grid point's rank; form "rho0_positions" = 0: never).

@@ -584,6 +584,15 @@ def _release_gene(lib, handle, _background_kept_alive):
 _PROGRESS_CB = ctypes.CFUNCTYPE(None, ctypes.c_long, ctypes.c_long, ctypes.c_void_p)
 
 
+#: per-test outputs of the association scans' ``effects=True`` (crm_scan_association_effects), in the C-ABI's order
+_EFFECT_KEYS = ("beta", "beta_se", "alt_delta", "alt_scale", "log_pvalue", "effect_status")
+EFFECT_OK, EFFECT_G_IN_SPAN_W, EFFECT_NO_FIT, EFFECT_NON_FINITE = 0, 1, 2, 3   # include/crm_hip.h: CRM_EFFECT_*
+
+
+def _effect_arrays(shape):
+    return {k: np.empty(shape, np.int32 if k == "effect_status" else float) for k in _EFFECT_KEYS}
+
+
 def _stream_chunk():
     """Variants per chunk of the streamed scan of a host matrix (``CellRegMap._scan_streamed``): two blocks of the
     scan's largest block size; CELLREGMAP_AMD_STREAM_CHUNK overrides (0: never stream)."""
@@ -1067,7 +1076,7 @@ class CellRegMap:
                     "rho_tie": (flags & 16) != 0, "statistic_at_tolerance": (flags & 32) != 0, "bound_Q": bq, "bound_p": bp}
 
     # -- association scans (_cellregmap.py:246-314) --------------------------------------------------
-    def _scan_association(self, G, fast, return_stats=False, progress=None):
+    def _scan_association(self, G, fast, return_stats=False, progress=None, effects=False):
         lib = _lib.load()
         p_user = None
         if not isinstance(G, GenotypePanel) and np.asarray(G).ndim == 2 and np.asarray(G).shape[1] == 0:
@@ -1075,6 +1084,18 @@ class CellRegMap:
             p_user = 0
             G = np.zeros((np.asarray(G).shape[0], 1))
         null = np.empty(6)
+
+        def scan(gene, panel, count, pv, alt, eff, j0=0):
+            # one library call over the first ``count`` variants of ``panel`` into the slices starting at ``j0``
+            j1 = j0 + count
+            if eff is None:
+                _lib.check(lib.crm_scan_association(gene, panel.handle, 0, count, int(bool(fast)), _lib.ptr(pv[j0:j1]),
+                                                    _lib.ptr(alt[j0:j1]), _lib.ptr(null)))
+            else:
+                _lib.check(lib.crm_scan_association_effects(gene, panel.handle, 0, count, int(bool(fast)),
+                                                            _lib.ptr(pv[j0:j1]), _lib.ptr(alt[j0:j1]), _lib.ptr(null),
+                                                            *[_lib.ptr(eff[k][j0:j1]) for k in _EFFECT_KEYS]))
+
         if p_user is None and not isinstance(G, GenotypePanel):
             G = np.asarray(G, float)
             if G.ndim == 2 and G.shape[0] == self.n_samples and G.shape[1] >= 2 * _stream_chunk() > 0:
@@ -1082,19 +1103,19 @@ class CellRegMap:
                 # fits the null model again -- the same eleven fits, the same numbers
                 p = G.shape[1]
                 pv, alt = np.empty(p), np.empty(p)
+                eff = _effect_arrays((p,)) if effects else None
                 progress, bar = self._one_bar(progress, p)
                 panels = self._streamed_panels(G)
                 try:
                     gene = self._bind_gene()
                     for j0, j1, panel in panels:
                         with _progress(self._device, progress, j1 - j0, offset=j0, grand_total=p):
-                            _lib.check(lib.crm_scan_association(gene, panel.handle, 0, j1 - j0, int(bool(fast)),
-                                                                _lib.ptr(pv[j0:j1]), _lib.ptr(alt[j0:j1]), _lib.ptr(null)))
+                            scan(gene, panel, j1 - j0, pv, alt, eff, j0)
                 finally:
                     panels.close()
                     if bar is not None:
                         bar.close()
-                return self._association_result(pv, alt, null, return_stats)
+                return self._association_result(pv, alt, null, return_stats, eff)
         panel = self._panel(G)
         n, p = panel.shape
         if p_user is not None:
@@ -1102,28 +1123,38 @@ class CellRegMap:
         gene = self._bind_gene()
         pv = np.empty(p)
         alt = np.empty(p)
+        eff = _effect_arrays((p,)) if effects else None
         with _progress(self._device, progress, p):
-            _lib.check(lib.crm_scan_association(gene, panel.handle, 0, p, int(bool(fast)), _lib.ptr(pv),
-                                                _lib.ptr(alt), _lib.ptr(null)))
-        return self._association_result(pv, alt, null, return_stats)
+            scan(gene, panel, p, pv, alt, eff)
+        return self._association_result(pv, alt, null, return_stats, eff)
 
     @staticmethod
-    def _association_result(pv, alt, null, return_stats):
+    def _association_result(pv, alt, null, return_stats, eff=None):
         info = {"rho1": np.asarray([null[0]], float), "e2": np.asarray([null[1]], float),
                 "g2": np.asarray([null[2]], float), "eps2": np.asarray([null[3]], float)}
-        if return_stats:
-            return pv, info, {"alt_lml": alt, "null_lml": null[4], "null_delta": null[5]}
+        if return_stats or eff is not None:
+            stats = {"alt_lml": alt, "null_lml": null[4], "null_delta": null[5]}
+            if eff is not None:
+                stats.update(eff)
+            return pv, info, stats
         return pv, info
 
-    def scan_association(self, G, return_stats: bool = False, progress=None):
+    def scan_association(self, G, return_stats: bool = False, progress=None, effects: bool = False):
         """Persistent-effect LRT with a full ML refit per SNP (_cellregmap.py:246-281; ``progress`` as in
-        ``scan_interaction`` -- the reference shows a tqdm bar over the SNPs, :270)."""
-        return self._scan_association(G, False, return_stats, progress)
+        ``scan_interaction`` -- the reference shows a tqdm bar over the SNPs, :270).
 
-    def scan_association_fast(self, G, return_stats: bool = False, progress=False):
+        ``effects=True`` (an extension) returns ``(pv, info, stats)`` with, beside the keys of
+        ``return_stats``, per variant ``beta`` (the coefficient of g in the alternative model y ~ [W, g]), ``beta_se``,
+        ``alt_delta`` and ``alt_scale`` (the alternative fit's variance ratio and ML scale), ``log_pvalue`` (natural log,
+        unclipped) and ``effect_status`` (``EFFECT_OK`` / ``EFFECT_G_IN_SPAN_W`` / ``EFFECT_NO_FIT`` /
+        ``EFFECT_NON_FINITE``); ``pv`` is bit for bit the plain call's."""
+        return self._scan_association(G, False, return_stats, progress, effects)
+
+    def scan_association_fast(self, G, return_stats: bool = False, progress=False, effects: bool = False):
         """Persistent-effect LRT with the covariance ratio frozen at the null model
-        (glimix-core FastScanner; _cellregmap.py:284-314 -- run with ``verbose=False`` there: no bar by default)."""
-        return self._scan_association(G, True, return_stats, progress)
+        (glimix-core FastScanner; _cellregmap.py:284-314 -- run with ``verbose=False`` there: no bar by default).
+        ``effects`` as in ``scan_association``; ``alt_delta`` is then the null model's delta."""
+        return self._scan_association(G, True, return_stats, progress, effects)
 
     # -- effect sizes (_cellregmap.py:137-244) -----------------------------------------------------
     def _lmm_fit(self, bg, M):
@@ -1428,8 +1459,16 @@ def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=Fals
     ``pvalues`` of shape (len(crms), p), row i equal to ``crms[i].scan_association(_fast)(G)``; ``info`` holds ``rho1``,
     ``e2``, ``g2``, ``eps2`` as (len(crms),) arrays.  ``cis_index`` as in ``scan_interaction_many``: ``pvalues`` is then a
     list whose entry i follows the columns of ``cis_index[i]`` (repeats included).  ``return_stats`` adds ``alt_lml`` (the
-    shape of ``pvalues``), ``null_lml`` and ``null_delta`` (len(crms),) to ``info``.  ``progress``: ``True`` for a tqdm
+    shape of ``pvalues``), ``null_lml`` and ``null_delta`` (len(crms),) to ``info``.  ``return_stats="effects"`` adds to
+    these the effect sizes of every test (``effects=True`` of ``CellRegMap.scan_association``; this function's parameter
+    list is part of its contract, so the request travels in ``return_stats``; ``run_association_many`` has the keyword):
+    ``beta``, ``beta_se``, ``alt_delta``, ``alt_scale``, ``log_pvalue`` and ``effect_status`` in the shape of
+    ``pvalues``; the p-values are bit for bit the plain call's.  ``progress``: ``True`` for a tqdm
     bar, or a callable ``(done, total)`` counted in variants of the panel that at least one phenotype tests."""
+    effects = isinstance(return_stats, str) and return_stats == "effects"
+    if isinstance(return_stats, str) and not effects:
+        raise ValueError(f"return_stats={return_stats!r}: False, True or 'effects'")
+    return_stats = bool(return_stats)
     lib = _lib.load()
     crms = list(crms)
     if not crms:
@@ -1459,12 +1498,17 @@ def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=Fals
         info["null_delta"] = null[:, 5].copy()
     fast = int(bool(fast))
 
-    def scan(idx, a, count, pv, alt, offset, total):
+    def scan(idx, a, count, pv, alt, offset, total, eff=None):
         hs = (ctypes.c_void_p * len(idx))(*[genes[i].value for i in idx])
         rows = np.ascontiguousarray(null[idx])
         with _progress(first._device, progress, count, offset=offset, grand_total=total):
-            _lib.check(lib.crm_scan_association_multi(hs, len(idx), panel.handle, a, count, fast, _lib.ptr(rows),
-                                                      _lib.ptr(pv), _lib.ptr(alt)))
+            if eff is None:
+                _lib.check(lib.crm_scan_association_multi(hs, len(idx), panel.handle, a, count, fast, _lib.ptr(rows),
+                                                          _lib.ptr(pv), _lib.ptr(alt)))
+            else:
+                _lib.check(lib.crm_scan_association_multi_effects(hs, len(idx), panel.handle, a, count, fast,
+                                                                  _lib.ptr(rows), _lib.ptr(pv), _lib.ptr(alt),
+                                                                  *[_lib.ptr(eff[k]) for k in _EFFECT_KEYS]))
 
     if cis_index is None:
         columns, runs = None, ([(0, p, np.arange(ng))] if p else [])
@@ -1484,41 +1528,57 @@ def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=Fals
     try:
         if columns is None:
             pv, alt = np.empty((ng, p)), np.empty((ng, p))
+            eff = _effect_arrays((ng, p)) if effects else None
             if p:
-                scan(np.arange(ng), 0, p, pv, alt, 0, p)
+                scan(np.arange(ng), 0, p, pv, alt, 0, p, eff)
             if return_stats:
                 info["alt_lml"] = alt
+            if effects:
+                info.update(eff)
             return pv, info
         full_pv = [np.full(p, np.nan) if columns[i].size else None for i in range(ng)]
         full_alt = [np.full(p, np.nan) if columns[i].size else None for i in range(ng)]
+        full_eff = None
+        if effects:   # (untested positions: NaN, status -1 -- never selected, ``columns`` only names tested ones)
+            full_eff = {k: [np.full(p, -1 if k == "effect_status" else np.nan, np.int32 if k == "effect_status" else float)
+                            if columns[i].size else None for i in range(ng)] for k in _EFFECT_KEYS}
         seen = 0
         for a, count, active in runs:
             pv, alt = np.empty((len(active), count)), np.empty((len(active), count))
-            scan(active, a, count, pv, alt, seen, tested)
+            eff = _effect_arrays((len(active), count)) if effects else None
+            scan(active, a, count, pv, alt, seen, tested, eff)
             seen += count
             for row, i in enumerate(active):
                 full_pv[i][a:a + count] = pv[row]
                 full_alt[i][a:a + count] = alt[row]
+                if effects:
+                    for k in _EFFECT_KEYS:
+                        full_eff[k][i][a:a + count] = eff[k][row]
         pvs = [full_pv[i][columns[i]] if columns[i].size else np.empty(0) for i in range(ng)]
         if return_stats:
             info["alt_lml"] = [full_alt[i][columns[i]] if columns[i].size else np.empty(0) for i in range(ng)]
+        if effects:
+            for k in _EFFECT_KEYS:
+                info[k] = [full_eff[k][i][columns[i]] if columns[i].size
+                           else np.empty(0, np.int32 if k == "effect_status" else float) for i in range(ng)]
         return pvs, info
     finally:
         if bar is not None:
             bar.close()
 
 
-def run_association_many(Y, W, E, G, hK=None, *, cis_index=None, fast=False, device=0):
+def run_association_many(Y, W, E, G, hK=None, *, cis_index=None, fast=False, device=0, effects=False):
     """``run_association`` (``run_association_fast`` with ``fast=True``) for the columns of ``Y`` (n x genes) with one
     background decomposition, one genotype upload and shared per-variant work.  Keeps the reference's positional
     binding (_cellregmap.py:498, :529): ``W`` goes to the contexts slot, ``E`` to the fixed effects.  Returns
-    ``(pvalues, info)`` as ``scan_association_many``."""
+    ``(pvalues, info)`` as ``scan_association_many``; ``effects=True``: as its ``return_stats="effects"`` (beta is the
+    coefficient of g beside the columns of ``E``)."""
     Y = np.asarray(Y, float)
     if Y.ndim != 2:
         raise ValueError("Y must be n x genes")
     first = CellRegMap(Y[:, 0], W, E, hK=hK, device=device)
     crms = [first] + [CellRegMap(Y[:, i], W, E, hK=hK, device=device, background=first._bg) for i in range(1, Y.shape[1])]
-    return scan_association_many(crms, G, cis_index=cis_index, fast=fast)
+    return scan_association_many(crms, G, cis_index=cis_index, fast=fast, return_stats="effects" if effects else False)
 
 
 def scan_interaction_resumable(crm, G, checkpoint, idx_E=None, idx_G=None, chunk=8192, scan=None):
@@ -1637,17 +1697,24 @@ def run_interaction(y, E, G, W=None, E1=None, E2=None, hK=None, idx_G=None, *, d
     return pv
 
 
-def run_association(y, W, E, G, hK=None, *, device=0):
+def run_association(y, W, E, G, hK=None, *, device=0, effects=False):
     """Association test (_cellregmap.py:471-500).  The reference's positional constructor call
-    (:498) binds ``W`` to the contexts slot and ``E`` to the covariates slot; kept as is."""
+    (:498) binds ``W`` to the contexts slot and ``E`` to the covariates slot; kept as is.
+    ``effects=True``: ``(pv, info, stats)`` of ``CellRegMap.scan_association(G, effects=True)`` -- with that binding beta
+    is the coefficient of g beside the columns of ``E``."""
     crm = CellRegMap(y, W, E, hK=hK, device=device)
+    if effects:
+        return crm.scan_association(G, effects=True)
     pv = crm.scan_association(G)
     return pv
 
 
-def run_association_fast(y, W, E, G, hK=None, *, device=0):
-    """Fast association test (_cellregmap.py:502-531); same positional binding (:529)."""
+def run_association_fast(y, W, E, G, hK=None, *, device=0, effects=False):
+    """Fast association test (_cellregmap.py:502-531); same positional binding (:529).  ``effects`` as in
+    ``run_association``."""
     crm = CellRegMap(y, W, E, hK=hK, device=device)
+    if effects:
+        return crm.scan_association_fast(G, effects=True)
     pv = crm.scan_association_fast(G)
     return pv
 

@@ -70,6 +70,9 @@ SIGNATURES = {
     "crm_association_null_multi": (ctypes.c_int, [vp, ctypes.c_int, vp]),
     "crm_scan_association_multi": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, vp, vp,
                                                   vp]),
+    "crm_scan_association_effects": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int] + [vp] * 9),
+    "crm_scan_association_multi_effects": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int]
+                                           + [vp] * 9),
     "crm_lmm_fit": (ctypes.c_int, [vp, ctypes.c_int, vp, vp]),
     "crm_cov_solve": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp, ctypes.c_int, vp]),
     "crm_effects_multi": (ctypes.c_int, [vp, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -118,6 +121,7 @@ SIGNATURES = {
     "crm_test_davies": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
     "crm_test_davies_trace": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "crm_test_tail_pvalue": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
+    "crm_test_lrt_logp": (ctypes.c_int, [vp, ctypes.c_int, vp, vp]),
 }
 
 _lib = None

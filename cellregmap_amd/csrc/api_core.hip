@@ -693,4 +693,19 @@ int crm_test_tail_pvalue(crm_ctx* c, int count, int k, const double* Q, const do
     });
 }
 
+int crm_test_lrt_logp(crm_ctx* c, int count, const double* lrs, double* logp) {
+    return crm::guarded_on("crm_test_lrt_logp", c, [&]() -> int {
+    if (!c || count <= 0 || !lrs || !logp) return CRM_ERR_ARG;
+    CRM_HIP(hipSetDevice(c->device));
+    DevBuf bX, bG;
+    CRM_TRY(bX.ensure(sizeof(double) * count));
+    CRM_TRY(bG.ensure(sizeof(double) * count));
+    CRM_HIP(hipMemcpyAsync(bX.ptr, lrs, sizeof(double) * count, hipMemcpyHostToDevice, c->stream));
+    CRM_TRY(launch_lrt_logp(c->stream, bX.as<double>(), count, bG.as<double>()));
+    CRM_HIP(hipMemcpyAsync(logp, bG.ptr, sizeof(double) * count, hipMemcpyDeviceToHost, c->stream));
+    CRM_HIP(hipStreamSynchronize(c->stream));
+    return CRM_OK;
+    });
+}
+
 }  // extern "C"

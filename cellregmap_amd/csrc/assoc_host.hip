@@ -1,4 +1,4 @@
-// Host orchestration of the association scans (C-ABI crm_scan_association).
+// Host orchestration of the association scans (C-ABI crm_scan_association, crm_scan_association_effects).
 // Reference: cellregmap/_cellregmap.py:246-314 and :443-469.
 #include <algorithm>
 
@@ -7,9 +7,12 @@
 
 using namespace crm;
 
-extern "C" int crm_scan_association(crm_gene* gene, crm_panel* panel, long first, long count, int fast,
-                                    double* out_pvalue, double* out_alt_lml, double* out_null) {
-    return crm::guarded_on("crm_scan_association", gene ? gene->ctx : nullptr, [&]() -> int {
+namespace {
+
+// The scan behind crm_scan_association (eff null: its launches and nothing else) and crm_scan_association_effects (one
+// more launch per block, after the alt fits: assoc_effects.hip).
+int scan_association(crm_gene* gene, crm_panel* panel, long first, long count, int fast, double* out_pvalue,
+                     double* out_alt_lml, double* out_null, const AssocEffectsOut* eff) {
     if (!gene || !panel) return CRM_ERR_ARG;
     crm_background* bg = gene->bg;
     crm_ctx* ctx = bg->ctx;
@@ -49,6 +52,8 @@ extern "C" int crm_scan_association(crm_gene* gene, crm_panel* panel, long first
                  o_part = carve(variant_stats_workspace(BLK, std::min(c, CRM_MAX_COV))),
                  o_coef = carve(sizeof(double) * (size_t)c * ldb), o_thr = carve(sizeof(double) * BLK),
                  o_drop = carve(sizeof(int) * BLK);
+    const size_t o_eff = eff ? carve(sizeof(double) * 5 * BLK + sizeof(int) * BLK) : 0,
+                 o_effg = eff ? carve(sizeof(AssocEffectsGene)) : 0;
     CRM_TRY(ctx->ws_small.ensure(off));
     char* sm = ctx->ws_small.as<char>();
     double* d_gg = (double*)(sm + o_gg);
@@ -122,6 +127,19 @@ extern "C" int crm_scan_association(crm_gene* gene, crm_panel* panel, long first
     aa.r = bg->r[ri]; aa.c = c; aa.n = n; aa.delta0 = null.delta;
     aa.WW = fa.WW; aa.Wy = fa.Wy; aa.yy = fa.yy; aa.gg = d_gg; aa.gy = d_gy; aa.gW = d_gW; aa.ld_gW = ld_gW;
     if (fast) CRM_TRY(launch_fastscan_prep(st, aa, d_prep, d_wts));
+    AssocEffectsGene eg{};   // (host source of an asynchronous copy: alive until the first block's sync)
+    double* d_eff = eff ? (double*)(sm + o_eff) : nullptr;
+    if (eff) {
+        eg.T = aa.T; eg.t_sb = ldT; eg.t_sk = 1;
+        eg.ty = aa.ty; eg.tW = aa.tW; eg.S0 = aa.S0; eg.ldW = aa.ldW; eg.r = aa.r; eg.c = c; eg.n = n;
+        eg.WW = aa.WW; eg.Wy = aa.Wy; eg.yy = aa.yy;
+        eg.gg = d_gg; eg.gy = d_gy; eg.gW = d_gW; eg.gW_sb = ld_gW; eg.gW_su = 1;
+        eg.prep = d_prep; eg.wts = d_wts; eg.delta0 = null.delta;
+        eg.trial = d_trial; eg.alt_lml = d_lml; eg.null_lml = null.lml;
+        eg.out_beta = d_eff; eg.out_se = d_eff + BLK; eg.out_delta = d_eff + 2 * BLK; eg.out_scale = d_eff + 3 * BLK;
+        eg.out_logp = d_eff + 4 * BLK; eg.out_status = (int*)(d_eff + 5 * BLK);
+        CRM_HIP(hipMemcpyAsync(sm + o_effg, &eg, sizeof eg, hipMemcpyHostToDevice, st));
+    }
 
     for (long done = 0; done < count; done += BLK) {
         const int nb = (int)std::min<long>(BLK, count - done);
@@ -158,9 +176,37 @@ extern "C" int crm_scan_association(crm_gene* gene, crm_panel* panel, long first
         CRM_TRY(launch_lrt(st, d_lml, null.lml, nb, d_pv));
         if (out_pvalue) CRM_HIP(hipMemcpyAsync(out_pvalue + done, d_pv, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
         if (out_alt_lml) CRM_HIP(hipMemcpyAsync(out_alt_lml + done, d_lml, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+        if (eff) {
+            // T(rho*), the block's plain products and the alt fits are still in place
+            CRM_TRY(launch_assoc_effects(st, (const AssocEffectsGene*)(sm + o_effg), 1, nb, c, fast != 0));
+            double* const outs[5] = {eff->beta, eff->se, eff->delta, eff->scale, eff->logp};
+            for (int q = 0; q < 5; q++)
+                if (outs[q])
+                    CRM_HIP(hipMemcpyAsync(outs[q] + done, d_eff + (size_t)q * BLK, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
+            if (eff->status)
+                CRM_HIP(hipMemcpyAsync(eff->status + done, d_eff + (size_t)5 * BLK, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
+        }
         CRM_HIP(hipStreamSynchronize(st));
         ctx->report(done + nb, count);   // (the reference's tqdm, :270)
     }
     return CRM_OK;
+}
+
+}  // namespace
+
+extern "C" int crm_scan_association(crm_gene* gene, crm_panel* panel, long first, long count, int fast,
+                                    double* out_pvalue, double* out_alt_lml, double* out_null) {
+    return crm::guarded_on("crm_scan_association", gene ? gene->ctx : nullptr, [&]() -> int {
+    return scan_association(gene, panel, first, count, fast, out_pvalue, out_alt_lml, out_null, nullptr);
+    });
+}
+
+extern "C" int crm_scan_association_effects(crm_gene* gene, crm_panel* panel, long first, long count, int fast,
+                                            double* out_pvalue, double* out_alt_lml, double* out_null, double* out_beta,
+                                            double* out_se, double* out_delta, double* out_scale, double* out_logp,
+                                            int* out_status) {
+    return crm::guarded_on("crm_scan_association_effects", gene ? gene->ctx : nullptr, [&]() -> int {
+    const AssocEffectsOut eff{out_beta, out_se, out_delta, out_scale, out_logp, out_status};
+    return scan_association(gene, panel, first, count, fast, out_pvalue, out_alt_lml, out_null, &eff);
     });
 }

@@ -18,6 +18,8 @@
 // fastscan_kernel / lrt_kernel (assoc.hip).
 // Full refit: the block is orthogonalised against the shared W once; per gene the null-fit kernels run over the block on
 // the shared T(rho*) with that gene's y quantities.
+// crm_scan_association_multi_effects: the same launches, then the effect sizes of every (gene, variant) from the T(rho*)
+// still in place (assoc_effects.hip).
 #include <algorithm>
 
 #include "delta_search.h"
@@ -266,9 +268,13 @@ extern "C" int crm_association_null_multi(crm_gene* const* genes, int ngenes, do
     });
 }
 
-extern "C" int crm_scan_association_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
-                                          int fast, const double* null, double* out_pvalue, double* out_alt_lml) {
-    return crm::guarded_on("crm_scan_association_multi", (genes && ngenes > 0 && genes[0]) ? genes[0]->ctx : nullptr, [&]() -> int {
+namespace {
+
+// The scan behind crm_scan_association_multi (eff null: its launches and nothing else) and
+// crm_scan_association_multi_effects (assoc_effects.hip: fast, one more launch per block over every (variant, gene); full
+// refit, one per gene after its alt fits, whose trial records the next gene overwrites).
+int scan_association_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count, int fast,
+                           const double* null, double* out_pvalue, double* out_alt_lml, const AssocEffectsOut* eff) {
     CRM_TRY(check_genes(genes, ngenes, "association multi"));
     if (!panel || !null) {
         set_error("association multi: %s is NULL", panel ? "null" : "panel");
@@ -401,6 +407,9 @@ extern "C" int crm_scan_association_multi(crm_gene* const* genes, int ngenes, cr
                  o_trial = !fast ? carve(sizeof(NullFitTrial) * BLK) : 0, o_fit = !fast ? carve(sizeof(NullFitOut) * BLK) : 0,
                  o_coef = !fast ? carve(sizeof(double) * (size_t)c * ldb) : 0, o_thr = !fast ? carve(sizeof(double) * BLK) : 0,
                  o_drop = !fast ? carve(sizeof(int) * BLK) : 0, o_src = carve(sizeof(ColumnSource) * srcs.size());
+    const size_t eff_rows = (size_t)ngenes * BLK;   // per output: [ngenes x BLK], five of doubles, then the status
+    const size_t o_eff = eff ? carve((sizeof(double) * 5 + sizeof(int)) * eff_rows) : 0,
+                 o_effg = eff ? carve(sizeof(AssocEffectsGene) * ngenes) : 0;
     CRM_TRY(ctx->ws_small.ensure(off));
     char* sm = ctx->ws_small.as<char>();
     double* d_cy = (double*)(sm + o_cy);
@@ -472,6 +481,47 @@ extern "C" int crm_scan_association_multi(crm_gene* const* genes, int ngenes, cr
             CRM_TRY(ctx->ws_xwide.ensure(sizeof(double) * nullfit_xwide_scratch_doubles(BLK, nrho, c)));
             alt.xwide = ctx->ws_xwide.as<double>();
         }
+    }
+
+    // the per-gene records of the effects launch; fast: in the order of the rho groups, so that the tests that read one
+    // row of T are neighbours in the grid (record q writes the rows of gene eff_gene[q])
+    std::vector<AssocEffectsGene> eg(eff ? ngenes : 0);   // (host source of an asynchronous copy)
+    double* d_eff = eff ? (double*)(sm + o_eff) : nullptr;
+    const AssocEffectsGene* d_effg = eff ? (const AssocEffectsGene*)(sm + o_effg) : nullptr;
+    if (eff) {
+        std::vector<int> eff_gene(ngenes);
+        for (int i = 0; i < ngenes; i++) eff_gene[i] = i;
+        if (fast) std::stable_sort(eff_gene.begin(), eff_gene.end(), [&](int x, int y) { return grp_of_rho[ri[x]] < grp_of_rho[ri[y]]; });
+        for (int q = 0; q < ngenes; q++) {
+            const int i = eff_gene[q], k = ri[i];
+            crm_gene* g = genes[i];
+            AssocEffectsGene& E = eg[q];
+            E.T = Tb + (size_t)grp_of_rho[k] * tslab;
+            E.t_sb = fast ? 1 : ldq; E.t_sk = fast ? ldt : 1;
+            E.ty = g->rot.as<double>() + (long)k * slab;
+            E.tW = E.ty + ldq; E.ldW = ldq; E.S0 = bg->S0[k].as<double>();
+            E.r = bg->r[k]; E.c = c; E.n = n;
+            E.WW = g->WW.as<double>(); E.Wy = g->Wy.as<double>(); E.yy = g->yy;
+            E.gg = d_gg;
+            if (fast) {
+                E.gy = d_cy + (size_t)(yoff + i) * ldcy;
+                E.gW = d_cy; E.gW_sb = 1; E.gW_su = ldcy;
+                E.prep = (const double*)(sm + o_prep) + (size_t)i * prep_d;
+                E.wts = (const double*)(sm + o_wts) + (size_t)i * ldq;
+                E.delta0 = null[6 * (size_t)i + 5];
+            } else {
+                E.gy = d_cy + (size_t)i * ldcy;
+                E.gW = d_gW; E.gW_sb = ld_gW; E.gW_su = 1;
+                E.trial = alt.trial;
+            }
+            E.alt_lml = d_alt + (size_t)i * BLK;
+            E.null_lml = null_lml[i];
+            double* o = d_eff + (size_t)i * BLK;
+            E.out_beta = o; E.out_se = o + eff_rows; E.out_delta = o + 2 * eff_rows; E.out_scale = o + 3 * eff_rows;
+            E.out_logp = o + 4 * eff_rows;
+            E.out_status = (int*)(d_eff + 5 * eff_rows) + (size_t)i * BLK;
+        }
+        CRM_HIP(hipMemcpyAsync(sm + o_effg, eg.data(), sizeof(AssocEffectsGene) * ngenes, hipMemcpyHostToDevice, st));
     }
 
     std::vector<GemmProblem> probs, pp;
@@ -562,6 +612,7 @@ extern "C" int crm_scan_association_multi(crm_gene* const* genes, int ngenes, cr
                 hipLaunchKernelGGL(multi_finish_kernel<0>, grid, dim3(128), 0, st, (const MultiGene*)(sm + o_mg), d_grp, c, n, nb,
                                    C1, ld1, C2, ld2, d_gg, d_cy, ldcy, d_alt, d_pv, (long)BLK);
             CRM_HIP(hipGetLastError());
+            if (eff) CRM_TRY(launch_assoc_effects(st, d_effg, ngenes, nb, c, true));
         } else {
             for (int i = 0; i < ngenes; i++) {
                 crm_gene* g = genes[i];
@@ -576,6 +627,7 @@ extern "C" int crm_scan_association_multi(crm_gene* const* genes, int ngenes, cr
                 alt.gy = d_cy + (size_t)i * ldcy;
                 CRM_TRY(launch_nullfit(st, alt, nb));
                 CRM_TRY(launch_gather_trial_lml(st, alt.trial, nb, d_alt + (size_t)i * BLK));
+                if (eff) CRM_TRY(launch_assoc_effects(st, d_effg + i, 1, nb, c, false));
             }
             hipLaunchKernelGGL(multi_lrt_kernel, dim3((nb + 255) / 256, ngenes), dim3(256), 0, st, d_alt, d_nl, nb, (long)BLK,
                                d_pv);
@@ -587,9 +639,37 @@ extern "C" int crm_scan_association_multi(crm_gene* const* genes, int ngenes, cr
         if (out_alt_lml)
             CRM_HIP(hipMemcpy2DAsync(out_alt_lml + done, sizeof(double) * count, d_alt, sizeof(double) * BLK,
                                      sizeof(double) * nb, ngenes, hipMemcpyDeviceToHost, st));
+        if (eff) {
+            double* const outs[5] = {eff->beta, eff->se, eff->delta, eff->scale, eff->logp};
+            for (int q = 0; q < 5; q++)
+                if (outs[q])
+                    CRM_HIP(hipMemcpy2DAsync(outs[q] + done, sizeof(double) * count, d_eff + q * eff_rows, sizeof(double) * BLK,
+                                             sizeof(double) * nb, ngenes, hipMemcpyDeviceToHost, st));
+            if (eff->status)
+                CRM_HIP(hipMemcpy2DAsync(eff->status + done, sizeof(int) * count, (const int*)(d_eff + 5 * eff_rows),
+                                         sizeof(int) * BLK, sizeof(int) * nb, ngenes, hipMemcpyDeviceToHost, st));
+        }
         CRM_HIP(hipStreamSynchronize(st));
         ctx->report(done + nb, count);
     }
     return CRM_OK;
+}
+
+}  // namespace
+
+extern "C" int crm_scan_association_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
+                                          int fast, const double* null, double* out_pvalue, double* out_alt_lml) {
+    return crm::guarded_on("crm_scan_association_multi", (genes && ngenes > 0 && genes[0]) ? genes[0]->ctx : nullptr, [&]() -> int {
+    return scan_association_multi(genes, ngenes, panel, first, count, fast, null, out_pvalue, out_alt_lml, nullptr);
+    });
+}
+
+extern "C" int crm_scan_association_multi_effects(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
+                                                  int fast, const double* null, double* out_pvalue, double* out_alt_lml,
+                                                  double* out_beta, double* out_se, double* out_delta, double* out_scale,
+                                                  double* out_logp, int* out_status) {
+    return crm::guarded_on("crm_scan_association_multi_effects", (genes && ngenes > 0 && genes[0]) ? genes[0]->ctx : nullptr, [&]() -> int {
+    const AssocEffectsOut eff{out_beta, out_se, out_delta, out_scale, out_logp, out_status};
+    return scan_association_multi(genes, ngenes, panel, first, count, fast, null, out_pvalue, out_alt_lml, &eff);
     });
 }

@@ -94,6 +94,37 @@ int launch_fastscan(hipStream_t st, const AssocArgs& a, const double* prep, cons
 int launch_lrt(hipStream_t st, const double* alt_lml, double null_lml, int count, double* pv);
 int launch_gather_trial_lml(hipStream_t st, const NullFitTrial* trial, int count, double* out);
 
+// ---- effect sizes of the association scans (assoc_effects.hip) ------------------------------------
+// One phenotype of an effects launch (device copy).  Test (gene a, variant b) reads the variant's row of T(rho*) at
+// T[b t_sb + k t_sk] (k over the spectrum), its plain products g'W_u at gW[b gW_sb + u gW_su], gg[b] and gy[b], and
+// writes entry b of the outputs (each may be null).
+struct AssocEffectsGene {
+    const double* T; long t_sb, t_sk;
+    const double* ty;  // [r]
+    const double* tW;  // [c x ldW]
+    const double* S0;  // [r]
+    long ldW;
+    int r, c;
+    long n;
+    const double* WW; const double* Wy; double yy;
+    const double* gg; const double* gy; const double* gW; long gW_sb, gW_su;
+    const double* prep; const double* wts; double delta0;   // fast: the gene's fastscan_prep record, weights and delta
+    const NullFitTrial* trial;                               // full refit: [variants] the alt fits (delta, use_g, lml)
+    const double* alt_lml;                                   // [variants] what the scan returns
+    double null_lml;
+    double* out_beta; double* out_se; double* out_delta; double* out_scale; double* out_logp;
+    int* out_status;
+};
+// the host arrays an effects call fills (each may be null)
+struct AssocEffectsOut {
+    double* beta; double* se; double* delta; double* scale; double* logp;
+    int* status;
+};
+// tests in the order b ngenes + a; c: the covariate columns of every gene of the launch
+int launch_assoc_effects(hipStream_t st, const AssocEffectsGene* genes_dev, int ngenes, int variants, int c, bool fast);
+// logp[i] = log erfc(sqrt(lrs[i] / 2)), lrs below 0 taken as 0 (the effects kernels' statement; test hook)
+int launch_lrt_logp(hipStream_t st, const double* lrs, int count, double* logp);
+
 // ---- small per-block kernels (blockops.hip) ----------------------------------------------------
 // gg, gy, gW for a block of variants: column reductions of G (cells x ldg), deterministic.
 int launch_variant_stats(hipStream_t st, const double* G, long ldg, long cells, int variants,

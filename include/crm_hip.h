@@ -308,6 +308,31 @@ int crm_association_null_multi(crm_gene* const* genes, int ngenes, double* out_n
 int crm_scan_association_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
                                int fast, const double* null, double* out_pvalue, double* out_alt_lml);
 
+/* ---- effect sizes of the association scans (an extension: the reference keeps only the lml, _cellregmap.py:276,
+ * :308-309).  The _effects forms take the arguments of the plain calls, return bit for bit their p-values and alt lml, and
+ * after the alt fits of each block run one more launch that evaluates the ML profile of y ~ [W, g] at the variance ratio
+ * delta the scan settled on -- the null model's (fast), the optimum of the variant's own search (full refit) -- with
+ * K = (1 - delta) Sigma(rho*) + delta I.  Added outputs, `count` entries each (rows per gene,
+ * ngenes x count gene-major, in the multi form); any may be NULL:
+ *   out_beta    the coefficient of g in (X'K^-1X)^-1 X'K^-1y, X = [W, g]
+ *   out_se      sqrt(scale / schur), schur = the Schur complement of g against W in the K^-1 metric
+ *   out_delta   delta;  out_scale  (y'K^-1y - b'beta_hat) / n, the alternative's ML scale
+ *   out_logp    natural log of erfc(sqrt(lrs / 2)), lrs = max(2 (alt lml - null lml), 0): no clip at either end
+ *   out_status  CRM_EFFECT_OK, or G_IN_SPAN_W (the scan's own rank rule dropped g: beta and se are NaN, the p-value is
+ *               the plain call's), NO_FIT (the alt lml is NaN), NON_FINITE (a result is not finite) */
+#define CRM_EFFECT_OK 0
+#define CRM_EFFECT_G_IN_SPAN_W 1
+#define CRM_EFFECT_NO_FIT 2
+#define CRM_EFFECT_NON_FINITE 3
+int crm_scan_association_effects(crm_gene* gene, crm_panel* panel, long first, long count, int fast,
+                                 double* out_pvalue, double* out_alt_lml, double* out_null, double* out_beta,
+                                 double* out_se, double* out_delta, double* out_scale, double* out_logp,
+                                 int* out_status);
+int crm_scan_association_multi_effects(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
+                                       int fast, const double* null, double* out_pvalue, double* out_alt_lml,
+                                       double* out_beta, double* out_se, double* out_delta, double* out_scale,
+                                       double* out_logp, int* out_status);
+
 /* ---- effect sizes: the device operations behind predict_interaction (_cellregmap.py:137-205) and
  * estimate_aggregate_environment (:207-244).
  * crm_lmm_fit: LMM(y, M, QS(rho), restricted).fit() for every grid point of the gene's background

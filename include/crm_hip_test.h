@@ -146,6 +146,9 @@ int crm_test_davies_trace(crm_ctx* ctx, int count, int k, const double* Q, const
 int crm_test_tail_pvalue(crm_ctx* ctx, int count, int k, const double* Q, const double* lambda, double* pvalue,
                          double* logp, int* status);
 
+/* The log p-value of the association effects calls (out_logp) for `count` likelihood-ratio statistics. */
+int crm_test_lrt_logp(crm_ctx* ctx, int count, const double* lrs, double* logp);
+
 /* The background constructor's symmetric eigen-solver on `batch` host matrices A (dim x dim each, row-major,
  * tight): lam (batch x dim, ascending), Z (batch x dim x dim, column j = eigenvector j; may be NULL).
  * stage 0: the whole solver; 1: tridiagonalisation only (d_out / e_out: batch x dim diagonals and

@@ -967,6 +967,8 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
         return CRM_ERR_UNSUPPORTED;
     }
     const int ts = (KT + 15) / 16;
+    // (the Gram is in wb_Gw already: launch_wb_gram_fused has formed it from the pair products -- a direct-to-LDS form too)
+    const bool gram_done = a.wb_k1 > 0 && a.wb_gram_done != 0;
     // LDS-DMA forms: 16-byte loads, so every row must start on a 16-byte boundary and hold an even number of doubles
     bool dma = ts <= 9 && a.ldA % 2 == 0 && (reinterpret_cast<uintptr_t>(a.A) & 15) == 0 && !form("gram_staged", 0);
     for (int i = 0; dma && i < CRM_MAX_RHO; i++) {
@@ -985,7 +987,8 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
         hipLaunchKernelGGL(KERNEL<NTL>, dim3(variants), dim3(256), lds, st, a, Gext, KT);                     \
     } while (0)
 #define CRM_GRAM_DMA_WIDE(NTL) CRM_GRAM_DMA(gram_ext_dma_wide_kernel, gram_dma_wide_lds_doubles, NTL)
-    if (dma) {
+    if (gram_done) {
+    } else if (dma) {
         // (up to 4 tile rows every wavefront keeps every tile; past that the tiles are dealt to the wavefronts)
         if (ts <= 2) CRM_GRAM_DMA(gram_ext_dma_kernel, gram_dma_lds_doubles, 2);
         else if (ts <= 4) CRM_GRAM_DMA(gram_ext_dma_kernel, gram_dma_lds_doubles, 4);
@@ -1012,7 +1015,7 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                   \
         hipLaunchKernelGGL((gram_ext_kernel<NTL, NG>), dim3(variants, NG), dim3(256), lds, st, a, Gext, KT);  \
     } while (0)
-    if (dma) {
+    if (dma || gram_done) {
     } else if (ts <= 2) CRM_GRAM(2);
     else if (ts <= 4) CRM_GRAM(4);
     else if (ts <= 6) CRM_GRAM(6);
@@ -1024,7 +1027,7 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
 #undef CRM_GRAM
 #undef CRM_GRAM_GROUPS
     CRM_HIP(hipGetLastError());
-    if (dma && dma_launches) ++*dma_launches;
+    if ((dma || gram_done) && dma_launches) ++*dma_launches;
     const bool yty = a.wb_k1 > 0 && form("woodbury_ytY", 1) != 0;
     if (a.wb_k1 > 0) {
         // form("woodbury_ytY", 0): the factor, then both substitutions, one column of C^-1 M_Ev per thread

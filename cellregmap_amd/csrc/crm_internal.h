@@ -118,6 +118,7 @@ struct crm_ctx {
     long donor_pair_blocks = 0;   // blocks whose per-donor sums came from the symmetric pair features (crm_test_donor_pair_blocks)
     long rotation_tail_launches = 0;   // blocks whose rotations sent the last few columns of their spectra through it (crm_test_rotation_tail_launches)
     long rho0_position_blocks = 0;     // blocks whose null fits at rho = 0 read the position basis (crm_test_rho0_position_blocks)
+    long wb_gram_fused_blocks = 0;     // blocks whose unrelated-donor Gram came straight from the pair products (crm_test_wb_gram_fused_blocks)
     long fused_blocks = 0;             // blocks read in place in the panel and prepared by the fused pass (crm_test_fused_blocks)
     long unrelated_donor_blocks = 0;   // blocks served by the unrelated-donor form (crm_test_unrelated_donor_blocks)
     long gram_dma_launches = 0;   // score-statistic Grams that went through a direct-to-LDS kernel (crm_test_gram_dma_launches)

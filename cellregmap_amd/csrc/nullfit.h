@@ -245,6 +245,7 @@ struct AssembleArgs {
     const double* wb_E1g; long wb_ldE1g;     // [k1 x ld]: column b
     const double* wb_EE;                     // [k1 x k1]
     double* wb_Gw;                           // workspace [variants x (k0 + c + 2 + k1)^2]
+    int wb_gram_done;                        // wb_Gw holds the Gram already (launch_wb_gram_fused): the assembly starts behind it
 };
 
 // Gext: workspace [variants x (k0+c+2)^2]; fin_rows: assemble_rows_scratch_doubles(...) doubles (0: not needed -- the
@@ -255,6 +256,25 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
 size_t assemble_rows_scratch_doubles(int variants, int k0, int c);
 // LDS of the unrelated-donor correction (assemble.hip: woodbury_kernel) for KT = k0 + c + 2 rows and k1 E1 columns
 size_t woodbury_lds_bytes(int KT, int k1);
+
+// ---- the unrelated-donor Gram straight from the per-donor pair products (wb_gram_fused.hip) -------
+// The operands of launch_donor_pairs_rotate that the assembly's arguments do not hold: P [donors][variants x ldp] pair
+// products (the variant's row is its place in the block), U [donors][k2pad x ldu] = Psi_d, the donor sums Psum [splits] slabs
+struct WbFusedArgs {
+    const double* P; long p_slab, ldp;
+    const double* U; long u_slab, ldu;
+    double* Psum; long psum_slab;
+    int donors, splits, k2pad;
+};
+// LDS of wb_gram_fused_kernel, in doubles (tools/wb_gram_fused_prototype.py walks the same table): the Gram's image
+// [KT][RS] from 0 (rows from k0 on in nO DMA instructions of 128 doubles), the variant's pair products at off_P (nP
+// instructions), Psi_d [urows][UW] at off_U (nU), S0 and d_j of the chunk by column, the row pointers of the rows_o other rows
+struct WbFusedLayout { int RS, UW, urows, rows_o, nP, nU, nO, off_P, off_U, off_S0, off_d, off_rp, total; };
+WbFusedLayout wb_gram_fused_layout(int k0, int KT, long ldp);
+bool wb_gram_fused_serves(const AssembleArgs& a, const WbFusedArgs& f, int nrho);
+// wb_Gw of every variant of the block (a.fit, a.sorted_pos, a.rho[.].{ty, tW, T, S0, r}, a.wb_R, a.A_none as the assembly
+// reads them) and the donor sums as launch_donor_pairs_rotate leaves them
+int launch_wb_gram_fused(hipStream_t st, const AssembleArgs& a, const WbFusedArgs& f, int nrho, int variants);
 
 // ---- eigenvalues + Davies / Liu (davies.hip) -----------------------------------------------------
 // lambda: ascending eigenvalues of the lower triangle of F (count x k x k); pvalue per SKAT rule.

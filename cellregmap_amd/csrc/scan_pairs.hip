@@ -247,7 +247,21 @@ int ScanPass::folded_S(const Block& B, const SubRange& R, const Pairs& Q) {
         double* AH = ctx->ws_AH.as<double>();
         if (probed.donor_pairs) {
             CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, npair, maxlen, false, 0, 1, 0));
-            if (probed.wb_rotate)   // (the rotated S straight from the pair products: the rows of S are not formed)
+            // One phenotype, no second assembly from the rotated S (flags: flat_probes) and no replay: the Gram of the
+            // assembly straight from the pair products, the rotated S stays in LDS (wb_gram_fused.hip)
+            if (probed.wb_rotate && may_fuse_gram() && R.b0 == 0 && R.nb == B.nb) {
+                const AssembleArgs aa = assemble_args(R, 0);
+                const WbFusedArgs fa{ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, bg->wb_U.as<double>(), (long)bg->wb_k2pad * 128, 128,
+                                     AH, P.pd_slab, (int)groups, P.donor_pair_splits, bg->wb_k2pad};
+                if (wb_gram_fused_serves(aa, fa, nrho)) {
+                    CRM_TRY(launch_wb_gram_fused(st, aa, fa, nrho, ncol));
+                    gram_fused = true;
+                    ctx->wb_gram_fused_blocks++;
+                }
+            }
+            if (!gram_fused && P.wb()) CRM_TRY(ctx->ws_A.ensure(ws_A_bytes()));   // (workspaces() left it to the fused Gram)
+            if (gram_fused) {
+            } else if (probed.wb_rotate)   // (the rotated S straight from the pair products: the rows of S are not formed)
                 CRM_TRY(launch_donor_pairs_rotate(st, ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, (int)groups, ncol, k0,
                                                   bg->wb_U.as<double>(), (long)bg->wb_k2pad * 128, 128, bg->wb_k2pad,
                                                   ctx->ws_A.as<double>(), P.ldAw, AH, P.pd_slab, P.donor_pair_splits));
@@ -347,6 +361,7 @@ int ScanPass::direct_AH(const Block& B, const SubRange& R, const Pairs& Q, AGrou
 // Unrelated-donor form: the rotated S, rows (col k0 + i) over the donors k2 positions -- per donor
 // (U_d Lambda_d^-1/2)' S_d, stored transposed into ws_A; col = the pair (one phenotype) or the block position
 int ScanPass::woodbury_S(const SubRange& R, const Pairs& Q) {
+    CRM_TRY(ctx->ws_A.ensure(ws_A_bytes()));   // (workspaces() leaves it out where the fused Gram may serve)
     const long groups = bg->kin_groups;
     const int ncol = P.wb_block ? R.nb : Q.npairs;
     std::vector<GemmProblem> kp((size_t)groups);
@@ -364,6 +379,7 @@ int ScanPass::woodbury_S(const SubRange& R, const Pairs& Q) {
 //    n-length Khatri-Rao contraction is then done once per variant against H (stored transposed)
 //    and every (variant, rho) pair costs a cols-length product with Mix(rho) instead.
 int ScanPass::form_A(const Block& B, const SubRange& R, const Pairs& Q) {
+    gram_fused = false;   // (set by folded_S where the fused Gram serves the sub-range)
     bool via_H = P.kin();
     if (P.fastT && ng > 1 && !P.kin()) {
         double direct = 0.0, via = (double)R.nb * (double)bg->cols * (double)n;

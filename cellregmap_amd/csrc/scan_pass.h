@@ -164,6 +164,7 @@ struct ScanPass {
     bool rho0_pos[CRM_MAX_RHO] = {false};   // grid points whose null fits of this block read the position basis (plan_rotations)
     std::vector<GemmProblem> rot_tails;     // the rotations' spectrum tails of the block (plan_rotations)
     std::vector<GemmProblem> phi_recs;      // the donors' records of Phi'gx of the block (woodbury_phi)
+    bool gram_fused = false;                // the sub-range's wb_Gw came from the pair products (folded_S: launch_wb_gram_fused)
 
     ScanPass(const std::vector<crm_gene*>& genes_, crm_panel* panel_, long first_, long count_, const int* idx_E_,
              const int* idx_G_, const std::vector<ScanOut>& outs_, bool allow_collapse, std::vector<long>* near_out_)
@@ -252,6 +253,18 @@ struct ScanPass {
     // ---- scan_results.hip -------------------------------------------------------------------------------------------
     int flat_probes(const Block& B, const SubRange& R, int gi, const AssembleArgs& aa, double* slow_ws, std::vector<char>& flat,
                     std::vector<double>& probe_rec);
+    AssembleArgs assemble_args(const SubRange& R, int gi) const;
+    // the rotated test direction's buffer (unrelated-donor form: the rotated S in block order for several phenotypes -- BLK
+    // of them at most), and whether this pass can do without it: every condition of the fused Gram that is known before
+    // the first block (the operands' alignment has the last word: wb_gram_fused_serves)
+    size_t ws_A_bytes() const {
+        return sizeof(double) * (size_t)(P.wb() ? std::max(P.pair_cap, P.BLK) : P.pair_cap) * k0 * P.ldAw;
+    }
+    bool may_fuse_gram() const {
+        const int ts = (2 * k0 + c + 2 + 15) / 16;
+        return P.wb_rotate && ng == 1 && P.wb_block && !outs[0].flags && ctx->replay_mode == 0 && k0 % 2 == 0 && ts >= 5 && ts <= 8 &&
+               form("wb_gram_fused", 1) != 0 && form("gram_staged", 0) == 0;
+    }
     int gene_results(const Block& B, const SubRange& R, int gi);
 };
 

@@ -47,7 +47,9 @@ int ScanPass::workspaces() {
     const long ldb = P.ldb;
     CRM_TRY(ctx->ws_T.ensure(sizeof(double) * (size_t)nrho * BLK * P.ldT));
     // (unrelated-donor form: the rotated S stays in block order for several phenotypes -- BLK of them at most)
-    CRM_TRY(ctx->ws_A.ensure(sizeof(double) * (size_t)(P.wb() ? std::max(max_pairs, BLK) : max_pairs) * k0 * P.ldAw));
+    // (not where the pass's Grams come straight from the pair products, wb_gram_fused.hip: the rotated S is not formed at
+    // all; a block that the fused launch does not serve after all asks for the buffer itself, scan_pairs.hip)
+    if (!may_fuse_gram()) CRM_TRY(ctx->ws_A.ensure(ws_A_bytes()));
     CRM_TRY(ctx->ws_Anone.ensure(sizeof(double) * (size_t)P.ldAw));
     CRM_HIP(hipMemsetAsync(ctx->ws_Anone.ptr, 0, sizeof(double) * (size_t)P.ldAw, st));
     // (the aligned copy: not where every block of the pass is read in place, scan_block.hip: copy_block)

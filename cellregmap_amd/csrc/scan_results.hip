@@ -87,12 +87,10 @@ int ScanPass::flat_probes(const Block& B, const SubRange& R, int gi, const Assem
     return CRM_OK;
 }
 
-// 10.-11. per gene: Q and F, eigenvalues + Davies (or the exact tail), results
-int ScanPass::gene_results(const Block& B, const SubRange& R, int gi) {
+// the assembly's operands of gene gi over a sub-range (also what the fused Gram of the pair stage reads: folded_S)
+AssembleArgs ScanPass::assemble_args(const SubRange& R, int gi) const {
     crm_gene* g = genes[gi];
-    const ScanOut& o = outs[gi];
-    const int nb = R.nb, BLK = P.BLK, b0 = R.b0;
-    const long done = R.done;
+    const int BLK = P.BLK, b0 = R.b0;
     AssembleArgs aa{};
     for (int i = 0; i < nrho; i++) {
         AssembleRho& Rr = aa.rho[i];
@@ -124,6 +122,16 @@ int ScanPass::gene_results(const Block& B, const SubRange& R, int gi) {
         aa.wb_E1yW = wb_E1yW + (size_t)gi * bg->kin_k1 * 128; aa.wb_ldE1yW = 128;
         aa.wb_E1g = ctx->ws_TH.as<double>() + b0; aa.wb_ldE1g = P.ldb; aa.wb_EE = bg->wb_EE.as<double>(); aa.wb_Gw = wb_Gw;
     }
+    return aa;
+}
+
+// 10.-11. per gene: Q and F, eigenvalues + Davies (or the exact tail), results
+int ScanPass::gene_results(const Block& B, const SubRange& R, int gi) {
+    const ScanOut& o = outs[gi];
+    const int nb = R.nb, BLK = P.BLK, b0 = R.b0;
+    const long done = R.done;
+    AssembleArgs aa = assemble_args(R, gi);
+    aa.wb_gram_done = gram_fused ? 1 : 0;   // (folded_S: wb_Gw of this sub-range is formed)
     double* slow_ws = P.slow_forms ? ctx->ws_xwide.as<double>() : nullptr;   // (the null fits of the block are done: their scratch is free)
     CRM_TRY(launch_assemble(st, aa, nb, ctx->ws_Gext.as<double>(), slow_ws, &ctx->gram_dma_launches));
     CRM_TRY(launch_eig_davies(st, ctx->ws_F.as<double>(), d_Q, nb, k0, d_lam, d_pv, d_if, d_liu, true, slow_ws));

@@ -1,0 +1,383 @@
+// Unrelated-donor form, one phenotype: the weighted Gram Gw of [rotated S ; W ; gx ; y ; E1] straight from the per-donor pair
+// products -- donor_pairs_rotate_kernel (blockops.hip) and gram_ext_dma_wide_kernel (assemble.hip) in one launch, so that the
+// rotated S (ws_A: variants x k0 rows x donors k2 positions) is neither written nor read back.
+//
+// One workgroup per variant of the block walks the donors.  A donor d owns the positions [k0 d, k0 d + k0) of the Gram's
+// contraction; the Gram sums positions in groups of four from position 0 in one accumulator per output, so the walk is cut at
+// the multiples of four: chunk d is [start_d, end_d), start_d = 4 floor(k0 d / 4), end_d = start_(d + 1) (the last one:
+// 4 ceil(donors k0 / 4), zeros past the end).  With k0 even a chunk is k0 - 2, k0 or k0 + 2 positions and every group of
+// four is the two launches' group: Gw has their bits (up to the sign of a zero).  Per donor:
+//   rotation  A_d = S_d Psi_d (k0 x k0) on the FP64 MFMA as donor_pairs_rotate_kernel forms it (symmetric lookup into the
+//             donor's pair products, k ascending in groups of four, one accumulator per output), written into the Gram's
+//             LDS image; the donor sums Psum are accumulated from the same LDS copy of P_d;
+//   Gram      over the chunk's columns of the image: rows [0, k0) the rotated S, rows [k0, KT) the other operand rows
+//             brought in by LDS-DMA; the weight d_j = s / (1 + s), s = (v0 / v1) S0_j, goes onto the B operand; the upper
+//             triangle of 16 x 16 tiles dealt to the four wavefronts as in gram_ext_dma_wide_kernel.
+// LDS image of the Gram: row R at R * RS doubles, RS = (k0 + 4) | 2 (an odd multiple of two: the sixteen rows of a fragment
+// read start two 8-byte slots apart); a position p of chunk d sits in column p - start_d + c0_d, c0_d = 2 - (k0 d - start_d),
+// so that A_d[., j] is column j + 2 in every chunk -- except the last two of a donor whose chunk ends two short (k0 = 2 mod 4,
+// d even): they belong to chunk d + 1 and go to its columns 0 and 1, which chunk d does not read and the rotation of d + 1
+// does not write.  Columns that no chunk fills are zeros: written once for the rotated rows, and by every DMA for the
+// others (lanes off the chunk read a row of zeros, AssembleArgs::A_none).
+// Every buffer is single: a load is issued behind the barrier that frees its buffer and waited for (vmcnt(0), written out:
+// dma_barrier) before the next barrier, so it is in flight during the MFMAs of the phase between the two --
+//     rotation d | wait + barrier | issue P, Psi, S0 of d + 1 | Gram d | wait + barrier | issue the other rows of d + 1 | rotation d + 1 ...
+// (two of everything would not fit two workgroups per CU: 79 KB per workgroup at k0 = 50 as it is), and the second
+// workgroup of the CU fills what is left.  The loop holds no ordinary global load: each would be waited for together with
+// every LDS-DMA in flight.
+#include <type_traits>
+
+#include "nullfit.h"
+
+namespace crm {
+
+namespace {
+
+typedef double v4d __attribute__((ext_vector_type(4)));
+typedef const double __attribute__((address_space(1))) * fused_gptr_t;
+typedef __attribute__((address_space(3))) void* fused_lptr_t;
+
+__device__ __forceinline__ void fused_dma16(const double* src, double* lds_wave_uniform) {
+    __builtin_amdgcn_global_load_lds((fused_gptr_t)src, (fused_lptr_t)lds_wave_uniform, 16, 0, 0);
+}
+
+// The barrier behind LDS-DMA: s_barrier does not wait for memory operations in flight, and the compiler adds the vmcnt wait
+// only for a DMA issued in the straight-line code before a __syncthreads(), not for one pending across the loop's back-edge.
+// Every barrier whose opening lets a wavefront read what a DMA wrote therefore waits explicitly, for this wavefront's loads
+// (vmcnt) and LDS operations (lgkmcnt); behind the barrier every wavefront's have landed.
+__device__ __forceinline__ void dma_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+constexpr int WF_MAXQ_P = 10, WF_MAXQ_O = 9, WF_PSUM = 6;   // DMA instructions per wavefront (P, Psi, S0 / other rows); sums per thread
+constexpr int WF_UW = 56;   // LDS row of Psi_d: a constant, so that the fragment reads carry their offsets as immediates (k0 <= 54)
+
+}  // namespace
+
+WbFusedLayout wb_gram_fused_layout(int k0, int KT, long ldp) {
+    WbFusedLayout L;
+    const int KS = (k0 + 3) / 4;
+    L.urows = 4 * KS;
+    L.UW = WF_UW;
+    L.RS = (k0 + 4) | 2;
+    L.nP = (int)(ldp / 128);
+    L.nU = (L.urows * (L.UW / 2) + 63) / 64;
+    L.rows_o = KT - k0;
+    L.nO = (L.rows_o * (L.RS / 2) + 63) / 64;
+    L.off_P = k0 * L.RS + L.nO * 128;
+    L.off_U = L.off_P + L.nP * 128;
+    L.off_S0 = L.off_U + L.nU * 128;
+    L.off_d = L.off_S0 + 128;
+    L.off_rp = L.off_d + 64;
+    L.total = L.off_rp + ((L.rows_o + 1) & ~1);
+    return L;
+}
+
+namespace {
+
+template <int NTL>
+__global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(AssembleArgs a, WbFusedArgs f, WbFusedLayout L, int KT) {
+    constexpr int NTILES = NTL * (NTL + 1) / 2, MAXT = (NTILES + 3) / 4;
+    extern __shared__ __align__(16) double smem[];
+    double* const img = smem;                      // [KT][RS] (+ what the last DMA instruction overshoots)
+    double* const Pl = smem + L.off_P;             // the donor's pair products of this variant
+    double* const Ul = smem + L.off_U;             // Psi_d [urows][UW]
+    double* const S0l = smem + L.off_S0;           // S0 of the chunk, by column
+    double* const dS = smem + L.off_d;             // d_j of the chunk, by column
+    const double** const rowp = reinterpret_cast<const double**>(smem + L.off_rp);
+    const int b = blockIdx.x;
+    const NullFitOut fit = a.fit[b];
+    const AssembleRho R = a.rho[fit.rho_index];
+    const double ratio = fit.v0 / fit.v1;
+    const bool has_A = a.sorted_pos[b] >= 0;       // (block order: the position is the variant's own; none: rows of zeros)
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int l15 = lane & 15, lq = lane >> 4;
+    const int k0 = a.k0, c = a.c, RS = L.RS;
+    constexpr int UW = WF_UW;
+    const int npair = k0 * (k0 + 1) / 2, KS = (k0 + 3) / 4, JT = (k0 + 15) / 16;
+    const int D = f.donors, Ptot = D * k0;
+    const double* __restrict__ zeros = a.A_none;
+
+    for (int e = tid; e < k0 * RS; e += 256) img[e] = 0.0;
+    for (int t = tid; t < L.rows_o; t += 256) {
+        const double* p;
+        if (t < c) p = R.tW + (long)t * R.ldW;
+        else if (t == c) p = R.T + (long)b * R.ldT;
+        else if (t == c + 1) p = R.ty;
+        else p = a.wb_R + (long)(t - c - 2) * a.wb_ldR;
+        rowp[t] = p;
+    }
+    // what each DMA instruction of this lane reads: instruction I = wave + 4 q carries the 16-byte units 64 I .. 64 I + 63 of
+    // its LDS region.  P, Psi, S0: an element offset (P: into the variant's row; Psi: k ldu + column; S0: the column);
+    // the other rows: (row << 8) | column, -1 off the rows
+    const int nPU = L.nP + L.nU + 1;
+    int poff[WF_MAXQ_P], ocode[WF_MAXQ_O];
+#pragma unroll
+    for (int q = 0; q < WF_MAXQ_P; q++) {
+        const int I = wave + 4 * q;
+        if (I < L.nP) poff[q] = 128 * I + 2 * lane;
+        else if (I < L.nP + L.nU) {
+            const int u = 64 * (I - L.nP) + lane, k = u / (UW / 2), cu = u - k * (UW / 2);
+            poff[q] = k < L.urows ? k * (int)f.ldu + 2 * cu : 0;
+        } else poff[q] = 2 * lane;
+    }
+#pragma unroll
+    for (int q = 0; q < WF_MAXQ_O; q++) {
+        const int u = 64 * (wave + 4 * q) + lane, t = u / (RS / 2), cu = u - t * (RS / 2);
+        ocode[q] = t < L.rows_o ? (t << 8) | (2 * cu) : -1;
+    }
+    // the chunk of donor d: positions [start, end) at columns c0 .., the columns [c0, c0 + lim - start) hold data
+    auto chunk = [&](int d, int& start, int& end, int& c0, int& lim) __attribute__((always_inline)) {
+        start = (k0 * d) & ~3;
+        end = d + 1 < D ? (k0 * (d + 1)) & ~3 : (Ptot + 3) & ~3;
+        c0 = 2 - (k0 * d - start);
+        lim = end < Ptot ? end : Ptot;
+    };
+    auto issue_pus = [&](int d) __attribute__((always_inline)) {
+        int start, end, c0, lim;
+        chunk(d, start, end, c0, lim);
+        const double* __restrict__ Pd = f.P + (size_t)d * f.p_slab + (long)b * f.ldp;
+        const double* __restrict__ Ud = f.U + (size_t)d * f.u_slab;
+        const double* __restrict__ S0 = R.S0 + (start - c0);
+#pragma unroll
+        for (int q = 0; q < WF_MAXQ_P; q++) {
+            const int I = wave + 4 * q;
+            if (I < L.nP) fused_dma16(Pd + poff[q], Pl + 128 * I);
+            else if (I < L.nP + L.nU) fused_dma16(Ud + poff[q], Ul + 128 * (I - L.nP));
+            else if (I < nPU) {
+                const int col = poff[q];
+                fused_dma16(col >= c0 && start - c0 + col < lim ? S0 + col : zeros, S0l);
+            }
+        }
+    };
+    auto issue_others = [&](int d) __attribute__((always_inline)) {
+        int start, end, c0, lim;
+        chunk(d, start, end, c0, lim);
+        const int shift = start - c0;
+#pragma unroll
+        for (int q = 0; q < WF_MAXQ_O; q++) {
+            const int I = wave + 4 * q;
+            if (I < L.nO) {
+                const int code = ocode[q], col = code & 255;
+                const bool in = code >= 0 && col >= c0 && shift + col < lim;
+                const double* src = zeros;
+                if (in) src = rowp[code >> 8] + (shift + col);
+                fused_dma16(src, img + k0 * RS + 128 * I);
+            }
+        }
+    };
+    // rotation fragments: lane (l15, lq) of k-step ks reads S_d[k = 4 ks + lq, i = 16 w + l15] (pair (0, 0) off the matrix)
+    const int iw = 16 * wave + l15;
+    int pidx[16];
+#pragma unroll
+    for (int ks = 0; ks < 16; ks++) {
+        const int k = 4 * ks + lq, lo = k < iw ? k : iw, hi = k < iw ? iw : k;
+        pidx[ks] = k < k0 && iw < k0 ? lo * k0 - lo * (lo - 1) / 2 + (hi - lo) : 0;
+    }
+    // tiles of this wavefront, as gram_ext_dma_wide_kernel deals them (rows past KT read row 0: never stored)
+    const int first = (wave + b) & 3;
+    const int ntw = (NTILES - first + 3) / 4;
+    int t_i[MAXT], t_j[MAXT], t_ij[MAXT];
+#pragma unroll
+    for (int t = 0; t < MAXT; t++) {
+        int ti = 0, rem = first + 4 * t < NTILES ? first + 4 * t : 0;
+        while (rem >= NTL - ti) { rem -= NTL - ti; ti++; }
+        t_ij[t] = ti | ((ti + rem) << 8);
+        const int ri = 16 * ti + l15, rj = 16 * (ti + rem) + l15;
+        t_i[t] = (ri < KT ? ri : 0) * RS + lq;
+        t_j[t] = (rj < KT ? rj : 0) * RS + lq;
+    }
+    v4d acc[MAXT];
+#pragma unroll
+    for (int t = 0; t < MAXT; t++) acc[t] = (v4d){0.0, 0.0, 0.0, 0.0};
+    double psum[WF_PSUM];
+#pragma unroll
+    for (int q = 0; q < WF_PSUM; q++) psum[q] = 0.0;
+    // the donor sums by ranges of donors, as donor_pairs_rotate_kernel's grid splits them
+    const int per = (D + f.splits - 1) / f.splits;
+    int split = 0;
+
+    auto gram = [&](int col0, int nks, auto nt_tag) __attribute__((always_inline)) {
+        constexpr int NT = decltype(nt_tag)::value;
+        const double* __restrict__ S = img + col0;
+        const double* __restrict__ Dw = dS + col0 + lq;
+        // one set of fragments: an MFMA has read its operands when it is issued, so the reads of k-step ks + 1 follow the
+        // MFMAs of ks into the same registers and land while those run (16 passes each); the other workgroup of the CU
+        // covers what is left.  Two sets would cost 4 NT registers beside the accumulators.
+        // (tile by tile: the reads of tile t for k-step ks + 1 go out behind its MFMA of ks and have the other tiles' MFMAs
+        // to land in; the weight is multiplied in just before the use)
+        double fa[NT], fr[NT];
+        double dk = Dw[0];
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+            fa[t] = S[t_i[t]];
+            fr[t] = S[t_j[t]];
+        }
+        for (int ks = 0; ks < nks; ks++) {
+            const bool more = ks + 1 < nks;
+            const int nx = more ? 4 * (ks + 1) : 4 * ks;     // (the last step re-reads its own fragments: no branch in the loop)
+            const double dn = Dw[nx];
+#pragma unroll
+            for (int t = 0; t < NT; t++) {
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[t], fr[t] * dk, acc[t], 0, 0, 0);
+                fa[t] = S[t_i[t] + nx];
+                fr[t] = S[t_j[t] + nx];
+            }
+            dk = dn;
+        }
+    };
+
+    __syncthreads();   // (the row pointers are read by the first loads)
+    issue_pus(0);
+    issue_others(0);
+    dma_barrier();     // (P, Psi, S0 and the other rows of donor 0 have landed)
+    for (int d = 0; d < D; d++) {
+        int start, end, c0, lim;
+        chunk(d, start, end, c0, lim);
+        // ---- rotation phase: weights, donor sums, A_d into the image (the other rows of chunk d are in flight) ----
+        if (tid < RS) {
+            // (the product rounded on its own, as the Gram launch rounds it: contracted into 1 + ratio S0 the weight would
+            // differ in its last bit)
+#pragma clang fp contract(off)
+            const double s = ratio * S0l[tid];     // (zeros off the chunk: d = 0)
+            dS[tid] = s / (1.0 + s);
+        }
+#pragma unroll
+        for (int q = 0; q < WF_PSUM; q++)
+            if (tid + 256 * q < npair) psum[q] += Pl[tid + 256 * q];
+        if (d + 1 == D || d + 1 == (split + 1) * per) {
+            double* __restrict__ out = f.Psum + (size_t)split * f.psum_slab + (long)b * f.ldp;
+#pragma unroll
+            for (int q = 0; q < WF_PSUM; q++)
+                if (tid + 256 * q < npair) { out[tid + 256 * q] = psum[q]; psum[q] = 0.0; }
+            split++;
+        }
+        if (has_A && wave < JT) {
+            unsigned uo = (unsigned)(lq * UW + l15);
+            asm volatile("" : "+v"(uo));
+            const double* __restrict__ ub = Ul + uo;
+            // column of A_d[., j]: j + 2, or -- past the chunk's end -- columns 0, 1 of the next chunk
+            const int jcut = end - k0 * d;
+            // (two column tiles at a time: four would hold 32 more registers beside the Gram's accumulators)
+#pragma unroll
+            for (int th = 0; th < 4; th += 2) {
+                if (th < JT) {
+                    v4d cr[2];
+#pragma unroll
+                    for (int t = 0; t < 2; t++) cr[t] = (v4d){0.0, 0.0, 0.0, 0.0};
+                    // the fragments of k-step ks + 2 are read before the MFMAs of ks are issued (two MFMAs a step: one step
+                    // ahead would leave a read 128 cycles to land), and no further (the scheduler would pull every read up front)
+                    double af[3], bf[3][2];
+                    auto frag = [&](int ks, int slot) __attribute__((always_inline)) {
+                        af[slot] = Pl[pidx[ks]];
+#pragma unroll
+                        for (int t = 0; t < 2; t++)
+                            if (th + t < JT) bf[slot][t] = ub[4 * ks * UW + 16 * (th + t)];
+                    };
+                    frag(0, 0);
+                    if (1 < KS) frag(1, 1);
+#pragma unroll
+                    for (int ks = 0; ks < 16; ks++) {
+                        if (ks < KS) {
+                            if (ks + 2 < KS) frag(ks + 2, (ks + 2) % 3);
+#pragma unroll
+                            for (int t = 0; t < 2; t++)
+                                if (th + t < JT)
+                                    cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[ks % 3], bf[ks % 3][t], cr[t], 0, 0, 0);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+#pragma unroll
+                    for (int reg = 0; reg < 4; reg++) {
+                        const int r = 16 * wave + lq + 4 * reg;
+                        if (r < k0) {
+#pragma unroll
+                            for (int t = 0; t < 2; t++) {
+                                const int j = 16 * (th + t) + l15;
+                                if (th + t < JT && j < k0) img[r * RS + (j < jcut ? j + 2 : j - jcut)] = cr[t][reg];
+                            }
+                        }
+                    }
+                }
+            }
+        }
+        dma_barrier();     // (A_d and the weights are written; P_d, Psi_d and S0 are free; the other rows of chunk d, issued
+                           // behind the previous barrier, are waited for here: nothing else of this wavefront is in flight)
+        if (d + 1 < D) issue_pus(d + 1);
+        // ---- Gram phase ----
+        const int nks = (end - start) / 4;
+        if (ntw == MAXT) gram(c0, nks, std::integral_constant<int, MAXT>{});
+        else gram(c0, nks, std::integral_constant<int, MAXT - 1>{});
+        dma_barrier();     // (the image is free; P, Psi and S0 of d + 1 are waited for)
+        if (d + 1 < D) issue_others(d + 1);
+    }
+    // ranges of donors that hold no donor (more splits than ranges): zeros, so that the sum over the splits is the sum
+    for (; split < f.splits; split++) {
+        double* __restrict__ out = f.Psum + (size_t)split * f.psum_slab + (long)b * f.ldp;
+        for (int e = tid; e < npair; e += 256) out[e] = 0.0;
+    }
+    double* __restrict__ out = a.wb_Gw + (long)b * KT * KT;
+#pragma unroll
+    for (int t = 0; t < MAXT; t++) {
+        if (t >= ntw) continue;
+        const int ri = (t_ij[t] & 255) * 16, cj = (t_ij[t] >> 8) * 16;
+#pragma unroll
+        for (int reg = 0; reg < 4; reg++) {
+            const int row = ri + lq + 4 * reg, col = cj + l15;
+            if (row < KT && col < KT) {
+                out[(long)row * KT + col] = acc[t][reg];
+                if (ri != cj) out[(long)col * KT + row] = acc[t][reg];
+            }
+        }
+    }
+}
+
+bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+// Does the fused launch serve this assembly?  One phenotype in block order on the pair-rotation form, an even context count
+// (whole groups of four positions per pair of donors), 5 to 8 tile rows, every DMA source on a 16-byte boundary
+bool wb_gram_fused_serves(const AssembleArgs& a, const WbFusedArgs& f, int nrho) {
+    const int k0 = a.k0, KT = k0 + a.c + 2 + a.wb_k1, ts = (KT + 15) / 16;
+    if (form("wb_gram_fused", 1) == 0 || form("gram_staged", 0) != 0) return false;
+    if (a.wb_k1 <= 0 || k0 % 2 != 0 || !donor_pairs_rotate_serves(k0) || ts < 5 || ts > 8 || f.donors < 1 || f.splits < 1) return false;
+    if (f.ldp % 128 != 0 || f.ldp < k0 * (k0 + 1) / 2 || f.p_slab % 2 != 0 || f.u_slab % 2 != 0 || f.ldu % 2 != 0 || f.ldu < 4 * ((k0 + 3) / 4) ||
+        f.k2pad < 4 * ((k0 + 3) / 4) || !aligned16(f.P) || !aligned16(f.U) || !aligned16(a.A_none) || !a.wb_Gw)
+        return false;
+    if (a.wb_ldR % 2 != 0 || !aligned16(a.wb_R)) return false;
+    for (int i = 0; i < nrho; i++) {
+        const AssembleRho& R = a.rho[i];
+        if (R.r != f.donors * k0 || R.ldW % 2 != 0 || R.ldT % 2 != 0 || !aligned16(R.ty) || !aligned16(R.tW) || !aligned16(R.T) ||
+            !aligned16(R.S0))
+            return false;
+    }
+    const WbFusedLayout L = wb_gram_fused_layout(k0, KT, f.ldp);
+    return L.nP + L.nU + 1 <= 4 * WF_MAXQ_P && L.nO <= 4 * WF_MAXQ_O && L.RS <= 64 && k0 * (k0 + 1) / 2 <= 256 * WF_PSUM &&
+           sizeof(double) * (size_t)L.total <= 160 * 1024;
+}
+
+int launch_wb_gram_fused(hipStream_t st, const AssembleArgs& a, const WbFusedArgs& f, int nrho, int variants) {
+    if (variants <= 0) return CRM_OK;
+    if (!wb_gram_fused_serves(a, f, nrho)) {
+        set_error("fused unrelated-donor Gram: k0=%d, c=%d outside the supported range", a.k0, a.c);
+        return CRM_ERR_INTERNAL;
+    }
+    const int KT = a.k0 + a.c + 2 + a.wb_k1, ts = (KT + 15) / 16;
+    const WbFusedLayout L = wb_gram_fused_layout(a.k0, KT, f.ldp);
+    const size_t lds = sizeof(double) * (size_t)L.total;
+#define CRM_WB_FUSED(NTL)                                                                                             \
+    do {                                                                                                              \
+        CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wb_gram_fused_kernel<NTL>),                        \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
+        hipLaunchKernelGGL(wb_gram_fused_kernel<NTL>, dim3(variants), dim3(256), lds, st, a, f, L, KT);               \
+    } while (0)
+    if (ts == 5) CRM_WB_FUSED(5);
+    else if (ts == 6) CRM_WB_FUSED(6);
+    else if (ts == 7) CRM_WB_FUSED(7);   // (config 3: 50 + 3 + 50 rows)
+    else CRM_WB_FUSED(8);
+#undef CRM_WB_FUSED
+    CRM_HIP(hipGetLastError());
+    return CRM_OK;
+}
+
+}  // namespace crm

@@ -36,6 +36,8 @@ extern "C" {
  *                         skinny one-pass kernel (default 1: where that saves a round; "kr_no_tail" 1 switches them off too)
  *   "block_fused" 0       a block of a dense panel goes through the copy and the elementwise launches after it, not read in
  *                         place and prepared by the fused pass (default 1; crm_test_fused_blocks)
+ *   "wb_gram_fused" 0     unrelated-donor form: the rotated S goes through memory between the rotation launch and the Gram launch,
+ *                         not from the pair products straight into the Gram (default 1; crm_test_wb_gram_fused_blocks)
  *   "flat_kappa_milli" v  factor (in thousandths) on the noise bound of CRM_MODEL_FLAT_OPTIMUM / CRM_MODEL_RHO_TIE (study tool)
  * These replace the environment switches of earlier versions; the GPU suite flips every one of them. */
 int crm_test_set_form(const char* name, int value, int reset);
@@ -97,6 +99,12 @@ int crm_test_unrelated_donor_blocks(const crm_ctx* ctx, long* blocks);
  * 0 keeps those launches, 1 (default) fuses every block of a dense panel that starts at a multiple of 128 variants; a block
  * that kept the copy does not count.  *blocks: the count so far. */
 int crm_test_fused_blocks(const crm_ctx* ctx, long* blocks);
+/* Blocks of this context's scans on the unrelated-donor form whose weighted Gram was formed straight from the per-donor pair
+ * products, the rotated S staying in LDS (wb_gram_fused.hip), instead of by the rotation launch and the Gram launch with the
+ * rotated S between them.  Form "wb_gram_fused": 0 keeps the two launches, 1 (default) fuses where one phenotype is scanned
+ * without model flags or permutation replay, the context count is even and the Gram has 65 to 128 rows.  *blocks: the count
+ * so far. */
+int crm_test_wb_gram_fused_blocks(const crm_ctx* ctx, long* blocks);
 /* Blocks of this context's scans on the unrelated-donor form whose null fits at rho = 0 read the position basis -- Phi'gx,
  * Phi'[y, W] and s_p(0), the assembly's own operands -- so that the rotation MixK(0)'(H'Gx) was not formed (scan_block.hip:
  * plan_rotations; taken where the kept positions are as many as the grid point's rank; form "rho0_positions" = 0: never).

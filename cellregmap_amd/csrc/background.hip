@@ -6,8 +6,8 @@
 // cols < n  (the reference's thin-SVD branch): the cols x cols Gram matrix of [E1, B] is formed
 //   once with the FP64-MFMA contraction kernel, rescaled per rho, diagonalised -- all grid points in
 //   one batch by the hand-written solver of eigh*.hip (tridiagonalisation, divide & conquer,
-//   back-transformation) -- and Q0 = hS V L^-1/2 is formed by the contraction kernel again; two Newton-Schulz steps
-//   (contractions only) restore orthonormality of the columns that belong to small
+//   back-transformation) -- and Q0 = hS V L^-1/2 is formed by the contraction kernel again; Newton-Schulz steps
+//   (contractions only) on (H Mix)'(H Mix) restore orthonormality of the columns that belong to small
 //   eigenvalues.  Columns with eigenvalue <= rel_tol * max are dropped: they are inert in
 //   every bilinear form of the path (weight (1-d) S + d == d, cancelled by the complement
 //   term) whereas the reference's SVD keeps them with S0 ~ 1e-29.
@@ -454,6 +454,55 @@ static int background_begin(crm_ctx* ctx, long n, const double* E1, int k1, cons
     return CRM_OK;
 }
 
+// N = 1.5 I - 0.5 G (r x r, in the second half of dG), *err_out = max |G - I|
+static int defect_and_correction(crm_background* bg, crm_background_builder* bb, int r, double* err_out) {
+    hipStream_t st = bg->ctx->stream;
+    const long ldq = bg->ldq;
+    DevBuf &dG = bb->scratch[10], &dErr = bb->scratch[11];
+    double* Gq = dG.as<double>();
+    double* N = Gq + ldq * ldq;
+    dim3 grid((unsigned)((r + 255) / 256), (unsigned)r);
+    CRM_HIP(hipMemsetAsync(N, 0, sizeof(double) * ldq * ldq, st));
+    hipLaunchKernelGGL(newton_schulz_kernel, grid, dim3(256), 0, st, Gq, ldq, r, N, ldq, dErr.as<double>());
+    CRM_HIP(hipGetLastError());
+    std::vector<double> herr((size_t)grid.x * grid.y);
+    CRM_HIP(hipMemcpyAsync(herr.data(), dErr.ptr, sizeof(double) * herr.size(), hipMemcpyDeviceToHost, st));
+    CRM_HIP(hipStreamSynchronize(st));
+    double err = 0.0;
+    for (double e : herr) err = std::max(err, e);
+    *err_out = err;
+    return CRM_OK;
+}
+
+// Newton-Schulz on the columns of Q0(rho_i) themselves, in the cell axis: G = Q0'Q0 has entries of order one and no
+// cancellation, so it is known to rounding whatever the spectrum.  One check, and corrections while needed.
+static int polish_q0_in_cell_space(crm_background* bg, crm_background_builder* bb, int i) {
+    crm_ctx* ctx = bg->ctx;
+    hipStream_t st = ctx->stream;
+    const long n = bb->n, np = bb->np, ldq = bg->ldq;
+    const int r = bg->r[i];
+    if (r == 0) return CRM_OK;
+    DevBuf &dG = bb->scratch[10], &dQt = bb->scratch[12];
+    double* Gq = dG.as<double>();
+    double* N = Gq + ldq * ldq;
+    for (int pass = 0; pass < 3; pass++) {
+        CRM_TRY(contract(ctx, bg->Q0[i].as<double>(), ldq, bg->Q0[i].as<double>(), ldq, Gq, ldq, r, r, np));
+        double err = 0.0;
+        CRM_TRY(defect_and_correction(bg, bb, r, &err));
+        if (!(err < 0.5)) {
+            set_error("background: Q0 lost orthonormality at rho=%g (defect %g)", bg->rho[i], err);
+            return CRM_ERR_NUMERIC;
+        }
+        bg->ortho_defect[i] = err;
+        if (err < 2e-14 || pass == 2) break;
+        // Q0 <- Q0 N : contraction over r with X = Q0' (r x cells)
+        CRM_HIP(hipMemsetAsync(dQt.ptr, 0, sizeof(double) * ldq * np, st));
+        CRM_TRY(transpose(st, bg->Q0[i].as<double>(), ldq, n, r, dQt.as<double>(), np));
+        CRM_TRY(contract(ctx, dQt.as<double>(), np, N, ldq, bg->Q0[i].as<double>(), ldq, (int)n, r, round_up(r, GEMM_BK)));
+    }
+    return CRM_OK;
+}
+
 // ranks of all grid points known: buffers for every grid point; Q0 = H Mix and the polish for the owned ones
 static int background_complete(crm_background* bg, const int* r_all) {
     crm_background_builder* bb = bg->builder;
@@ -482,7 +531,7 @@ static int background_complete(crm_background* bg, const int* r_all) {
     bg->ldq = round_up(rmax, 128);
     const long ldq = bg->ldq;
     DevBuf &dH = bb->scratch[0], &dHt = bb->scratch[1], &dC = bb->scratch[2], &dMt = bb->scratch[9], &dG = bb->scratch[10],
-           &dErr = bb->scratch[11], &dQt = bb->scratch[12], &dT1 = bb->scratch[3];
+           &dErr = bb->scratch[11], &dQt = bb->scratch[12], &dT1 = bb->scratch[3], &dQ = bb->scratch[4];
     dG.release();
     dMt.release();
     if (thin) {
@@ -518,20 +567,6 @@ static int background_complete(crm_background* bg, const int* r_all) {
     trace.lap("  buffers of the grid points");
     double* Gq = dG.as<double>();
     double* N = Gq + ldq * ldq;
-    auto defect_and_correction = [&](int r, double* err_out) -> int {
-        // N = 1.5 I - 0.5 G, err = max |G - I|
-        dim3 grid((unsigned)((r + 255) / 256), (unsigned)r);
-        CRM_HIP(hipMemsetAsync(N, 0, sizeof(double) * ldq * ldq, st));
-        hipLaunchKernelGGL(newton_schulz_kernel, grid, dim3(256), 0, st, Gq, ldq, r, N, ldq, dErr.as<double>());
-        CRM_HIP(hipGetLastError());
-        std::vector<double> herr((size_t)grid.x * grid.y);
-        CRM_HIP(hipMemcpyAsync(herr.data(), dErr.ptr, sizeof(double) * herr.size(), hipMemcpyDeviceToHost, st));
-        CRM_HIP(hipStreamSynchronize(st));
-        double err = 0.0;
-        for (double e : herr) err = std::max(err, e);
-        *err_out = err;
-        return CRM_OK;
-    };
     for (int i : bb->mine) {
         const int r = bg->r[i];
         if (r == 0) continue;   // (an empty grid point: require_q0 just allocates zeros)
@@ -543,14 +578,12 @@ static int background_complete(crm_background* bg, const int* r_all) {
                                      cols, hipMemcpyDeviceToDevice, st));
             CRM_HIP(hipStreamSynchronize(st));
             bb->Mbuf[i].release();
-            // Newton-Schulz polish of the orthonormality, in the space of the half factor's columns:
-            // Q0'Q0 = Mix' (H'H) Mix with the Gram matrix C = H'H at hand, so a pass costs three products of
-            // order cols^2 r instead of n r^2; Q0 = H Mix is then formed once.  The Gram route loses
-            // orthonormality for small eigenvalues (defect ~ eps * S_max / S_j) and the path's complement
-            // terms (u'v - (Q0'u)'(Q0'v)) / d see any defect directly.
-            // First a look at the columns that belong to the 256 .. 383 smallest kept eigenvalues (the last ones: the defect of
-            // the Gram route is ~ eps |C| / sqrt(lambda_i lambda_j), largest there): 256 / r of the cost of a pass.
-            // Below 2e-13 the mixing matrix stays as the eigen-solver left it.
+            // Newton-Schulz polish of the orthonormality.  The Gram route loses orthonormality for small eigenvalues
+            // (defect ~ eps * S_max / S_j) and the path's complement terms (u'v - (Q0'u)'(Q0'v)) / d see any defect directly.
+            // First a look in the space of the half factor's columns, Q0'Q0 = Mix' (H'H) Mix with the Gram matrix C = H'H at
+            // hand, at the columns that belong to the 256 .. 383 smallest kept eigenvalues (the last ones: the defect of the
+            // Gram route is ~ eps |C| / sqrt(lambda_i lambda_j), largest there): 256 / r of the cost of three products of
+            // order cols^2 r.  Below 2e-13 the mixing matrix stays as the eigen-solver left it.
             {
                 // (offset on a tile boundary: the operand tiles of the contraction then end with the row, ldq % 128 == 0)
                 const int off = r > 256 ? (r - 256) / 128 * 128 : 0, ns = r - off;
@@ -567,13 +600,18 @@ static int background_complete(crm_background* bg, const int* r_all) {
                 if (trace.on) fprintf(stderr, "[crm background]     rho[%d] defect over the last %d columns: %.3g\n", i, ns, est);
                 bg->ortho_defect[i] = est;
                 if (est < 2e-13) continue;
-                if (ns < r) CRM_HIP(hipMemsetAsync(dT1.ptr, 0, sizeof(double) * cp * ldq, st));
             }
+            // The correction itself is taken in the cell axis, G = (H Mix)'(H Mix): the rounded C carries an error of
+            // eps |C| of its own, which Mix' C Mix amplifies by 1 / S_min exactly like the defect it is meant to show -- a
+            // polish against C converges to Mix' C Mix = I and leaves Q0'Q0 - I where it was (1e-11 at S_max = 5e5 S_min,
+            // 1e-7 at 1e10; tests/test_gpu_background_reference.py).  The product H Mix only carries |Mix| ~ S_min^-1/2.
+            CRM_TRY(dQ.ensure(sizeof(double) * np * ldq));
+            CRM_HIP(hipMemsetAsync(dQ.ptr, 0, sizeof(double) * np * ldq, st));
             for (int pass = 0; pass < 3; pass++) {
-                CRM_TRY(contract(ctx, dC.as<double>(), cp, Mix, ldq, dT1.as<double>(), ldq, (int)cols, r, cp));   // C Mix
-                CRM_TRY(contract(ctx, Mix, ldq, dT1.as<double>(), ldq, Gq, ldq, r, r, cp));                         // Mix' C Mix
+                CRM_TRY(contract(ctx, bg->Ht.as<double>(), np, Mix, ldq, dQ.as<double>(), ldq, (int)n, r, cp));    // H Mix
+                CRM_TRY(contract(ctx, dQ.as<double>(), ldq, dQ.as<double>(), ldq, Gq, ldq, r, r, np));            // (H Mix)'(H Mix)
                 double err = 0.0;
-                CRM_TRY(defect_and_correction(r, &err));
+                CRM_TRY(defect_and_correction(bg, bb, r, &err));
                 if (!(err < 0.5)) {
                     set_error("background: Q0 lost orthonormality at rho=%g (defect %g)", bg->rho[i], err);
                     return CRM_ERR_NUMERIC;
@@ -585,8 +623,8 @@ static int background_complete(crm_background* bg, const int* r_all) {
                 CRM_HIP(hipMemsetAsync(dQt.ptr, 0, sizeof(double) * ldq * cp, st));
                 CRM_TRY(transpose(st, Mix, ldq, cols, r, dQt.as<double>(), cp));
                 CRM_TRY(contract(ctx, dQt.as<double>(), cp, N, ldq, Mix, ldq, (int)cols, r, round_up(r, GEMM_BK)));
-                // the step squares the defect: from below 1e-8 it lands at rounding level (measured 3e-14 ..
-                // 7e-13 before, 1e-15 .. 6e-15 after at config 3) -- no second look needed
+                // the step squares the defect: from below 1e-8 it lands at the level G itself is known to -- no second look
+                // needed
                 if (err < 1e-8) {
                     bg->ortho_defect[i] = err * err + 8e-15;
                     break;
@@ -600,21 +638,7 @@ static int background_complete(crm_background* bg, const int* r_all) {
             bg->q0_ready[i] = true;
             // eigenvectors of the n x n route: orthonormal to ~1e-14 sqrt(n) as they come; one check, and a
             // correction if ever needed
-            for (int pass = 0; pass < 3; pass++) {
-                CRM_TRY(contract(ctx, bg->Q0[i].as<double>(), ldq, bg->Q0[i].as<double>(), ldq, Gq, ldq, r, r, np));
-                double err = 0.0;
-                CRM_TRY(defect_and_correction(r, &err));
-                if (!(err < 0.5)) {
-                    set_error("background: Q0 lost orthonormality at rho=%g (defect %g)", bg->rho[i], err);
-                    return CRM_ERR_NUMERIC;
-                }
-                bg->ortho_defect[i] = err;
-                if (err < 2e-14 || pass == 2) break;
-                // Q0 <- Q0 N : contraction over r with X = Q0' (r x cells)
-                CRM_HIP(hipMemsetAsync(dQt.ptr, 0, sizeof(double) * ldq * np, st));
-                CRM_TRY(transpose(st, bg->Q0[i].as<double>(), ldq, n, r, dQt.as<double>(), np));
-                CRM_TRY(contract(ctx, dQt.as<double>(), np, N, ldq, bg->Q0[i].as<double>(), ldq, (int)n, r, round_up(r, GEMM_BK)));
-            }
+            CRM_TRY(polish_q0_in_cell_space(bg, bb, i));
         }
     }
     CRM_HIP(hipStreamSynchronize(st));
@@ -654,15 +678,22 @@ static int background_seal(crm_background* bg) {
         if (!(smax <= 1e6 * smin)) bg->fast_T = false;
     }
     const bool thin = bb->thin;
+    if (!bg->fast_T && thin) {
+        // the scan will rotate with Q0 itself: form all of them now, then drop H and the mixing matrices.  Each Q0 = H Mix
+        // carries the rounding of a product with |Mix| ~ S_min^-1/2 and what the polish of Mix could not see at such a
+        // spectrum; with the mixing matrices gone nothing ties Q0 to them, so its columns are set right themselves (imported
+        // grid points too: every process forms the same Q0 from the same H and Mix and corrects it the same way)
+        for (int k : {2, 3, 4}) bb->scratch[k].release();   // (C and the polish's products with it: not needed any more)
+        bg->fast_T = true;
+        int rc = crm_background_require_q0(bg, -1);
+        bg->fast_T = false;
+        for (int i = 0; rc == CRM_OK && i < bg->nrho; i++) rc = polish_q0_in_cell_space(bg, bb, i);
+        if (rc != CRM_OK) return rc;
+        CRM_HIP(hipStreamSynchronize(bg->ctx->stream));
+    }
     delete bb;
     bg->builder = nullptr;
     if (!bg->fast_T) {
-        if (thin) {   // the scan will rotate with Q0 itself: form all of them now, then drop H and the mixing matrices
-            bg->fast_T = true;
-            const int rc = crm_background_require_q0(bg, -1);
-            bg->fast_T = false;
-            CRM_TRY(rc);
-        }
         bg->H.release();
         bg->Ht.release();
         for (int i = 0; i < bg->nrho; i++) bg->Mix[i].release();

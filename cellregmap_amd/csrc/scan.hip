@@ -147,16 +147,8 @@ static int scan_core(const std::vector<crm_gene*>& genes, crm_panel* panel, long
         size_t j = i + 1;
         while (j < near.size() && near[j] <= near[j - 1] + 32) j++;
         const long off = near[i], len = near[j - 1] - near[i] + 1;
-        std::vector<ScanOut> shifted(outs);
-        for (ScanOut& o : shifted) {
-            auto at = [&](double* p, long stride) { return p ? p + off * stride : nullptr; };
-            o.pv = at(o.pv, 1); o.rho1 = at(o.rho1, 1); o.e2 = at(o.e2, 1); o.g2 = at(o.g2, 1); o.eps2 = at(o.eps2, 1);
-            o.Q = at(o.Q, 1); o.lml = at(o.lml, 1); o.delta = at(o.delta, 1); o.scale = at(o.scale, 1);
-            o.lambda = at(o.lambda, k0); o.F = at(o.F, (long)k0 * k0); o.liu = at(o.liu, 1); o.logp = at(o.logp, 1);
-            if (o.ifault) o.ifault += off;
-            if (o.status) o.status += off;
-            if (o.flags) o.flags += off;
-        }
+        std::vector<ScanOut> shifted;
+        for (const ScanOut& o : outs) shifted.push_back(o.advanced(off, k0));   // (every array: scan_pass.h)
         CRM_TRY(scan_pass(genes, panel, first + off, len, idx_E, idx_G, shifted, false, nullptr));
         i = j;
     }

@@ -39,6 +39,21 @@ struct ScanOut {  // per-gene output bases (host), each `count` long (lambda: co
     bool exact = false;      // the p-value by the exact tail method (tail_pvalue.hip) instead of Davies / Liu
     double* logp = nullptr;  // exact method: log p and CRM_TAIL_* status per variant
     int* status = nullptr;
+
+    // The same outputs from variant `off` on: what scan_core hands to the dense repeat of a run of variants.  EVERY
+    // per-variant array of the list above is shifted here and nowhere else -- a field added to the list gets its line in
+    // `advanced` with it, or the repeat writes it at the start of the call's range (as bound_Q / bound_p once were).
+    ScanOut advanced(long off, int k0) const {
+        ScanOut o = *this;
+        auto at = [off](auto* p, long stride) { return p ? p + off * stride : nullptr; };
+        o.pv = at(pv, 1); o.rho1 = at(rho1, 1); o.e2 = at(e2, 1); o.g2 = at(g2, 1); o.eps2 = at(eps2, 1);
+        o.Q = at(Q, 1); o.lml = at(lml, 1); o.delta = at(delta, 1); o.scale = at(scale, 1);
+        o.lambda = at(lambda, k0); o.F = at(F, (long)k0 * k0);
+        o.ifault = at(ifault, 1); o.liu = at(liu, 1); o.flags = at(flags, 1);
+        o.bound_Q = at(bound_Q, 1); o.bound_p = at(bound_p, 1);
+        o.logp = at(logp, 1); o.status = at(status, 1);
+        return o;
+    }
 };
 
 // How the rotated test direction A~ = Q0(rho*)'(g o E0) of step 6 is formed -- and with it the rotations of step 3 and the

@@ -20,6 +20,7 @@ from ._engine import (
     run_association_fast,
     run_association_many,
     run_interaction,
+    run_interaction_contexts,
     run_interaction_many,
     scan_association_many,
     scan_interaction_many,
@@ -46,6 +47,7 @@ __all__ = [
     "run_association_fast",
     "run_association_many",
     "run_interaction",
+    "run_interaction_contexts",
     "run_interaction_many",
     "scan_association_many",
     "scan_interaction_many",

@@ -587,6 +587,7 @@ _PROGRESS_CB = ctypes.CFUNCTYPE(None, ctypes.c_long, ctypes.c_long, ctypes.c_voi
 #: per-test outputs of the association scans' ``effects=True`` (crm_scan_association_effects), in the C-ABI's order
 _EFFECT_KEYS = ("beta", "beta_se", "alt_delta", "alt_scale", "log_pvalue", "effect_status")
 EFFECT_OK, EFFECT_G_IN_SPAN_W, EFFECT_NO_FIT, EFFECT_NON_FINITE = 0, 1, 2, 3   # include/crm_hip.h: CRM_EFFECT_*
+CONTEXT_OK, CONTEXT_COLLINEAR, CONTEXT_NO_FIT, CONTEXT_NON_FINITE = 0, 1, 2, 3   # include/crm_hip.h: CRM_CONTEXT_*
 
 
 def _effect_arrays(shape):
@@ -1156,6 +1157,101 @@ class CellRegMap:
         ``effects`` as in ``scan_association``; ``alt_delta`` is then the null model's delta."""
         return self._scan_association(G, True, return_stats, progress, effects)
 
+    # -- per-context fixed-effect GxC tests (cellregmap/test/test_fixed_gxe.py:79-102) -----------------
+    def _bind_context_gene(self, C, own):
+        """The phenotype bound for ``scan_interaction_contexts``: covariates = the basis ``U * s`` of the economic SVD of
+        ``[W, C]`` (what ``_lmm_fit`` hands over), context slot = C.  The most recent binding is kept (``own``: C is the
+        object's ``E``; other contexts are told apart by their content)."""
+        key = "E" if own else _digest(C)
+        kept = getattr(self, "_context_gene", None)
+        if kept is not None and kept[0] == key:
+            return kept[1]
+        lib = _lib.load()
+        U, s, _ = _economic_svd(np.concatenate([self._W, C], axis=1))
+        X0, y, Cc = _lib.f64(U * s), _lib.f64(self._y), _lib.f64(C)
+        h = ctypes.c_void_p()
+        _lib.check(lib.crm_gene_create(self._bg.handle, _lib.ptr(y), _lib.ptr(X0), X0.shape[1], _lib.ptr(Cc), C.shape[1],
+                                       ctypes.byref(h)))
+        if kept is not None:
+            kept[2]()       # (release the binding it replaces)
+        self._context_gene = (key, h, weakref.finalize(self, _release_gene, lib, h, self._bg))
+        return h
+
+    def scan_interaction_contexts(self, G, contexts=None, fast: bool = True, return_stats: bool = False, progress=False):
+        """In which context does a variant's effect change, by how much, and with what p-value?  Per variant g and per
+        column C_j of ``contexts`` (n x k; ``None``: the object's ``E``) a one-degree-of-freedom likelihood-ratio test of
+        ``x_j = g * C_j`` beside the fixed effects ``[W, C, g]`` -- the analysis the reference poses in its
+        test_fixed_gxe.py ("Test 2": the ML null ``LMM(y, [M, g, E])``, then a FastScanner pass over ``E * g`` and
+        ``lrt_pvalues``), for all variants in batched kernels.
+
+        The gene-level null ``LMM(y, [W, C], QS(rho))`` is fitted by ML over the rho grid (first strict maximum, as
+        ``scan_association`` picks its own); every variant is then tested at that rho.  ``fast=True`` freezes the variance
+        ratio delta at the gene-level fit; ``fast=False`` refits it per variant under ``[W, C, g]`` (what the reference's
+        Test 2 does).  ``[W, C]`` enters through the basis of its economic SVD, so a ``W`` that already holds some context
+        columns is no error; its rank may be 128 at most, k 256.
+
+        ``G``: n x p (array-like; many variants are streamed in column chunks) or a ``GenotypePanel``.
+
+        Returns ``(pv, info)``: ``pv`` is p x k; ``info`` holds ``rho1, e2, g2, eps2`` of the gene-level null (one entry
+        each) and, p x k, ``beta`` (the coefficient of ``g * C_j``), ``beta_se``, ``log_pvalue`` (natural log, not
+        clipped: finite where ``pv`` sits at 2.2e-308) and ``status`` (``CONTEXT_OK``; ``CONTEXT_COLLINEAR``: the
+        candidate lies in the span of ``[W, C, g]`` -- a constant context column -- or g in the span of ``[W, C]``:
+        ``pv = 1 - eps``, beta and beta_se NaN; ``CONTEXT_NO_FIT``; ``CONTEXT_NON_FINITE``).  ``return_stats=True`` adds
+        ``null_lml`` and ``null_delta`` (per variant), ``alt_lml`` (p x k), ``gene_null_lml`` and ``gene_null_delta``."""
+        lib = _lib.load()
+        C = self._E0 if contexts is None else np.asarray(contexts, float)
+        if C.ndim != 2 or C.shape[0] != self.n_samples or C.shape[1] < 1:
+            raise ValueError(f"contexts must be {self.n_samples} x k, got {C.shape}")
+        if not (np.all(np.isfinite(C)) and np.all(np.isfinite(self._W)) and np.all(np.isfinite(self._y))):
+            raise ValueError("There are non-finite values in the outcome, the covariates or the contexts.")
+        k = C.shape[1]
+        p_user = None
+        if not isinstance(G, GenotypePanel) and np.asarray(G).ndim == 2 and np.asarray(G).shape[1] == 0:
+            p_user = 0   # no variants: the gene-level null is still fitted and reported
+            G = np.zeros((np.asarray(G).shape[0], 1))
+        chunks = None
+        if not isinstance(G, GenotypePanel):
+            G = np.asarray(G, float)
+            if p_user is None and G.ndim == 2 and G.shape[0] == self.n_samples and G.shape[1] >= 2 * _stream_chunk() > 0:
+                chunks, p = self._streamed_panels(G), G.shape[1]
+        if chunks is None:
+            panel = self._panel(G)
+            p = panel.shape[1] if p_user is None else p_user
+        out = {key: np.empty((p, k)) for key in ("pv", "alt_lml", "beta", "beta_se", "log_pvalue")}
+        out["status"] = np.empty((p, k), np.int32)
+        out["null_lml"], out["null_delta"] = np.empty(p), np.empty(p)
+        null = np.empty(6)
+        order = ("pv", "alt_lml", "beta", "beta_se", "log_pvalue", "status", "null_lml", "null_delta")
+
+        def scan(gene, panel, count, j0=0):
+            _lib.check(lib.crm_scan_interaction_contexts(gene, panel.handle, 0, count, int(bool(fast)),
+                                                         *[_lib.ptr(out[key][j0:j0 + count]) for key in order], _lib.ptr(null)))
+
+        try:
+            gene = self._bind_context_gene(C, contexts is None)
+            if chunks is None:
+                with _progress(self._device, progress, p):
+                    scan(gene, panel, p)
+            else:
+                progress, bar = self._one_bar(progress, p)
+                try:
+                    for j0, j1, panel in chunks:
+                        with _progress(self._device, progress, j1 - j0, offset=j0, grand_total=p):
+                            scan(gene, panel, j1 - j0, j0)
+                finally:
+                    if bar is not None:
+                        bar.close()
+        finally:
+            if chunks is not None:
+                chunks.close()
+        info = {"rho1": np.asarray([null[0]], float), "e2": np.asarray([null[1]], float),
+                "g2": np.asarray([null[2]], float), "eps2": np.asarray([null[3]], float),
+                "beta": out["beta"], "beta_se": out["beta_se"], "log_pvalue": out["log_pvalue"], "status": out["status"]}
+        if return_stats:
+            info.update(null_lml=out["null_lml"], null_delta=out["null_delta"], alt_lml=out["alt_lml"],
+                        gene_null_lml=null[4], gene_null_delta=null[5])
+        return out["pv"], info
+
     # -- effect sizes (_cellregmap.py:137-244) -----------------------------------------------------
     def _lmm_fit(self, bg, M):
         """Best restricted fit of LMM(y, M, QS(rho)) over the grid of ``bg``:
@@ -1695,6 +1791,18 @@ def run_interaction(y, E, G, W=None, E1=None, E2=None, hK=None, idx_G=None, *, d
     crm = CellRegMap(y=y, E=E, W=W, E1=E1, Ls=Ls, device=device)
     pv = crm.scan_interaction(G, idx_G, pvalue=pvalue)
     return pv
+
+
+def run_interaction_contexts(y, E, G, W=None, E1=None, E2=None, hK=None, *, contexts=None, fast=True, device=0):
+    """Per-context fixed-effect GxC tests with the model of ``run_interaction`` (same ``E1`` / ``E2`` / ``hK`` defaults):
+    ``CellRegMap.scan_interaction_contexts(G, contexts=contexts, fast=fast)`` -- ``(pv (p x k), info)``."""
+    if E1 is None:
+        E1 = E
+    if E2 is None:
+        E2 = E
+    Ls = None if hK is None else get_L_values(hK, E2)
+    crm = CellRegMap(y=y, E=E, W=W, E1=E1, Ls=Ls, device=device)
+    return crm.scan_interaction_contexts(G, contexts=contexts, fast=fast)
 
 
 def run_association(y, W, E, G, hK=None, *, device=0, effects=False):

@@ -73,6 +73,7 @@ SIGNATURES = {
     "crm_scan_association_effects": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int] + [vp] * 9),
     "crm_scan_association_multi_effects": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int]
                                            + [vp] * 9),
+    "crm_scan_interaction_contexts": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int] + [vp] * 9),
     "crm_lmm_fit": (ctypes.c_int, [vp, ctypes.c_int, vp, vp]),
     "crm_cov_solve": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp, ctypes.c_int, vp]),
     "crm_effects_multi": (ctypes.c_int, [vp, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp,
@@ -123,6 +124,7 @@ SIGNATURES = {
     "crm_test_davies_trace": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]),
     "crm_test_tail_pvalue": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp]),
     "crm_test_lrt_logp": (ctypes.c_int, [vp, ctypes.c_int, vp, vp]),
+    "crm_test_set_context_budget": (ctypes.c_int, [vp, ctypes.c_long]),
 }
 
 _lib = None

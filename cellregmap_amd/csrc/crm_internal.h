@@ -170,8 +170,10 @@ struct crm_ctx {
     crm::DevBuf ws_Pd;                // ... the per-donor products against the symmetric pair features (ScanPass::folded_S,
                                       // unfolded_AH)
     crm::DevBuf ws_Anone;             // a row of zeros: A~ of the tests whose fit has no kinship term (AssembleArgs::A_none)
+    crm::DevBuf ws_ctxE, ws_ctxP;     // per-context tests (context_host.hip): the contexts as operands; plain tables, weights, results
+    size_t context_budget = 0;        // bytes the rotated candidates of a sub-range may take (0: the default; crm_test_set_context_budget)
     std::vector<crm::DevBuf*> all_bufs() {
-        return {&sync_counters, &ws_xwide, &ws_Tcut, &ws_S, &ws_S2, &ws_Gk, &ws_Gkt, &ws_Pd, &ws_WB, &ws_Anone, &ws_AH, &ws_XG, &ws_TH, &ws_T, &ws_A, &ws_Gb, &ws_Gx, &ws_Gs, &ws_G2, &ws_GG, &ws_Gt, &ws_Z, &ws_small, &ws_probs, &ws_F, &ws_Gext};
+        return {&sync_counters, &ws_ctxE, &ws_ctxP, &ws_xwide, &ws_Tcut, &ws_S, &ws_S2, &ws_Gk, &ws_Gkt, &ws_Pd, &ws_WB, &ws_Anone, &ws_AH, &ws_XG, &ws_TH, &ws_T, &ws_A, &ws_Gb, &ws_Gx, &ws_Gs, &ws_G2, &ws_GG, &ws_Gt, &ws_Z, &ws_small, &ws_probs, &ws_F, &ws_Gext};
     }
 };
 

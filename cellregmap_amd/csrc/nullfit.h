@@ -125,6 +125,39 @@ int launch_assoc_effects(hipStream_t st, const AssocEffectsGene* genes_dev, int 
 // logp[i] = log erfc(sqrt(lrs[i] / 2)), lrs below 0 taken as 0 (the effects kernels' statement; test hook)
 int launch_lrt_logp(hipStream_t st, const double* lrs, int count, double* logp);
 
+// ---- per-context fixed-effect tests (context_lrt.hip) ----------------------------------------------
+// One launch over a sub-range of variants.  Variant b tests its k candidates x_j = g_b o C_j, one at a time, beside
+// X = [X0, g_b] at the variance ratio delta[b]; every n-length product arrives rotated (over the spectrum of Sigma(rho*))
+// or as a plain cell-space table.
+struct ContextLrtArgs {
+    const double* Tx; long tx_slab, ldT;   // candidate j of variant b: Tx + b tx_slab + j ldT, r entries: Q0(rho*)'(g_b o C_j)
+    const double* Tg; long ldTg;           // row b: Q0(rho*)'g_b
+    const double* tX; long ldW;            // [c x ldW] rows Q0(rho*)'X0_u
+    const double* ty;                      // [r]
+    const double* S0;                      // [r]
+    int r, c, k;
+    long n;
+    const double* WW; const double* Wy; double yy;                        // X0'X0 [c x c], X0'y [c], y'y
+    const double* gg; const double* gy; const double* gW; long ld_gW;     // per variant: g'g, g'y, g'X0
+    const double* xXy; long ld_xXy;        // row b k + j: column 0 x_j'y, columns 1 .. c x_j'X0_u
+    const double* xx; long ld_xx;          // row b, column j: x_j'x_j
+    const double* xg; long ld_xg;          // row b, column j: x_j'g_b
+    const double* delta;                   // [variants]
+    const int* drop;                       // [variants] 1: the scan's rank rule dropped g_b from [X0, g_b]; null: decided here
+    double* phi; long ld_phi;              // scratch, row b: r weights
+    // outputs: per candidate (index b k + j), per variant
+    double* pvalue; double* alt_lml; double* beta; double* beta_se; double* logp; int* status;
+    double* null_lml;
+};
+size_t context_lrt_lds_bytes(int c);
+int launch_context_lrt(hipStream_t st, const ContextLrtArgs& a, int variants);
+// Cq[i, j] = E[i, j], C2[i, j] = E[i, j]^2 for j < k, zeros up to ld_out: the contexts as the Khatri-Rao operand and as the
+// right-hand operands of the plain products x_j'g = (g o g)'C_j, x_j'x_j = (g o g)'C_j^2
+int launch_context_operands(hipStream_t st, const double* E, long lde, long cells_pad, int k, double* Cq, double* C2, long ld_out);
+// delta[b] and drop[b] of a sub-block: the gene's delta0 (trial == null), or the alt fits' own
+int launch_context_deltas(hipStream_t st, const NullFitTrial* trial, const int* g_drop, double delta0, int variants, double* delta,
+                          int* drop);
+
 // ---- small per-block kernels (blockops.hip) ----------------------------------------------------
 // gg, gy, gW for a block of variants: column reductions of G (cells x ldg), deterministic.
 int launch_variant_stats(hipStream_t st, const double* G, long ldg, long cells, int variants,

@@ -333,6 +333,40 @@ int crm_scan_association_multi_effects(crm_gene* const* genes, int ngenes, crm_p
                                        double* out_beta, double* out_se, double* out_delta, double* out_scale,
                                        double* out_logp, int* out_status);
 
+/* ---- per-context fixed-effect GxC tests: in WHICH context does a variant's effect change, by how much?  The reference
+ * poses the analysis in cellregmap/test/test_fixed_gxe.py:79-102 ("Test 2") with the pieces of scan_association_fast
+ * (_cellregmap.py:246-314) and lrt_pvalues (:443-469): per variant g the ML null LMM(y, [M, g, E]) and one FastScanner pass
+ * over the columns of E * g, each a one-degree-of-freedom LRT.  Here, for variants [first, first + count) of the panel and
+ * the k = k0 contexts C the gene was bound with (its context slot):
+ *   gene-level null   ML fit of LMM(y, X0, QS(rho)) over the grid, first strictly larger lml, X0 = the gene's covariates --
+ *                     bind the gene with a basis of span([W, C]) (U diag(s) of the thin SVD, as for every scan), rank <= 128
+ *   per variant       H0: X = [X0, g] at rho*.  fast != 0: delta_i = the gene-level delta (the FastScanner's frozen ratio);
+ *                     fast == 0: delta_i refitted per variant (crm_scan_association's refit; what Test 2 does)
+ *   per context j     H1: [X, x_j], x_j = g o C_j, delta frozen at delta_i, beta and one scale re-estimated in closed form
+ * Outputs (any may be NULL): count x k row-major --
+ *   out_pvalue      lrt_pvalues(null_lml_i, alt_lml_ij, 1) with its clips
+ *   out_alt_lml     the ML log-likelihood of H1_j
+ *   out_beta        the coefficient of x_j;  out_beta_se  sqrt(scale1_j / d_j), d_j the Schur complement of x_j against X
+ *   out_logp        natural log of erfc(sqrt(lrs / 2)), lrs = max(2 (alt - null), 0), no clip: finite where p underflows
+ *   out_status      CRM_CONTEXT_OK; COLLINEAR: x_j lies in the span of [X0, g] (d_j <= 1e-12 x_j'K^-1x_j, the rule of the
+ *                   FastScanner form here; a constant context column, say) or g itself in the span of X0 (all k entries):
+ *                   p = 1 - 2.220446049250313e-16, alt lml = the variant's null lml, beta = beta_se = NaN, log p = 0;
+ *                   NO_FIT: X0'K^-1X0 not positive definite at delta_i (everything NaN); NON_FINITE: a result is not finite
+ * count entries: out_null_lml (the ML log-likelihood of H0 at delta_i), out_null_delta (delta_i);
+ * out_null: the 6 doubles of crm_scan_association for the gene-level null {rho1, e2, g2, eps2, lml, delta}.
+ * Direct route only: the rotated candidates Q0(rho*)'(g o C_j) come from the Khatri-Rao contraction over all cells in
+ * sub-ranges of a block that keep them within a byte budget; donor-constant panels are expanded block by block.
+ * CRM_ERR_ARG: null handles, gene and panel on different contexts or cell counts, variants outside the panel;
+ * CRM_ERR_UNSUPPORTED: more than 256 contexts or 128 covariate columns (crm_gene_create refuses such a gene already), or a
+ * scan already running on the context. */
+#define CRM_CONTEXT_OK 0
+#define CRM_CONTEXT_COLLINEAR 1
+#define CRM_CONTEXT_NO_FIT 2
+#define CRM_CONTEXT_NON_FINITE 3
+int crm_scan_interaction_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int fast, double* out_pvalue,
+                                  double* out_alt_lml, double* out_beta, double* out_beta_se, double* out_logp,
+                                  int* out_status, double* out_null_lml, double* out_null_delta, double* out_null);
+
 /* ---- effect sizes: the device operations behind predict_interaction (_cellregmap.py:137-205) and
  * estimate_aggregate_environment (:207-244).
  * crm_lmm_fit: LMM(y, M, QS(rho), restricted).fit() for every grid point of the gene's background

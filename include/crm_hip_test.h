@@ -157,6 +157,11 @@ int crm_test_tail_pvalue(crm_ctx* ctx, int count, int k, const double* Q, const 
 /* The log p-value of the association effects calls (out_logp) for `count` likelihood-ratio statistics. */
 int crm_test_lrt_logp(crm_ctx* ctx, int count, const double* lrs, double* logp);
 
+/* Bytes the rotated candidates Q0(rho*)'(g o C_j) of one sub-range of crm_scan_interaction_contexts may take (a block of
+ * variants is cut into sub-ranges of at least one variant that stay within it); 0 restores the default of 8 GB.  The
+ * results do not depend on it, bit for bit. */
+int crm_test_set_context_budget(crm_ctx* ctx, long bytes);
+
 /* The background constructor's symmetric eigen-solver on `batch` host matrices A (dim x dim each, row-major,
  * tight): lam (batch x dim, ascending), Z (batch x dim x dim, column j = eigenvector j; may be NULL).
  * stage 0: the whole solver; 1: tridiagonalisation only (d_out / e_out: batch x dim diagonals and

@@ -21,6 +21,7 @@ from ._engine import (
     run_association_many,
     run_interaction,
     run_interaction_contexts,
+    run_interaction_contexts_joint,
     run_interaction_many,
     scan_association_many,
     scan_interaction_many,
@@ -48,6 +49,7 @@ __all__ = [
     "run_association_many",
     "run_interaction",
     "run_interaction_contexts",
+    "run_interaction_contexts_joint",
     "run_interaction_many",
     "scan_association_many",
     "scan_interaction_many",

@@ -1198,6 +1198,20 @@ class CellRegMap:
         candidate lies in the span of ``[W, C, g]`` -- a constant context column -- or g in the span of ``[W, C]``:
         ``pv = 1 - eps``, beta and beta_se NaN; ``CONTEXT_NO_FIT``; ``CONTEXT_NON_FINITE``).  ``return_stats=True`` adds
         ``null_lml`` and ``null_delta`` (per variant), ``alt_lml`` (p x k), ``gene_null_lml`` and ``gene_null_delta``."""
+        out, null = self._scan_contexts(G, contexts, fast, progress, joint=False)
+        info = {"rho1": np.asarray([null[0]], float), "e2": np.asarray([null[1]], float),
+                "g2": np.asarray([null[2]], float), "eps2": np.asarray([null[3]], float),
+                "beta": out["beta"], "beta_se": out["beta_se"], "log_pvalue": out["log_pvalue"], "status": out["status"]}
+        if return_stats:
+            info.update(null_lml=out["null_lml"], null_delta=out["null_delta"], alt_lml=out["alt_lml"],
+                        gene_null_lml=null[4], gene_null_delta=null[5])
+        return out["pv"], info
+
+    def _scan_contexts(self, G, contexts, fast, progress, joint):
+        """The body of ``scan_interaction_contexts`` (``joint=False``: crm_scan_interaction_contexts, every result p x k)
+        and ``scan_interaction_contexts_joint`` (crm_scan_interaction_contexts_joint: one test per variant): argument
+        checks, the kept gene binding, streaming of host matrices, the empty panel.  Returns (arrays by name, the six
+        numbers of the gene-level null)."""
         lib = _lib.load()
         C = self._E0 if contexts is None else np.asarray(contexts, float)
         if C.ndim != 2 or C.shape[0] != self.n_samples or C.shape[1] < 1:
@@ -1217,15 +1231,23 @@ class CellRegMap:
         if chunks is None:
             panel = self._panel(G)
             p = panel.shape[1] if p_user is None else p_user
-        out = {key: np.empty((p, k)) for key in ("pv", "alt_lml", "beta", "beta_se", "log_pvalue")}
-        out["status"] = np.empty((p, k), np.int32)
+        if joint:
+            out = {"pv": np.empty(p), "log_pvalue": np.empty(p), "alt_lml": np.empty(p), "dof": np.empty(p, np.int32),
+                   "beta": np.empty((p, k)), "beta_se": np.empty((p, k)), "dropped": np.empty((p, k), np.int32),
+                   "status": np.empty(p, np.int32)}
+            order = ("pv", "log_pvalue", "alt_lml", "dof", "beta", "beta_se", "dropped", "status", "null_lml", "null_delta")
+            entry = lib.crm_scan_interaction_contexts_joint
+        else:
+            out = {key: np.empty((p, k)) for key in ("pv", "alt_lml", "beta", "beta_se", "log_pvalue")}
+            out["status"] = np.empty((p, k), np.int32)
+            order = ("pv", "alt_lml", "beta", "beta_se", "log_pvalue", "status", "null_lml", "null_delta")
+            entry = lib.crm_scan_interaction_contexts
         out["null_lml"], out["null_delta"] = np.empty(p), np.empty(p)
         null = np.empty(6)
-        order = ("pv", "alt_lml", "beta", "beta_se", "log_pvalue", "status", "null_lml", "null_delta")
 
         def scan(gene, panel, count, j0=0):
-            _lib.check(lib.crm_scan_interaction_contexts(gene, panel.handle, 0, count, int(bool(fast)),
-                                                         *[_lib.ptr(out[key][j0:j0 + count]) for key in order], _lib.ptr(null)))
+            _lib.check(entry(gene, panel.handle, 0, count, int(bool(fast)),
+                             *[_lib.ptr(out[key][j0:j0 + count]) for key in order], _lib.ptr(null)))
 
         try:
             gene = self._bind_context_gene(C, contexts is None)
@@ -1244,9 +1266,35 @@ class CellRegMap:
         finally:
             if chunks is not None:
                 chunks.close()
+        return out, null
+
+    def scan_interaction_contexts_joint(self, G, contexts=None, fast: bool = True, return_stats: bool = False, progress=False):
+        """Is there any fixed-effect GxC at a variant?  Per variant g ONE likelihood-ratio test of all k columns
+        ``g * C_j`` of ``contexts`` (n x k; ``None``: the object's ``E``) at once beside ``[W, C, g]``, k degrees of
+        freedom -- the multi-environment LRT the interaction score test is compared against, and the joint sibling of
+        ``scan_interaction_contexts``: no Bonferroni step over k per-context p-values, and each context's effect
+        adjusted for the others.  With glimix-core it is the ML null ``LMM(y, [M, g, E])``, the
+        alternative ``LMM(y, [M, g, E, E * g])`` at the null's delta and ``lrt_pvalues(lml0, lml1, k)``.
+
+        The gene-level null, the per-variant null and ``fast`` are ``scan_interaction_contexts``'s, bit for bit.
+        Candidates that lie in the span of ``[W, C, g]`` and the candidates before them (a constant context column
+        beside an intercept; the last of a one-hot set) are dropped in column order and the test loses their degrees of
+        freedom.  At most 64 contexts; ``[W, C]`` of rank 128 at most.
+
+        ``G``: n x p (array-like; many variants are streamed in column chunks) or a ``GenotypePanel``.
+
+        Returns ``(pv, info)``: ``pv`` has p entries; ``info`` holds ``rho1, e2, g2, eps2`` of the gene-level null (one
+        entry each), per variant ``dof`` (candidates kept), ``log_pvalue`` (natural log, not clipped: finite where
+        ``pv`` sits at 2.2e-308) and ``status`` (``CONTEXT_OK``; ``CONTEXT_COLLINEAR``: nothing left to test -- every
+        candidate dropped or g in the span of ``[W, C]`` -- ``pv = 1 - eps``; ``CONTEXT_NO_FIT``;
+        ``CONTEXT_NON_FINITE``), and p x k ``beta`` (the joint coefficient of ``g * C_j``), ``beta_se`` (both NaN for a
+        dropped candidate) and ``dropped`` (bool).  ``return_stats=True`` adds ``null_lml``, ``null_delta`` and
+        ``alt_lml`` (per variant), ``gene_null_lml`` and ``gene_null_delta``."""
+        out, null = self._scan_contexts(G, contexts, fast, progress, joint=True)
         info = {"rho1": np.asarray([null[0]], float), "e2": np.asarray([null[1]], float),
                 "g2": np.asarray([null[2]], float), "eps2": np.asarray([null[3]], float),
-                "beta": out["beta"], "beta_se": out["beta_se"], "log_pvalue": out["log_pvalue"], "status": out["status"]}
+                "dof": out["dof"], "log_pvalue": out["log_pvalue"], "beta": out["beta"], "beta_se": out["beta_se"],
+                "dropped": out["dropped"].astype(bool), "status": out["status"]}
         if return_stats:
             info.update(null_lml=out["null_lml"], null_delta=out["null_delta"], alt_lml=out["alt_lml"],
                         gene_null_lml=null[4], gene_null_delta=null[5])
@@ -1803,6 +1851,18 @@ def run_interaction_contexts(y, E, G, W=None, E1=None, E2=None, hK=None, *, cont
     Ls = None if hK is None else get_L_values(hK, E2)
     crm = CellRegMap(y=y, E=E, W=W, E1=E1, Ls=Ls, device=device)
     return crm.scan_interaction_contexts(G, contexts=contexts, fast=fast)
+
+
+def run_interaction_contexts_joint(y, E, G, W=None, E1=None, E2=None, hK=None, *, contexts=None, fast=True, device=0):
+    """Joint fixed-effect GxC test with the model of ``run_interaction`` (same ``E1`` / ``E2`` / ``hK`` defaults):
+    ``CellRegMap.scan_interaction_contexts_joint(G, contexts=contexts, fast=fast)`` -- ``(pv (p,), info)``."""
+    if E1 is None:
+        E1 = E
+    if E2 is None:
+        E2 = E
+    Ls = None if hK is None else get_L_values(hK, E2)
+    crm = CellRegMap(y=y, E=E, W=W, E1=E1, Ls=Ls, device=device)
+    return crm.scan_interaction_contexts_joint(G, contexts=contexts, fast=fast)
 
 
 def run_association(y, W, E, G, hK=None, *, device=0, effects=False):

@@ -8,6 +8,10 @@
 // candidates T_x, against [y, X0] for x_j'[y, X0]; one launch of context_lrt.hip ends the sub-range.  T_x is the large
 // buffer (variants x k x ldq doubles: 8 GB for 4096 variants at 50 contexts and a spectrum of 5 000), so a block is cut
 // into sub-ranges that keep it within a byte budget, as the pair stage of the interaction scan sizes its own.
+//
+// The joint test of all k candidates (crm_scan_interaction_contexts_joint) runs the same body: one
+// more table per call (the context pair products C_i o C_j), one more plain product per block (x_i'x_j against it), and
+// context_joint.hip's launch in place of context_lrt.hip's.
 #include <algorithm>
 
 #include "nullfit.h"
@@ -23,6 +27,8 @@ struct ContextOut {
     double* pvalue; double* alt_lml; double* beta; double* beta_se; double* logp;
     int* status;
     double* null_lml; double* null_delta; double* null;
+    // joint test: pvalue, alt_lml, logp and status per variant, beta and beta_se per variant and context, and
+    bool joint; int* dof; int* dropped;
 };
 
 int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int fast, const ContextOut& out) {
@@ -46,6 +52,7 @@ int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int 
         set_error("context tests: the covariates and contexts span %d columns (supported 1..%d)", c, CRM_MAX_COV_XWIDE);
         return CRM_ERR_UNSUPPORTED;
     }
+    if (out.joint) CRM_TRY(context_joint_check(c, k));
     if (ctx->in_scan) {
         set_error("context tests: another scan is running on this context (started from a progress callback?)");
         return CRM_ERR_UNSUPPORTED;
@@ -59,6 +66,11 @@ int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int 
                                         round_up(std::max<long>(count, 1), 128));
     const long ldb = BLK + 128, ldT = ldq;
     const long ld_gW = round_up(c, 8), ld_p = round_up(1 + c, 8), ld_k = round_up(k, 8), ld_cq = round_up(k, 128);
+    const bool joint = out.joint;
+    const int npair = k * (k + 1) / 2;
+    const long ld_pp = joint ? round_up(npair, 128) : 0;
+    const bool v_global = joint && !context_joint_v_in_lds(c, k);
+    const long v_slab = (long)(c + 1) * k;
     // variants per sub-range: their rotated candidates stay within the budget
     const size_t budget = ctx->context_budget > 0 ? ctx->context_budget : CONTEXT_BUDGET;
     const int SUB = (int)std::min<size_t>((size_t)BLK, std::max<size_t>(budget / (sizeof(double) * (size_t)k * ldq), 1));
@@ -71,7 +83,7 @@ int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int 
         CRM_TRY(ctx->ws_GG.ensure(sizeof(double) * (size_t)np * ldb));
     }
     CRM_TRY(ctx->ws_A.ensure(sizeof(double) * (size_t)SUB * k * ldq));
-    CRM_TRY(ctx->ws_ctxE.ensure(sizeof(double) * 2 * (size_t)np * ld_cq));
+    CRM_TRY(ctx->ws_ctxE.ensure(sizeof(double) * (size_t)np * (2 * ld_cq + ld_pp)));
     size_t off = 0;
     auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
     const size_t o_gg = carve(sizeof(double) * BLK), o_gy = carve(sizeof(double) * BLK),
@@ -100,6 +112,8 @@ int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int 
                  o_delta = carve(sizeof(double) * BLK), o_cdrop = carve(sizeof(int) * BLK),
                  o_res = carve(sizeof(double) * 5 * tests), o_status = carve(sizeof(int) * tests),
                  o_nlml = carve(sizeof(double) * BLK);
+    const size_t o_xxp = carve(sizeof(double) * (size_t)BLK * ld_pp), o_V = carve(v_global ? sizeof(double) * (size_t)SUB * v_slab : 0),
+                 o_dof = carve(joint ? sizeof(int) * BLK : 0), o_dropped = carve(joint ? sizeof(int) * tests : 0);
     CRM_TRY(ctx->ws_ctxP.ensure(off));
     char* cp = ctx->ws_ctxP.as<char>();
     double* d_xXy = (double*)(cp + o_xXy);
@@ -110,7 +124,10 @@ int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int 
     double* d_res = (double*)(cp + o_res);
     int* d_status = (int*)(cp + o_status);
     double* d_nlml = (double*)(cp + o_nlml);
-    constexpr int SLOTS = 8;   // 0 T_g, 1 / 2 the squared block's products, 3 / 4 the two Khatri-Rao contractions
+    double* d_xxp = (double*)(cp + o_xxp);
+    int* d_dof = (int*)(cp + o_dof);
+    int* d_dropped = (int*)(cp + o_dropped);
+    constexpr int SLOTS = 8;   // 0 T_g, 1 / 2 the squared block's products, 3 / 4 the two Khatri-Rao contractions, 5 x_i'x_j (joint)
     CRM_TRY(ctx->ws_probs.ensure(sizeof(GemmProblem) * (CRM_MAX_RHO + SLOTS)));
     GemmProblem* d_probs = ctx->ws_probs.as<GemmProblem>();
     const double* d_y = gene->yW.as<double>();
@@ -166,6 +183,8 @@ int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int 
     double* Cq = ctx->ws_ctxE.as<double>();
     double* C2 = Cq + (size_t)np * ld_cq;
     CRM_TRY(launch_context_operands(st, gene->E0.as<double>(), gene->lde, np, k, Cq, C2, ld_cq));
+    double* CC = C2 + (size_t)np * ld_cq;   // joint: the pair products C_i o C_j, i >= j
+    if (joint) CRM_TRY(launch_context_pairs(st, gene->E0.as<double>(), gene->lde, np, k, CC, ld_pp));
     CRM_TRY(crm_background_require_q0(bg, ri));
     const int r = bg->r[ri];
 
@@ -179,6 +198,9 @@ int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int 
     ca.phi = (double*)(cp + o_phi); ca.ld_phi = ldq;
     ca.pvalue = d_res; ca.alt_lml = d_res + tests; ca.beta = d_res + 2 * tests; ca.beta_se = d_res + 3 * tests;
     ca.logp = d_res + 4 * tests; ca.status = d_status;
+    ContextJointArgs ja{};
+    ja.ld_xxp = ld_pp; ja.V = v_global ? (double*)(cp + o_V) : nullptr; ja.v_slab = v_slab; ja.v_in_lds = v_global ? 0 : 1;
+    ja.dof = d_dof; ja.dropped = d_dropped;
 
     for (long done = 0; done < count; done += BLK) {
         const int nb = (int)std::min<long>(BLK, count - done);
@@ -215,6 +237,14 @@ int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int 
         CRM_HIP(hipMemcpyAsync(d_probs, pr.data(), sizeof(GemmProblem) * 3, hipMemcpyHostToDevice, st));
         CRM_TRY(launch_gemm_tn(ctx, d_probs, 1, nb, (int)ldq, np, false, 0, 1, 0));
         CRM_TRY(launch_gemm_tn(ctx, d_probs + 1, 2, nb, k, np, false, 0, 1, 0));
+        if (joint) {
+            // x_i'x_j = (g o g)'(C_i o C_j), i >= j
+            GemmProblem& p5 = pr[5];
+            p5 = p2;
+            p5.Y = CC; p5.ldy = ld_pp; p5.C = d_xxp; p5.ldc = ld_pp; p5.N = npair;
+            CRM_HIP(hipMemcpyAsync(d_probs + 5, &p5, sizeof(GemmProblem), hipMemcpyHostToDevice, st));
+            CRM_TRY(launch_gemm_tn(ctx, d_probs + 5, 1, nb, npair, np, false, 0, 1, 0));
+        }
         if (!fast) CRM_TRY(launch_nullfit(st, alt, nb));
         CRM_TRY(launch_context_deltas(st, fast ? nullptr : d_trial, fast ? nullptr : d_drop, null.delta, nb, d_delta, d_cdrop));
         if (out.null_delta) CRM_HIP(hipMemcpyAsync(out.null_delta + done, d_delta, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
@@ -252,13 +282,29 @@ int scan_contexts(crm_gene* gene, crm_panel* panel, long first, long count, int 
             sa.gg = d_gg + b0; sa.gy = d_gy + b0; sa.gW = d_gW + (size_t)b0 * ld_gW;
             sa.xx = d_xx + (size_t)b0 * ld_k; sa.xg = d_xg + (size_t)b0 * ld_k;
             sa.delta = d_delta + b0; sa.drop = d_cdrop + b0; sa.null_lml = d_nlml + b0;
-            CRM_TRY(launch_context_lrt(st, sa, ns));
             const size_t at = (size_t)(done + b0) * k, cnt = (size_t)ns * k;
             double* const outs[5] = {out.pvalue, out.alt_lml, out.beta, out.beta_se, out.logp};
-            for (int q = 0; q < 5; q++)
-                if (outs[q])
-                    CRM_HIP(hipMemcpyAsync(outs[q] + at, d_res + (size_t)q * tests, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
-            if (out.status) CRM_HIP(hipMemcpyAsync(out.status + at, d_status, sizeof(int) * cnt, hipMemcpyDeviceToHost, st));
+            if (joint) {
+                ContextJointArgs sj = ja;
+                sj.base = sa;
+                sj.xxp = d_xxp + (size_t)b0 * ld_pp;
+                CRM_TRY(launch_context_joint(st, sj, ns));
+                for (int q = 0; q < 5; q++) {
+                    const bool each = q == 2 || q == 3;   // beta, beta_se: per variant and context
+                    if (outs[q])
+                        CRM_HIP(hipMemcpyAsync(outs[q] + (each ? at : (size_t)(done + b0)), d_res + (size_t)q * tests,
+                                               sizeof(double) * (each ? cnt : (size_t)ns), hipMemcpyDeviceToHost, st));
+                }
+                if (out.status) CRM_HIP(hipMemcpyAsync(out.status + done + b0, d_status, sizeof(int) * ns, hipMemcpyDeviceToHost, st));
+                if (out.dof) CRM_HIP(hipMemcpyAsync(out.dof + done + b0, d_dof, sizeof(int) * ns, hipMemcpyDeviceToHost, st));
+                if (out.dropped) CRM_HIP(hipMemcpyAsync(out.dropped + at, d_dropped, sizeof(int) * cnt, hipMemcpyDeviceToHost, st));
+            } else {
+                CRM_TRY(launch_context_lrt(st, sa, ns));
+                for (int q = 0; q < 5; q++)
+                    if (outs[q])
+                        CRM_HIP(hipMemcpyAsync(outs[q] + at, d_res + (size_t)q * tests, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+                if (out.status) CRM_HIP(hipMemcpyAsync(out.status + at, d_status, sizeof(int) * cnt, hipMemcpyDeviceToHost, st));
+            }
             CRM_HIP(hipStreamSynchronize(st));   // (the next sub-range writes the same buffers)
         }
         if (out.null_lml) CRM_HIP(hipMemcpyAsync(out.null_lml + done, d_nlml, sizeof(double) * nb, hipMemcpyDeviceToHost, st));
@@ -276,7 +322,18 @@ extern "C" int crm_scan_interaction_contexts(crm_gene* gene, crm_panel* panel, l
                                              double* out_null) {
     return crm::guarded_on("crm_scan_interaction_contexts", gene ? gene->ctx : nullptr, [&]() -> int {
     const ContextOut out{out_pvalue, out_alt_lml, out_beta, out_beta_se, out_logp, out_status, out_null_lml, out_null_delta,
-                         out_null};
+                         out_null, false, nullptr, nullptr};
+    return scan_contexts(gene, panel, first, count, fast, out);
+    });
+}
+
+extern "C" int crm_scan_interaction_contexts_joint(crm_gene* gene, crm_panel* panel, long first, long count, int fast,
+                                                   double* out_pvalue, double* out_logp, double* out_alt_lml, int* out_dof,
+                                                   double* out_beta, double* out_beta_se, int* out_dropped, int* out_status,
+                                                   double* out_null_lml, double* out_null_delta, double* out_null) {
+    return crm::guarded_on("crm_scan_interaction_contexts_joint", gene ? gene->ctx : nullptr, [&]() -> int {
+    const ContextOut out{out_pvalue, out_alt_lml, out_beta, out_beta_se, out_logp, out_status, out_null_lml, out_null_delta,
+                         out_null, true, out_dof, out_dropped};
     return scan_contexts(gene, panel, first, count, fast, out);
     });
 }

@@ -18,202 +18,44 @@
 // the rows are staged, w o T_x is never formed), B = 16 candidates, both staged through LDS in chunks of 32 spectrum
 // entries (rows contiguous along the spectrum: 256-byte runs per row).  Candidates beyond k and rows beyond c + 2 are
 // staged as zeros, so any k >= 1 and any r are served by the one form.
-#include "delta_search.h"
-#include "objects.h"
-#include "tile_gram.h"
+// Steps 1 to 3, the product scheme and the forward solves are stated once, in context_common.h: the joint test of all k
+// candidates (context_joint.hip) runs them too.
+#include "context_common.h"
 
 namespace crm {
 
+using namespace context_detail;
+
 namespace {
-
-constexpr double DBL_TINY = 2.2250738585072014e-308;   // numpy_sugar.epsilon.super_tiny
-constexpr int NG = 32;        // candidates per group (two 16-column MFMA tiles)
-constexpr int CH = 32;        // spectrum entries per staging step
-constexpr int LS = CH + 1;    // LDS row stride of the staged chunks
-constexpr int RTW = 3;        // 16-row tiles per wavefront: 4 x 3 x 16 = 192 >= CRM_MAX_COV_XWIDE + 2
-
-typedef double cl_v4d __attribute__((ext_vector_type(4)));
-
-// as assoc_effects.hip states it: log erfc(sqrt(lrs / 2)) without a clip
-__device__ inline double log_sf(double lrs) {
-    const double h = 0.5 * lrs;
-    const double x = sqrt(h);
-    if (x < 0.5) return log1p(-erf(x));
-    const double p = erfc(x);
-    return p > 1e-300 ? log(p) : log(erfcx(x)) - h;
-}
-
-__device__ inline double block_total(double v, double* red) {
-    const int tid = threadIdx.x;
-    red[tid] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    const double out = red[0];
-    __syncthreads();
-    return out;
-}
-
-// Pt[u][jj] = sum_s phi_s U_u[s] V_jj[s] for the R rows U = [tX; tg; ty] and the NG columns col(jj) (null: a column of
-// zeros); dacc (may be null): this thread's four partial sums of phi_s V_jj[s]^2, jj = tid / 32 + 8 i, over s = tid % 32 + 32 t.
-// zone: [Rp + NG][LS] while the chunks are staged, then Pt [Rp][NG] over the same memory.  Ends with a barrier.
-template <class Col>
-__device__ __forceinline__ void weighted_products(const ContextLrtArgs& a, const double* __restrict__ tg,
-                                                  const double* __restrict__ phi, int R, int Rp, double* zone, Col&& col,
-                                                  double* dacc) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lq = lane >> 4;
-    const int r = a.r, c = a.c, RT = Rp / 16;
-    double* const Us = zone;
-    double* const Vs = zone + Rp * LS;
-    cl_v4d acc[RTW][2];
-#pragma unroll
-    for (int t = 0; t < RTW; t++)
-#pragma unroll
-        for (int ct = 0; ct < 2; ct++) acc[t][ct] = (cl_v4d){0.0, 0.0, 0.0, 0.0};
-    const double* vcol[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) vcol[i] = col((tid >> 5) + 8 * i);
-    const int q = tid & 31;
-    for (int s0 = 0; s0 < r; s0 += CH) {
-        const int s = s0 + q;
-        const bool in = s < r;
-        const double ph = in ? phi[s] : 0.0;
-        for (int row = tid >> 5; row < Rp; row += 8) {
-            double v = 0.0;
-            if (in && row < R) {
-                const double* src = row < c ? a.tX + (long)row * a.ldW : (row == c ? tg : a.ty);
-                v = src[s] * ph;
-            }
-            Us[row * LS + q] = v;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const double v = (in && vcol[i]) ? vcol[i][s] : 0.0;
-            Vs[((tid >> 5) + 8 * i) * LS + q] = v;
-            if (dacc) dacc[i] += ph * v * v;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int kk = 0; kk < CH / 4; kk++) {
-            const double b0 = Vs[l15 * LS + kk * 4 + lq];
-            const double b1 = Vs[(16 + l15) * LS + kk * 4 + lq];
-#pragma unroll
-            for (int t = 0; t < RTW; t++) {
-                const int rt = wave + 4 * t;
-                if (rt < RT) {
-                    const double av = Us[(rt * 16 + l15) * LS + kk * 4 + lq];
-                    acc[t][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b0, acc[t][0], 0, 0, 0);
-                    acc[t][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, b1, acc[t][1], 0, 0, 0);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    // accumulator register `reg` of lane (l15, lq): row lq + 4 reg of the A tile, column l15 of the B tile
-    double* const Pt = zone;
-#pragma unroll
-    for (int t = 0; t < RTW; t++) {
-        const int rt = wave + 4 * t;
-        if (rt < RT) {
-#pragma unroll
-            for (int ct = 0; ct < 2; ct++)
-#pragma unroll
-                for (int reg = 0; reg < 4; reg++) Pt[(rt * 16 + lq + 4 * reg) * NG + ct * 16 + l15] = acc[t][ct][reg];
-        }
-    }
-    __syncthreads();
-}
 
 // (two workgroups per CU where the LDS allows it -- up to about 90 covariate columns: 233 VGPRs, nothing spilled)
 __global__ __launch_bounds__(256, 2) void context_lrt_kernel(ContextLrtArgs a) {
     extern __shared__ __align__(16) double cl_smem[];
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
-    const int c = a.c, k = a.k, r = a.r;
+    const int c = a.c, k = a.k;
     const int R = c + 2, Rp = (R + 15) / 16 * 16, iy = c + 1;
     double* const Hp = cl_smem;                          // packed lower triangle of the (c + 2)^2 Gram, then L with the y row
     double* const zone = Hp + R * (R + 1) / 2;           // [Rp + NG][LS]
     double* const red = zone + (Rp + NG) * LS;           // [NG * CH]
     double* const diag = red + NG * CH;                  // [NG]
     double* const scal = diag + NG;                      // [8]
-    const double delta = a.delta[b], inv_d = 1.0 / delta, omd = 1.0 - delta;
     const double n = (double)a.n;
     const double* __restrict__ tg = a.Tg + (long)b * a.ldTg;
     double* __restrict__ phi = a.phi + (long)b * a.ld_phi;
 
-    // 1. the weights and log|K|
-    double lpart = 0.0;
-    for (int s = tid; s < r; s += 256) {
-        const double S = a.S0[s], D = omd * S + delta;
-        phi[s] = omd * S / (delta * D);
-        lpart += log(D);
-    }
-    const double logdetK = block_total(lpart, red) + (n - (double)r) * log(delta);   // (its barriers publish phi)
-
-    // 2. the Gram of [tX; tg; ty], 32 columns at a time
-    for (int v0 = 0; v0 < R; v0 += NG) {
-        weighted_products(a, tg, phi, R, Rp, zone,
-                          [&](int jj) -> const double* {
-                              const int v = v0 + jj;
-                              return v < c ? a.tX + (long)v * a.ldW : (v == c ? tg : (v == iy ? a.ty : nullptr));
-                          },
-                          nullptr);
-        for (int e = tid; e < R * NG; e += 256) {
-            const int u = e / NG, jj = e - u * NG, v = v0 + jj;
-            if (v > u || v >= R) continue;
-            double plain;
-            if (u < c) plain = a.WW[u * c + v];
-            else if (u == c) plain = v < c ? a.gW[(long)b * a.ld_gW + v] : a.gg[b];
-            else plain = v < c ? a.Wy[v] : (v == c ? a.gy[b] : a.yy);
-            Hp[tri(u, v)] = plain * inv_d - zone[u * NG + jj];
-        }
-        __syncthreads();
-    }
-
-    // 3. Cholesky over [X0, g] with the y row carried along (its entries become z)
-    const double gKg = Hp[tri(c, c)];
-    const bool dropped_before = a.drop && a.drop[b] != 0;
-    bool ok = true;
-    int P = c + 1;
-    for (int j = 0; j <= c; j++) {
-        __syncthreads();
-        if (tid == 0) {
-            double d = Hp[tri(j, j)];
-            for (int kk = 0; kk < j; kk++) d -= Hp[tri(j, kk)] * Hp[tri(j, kk)];
-            scal[0] = d;
-        }
-        __syncthreads();
-        const double d = scal[0];
-        if (j == c) {
-            // g in the span of X0: the rank rule of fastscan_kernel (assoc.hip), or the scan's own (full refit)
-            if (dropped_before || !(d > 1e-12 * gKg)) { P = c; break; }
-        } else if (!(d > 0.0)) {
-            ok = false;
-            break;
-        }
-        const double l = sqrt(d);
-        for (int i = j + 1 + tid; i < R; i += 256) {
-            double s = Hp[tri(i, j)];
-            for (int kk = 0; kk < j; kk++) s -= Hp[tri(i, kk)] * Hp[tri(j, kk)];
-            Hp[tri(i, j)] = s / l;
-        }
-        if (tid == 0) Hp[tri(j, j)] = l;
-    }
-    __syncthreads();
-    double rss0 = Hp[tri(iy, iy)];
-    for (int kk = 0; kk < P; kk++) rss0 -= Hp[tri(iy, kk)] * Hp[tri(iy, kk)];
-    const double s_null = fmax(rss0 / n, EPS_SMALL);
-    const double lml0 = ok ? -0.5 * (n * LOG2PI + n + n * log(s_null) + logdetK) : NAN;
+    // 1 to 3: the weights and log|K|, the Gram of [tX; tg; ty], its Cholesky factor with the y row (context_common.h)
+    const ContextNull nm = context_null_model(a, b, tg, phi, Hp, zone, red, scal);
+    const double inv_d = 1.0 / nm.delta, logdetK = nm.logdetK, rss0 = nm.rss0, lml0 = nm.lml0;
+    const int P = nm.P;
+    const bool ok = nm.ok;
     if (tid == 0) a.null_lml[b] = lml0;
 
     // 4. the candidates
     const double* __restrict__ tx = a.Tx + (long)b * a.tx_slab;
     for (int j0 = 0; j0 < k; j0 += NG) {
         double dacc[4] = {0.0, 0.0, 0.0, 0.0};
-        weighted_products(a, tg, phi, R, Rp, zone,
-                          [&](int jj) -> const double* { return j0 + jj < k ? tx + (long)(j0 + jj) * a.ldT : nullptr; }, dacc);
+        context_candidate_products(a, tg, phi, tx, j0, zone, dacc);
 #pragma unroll
         for (int i = 0; i < 4; i++) red[((tid >> 5) + 8 * i) * CH + (tid & 31)] = dacc[i];
         __syncthreads();
@@ -222,30 +64,11 @@ __global__ __launch_bounds__(256, 2) void context_lrt_kernel(ContextLrtArgs a) {
             for (int qq = 0; qq < CH; qq++) s += red[tid * CH + qq];
             diag[tid] = s;
         }
-        // X'K^-1x_j and y'K^-1x_j in place
-        for (int e = tid; e < R * NG; e += 256) {
-            const int u = e / NG, jj = e - u * NG, j = j0 + jj;
-            if (j >= k) continue;
-            const double* row = a.xXy + ((long)b * k + j) * a.ld_xXy;
-            const double plain = u < c ? row[1 + u] : (u == c ? a.xg[(long)b * a.ld_xg + j] : row[0]);
-            zone[u * NG + jj] = plain * inv_d - zone[u * NG + jj];
-        }
+        context_candidate_metric(a, b, j0, inv_d, zone);   // X'K^-1x_j and y'K^-1x_j in place
         __syncthreads();
-        // forward solves: eight lanes per candidate share the dot product of a row
         const int col = tid >> 3, part = tid & 7;
-        double vv = 0.0, vz = 0.0;
-        for (int i = 0; i < P; i++) {
-            double s = 0.0;
-            for (int kk = part; kk < i; kk += 8) s += Hp[tri(i, kk)] * zone[kk * NG + col];
-            s += __shfl_xor(s, 1);
-            s += __shfl_xor(s, 2);
-            s += __shfl_xor(s, 4);
-            const double v = (zone[i * NG + col] - s) / Hp[tri(i, i)];
-            if (part == 0) zone[i * NG + col] = v;   // (read again by the same eight lanes only: one wavefront, in order)
-            __syncthreads();
-            vv += v * v;
-            vz += v * Hp[tri(iy, i)];
-        }
+        const SolveSums sums = context_forward_solves(Hp, P, iy, zone);
+        const double vv = sums.vv, vz = sums.vz;
         const int j = j0 + col;
         if (part == 0 && j < k) {
             const double xKx = a.xx[(long)b * a.ld_xx + j] * inv_d - diag[col];

@@ -158,6 +158,25 @@ int launch_context_operands(hipStream_t st, const double* E, long lde, long cell
 int launch_context_deltas(hipStream_t st, const NullFitTrial* trial, const int* g_drop, double delta0, int variants, double* delta,
                           int* drop);
 
+// ---- joint fixed-effect test of all contexts (context_joint.hip) --------------------------------------
+// One launch over a sub-range of variants: variant b tests its k candidates together beside X = [X0, g_b].  `base` as the
+// per-context launch takes it, with pvalue, alt_lml, logp and status per VARIANT (index b), beta and beta_se per candidate
+// (index b k + j); base.xx is not read.
+struct ContextJointArgs {
+    ContextLrtArgs base;
+    const double* xxp; long ld_xxp;        // row b, column i (i + 1) / 2 + j (j <= i): x_i'x_j
+    double* V; long v_slab;                // scratch, row b: (c + 1) x k -- read where context_joint_v_in_lds(c, k) is false
+    int v_in_lds;
+    int* dof;                              // [variants] candidates kept
+    int* dropped;                          // index b k + j: 1 where the candidate left the test
+};
+bool context_joint_v_in_lds(int c, int k);
+size_t context_joint_lds_bytes(int c, int k);
+int context_joint_check(int c, int k);     // CRM_ERR_UNSUPPORTED (with the message) past k <= CRM_JOINT_MAX_K, c <= CRM_MAX_COV_XWIDE
+int launch_context_joint(hipStream_t st, const ContextJointArgs& a, int variants);
+// CC[i, a (a + 1) / 2 + b] = E[i, a] E[i, b], b <= a < k, zeros up to ld_out: the right-hand operand of x_a'x_b = (g o g)'(C_a o C_b)
+int launch_context_pairs(hipStream_t st, const double* E, long lde, long cells_pad, int k, double* CC, long ld_out);
+
 // ---- small per-block kernels (blockops.hip) ----------------------------------------------------
 // gg, gy, gW for a block of variants: column reductions of G (cells x ldg), deterministic.
 int launch_variant_stats(hipStream_t st, const double* G, long ldg, long cells, int variants,

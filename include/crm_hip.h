@@ -367,6 +367,35 @@ int crm_scan_interaction_contexts(crm_gene* gene, crm_panel* panel, long first, 
                                   double* out_alt_lml, double* out_beta, double* out_beta_se, double* out_logp,
                                   int* out_status, double* out_null_lml, double* out_null_delta, double* out_null);
 
+/* ---- joint fixed-effect GxC test: is there ANY fixed-effect GxC at a variant?  One likelihood-ratio test of all k columns
+ * g o C at once, k degrees of freedom -- the multi-environment LRT the interaction score test is compared against.  The
+ * reference poses the model family in cellregmap/test/test_fixed_gxe.py:79-102 and lrt_pvalues(null, alt, dof)
+ * (_cellregmap.py:443-469): the ML null LMM(y, [M, g, E]), the alternative LMM(y, [M, g, E, E * g]) at the null's delta.
+ * Gene-level null and per-variant null exactly as crm_scan_interaction_contexts fits them (same launches: out_null_lml,
+ * out_null_delta and out_null are bit for bit that call's), then per variant
+ *   H1: [X0, g, x_1 .. x_k], x_j = g o C_j, delta frozen at delta_i, all coefficients and one scale in closed form
+ * through the Schur complement S of the candidates against [X0, g] and its Cholesky factor taken in column order.  A
+ * candidate whose pivot is <= 1e-12 x_j'K^-1x_j lies in the span of [X0, g] and the candidates before it and leaves the
+ * test (of a dependent set the last member in order); dof = the candidates kept.
+ * Outputs (any may be NULL).  count entries:
+ *   out_pvalue   lrt_pvalues(null_lml_i, alt_lml_i, dof_i) with its clips: the upper tail of chi^2_dof at
+ *                lrs = max(2 (alt - null), 2.2e-308), held to [2.2e-308, 1 - 2.2e-16]
+ *   out_logp     natural log of that tail at max(2 (alt - null), 0), no clip: finite where p underflows
+ *   out_alt_lml  the ML log-likelihood of H1;  out_dof  candidates kept (int)
+ *   out_status   CRM_CONTEXT_OK; COLLINEAR: dof = 0 -- every candidate dropped, or g in the span of X0: p = 1 - 2.2e-16,
+ *                log p = 0, alt lml = the variant's null lml, every beta NaN; NO_FIT, NON_FINITE as above
+ *   out_null_lml, out_null_delta  as above
+ * count x k row-major:
+ *   out_beta     the JOINT coefficient of x_j (adjusted for the other contexts);  out_beta_se  sqrt(scale1 (S^-1)_jj);
+ *                both NaN for a dropped candidate
+ *   out_dropped  (int) 1 where the candidate left the test
+ * out_null: the 6 doubles of the gene-level null.  Blocks, sub-ranges and the byte budget are the per-context call's.
+ * CRM_ERR_UNSUPPORTED, before anything is launched: more than 64 contexts or 128 covariate columns; CRM_ERR_ARG as above. */
+int crm_scan_interaction_contexts_joint(crm_gene* gene, crm_panel* panel, long first, long count, int fast,
+                                        double* out_pvalue, double* out_logp, double* out_alt_lml, int* out_dof,
+                                        double* out_beta, double* out_beta_se, int* out_dropped, int* out_status,
+                                        double* out_null_lml, double* out_null_delta, double* out_null);
+
 /* ---- effect sizes: the device operations behind predict_interaction (_cellregmap.py:137-205) and
  * estimate_aggregate_environment (:207-244).
  * crm_lmm_fit: LMM(y, M, QS(rho), restricted).fit() for every grid point of the gene's background

@@ -77,27 +77,31 @@ def test_the_reference_is_pinned_ml_with_a_shared_factorisation():
     assert pr.relative(one["beta"][0], each["beta"][1]) <= 1e-16 and pr.relative(one["beta_se"][0], each["beta_se"][1]) <= 1e-16
 
 
+def _oracle_rows(cs, sel=None):
+    """(rho, delta0, [(delta_i, the oracle's errors, the device form's errors)]) of a cohort at the oracle's own optimum, per
+    held variant (``sel``; default ``pinned_reference.pick``)."""
+    rho, null, (Q0, S0) = cc.oracle_gene_null(cs)
+    hS = np.asarray(cs.half(rho), LD)
+    gram = hS @ hS.T
+    rows = []
+    for j in pr.pick(cs.G.shape[1]) if sel is None else sel:
+        X, g = cs.X(j), cs.G[:, j]
+        o = LMM(cs.y, X, ((Q0,), S0), restricted=False)
+        o.fit(verbose=False)
+        ref = jr.joint_test(cs.y, X, g, cs.C, gram, o.delta)
+        own = jr.oracle_joint_at(cs.y, X, Q0, S0, g, cs.C, o.delta)
+        form = jr.device_form(cs.y, X, Q0, S0, g, cs.C, o.delta)
+        assert form["dof"] == cs.k and not form["dropped"].any(), (cs.name, j, form["dof"])
+        rows.append((o.delta, jr.errors(own, ref), jr.errors(form, ref)))
+    return rho, null.delta, rows
+
+
 _rows = {}
 
 
 def _case_rows(name):
-    """(rho, [(delta_i, the oracle's errors, the device form's errors)]) of a cohort at the oracle's own optimum."""
     if name not in _rows:
-        cs = jc.case(name)
-        rho, null, (Q0, S0) = cc.oracle_gene_null(cs)
-        hS = np.asarray(cs.half(rho), LD)
-        gram = hS @ hS.T
-        rows = []
-        for j in pr.pick(cs.G.shape[1]):
-            X, g = cs.X(j), cs.G[:, j]
-            o = LMM(cs.y, X, ((Q0,), S0), restricted=False)
-            o.fit(verbose=False)
-            ref = jr.joint_test(cs.y, X, g, cs.C, gram, o.delta)
-            own = jr.oracle_joint_at(cs.y, X, Q0, S0, g, cs.C, o.delta)
-            form = jr.device_form(cs.y, X, Q0, S0, g, cs.C, o.delta)
-            assert form["dof"] == cs.k and not form["dropped"].any(), (name, j, form["dof"])
-            rows.append((o.delta, jr.errors(own, ref), jr.errors(form, ref)))
-        _rows[name] = (rho, null.delta, rows)
+        _rows[name] = _oracle_rows(jc.case(name))
     return _rows[name]
 
 

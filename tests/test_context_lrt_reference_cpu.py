@@ -68,8 +68,9 @@ def test_the_reference_is_pinned_ml_with_a_shared_factorisation():
         assert abs(2 * (ref["alt_lml"][j] - ref["null_lml"]) - cs.n * np.log1p(z2 / cs.n)) <= 1e-16 * abs(lml), j
 
 
-def _oracle_rows(y, W, C, G, half_of, grid):
-    """Per held variant: the oracle's own composition at the oracle's delta against the reference there."""
+def _oracle_rows(y, W, C, G, half_of, grid, sel=None):
+    """Per held variant (``sel``; default ``pinned_reference.pick``): the oracle's own composition at the oracle's delta
+    against the reference there."""
     best = None
     X0 = np.column_stack([W, C])
     for rho in grid:
@@ -82,7 +83,7 @@ def _oracle_rows(y, W, C, G, half_of, grid):
     hS = np.asarray(half_of(rho), LD)
     gram = hS @ hS.T
     rows = []
-    for j in pr.pick(G.shape[1]):
+    for j in pr.pick(G.shape[1]) if sel is None else sel:
         X = np.column_stack([X0, G[:, j]])
         o = LMM(y, X, ((Q0,), S0), restricted=False)
         o.fit(verbose=False)

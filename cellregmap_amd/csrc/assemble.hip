@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "nullfit.h"
+#include "tile_gram.h"
 
 namespace crm {
 
@@ -394,7 +395,10 @@ constexpr int GRAM_WCH = 32;    // spectrum entries per chunk of gram_ext_dma_wi
 // d [2][GRAM_WCH], S0 as loaded [2][GRAM_WCH]
 constexpr int gram_dma_wide_lds_doubles(int ntl) { return 2 * (16 * ((ntl + 3) / 4)) * GRAM_QLD + 4 * GRAM_WCH; }
 
-template <int NTL>
+// STRIPS (form "gram_strips", the default): the tiles are dealt in strips (tile_gram.h: kStripDeal), a k-step reads every
+// operand tile row of the wavefront's role once and weights one fragment per column of the role; false: the round-robin
+// deal with two reads and a product per tile.  Every accumulator receives the same operands in the same order either way.
+template <int NTL, bool STRIPS>
 __global__ __launch_bounds__(256, NTL <= 8 ? 2 : 1) void gram_ext_dma_wide_kernel(AssembleArgs a, double* __restrict__ Gext,
                                                                                   int KT) {
     constexpr int WCH = GRAM_WCH;                  // spectrum entries per chunk
@@ -437,11 +441,14 @@ __global__ __launch_bounds__(256, NTL <= 8 ? 2 : 1) void gram_ext_dma_wide_kerne
     }
     // tiles of this wavefront: the entries first, first + 4, ... of the row-major upper triangle (MAXT or MAXT - 1 of
     // them), rotated by the block index so that the SIMDs of a CU see the same load
+    // (strips: `first` is the role of kStripDeal<NTL>; the fragments of tile row i start at row_off(16 i + l15) + lq, a
+    // constant past the lane's own part)
     const int first = (wave + b) & 3;
-    const int ntw = (NTILES - first + 3) / 4;
+    const int ntw = !STRIPS ? (NTILES - first + 3) / 4
+                            : first == 0 ? kStripDeal<NTL>.n[0] : first == 1 ? kStripDeal<NTL>.n[1] : first == 2 ? kStripDeal<NTL>.n[2] : kStripDeal<NTL>.n[3];
     int t_i[MAXT], t_j[MAXT], t_ij[MAXT];
 #pragma unroll
-    for (int t = 0; t < MAXT; t++) {
+    for (int t = 0; t < (STRIPS ? 0 : MAXT); t++) {
         int ti = 0, rem = first + 4 * t < NTILES ? first + 4 * t : 0;
         while (rem >= NTL - ti) { rem -= NTL - ti; ti++; }
         t_ij[t] = ti | ((ti + rem) << 8);
@@ -512,6 +519,33 @@ __global__ __launch_bounds__(256, NTL <= 8 ? 2 : 1) void gram_ext_dma_wide_kerne
                 acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[cur][t], fb[cur][t], acc[t], 0, 0, 0);
         }
     };
+    // one role of the strip deal: two sets of row fragments and of weighted fragments, read one k-step ahead
+    auto chunk_mma_strips = [&](int buf, auto role_tag) __attribute__((always_inline)) {
+        constexpr int ROLE = decltype(role_tag)::value;
+        constexpr int NT = kStripDeal<NTL>.n[ROLE];
+        const double* __restrict__ S = Ss + buf * BUF + l15 * QLD + lq;
+        const double* __restrict__ D = dS + buf * WCH + lq;
+        double fr[2][NTL], fw[2][NTL];
+        auto fragments = [&](int set, int ks) __attribute__((always_inline)) {
+            const double dk = D[4 * ks];
+            static_for<0, NTL>([&](auto ic) {
+                constexpr int i = decltype(ic)::value;
+                if constexpr (kStripDeal<NTL>.reads(ROLE, i)) {
+                    fr[set][i] = S[16 * (i >> 2) * QLD + (i & 3) * WCH + 4 * ks];
+                    if constexpr (kStripDeal<NTL>.is_b(ROLE, i)) fw[set][i] = fr[set][i] * dk;
+                }
+            });
+        };
+        fragments(0, 0);
+        static_for<0, WCH / 4>([&](auto kc) {
+            constexpr int ks = decltype(kc)::value, cur = ks & 1;
+            if constexpr (ks + 1 < WCH / 4) fragments(cur ^ 1, ks + 1);
+            static_for<0, NT>([&](auto tc) {
+                constexpr int t = decltype(tc)::value;
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[cur][kStripDeal<NTL>.ti[ROLE][t]], fw[cur][kStripDeal<NTL>.tj[ROLE][t]], acc[t], 0, 0, 0);
+            });
+        });
+    };
     if (wave == 0 && lane < WCH) weights(0, lane < r ? R.S0[lane] : 0.0);
     issue_s0(1);
     issue(0, 0);
@@ -523,9 +557,24 @@ __global__ __launch_bounds__(256, NTL <= 8 ? 2 : 1) void gram_ext_dma_wide_kerne
             issue(ch + 1, buf ^ 1);
         }
         issue_s0(ch + 2);
-        if (ntw == MAXT) chunk_mma(buf, std::integral_constant<int, MAXT>{});
-        else chunk_mma(buf, std::integral_constant<int, MAXT - 1>{});
+        if constexpr (STRIPS) {
+            if (first == 0) chunk_mma_strips(buf, std::integral_constant<int, 0>{});
+            else if (first == 1) chunk_mma_strips(buf, std::integral_constant<int, 1>{});
+            else if (first == 2) chunk_mma_strips(buf, std::integral_constant<int, 2>{});
+            else chunk_mma_strips(buf, std::integral_constant<int, 3>{});
+        } else {
+            if (ntw == MAXT) chunk_mma(buf, std::integral_constant<int, MAXT>{});
+            else chunk_mma(buf, std::integral_constant<int, MAXT - 1>{});
+        }
         __syncthreads();
+    }
+    if constexpr (STRIPS) {
+        static_for<0, MAXT>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            constexpr int i0 = kStripDeal<NTL>.ti[0][t], i1 = kStripDeal<NTL>.ti[1][t], i2 = kStripDeal<NTL>.ti[2][t], i3 = kStripDeal<NTL>.ti[3][t];
+            constexpr int j0 = kStripDeal<NTL>.tj[0][t], j1 = kStripDeal<NTL>.tj[1][t], j2 = kStripDeal<NTL>.tj[2][t], j3 = kStripDeal<NTL>.tj[3][t];
+            t_ij[t] = (first == 0 ? i0 : first == 1 ? i1 : first == 2 ? i2 : i3) | ((first == 0 ? j0 : first == 1 ? j1 : first == 2 ? j2 : j3) << 8);
+        });
     }
     double* __restrict__ out = Gext + (long)b * KT * KT;
 #pragma unroll
@@ -986,7 +1035,20 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));               \
         hipLaunchKernelGGL(KERNEL<NTL>, dim3(variants), dim3(256), lds, st, a, Gext, KT);                     \
     } while (0)
-#define CRM_GRAM_DMA_WIDE(NTL) CRM_GRAM_DMA(gram_ext_dma_wide_kernel, gram_dma_wide_lds_doubles, NTL)
+    const bool strips = form("gram_strips", 1) != 0;
+#define CRM_GRAM_DMA_WIDE_AS(NTL, STRIPS)                                                                     \
+    do {                                                                                                      \
+        const size_t lds = sizeof(double) * gram_dma_wide_lds_doubles(NTL);                                   \
+        if (lds > 60 * 1024)                                                                                  \
+            CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&gram_ext_dma_wide_kernel<NTL, STRIPS>), \
+                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));               \
+        hipLaunchKernelGGL((gram_ext_dma_wide_kernel<NTL, STRIPS>), dim3(variants), dim3(256), lds, st, a, Gext, KT); \
+    } while (0)
+#define CRM_GRAM_DMA_WIDE(NTL)                                                                                \
+    do {                                                                                                      \
+        if (strips) CRM_GRAM_DMA_WIDE_AS(NTL, true);                                                          \
+        else CRM_GRAM_DMA_WIDE_AS(NTL, false);                                                                \
+    } while (0)
     if (gram_done) {
     } else if (dma) {
         // (up to 4 tile rows every wavefront keeps every tile; past that the tiles are dealt to the wavefronts)
@@ -999,6 +1061,7 @@ int launch_assemble(hipStream_t st, const AssembleArgs& a, int variants, double*
         else CRM_GRAM_DMA_WIDE(9);
     }
 #undef CRM_GRAM_DMA_WIDE
+#undef CRM_GRAM_DMA_WIDE_AS
 #undef CRM_GRAM_DMA
 #define CRM_GRAM(NTL)                                                                                         \
     do {                                                                                                      \

@@ -47,6 +47,7 @@ inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 //   "kin_fold"          0: never fold the donor-level factor into the mixing matrices; 2: fold also with few columns of us
 //   "eigh_one_stage"    1: the constructor's eigen-solver tridiagonalises every grid point on its own (eigh_trd.hip)
 //   "nullfit_exact"     1: null-fit likelihood with IEEE division and one log per spectrum entry
+//   "gram_strips"       0: the 65-144-row direct-to-LDS Gram kernels deal their tiles round-robin (tile_gram.h: kStripDeal)
 int form(const char* name, int otherwise);
 
 // No C++ exception may cross the C-ABI (ctypes / cgo / JNI callers cannot unwind, the process would end in

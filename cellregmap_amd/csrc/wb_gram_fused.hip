@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "nullfit.h"
+#include "tile_gram.h"
 
 namespace crm {
 
@@ -73,9 +74,13 @@ WbFusedLayout wb_gram_fused_layout(int k0, int KT, long ldp) {
 
 namespace {
 
-template <int NTL>
+// STRIPS (form "gram_strips", the default): the tiles are dealt in strips (tile_gram.h: kStripDeal) and the Gram phase is
+// written out per role and k-step; false: the round-robin deal, one k-loop for every role.  Every accumulator receives the
+// same operands in the same order either way.
+template <int NTL, bool STRIPS>
 __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(AssembleArgs a, WbFusedArgs f, WbFusedLayout L, int KT) {
     constexpr int NTILES = NTL * (NTL + 1) / 2, MAXT = (NTILES + 3) / 4;
+    constexpr int MAXKS = 14;                      // k-steps of the longest chunk: (k0 + 2) / 4, k0 <= 54
     extern __shared__ __align__(16) double smem[];
     double* const img = smem;                      // [KT][RS] (+ what the last DMA instruction overshoots)
     double* const Pl = smem + L.off_P;             // the donor's pair products of this variant
@@ -174,11 +179,17 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
         pidx[ks] = k < k0 && iw < k0 ? lo * k0 - lo * (lo - 1) / 2 + (hi - lo) : 0;
     }
     // tiles of this wavefront, as gram_ext_dma_wide_kernel deals them (rows past KT read row 0: never stored)
+    // (strips: `first` is the role of kStripDeal<NTL>; a tile row's fragments start at r_off[row])
     const int first = (wave + b) & 3;
-    const int ntw = (NTILES - first + 3) / 4;
-    int t_i[MAXT], t_j[MAXT], t_ij[MAXT];
+    const int ntw = !STRIPS ? (NTILES - first + 3) / 4 : first == 0 ? kStripDeal<NTL>.n[0] : first == 1 ? kStripDeal<NTL>.n[1] : first == 2 ? kStripDeal<NTL>.n[2] : kStripDeal<NTL>.n[3];
+    int t_i[MAXT], t_j[MAXT], t_ij[MAXT], r_off[NTL];
 #pragma unroll
-    for (int t = 0; t < MAXT; t++) {
+    for (int i = 0; i < NTL; i++) {
+        const int row = 16 * i + l15;
+        r_off[i] = (row < KT ? row : 0) * RS + lq;
+    }
+#pragma unroll
+    for (int t = 0; t < (STRIPS ? 0 : MAXT); t++) {
         int ti = 0, rem = first + 4 * t < NTILES ? first + 4 * t : 0;
         while (rem >= NTL - ti) { rem -= NTL - ti; ti++; }
         t_ij[t] = ti | ((ti + rem) << 8);
@@ -224,6 +235,50 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
             }
             dk = dn;
         }
+    };
+    // The same for one role of the strip deal, every k-step written out: a step reads each operand tile row of the role
+    // once, at register base + immediate offset, and forms the weighted fragment once per column of the role.  One set of
+    // fragments as above: the read of a row for step ks + 1 follows the last MFMA of step ks that takes it.  Behind the
+    // chunk's last step that read goes up to four columns past the chunk (at most column k0 + 5 of a row of RS >= k0 + 4
+    // doubles: the next row's first columns or, behind the image's last row, the region that follows it in LDS) and is
+    // dropped; each step stands behind a wave-uniform compare with the chunk's step count (nks <= MAXKS).
+    auto gram_strips = [&](int col0, int nks, auto role_tag) __attribute__((always_inline)) {
+        constexpr int ROLE = decltype(role_tag)::value;
+        constexpr int NT = kStripDeal<NTL>.n[ROLE];
+        const double* __restrict__ S = img + col0;
+        const double* __restrict__ Dw = dS + col0 + lq;
+        const double* rows[NTL];
+        double fr[NTL], fw[NTL];
+        static_for<0, NTL>([&](auto ic) {
+            constexpr int i = decltype(ic)::value;
+            if constexpr (kStripDeal<NTL>.reads(ROLE, i)) {
+                rows[i] = S + r_off[i];
+                fr[i] = rows[i][0];
+            }
+        });
+        double dk = Dw[0];
+        auto step = [&](int off) __attribute__((always_inline)) {
+            static_for<0, NTL>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                if constexpr (kStripDeal<NTL>.is_b(ROLE, j)) {
+                    fw[j] = fr[j] * dk;
+                    if constexpr (kStripDeal<NTL>.last_a(ROLE, j) < 0) fr[j] = rows[j][off + 4];
+                }
+            });
+            static_for<0, NT>([&](auto tc) {
+                constexpr int t = decltype(tc)::value;
+                acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[kStripDeal<NTL>.ti[ROLE][t]], fw[kStripDeal<NTL>.tj[ROLE][t]], acc[t], 0, 0, 0);
+                static_for<0, NTL>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value;
+                    if constexpr (kStripDeal<NTL>.last_a(ROLE, i) == t) fr[i] = rows[i][off + 4];
+                });
+            });
+            dk = Dw[off + 4];
+        };
+        static_for<0, MAXKS>([&](auto kc) {
+            constexpr int ks = decltype(kc)::value;
+            if (ks < nks) step(4 * ks);
+        });
     };
 
     __syncthreads();   // (the row pointers are read by the first loads)
@@ -305,8 +360,17 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
         if (d + 1 < D) issue_pus(d + 1);
         // ---- Gram phase ----
         const int nks = (end - start) / 4;
-        if (ntw == MAXT) gram(c0, nks, std::integral_constant<int, MAXT>{});
-        else gram(c0, nks, std::integral_constant<int, MAXT - 1>{});
+        if constexpr (STRIPS) {
+            if (nks > 0) {
+                if (first == 0) gram_strips(c0, nks, std::integral_constant<int, 0>{});
+                else if (first == 1) gram_strips(c0, nks, std::integral_constant<int, 1>{});
+                else if (first == 2) gram_strips(c0, nks, std::integral_constant<int, 2>{});
+                else gram_strips(c0, nks, std::integral_constant<int, 3>{});
+            }
+        } else {
+            if (ntw == MAXT) gram(c0, nks, std::integral_constant<int, MAXT>{});
+            else gram(c0, nks, std::integral_constant<int, MAXT - 1>{});
+        }
         dma_barrier();     // (the image is free; P, Psi and S0 of d + 1 are waited for)
         if (d + 1 < D) issue_others(d + 1);
     }
@@ -316,6 +380,14 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
         for (int e = tid; e < npair; e += 256) out[e] = 0.0;
     }
     double* __restrict__ out = a.wb_Gw + (long)b * KT * KT;
+    if constexpr (STRIPS) {
+        static_for<0, MAXT>([&](auto tc) {
+            constexpr int t = decltype(tc)::value;
+            constexpr int i0 = kStripDeal<NTL>.ti[0][t], i1 = kStripDeal<NTL>.ti[1][t], i2 = kStripDeal<NTL>.ti[2][t], i3 = kStripDeal<NTL>.ti[3][t];
+            constexpr int j0 = kStripDeal<NTL>.tj[0][t], j1 = kStripDeal<NTL>.tj[1][t], j2 = kStripDeal<NTL>.tj[2][t], j3 = kStripDeal<NTL>.tj[3][t];
+            t_ij[t] = (first == 0 ? i0 : first == 1 ? i1 : first == 2 ? i2 : i3) | ((first == 0 ? j0 : first == 1 ? j1 : first == 2 ? j2 : j3) << 8);
+        });
+    }
 #pragma unroll
     for (int t = 0; t < MAXT; t++) {
         if (t >= ntw) continue;
@@ -365,16 +437,23 @@ int launch_wb_gram_fused(hipStream_t st, const AssembleArgs& a, const WbFusedArg
     const int KT = a.k0 + a.c + 2 + a.wb_k1, ts = (KT + 15) / 16;
     const WbFusedLayout L = wb_gram_fused_layout(a.k0, KT, f.ldp);
     const size_t lds = sizeof(double) * (size_t)L.total;
+    const bool strips = form("gram_strips", 1) != 0;
+#define CRM_WB_FUSED_AS(NTL, STRIPS)                                                                                  \
+    do {                                                                                                              \
+        CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wb_gram_fused_kernel<NTL, STRIPS>),                \
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
+        hipLaunchKernelGGL((wb_gram_fused_kernel<NTL, STRIPS>), dim3(variants), dim3(256), lds, st, a, f, L, KT);     \
+    } while (0)
 #define CRM_WB_FUSED(NTL)                                                                                             \
     do {                                                                                                              \
-        CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wb_gram_fused_kernel<NTL>),                        \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-        hipLaunchKernelGGL(wb_gram_fused_kernel<NTL>, dim3(variants), dim3(256), lds, st, a, f, L, KT);               \
+        if (strips) CRM_WB_FUSED_AS(NTL, true);                                                                       \
+        else CRM_WB_FUSED_AS(NTL, false);                                                                             \
     } while (0)
     if (ts == 5) CRM_WB_FUSED(5);
     else if (ts == 6) CRM_WB_FUSED(6);
     else if (ts == 7) CRM_WB_FUSED(7);   // (config 3: 50 + 3 + 50 rows)
     else CRM_WB_FUSED(8);
+#undef CRM_WB_FUSED_AS
 #undef CRM_WB_FUSED
     CRM_HIP(hipGetLastError());
     return CRM_OK;

@@ -555,7 +555,7 @@ def _panel_from_dosages(cls, dosage, donor_of_cell, standardize=True, device=0):
     self = cls.__new__(cls)
     D = np.ascontiguousarray(dosage)
     if D.dtype != np.int8:
-        if not np.array_equal(D, np.rint(D)) or np.abs(D).max(initial=0) > 127:
+        if not np.array_equal(D, np.rint(D)) or D.min(initial=0) < -128 or D.max(initial=0) > 127:
             raise ValueError("dosages must be integers in [-128, 127]")
         D = D.astype(np.int8)
     group = np.ascontiguousarray(donor_of_cell, dtype=np.int32)

@@ -107,6 +107,8 @@ SIGNATURES = {
     "crm_test_set_kinship_route": (ctypes.c_int, [vp, ctypes.c_int]),
     "crm_test_check_context": (ctypes.c_int, [vp]),
     "crm_test_overrun_selftest": (ctypes.c_int, [vp]),
+    "crm_test_panel_layout": (ctypes.c_int, [vp, c_long_p]),
+    "crm_test_panel_read": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_size_t]),
     "crm_test_null_fit_probe": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_double]),
     "crm_test_null_fit_probe_read": (ctypes.c_int, [vp, vp, ctypes.c_long]),
     "crm_test_contract": (ctypes.c_int, [vp, ctypes.c_long, ctypes.c_int, ctypes.c_int, vp, vp, vp,

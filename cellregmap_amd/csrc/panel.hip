@@ -256,6 +256,47 @@ int crm_panel_create_auto(crm_ctx* ctx, long n, const double* G, long ldg, long 
     });
 }
 
+// ---- read-back hooks (include/crm_hip_test.h) -------------------------------------------------------
+int crm_test_panel_layout(const crm_panel* P, long* out) {
+    return crm::guarded("crm_test_panel_layout", [&]() -> int {
+    if (!P || !out) return CRM_ERR_ARG;
+    const long v[8] = {P->n, P->n_pad, P->p, P->ld, P->grouped ? 1L : 0L, P->m, P->m_pad, P->ldz};
+    std::copy(v, v + 8, out);
+    return CRM_OK;
+    });
+}
+
+int crm_test_panel_read(crm_panel* P, int what, void* dst, size_t bytes) {
+    return crm::guarded_on("crm_test_panel_read", P ? P->ctx : nullptr, [&]() -> int {
+    if (!P || !dst) return CRM_ERR_ARG;
+    static const char* const names[4] = {"G", "Gd", "group", "Z"};
+    const DevBuf* src = nullptr;
+    size_t size = 0;
+    switch (what) {
+    case 0: src = &P->G; size = sizeof(double) * P->n_pad * P->ld; break;
+    case 1: src = &P->Gd; size = sizeof(double) * P->m_pad * P->ld; break;
+    case 2: src = &P->group; size = sizeof(int) * P->n; break;
+    case 3: src = &P->Z; size = sizeof(double) * P->n_pad * P->ldz; break;
+    default:
+        set_error("crm_test_panel_read: buffer %d is none of 0 (G), 1 (Gd), 2 (group), 3 (Z)", what);
+        return CRM_ERR_ARG;
+    }
+    if (!src->ptr || (what == 0) == P->grouped) {
+        set_error("crm_test_panel_read: a %s panel holds no %s", P->grouped ? "grouped" : "dense", names[what]);
+        return CRM_ERR_ARG;
+    }
+    if (bytes != size || src->bytes < size) {
+        set_error("crm_test_panel_read: %s is %zu bytes, the caller asked for %zu", names[what], size, bytes);
+        return CRM_ERR_ARG;
+    }
+    CRM_HIP(hipSetDevice(P->ctx->device));
+    CRM_HIP(hipStreamSynchronize(P->ctx->stream));
+    if (P->ctx->upload_stream) CRM_HIP(hipStreamSynchronize(P->ctx->upload_stream));
+    CRM_HIP(hipMemcpy(dst, src->ptr, size, hipMemcpyDeviceToHost));
+    return CRM_OK;
+    });
+}
+
 int crm_set_donor_collapse(crm_ctx* ctx, int on) {
     return crm::guarded_on("crm_set_donor_collapse", ctx, [&]() -> int {
     if (!ctx) return CRM_ERR_ARG;

@@ -4,6 +4,8 @@
 #ifndef CRM_HIP_TEST_H
 #define CRM_HIP_TEST_H
 
+#include <stddef.h>
+
 #include "crm_hip.h"
 
 #ifdef __cplusplus
@@ -62,6 +64,14 @@ int crm_test_check_context(crm_ctx* ctx);
 /* Self-test of that detector: writes eight bytes past the end of a scratch buffer on purpose (CRM_POISON=1 only) and
  * returns by how much the overrun count grew (1 with the poison fill, 0 without). */
 int crm_test_overrun_selftest(crm_ctx* ctx);
+/* What a genotype panel holds in device memory, read back as it lies (padding included) so that the builders can be held
+ * to a reference.  Layout: out[8] = n, n_pad, p, ld, grouped (0 / 1), m, m_pad, ldz (the last three 0 for a dense panel). */
+int crm_test_panel_layout(const crm_panel* panel, long out[8]);
+/* One whole buffer of the panel to the host -- what = 0: G double[n_pad x ld] (dense panels), 1: Gd double[m_pad x ld],
+ * 2: group int[n], 3: Z double[n_pad x ldz] (grouped panels) -- after waiting for the context's stream and its upload
+ * stream, under the context's lock.  A buffer the panel does not hold, or `bytes` other than the buffer's size, is
+ * CRM_ERR_ARG with a message; the panel is left as it was. */
+int crm_test_panel_read(crm_panel* panel, int what, void* dst, size_t bytes);
 /* C (M x N, ld N) = X' Y with X: cells x M, Y: cells x N (row-major, tight). */
 int crm_test_contract(crm_ctx* ctx, long cells, int M, int N, const double* X, const double* Y,
                       double* C, int ksplit);

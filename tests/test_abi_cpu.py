@@ -244,3 +244,29 @@ def test_stream_chunk_setting(monkeypatch):
     for text, want in (("0", 0), ("4096", 4096), ("-7", 0), ("many", 8192)):
         monkeypatch.setenv("CELLREGMAP_AMD_STREAM_CHUNK", text)
         assert _engine._stream_chunk() == want
+
+
+def test_from_dosages_takes_the_whole_int8_range(monkeypatch):
+    """``GenotypePanel.from_dosages`` documents integers in [-128, 127] for input that is not int8 yet: -128 is a dosage
+    like any other, -129, 128 and fractions are refused.  (The check runs before the device is touched: the context
+    is replaced by a marker that shows the input got that far.)"""
+    from cellregmap_amd import GenotypePanel, _engine
+
+    class Reached(Exception):
+        pass
+
+    def no_device(device=0):
+        raise Reached
+
+    monkeypatch.setattr(_engine, "_context", no_device)
+    donor = np.array([0, 1, 2, 2], np.int32)
+    for dtype in (np.int64, np.int16, float):
+        with pytest.raises(Reached):
+            GenotypePanel.from_dosages(np.array([[-128, 0], [127, 1], [-127, 2]], dtype), donor)
+        for bad in (-129, 128):
+            with pytest.raises(ValueError, match=r"\[-128, 127\]"):
+                GenotypePanel.from_dosages(np.array([[bad, 0], [1, 1], [0, 2]], dtype), donor)
+    with pytest.raises(ValueError, match=r"\[-128, 127\]"):
+        GenotypePanel.from_dosages(np.array([[0.5, 0], [1, 1], [0, 2]]), donor)
+    with pytest.raises(ValueError, match=r"\[-128, 127\]"):
+        GenotypePanel.from_dosages(np.array([[200, 0], [1, 1], [0, 2]], np.uint8), donor)

@@ -22,8 +22,12 @@ from ._engine import (
     run_interaction,
     run_interaction_contexts,
     run_interaction_contexts_joint,
+    run_interaction_contexts_joint_many,
+    run_interaction_contexts_many,
     run_interaction_many,
     scan_association_many,
+    scan_interaction_contexts_joint_many,
+    scan_interaction_contexts_many,
     scan_interaction_many,
     scan_interaction_resumable,
 )
@@ -50,8 +54,12 @@ __all__ = [
     "run_interaction",
     "run_interaction_contexts",
     "run_interaction_contexts_joint",
+    "run_interaction_contexts_joint_many",
+    "run_interaction_contexts_many",
     "run_interaction_many",
     "scan_association_many",
+    "scan_interaction_contexts_joint_many",
+    "scan_interaction_contexts_many",
     "scan_interaction_many",
     "scan_interaction_resumable",
     "compute_maf",

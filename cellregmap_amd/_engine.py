@@ -1711,6 +1711,205 @@ def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=Fals
             bar.close()
 
 
+def _bind_context_genes(crms, C, own, batch=64):
+    """The context genes of ``crms`` for the contexts ``C`` (``CellRegMap._bind_context_gene``: covariates = the basis of
+    ``[W, C]``, context slot = C).  Bindings the objects already keep for these contexts are used as they are; the first
+    missing one is bound by itself and the others on its cohort through ``crm_gene_create_batch``."""
+    lib = _lib.load()
+    key = "E" if own else _digest(C)
+    have = [getattr(c, "_context_gene", None) for c in crms]
+    have = [kept[1] if kept is not None and kept[0] == key else None for kept in have]
+    like = next((h for h in have if h is not None), None)
+    if like is None:
+        like = have[0] = crms[0]._bind_context_gene(C, own)
+    todo = [i for i, h in enumerate(have) if h is None]
+    for a in range(0, len(todo), batch):
+        part = todo[a:a + batch]
+        for i in part:
+            if not np.all(np.isfinite(crms[i]._y)):
+                raise ValueError("There are non-finite values in the outcome.")
+        Y = np.ascontiguousarray(np.stack([crms[i]._y for i in part], axis=1), dtype=np.float64)
+        handles = (ctypes.c_void_p * len(part))()
+        _lib.check(lib.crm_gene_create_batch(like, _lib.ptr(Y), Y.shape[1], len(part), handles))
+        for i, h in zip(part, handles):
+            c, h = crms[i], ctypes.c_void_p(h)
+            kept = getattr(c, "_context_gene", None)
+            if kept is not None:
+                kept[2]()       # (release the binding it replaces)
+            c._context_gene = (key, h, weakref.finalize(c, _release_gene, lib, h, c._bg))
+            have[i] = h
+    return have
+
+
+_CONTEXT_MANY_KEYS = {
+    # name: (per variant and context?, dtype), in the order of the C-ABI's outputs
+    False: (("pv", True, float), ("alt_lml", True, float), ("beta", True, float), ("beta_se", True, float),
+            ("log_pvalue", True, float), ("status", True, np.int32), ("null_lml", False, float), ("null_delta", False, float)),
+    True: (("pv", False, float), ("log_pvalue", False, float), ("alt_lml", False, float), ("dof", False, np.int32),
+           ("beta", True, float), ("beta_se", True, float), ("dropped", True, np.int32), ("status", False, np.int32),
+           ("null_lml", False, float), ("null_delta", False, float)),
+}
+
+
+def _scan_contexts_many(crms, G, cis_index, contexts, fast, return_stats, progress, joint):
+    """The body of ``scan_interaction_contexts_many`` and ``scan_interaction_contexts_joint_many``."""
+    lib = _lib.load()
+    crms = list(crms)
+    if not crms:
+        raise ValueError("no phenotypes given")
+    first = crms[0]
+    for c in crms[1:]:
+        if c._bg is not first._bg:
+            raise ValueError("all CellRegMap objects must share one background (pass background=...)")
+        if c._W.shape != first._W.shape or c._E0.shape != first._E0.shape:
+            raise ValueError("all CellRegMap objects must share W and E")
+        if not (c._W is first._W or np.array_equal(c._W, first._W)):
+            raise ValueError("all CellRegMap objects of one pass must hold the same covariates W")
+        if not (c._E0 is first._E0 or np.array_equal(c._E0, first._E0)):
+            raise ValueError("all CellRegMap objects of one pass must hold the same contexts E")
+    C = first._E0 if contexts is None else np.asarray(contexts, float)
+    if C.ndim != 2 or C.shape[0] != first.n_samples or C.shape[1] < 1:
+        raise ValueError(f"contexts must be {first.n_samples} x k, got {C.shape}")
+    if not (np.all(np.isfinite(C)) and np.all(np.isfinite(first._W)) and all(np.all(np.isfinite(c._y)) for c in crms)):
+        raise ValueError("There are non-finite values in the outcome, the covariates or the contexts.")
+    k = C.shape[1]
+    if not isinstance(G, GenotypePanel) and np.asarray(G).ndim == 2 and np.asarray(G).shape[1] == 0:
+        panel, p = None, 0   # no variants: the gene-level nulls are still fitted and reported
+    else:
+        panel = first._panel(G)
+        p = panel.shape[1]
+    genes = _bind_context_genes(crms, C, contexts is None)
+    ng = len(genes)
+    handles = (ctypes.c_void_p * ng)(*[g.value for g in genes])
+    null = np.empty((ng, 6))
+    _lib.check(lib.crm_association_null_multi(handles, ng, _lib.ptr(null)))
+    info = {"rho1": null[:, 0].copy(), "e2": null[:, 1].copy(), "g2": null[:, 2].copy(), "eps2": null[:, 3].copy()}
+    keys = _CONTEXT_MANY_KEYS[bool(joint)]
+    entry = lib.crm_scan_interaction_contexts_joint_multi if joint else lib.crm_scan_interaction_contexts_multi
+    fast = int(bool(fast))
+
+    def arrays(lead, count, fill=False):
+        out = {}
+        for name, each, dtype in keys:
+            shape = (*lead, count, k) if each else (*lead, count)
+            out[name] = np.full(shape, -1 if dtype is np.int32 else np.nan, dtype) if fill else np.empty(shape, dtype)
+        return out
+
+    def scan(idx, a, count, out, offset, total):
+        hs = (ctypes.c_void_p * len(idx))(*[genes[i].value for i in idx])
+        rows = np.ascontiguousarray(null[idx])
+        with _progress(first._device, progress, count, offset=offset, grand_total=total):
+            _lib.check(entry(hs, len(idx), panel.handle, a, count, fast, _lib.ptr(rows),
+                             *[_lib.ptr(out[name]) for name, _, _ in keys]))
+
+    def finish(out):
+        pv = out.pop("pv")
+        if joint:
+            out["dropped"] = [d.astype(bool) for d in out["dropped"]] if isinstance(out["dropped"], list) \
+                else out["dropped"].astype(bool)
+        stats = {name: out.pop(name) for name in ("null_lml", "null_delta", "alt_lml")}
+        info.update(out)
+        if return_stats:
+            info.update(stats, gene_null_lml=null[:, 4].copy(), gene_null_delta=null[:, 5].copy())
+        return pv, info
+
+    if cis_index is None:
+        columns, runs = None, ([(0, p, np.arange(ng))] if p else [])
+    else:
+        columns, runs = _cis_runs(cis_index, ng, p)
+    tested = int(sum(count for _, count, _ in runs))
+    bar = None
+    if progress is True:   # one bar over the whole pass
+        from tqdm import tqdm
+
+        bar = tqdm(total=tested)
+        state = {"done": 0}
+
+        def progress(done, total, _bar=bar, _state=state):
+            _bar.update(done - _state["done"])
+            _state["done"] = done
+    try:
+        if columns is None:
+            out = arrays((ng,), p)
+            if p:
+                scan(np.arange(ng), 0, p, out, 0, p)
+            return finish(out)
+        full = [arrays((), p, fill=True) if columns[i].size else None for i in range(ng)]
+        seen = 0
+        for a, count, active in runs:
+            out = arrays((len(active),), count)
+            scan(active, a, count, out, seen, tested)
+            seen += count
+            for row, i in enumerate(active):
+                for name, _, _ in keys:
+                    full[i][name][a:a + count] = out[name][row]
+        empty = arrays((), 0)
+        return finish({name: [full[i][name][columns[i]] if columns[i].size else empty[name] for i in range(ng)]
+                       for name, _, _ in keys})
+    finally:
+        if bar is not None:
+            bar.close()
+
+
+def scan_interaction_contexts_many(crms, G, cis_index=None, contexts=None, fast=True, return_stats=False, progress=False):
+    """``CellRegMap.scan_interaction_contexts`` of several phenotypes against one genotype panel in a single pass
+    (DESIGN.md section 14).
+
+    ``crms``: ``CellRegMap`` objects that share the background, ``W`` and ``E``.  Their context genes are bound in
+    batches and their gene-level nulls fitted once per call; per block of variants the block, its plain products and,
+    per distinct rho* among the phenotypes, ONE Khatri-Rao contraction for the rotated candidates serve all of them.
+    Returns ``(pv, info)`` with a leading phenotype axis: ``pv`` is (len(crms), p, k), ``info`` holds ``rho1``, ``e2``,
+    ``g2``, ``eps2`` with one entry per phenotype and ``beta``, ``beta_se``, ``log_pvalue``, ``status`` in the shape of
+    ``pv``; ``return_stats=True`` adds ``null_lml``, ``null_delta`` (len(crms), p), ``alt_lml`` and, per phenotype,
+    ``gene_null_lml`` and ``gene_null_delta``.  Row i is ``crms[i].scan_interaction_contexts(G, contexts, fast)`` up to the
+    order of the sums in g'y and x_j'y; its discrete outputs are the same.
+
+    ``cis_index`` as in ``scan_interaction_many`` (pairs, slices, masks, index arrays with repeats): the results are then
+    lists whose entry i follows the columns of ``cis_index[i]``.  ``progress``: ``True`` for a tqdm bar, or a callable
+    ``(done, total)`` counted in variants of the panel that at least one phenotype tests."""
+    return _scan_contexts_many(crms, G, cis_index, contexts, fast, return_stats, progress, joint=False)
+
+
+def scan_interaction_contexts_joint_many(crms, G, cis_index=None, contexts=None, fast=True, return_stats=False,
+                                         progress=False):
+    """``CellRegMap.scan_interaction_contexts_joint`` of several phenotypes against one genotype panel in a single pass;
+    arguments, sharing and ``cis_index`` as ``scan_interaction_contexts_many``.  Returns ``(pv, info)``: ``pv`` is
+    (len(crms), p); ``info`` holds ``rho1``, ``e2``, ``g2``, ``eps2`` per phenotype, ``dof``, ``log_pvalue``, ``status``
+    (len(crms), p) and ``beta``, ``beta_se``, ``dropped`` (len(crms), p, k); ``return_stats`` as there."""
+    return _scan_contexts_many(crms, G, cis_index, contexts, fast, return_stats, progress, joint=True)
+
+
+def _context_many_crms(Y, E, W, E1, E2, hK, device):
+    Y = np.asarray(Y, float)
+    if Y.ndim != 2:
+        raise ValueError("Y must be n x genes")
+    if E1 is None:
+        E1 = E
+    if E2 is None:
+        E2 = E
+    Ls = None if hK is None else get_L_values(hK, E2)
+    first = CellRegMap(y=Y[:, 0], E=E, W=W, E1=E1, Ls=Ls, device=device)
+    return [first] + [CellRegMap(y=Y[:, i], E=E, W=W, E1=E1, Ls=Ls, device=device, background=first._bg)
+                      for i in range(1, Y.shape[1])]
+
+
+def run_interaction_contexts_many(Y, E, G, W=None, E1=None, E2=None, hK=None, *, cis_index=None, contexts=None, fast=True,
+                                  device=0):
+    """``run_interaction_contexts`` for the columns of ``Y`` (n x genes) with one background decomposition, one genotype
+    upload and shared per-variant work: ``scan_interaction_contexts_many`` -- ``(pv (genes, p, k), info)``, lists with
+    ``cis_index``."""
+    crms = _context_many_crms(Y, E, W, E1, E2, hK, device)
+    return scan_interaction_contexts_many(crms, G, cis_index=cis_index, contexts=contexts, fast=fast)
+
+
+def run_interaction_contexts_joint_many(Y, E, G, W=None, E1=None, E2=None, hK=None, *, cis_index=None, contexts=None,
+                                        fast=True, device=0):
+    """``run_interaction_contexts_joint`` for the columns of ``Y`` (n x genes): ``scan_interaction_contexts_joint_many`` --
+    ``(pv (genes, p), info)``, lists with ``cis_index``."""
+    crms = _context_many_crms(Y, E, W, E1, E2, hK, device)
+    return scan_interaction_contexts_joint_many(crms, G, cis_index=cis_index, contexts=contexts, fast=fast)
+
+
 def run_association_many(Y, W, E, G, hK=None, *, cis_index=None, fast=False, device=0, effects=False):
     """``run_association`` (``run_association_fast`` with ``fast=True``) for the columns of ``Y`` (n x genes) with one
     background decomposition, one genotype upload and shared per-variant work.  Keeps the reference's positional

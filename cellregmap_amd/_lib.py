@@ -75,6 +75,10 @@ SIGNATURES = {
                                            + [vp] * 9),
     "crm_scan_interaction_contexts": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int] + [vp] * 9),
     "crm_scan_interaction_contexts_joint": (ctypes.c_int, [vp, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int] + [vp] * 11),
+    "crm_scan_interaction_contexts_multi": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long, ctypes.c_int]
+                                            + [vp] * 9),
+    "crm_scan_interaction_contexts_joint_multi": (ctypes.c_int, [vp, ctypes.c_int, vp, ctypes.c_long, ctypes.c_long,
+                                                                 ctypes.c_int] + [vp] * 11),
     "crm_lmm_fit": (ctypes.c_int, [vp, ctypes.c_int, vp, vp]),
     "crm_cov_solve": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_double, ctypes.c_double, vp, ctypes.c_int, vp]),
     "crm_effects_multi": (ctypes.c_int, [vp, vp, ctypes.c_long, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp,

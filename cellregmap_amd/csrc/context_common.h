@@ -1,5 +1,6 @@
 // What the two kernels of the fixed-effect GxC tests share (context_lrt.hip: k tests of one degree of freedom, DESIGN.md
-// section 12; context_joint.hip: one test of k degrees of freedom, section 13): the staging and MFMA scheme of the products
+// section 12; context_joint.hip: one test of k degrees of freedom, section 13; both over one phenotype per launch or over
+// the genes of a rho group, section 14): the staging and MFMA scheme of the products
 // in the phi metric, and the null model of a variant -- phi, log|K|, the Gram of [tX; tg; ty] and its Cholesky factor with
 // the y row carried along.  One statement of each, so that the two calls report the same null bit for bit.
 #pragma once
@@ -210,13 +211,17 @@ __device__ __forceinline__ void context_candidate_products(const ContextLrtArgs&
 }
 
 // X'K^-1x_j and y'K^-1x_j from the weighted products in zone and the plain tables, in place.  No barrier.
+// MULTI (a launch over several phenotypes): x_j'X0 from the shared table, x_j'y from the gene's own.
+template <bool MULTI>
 __device__ __forceinline__ void context_candidate_metric(const ContextLrtArgs& a, int b, int j0, double inv_d, double* zone) {
     const int c = a.c, k = a.k, R = c + 2;
     for (int e = threadIdx.x; e < R * NG; e += 256) {
         const int u = e / NG, jj = e - u * NG, j = j0 + jj;
         if (j >= k) continue;
         const double* row = a.xXy + ((long)b * k + j) * a.ld_xXy;
-        const double plain = u < c ? row[1 + u] : (u == c ? a.xg[(long)b * a.ld_xg + j] : row[0]);
+        double plain;
+        if (MULTI) plain = u < c ? row[u] : (u == c ? a.xg[(long)b * a.ld_xg + j] : a.xy[((long)b * k + j) * a.ld_xy]);
+        else plain = u < c ? row[1 + u] : (u == c ? a.xg[(long)b * a.ld_xg + j] : row[0]);
         zone[u * NG + jj] = plain * inv_d - zone[u * NG + jj];
     }
 }

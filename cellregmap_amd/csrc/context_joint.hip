@@ -51,12 +51,12 @@ __device__ inline double log_chi2_sf(int dof, double lrs) {
 
 __device__ inline int round16(int v) { return (v + 15) / 16 * 16; }
 
-// (two workgroups per CU up to 80 KB of LDS: config 3's k = 50, c = 51 takes 69 KB with V in LDS; 115 VGPRs, nothing spilled)
-__global__ __launch_bounds__(256, 2) void context_joint_kernel(ContextJointArgs ja) {
+// Variant b of the launch described by `ja`.  MULTI: `ja` is one gene's record of a launch over several phenotypes.
+template <bool MULTI>
+__device__ __forceinline__ void context_joint_body(const ContextJointArgs& ja, const int b) {
     extern __shared__ __align__(16) double cj_smem[];
     const ContextLrtArgs& a = ja.base;
     const int tid = threadIdx.x;
-    const int b = blockIdx.x;
     const int c = a.c, k = a.k;
     const int R = c + 2, Rp = round16(R), iy = c + 1, Kp = round16(k);
     const int zrows = (Rp > Kp ? Rp : Kp) + NG;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void context_joint_kernel(ContextJointArgs 
     const double* __restrict__ tx = a.Tx + (long)b * a.tx_slab;
     for (int j0 = 0; j0 < k; j0 += NG) {
         context_candidate_products(a, tg, phi, tx, j0, zone, nullptr);
-        context_candidate_metric(a, b, j0, inv_d, zone);
+        context_candidate_metric<MULTI>(a, b, j0, inv_d, zone);
         __syncthreads();
         const SolveSums sums = context_forward_solves(Hp, P, iy, zone);
         const int col = tid >> 3, j = j0 + col;
@@ -232,6 +232,16 @@ __global__ __launch_bounds__(256, 2) void context_joint_kernel(ContextJointArgs 
     }
 }
 
+// (two workgroups per CU up to 80 KB of LDS: config 3's k = 50, c = 51 takes 69 KB with V in LDS; 115 VGPRs, nothing spilled)
+__global__ __launch_bounds__(256, 2) void context_joint_kernel(ContextJointArgs ja) { context_joint_body<false>(ja, blockIdx.x); }
+
+// Several phenotypes: workgroup (b, q) reads the record of gene q of the rho group and runs variant b on it
+// (context_lrt_multi_kernel's scheme; a record's V row in global memory is indexed by its gene and the variant).
+__global__ __launch_bounds__(256, 2) void context_joint_multi_kernel(const ContextJointArgs* __restrict__ genes) {
+    const ContextJointArgs ja = genes[blockIdx.y];
+    context_joint_body<true>(ja, blockIdx.x);
+}
+
 // CC[i, tri(a, b)] = E[i, a] E[i, b] for b <= a < k, zeros up to ld_out
 __global__ void context_pairs_kernel(const double* __restrict__ E, long lde, long cells_pad, int k, double* __restrict__ CC,
                                      long ld_out) {
@@ -292,6 +302,22 @@ int launch_context_joint(hipStream_t st, const ContextJointArgs& ja, int variant
     CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&context_joint_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds));
     hipLaunchKernelGGL(context_joint_kernel, dim3((unsigned)variants), dim3(256), lds, st, ja);
+    CRM_HIP(hipGetLastError());
+    return CRM_OK;
+}
+
+int launch_context_joint_multi(hipStream_t st, const ContextJointArgs* genes_dev, int ngenes, int c, int k, bool v_global,
+                               int variants) {
+    if (variants <= 0 || ngenes <= 0) return CRM_OK;
+    CRM_TRY(context_joint_check(c, k));
+    if (!genes_dev || ngenes > 65535 || v_global == context_joint_v_in_lds(c, k)) {
+        set_error("joint context test: the launch over %d genes does not match the kernel's layout", ngenes);
+        return CRM_ERR_ARG;
+    }
+    const size_t lds = context_joint_lds_bytes(c, k);
+    CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&context_joint_multi_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(context_joint_multi_kernel, dim3((unsigned)variants, (unsigned)ngenes), dim3(256), lds, st, genes_dev);
     CRM_HIP(hipGetLastError());
     return CRM_OK;
 }

@@ -28,11 +28,11 @@ using namespace context_detail;
 
 namespace {
 
-// (two workgroups per CU where the LDS allows it -- up to about 90 covariate columns: 233 VGPRs, nothing spilled)
-__global__ __launch_bounds__(256, 2) void context_lrt_kernel(ContextLrtArgs a) {
+// Variant b of the launch described by `a`.  MULTI: `a` is one gene's record of a launch over several phenotypes.
+template <bool MULTI>
+__device__ __forceinline__ void context_lrt_body(const ContextLrtArgs& a, const int b) {
     extern __shared__ __align__(16) double cl_smem[];
     const int tid = threadIdx.x;
-    const int b = blockIdx.x;
     const int c = a.c, k = a.k;
     const int R = c + 2, Rp = (R + 15) / 16 * 16, iy = c + 1;
     double* const Hp = cl_smem;                          // packed lower triangle of the (c + 2)^2 Gram, then L with the y row
@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void context_lrt_kernel(ContextLrtArgs a) {
             for (int qq = 0; qq < CH; qq++) s += red[tid * CH + qq];
             diag[tid] = s;
         }
-        context_candidate_metric(a, b, j0, inv_d, zone);   // X'K^-1x_j and y'K^-1x_j in place
+        context_candidate_metric<MULTI>(a, b, j0, inv_d, zone);   // X'K^-1x_j and y'K^-1x_j in place
         __syncthreads();
         const int col = tid >> 3, part = tid & 7;
         const SolveSums sums = context_forward_solves(Hp, P, iy, zone);
@@ -112,6 +112,16 @@ __global__ __launch_bounds__(256, 2) void context_lrt_kernel(ContextLrtArgs a) {
     }
 }
 
+// (two workgroups per CU where the LDS allows it -- up to about 90 covariate columns: 233 VGPRs, nothing spilled)
+__global__ __launch_bounds__(256, 2) void context_lrt_kernel(ContextLrtArgs a) { context_lrt_body<false>(a, blockIdx.x); }
+
+// Several phenotypes: workgroup (b, q) reads the record of gene q of the rho group (uniform: scalar loads) and runs variant b
+// on it.  The records share Tx, Tg, S0 and the plain tables of the block; a second gene finds T_x in L2 or HBM.
+__global__ __launch_bounds__(256, 2) void context_lrt_multi_kernel(const ContextLrtArgs* __restrict__ genes) {
+    const ContextLrtArgs a = genes[blockIdx.y];
+    context_lrt_body<true>(a, blockIdx.x);
+}
+
 __global__ void context_operands_kernel(const double* __restrict__ E, long lde, long cells_pad, int k, double* __restrict__ Cq,
                                         double* __restrict__ C2, long ld_out) {
     const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -149,6 +159,21 @@ int launch_context_lrt(hipStream_t st, const ContextLrtArgs& a, int variants) {
     CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&context_lrt_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds));
     hipLaunchKernelGGL(context_lrt_kernel, dim3((unsigned)variants), dim3(256), lds, st, a);
+    CRM_HIP(hipGetLastError());
+    return CRM_OK;
+}
+
+int launch_context_lrt_multi(hipStream_t st, const ContextLrtArgs* genes_dev, int ngenes, int c, int k, int variants) {
+    if (variants <= 0 || ngenes <= 0) return CRM_OK;
+    if (!genes_dev || c < 1 || c > CRM_MAX_COV_XWIDE || k < 1 || k > CRM_MAX_K0 || ngenes > 65535) {
+        set_error("context tests: %d genes, %d covariate columns, %d contexts (supported 1..65535, 1..%d, 1..%d)", ngenes, c, k,
+                  CRM_MAX_COV_XWIDE, CRM_MAX_K0);
+        return CRM_ERR_UNSUPPORTED;
+    }
+    const size_t lds = context_lrt_lds_bytes(c);
+    CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&context_lrt_multi_kernel),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(context_lrt_multi_kernel, dim3((unsigned)variants, (unsigned)ngenes), dim3(256), lds, st, genes_dev);
     CRM_HIP(hipGetLastError());
     return CRM_OK;
 }

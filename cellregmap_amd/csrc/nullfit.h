@@ -148,9 +148,15 @@ struct ContextLrtArgs {
     // outputs: per candidate (index b k + j), per variant
     double* pvalue; double* alt_lml; double* beta; double* beta_se; double* logp; int* status;
     double* null_lml;
+    // several phenotypes in one launch only (xXy then holds x_j'X0_u in columns 0 .. c - 1, shared by the genes)
+    const double* xy; long ld_xy;          // row b k + j: x_j'y of this gene
 };
 size_t context_lrt_lds_bytes(int c);
 int launch_context_lrt(hipStream_t st, const ContextLrtArgs& a, int variants);
+// The same test over the grid (variant, gene): workgroup (b, q) runs variant b on genes_dev[q] -- one record per gene of a
+// rho group, in device memory, whose per-gene tables (ty, X0'y, y'y, g'y, x_j'y, delta, drop), scratch row (phi) and outputs
+// are that gene's own and whose Tx, Tg, S0 and plain tables are the group's.  c, k: of every record.
+int launch_context_lrt_multi(hipStream_t st, const ContextLrtArgs* genes_dev, int ngenes, int c, int k, int variants);
 // Cq[i, j] = E[i, j], C2[i, j] = E[i, j]^2 for j < k, zeros up to ld_out: the contexts as the Khatri-Rao operand and as the
 // right-hand operands of the plain products x_j'g = (g o g)'C_j, x_j'x_j = (g o g)'C_j^2
 int launch_context_operands(hipStream_t st, const double* E, long lde, long cells_pad, int k, double* Cq, double* C2, long ld_out);
@@ -174,6 +180,9 @@ bool context_joint_v_in_lds(int c, int k);
 size_t context_joint_lds_bytes(int c, int k);
 int context_joint_check(int c, int k);     // CRM_ERR_UNSUPPORTED (with the message) past k <= CRM_JOINT_MAX_K, c <= CRM_MAX_COV_XWIDE
 int launch_context_joint(hipStream_t st, const ContextJointArgs& a, int variants);
+// grid (variant, gene) as launch_context_lrt_multi; every record's V row (where V lives in global memory) is its gene's own
+int launch_context_joint_multi(hipStream_t st, const ContextJointArgs* genes_dev, int ngenes, int c, int k, bool v_global,
+                               int variants);
 // CC[i, a (a + 1) / 2 + b] = E[i, a] E[i, b], b <= a < k, zeros up to ld_out: the right-hand operand of x_a'x_b = (g o g)'(C_a o C_b)
 int launch_context_pairs(hipStream_t st, const double* E, long lde, long cells_pad, int k, double* CC, long ld_out);
 

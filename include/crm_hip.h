@@ -396,6 +396,29 @@ int crm_scan_interaction_contexts_joint(crm_gene* gene, crm_panel* panel, long f
                                         double* out_beta, double* out_beta_se, int* out_dropped, int* out_status,
                                         double* out_null_lml, double* out_null_delta, double* out_null);
 
+/* ---- the two tests above for several phenotypes of one cohort in one pass.  genes: context genes (covariates = the basis of
+ * [W, C], context slot = C) that share the background, the context, c, k and the contents of X0 and C, else CRM_ERR_ARG
+ * before any launch.  null: ngenes x 6, the rows crm_association_null_multi returns for these genes (a context gene's null
+ * is crm_scan_association's null of that gene); as for crm_scan_association_multi rho1 must be a grid point and lml finite,
+ * else CRM_ERR_ARG -- a cis walk fits the nulls once and calls this once per run of constant phenotypes.
+ * Per block of variants the block, its plain products and g'X0 are formed once; per distinct rho* among the genes T_g and,
+ * per sub-range, ONE Khatri-Rao contraction T_x = Q0(rho*)'(g o C_j) serve every gene of that grid point; g'y and x_j'y of
+ * all genes are products against the phenotype matrix; delta_i (fast == 0: the refit launches, per gene) and the test
+ * kernel, whose grid is (variant, gene), are per gene.  Outputs as the single-gene entries', gene-major: ngenes x count x k
+ * (per-context: all six; joint: out_beta, out_beta_se, out_dropped) or ngenes x count; any may be NULL.  A gene's rows do
+ * not depend on the other genes of the call, their order, the window or the block size, bit for bit; they are the
+ * single-gene entry's up to the order of the sums in g'y and x_j'y.  Limits, CRM_ERR_UNSUPPORTED, blocks, sub-ranges and the
+ * byte budget (one rho group's T_x at a time) as the single-gene entries; ngenes < 1: CRM_ERR_ARG; count == 0: CRM_OK. */
+int crm_scan_interaction_contexts_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
+                                        int fast, const double* null, double* out_pvalue, double* out_alt_lml,
+                                        double* out_beta, double* out_beta_se, double* out_logp, int* out_status,
+                                        double* out_null_lml, double* out_null_delta);
+int crm_scan_interaction_contexts_joint_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count,
+                                              int fast, const double* null, double* out_pvalue, double* out_logp,
+                                              double* out_alt_lml, int* out_dof, double* out_beta, double* out_beta_se,
+                                              int* out_dropped, int* out_status, double* out_null_lml,
+                                              double* out_null_delta);
+
 /* ---- effect sizes: the device operations behind predict_interaction (_cellregmap.py:137-205) and
  * estimate_aggregate_environment (:207-244).
  * crm_lmm_fit: LMM(y, M, QS(rho), restricted).fit() for every grid point of the gene's background

@@ -101,6 +101,7 @@ SIGNATURES = {
     "crm_test_gram_dma_launches": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_long)]),
     "crm_test_fused_blocks": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_long)]),
     "crm_test_wb_gram_fused_blocks": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_long)]),
+    "crm_test_side_stream_blocks": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_long)]),
     "crm_test_rho0_position_blocks": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_long)]),
     "crm_test_rotation_tail_launches": (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_long)]),
     "crm_test_tests_without_pair": (ctypes.c_long, [vp]),

@@ -216,6 +216,10 @@ int crm_ctx_create(int device, crm_ctx** out) {
     CRM_HIP(hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking));
     CRM_HIP(hipEventCreate(&c->ev0));
     CRM_HIP(hipEventCreate(&c->ev1));
+    int prio_least = 0, prio_greatest = 0;   // (least: the numerically largest value; the main stream keeps its priority)
+    CRM_HIP(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+    CRM_HIP(hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, prio_least));
+    for (hipEvent_t* e : {&c->ev_fork, &c->ev_side, &c->ev_main, &c->ev_fits}) CRM_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
     {
         std::lock_guard<std::mutex> lock(g_ctx_mutex);
         g_contexts.push_back(c);
@@ -230,6 +234,7 @@ int crm_ctx_trim(crm_ctx* c) {
     if (!c) return CRM_ERR_ARG;
     CRM_HIP(hipSetDevice(c->device));
     CRM_HIP(hipStreamSynchronize(c->stream));
+    if (c->side_stream) CRM_HIP(hipStreamSynchronize(c->side_stream));
     std::lock_guard<std::mutex> lock(g_ctx_mutex);
     (void)trim_context(c);
     return CRM_OK;
@@ -241,6 +246,7 @@ void crm_ctx_destroy(crm_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     {
         std::lock_guard<std::mutex> lock(g_ctx_mutex);
         g_contexts.erase(std::remove(g_contexts.begin(), g_contexts.end(), c), g_contexts.end());
@@ -255,6 +261,9 @@ void crm_ctx_destroy(crm_ctx* c) {
     }
     (void)hipEventDestroy(c->ev0);
     (void)hipEventDestroy(c->ev1);
+    for (hipEvent_t e : {c->ev_fork, c->ev_side, c->ev_main, c->ev_fits})
+        if (e) (void)hipEventDestroy(e);
+    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     (void)hipStreamDestroy(c->stream);
     if (c->upload_stream) (void)hipStreamDestroy(c->upload_stream);
     if (c->sync_timeouts_host) (void)hipHostFree(c->sync_timeouts_host);
@@ -268,6 +277,7 @@ int crm_ctx_synchronize(crm_ctx* c) {
     if (!c) return CRM_ERR_ARG;
     CRM_HIP(hipSetDevice(c->device));
     CRM_HIP(hipStreamSynchronize(c->stream));
+    if (c->side_stream) CRM_HIP(hipStreamSynchronize(c->side_stream));
     return CRM_OK;
     });
 }
@@ -315,7 +325,7 @@ FormSlot g_forms[] = {{"gram_staged", 0, false}, {"kr_no_tail", 0, false}, {"nul
                       {"kin_diag", 0, false}, {"donor_pairs_rotate", 0, false}, {"rho0_positions", 0, false},
                       {"rotation_tails", 0, false}, {"woodbury_ytY", 0, false},
                       {"wb_block_order", 0, false}, {"block_fused", 0, false}, {"wb_gram_fused", 0, false},
-                      {"gram_strips", 0, false}};
+                      {"gram_strips", 0, false}, {"side_stream", 0, false}};
 std::mutex g_forms_mu;
 }  // namespace
 int form(const char* name, int otherwise) {
@@ -377,6 +387,14 @@ int crm_test_wb_gram_fused_blocks(const crm_ctx* ctx, long* blocks) {
     return crm::guarded("crm_test_wb_gram_fused_blocks", [&]() -> int {
     if (!ctx || !blocks) return CRM_ERR_ARG;
     *blocks = ctx->wb_gram_fused_blocks;
+    return CRM_OK;
+    });
+}
+
+int crm_test_side_stream_blocks(const crm_ctx* ctx, long* blocks) {
+    return crm::guarded("crm_test_side_stream_blocks", [&]() -> int {
+    if (!ctx || !blocks) return CRM_ERR_ARG;
+    *blocks = ctx->side_stream_blocks;
     return CRM_OK;
     });
 }

@@ -48,6 +48,7 @@ inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 //   "eigh_one_stage"    1: the constructor's eigen-solver tridiagonalises every grid point on its own (eigh_trd.hip)
 //   "nullfit_exact"     1: null-fit likelihood with IEEE division and one log per spectrum entry
 //   "gram_strips"       0: the 65-144-row direct-to-LDS Gram kernels deal their tiles round-robin (tile_gram.h: kStripDeal)
+//   "side_stream"       0: the fit-independent products of a block stay in the pair stage; 2 / 3: side first / side last (scan_side.hip)
 int form(const char* name, int otherwise);
 
 // No C++ exception may cross the C-ABI (ctypes / cgo / JNI callers cannot unwind, the process would end in
@@ -123,6 +124,10 @@ struct GemmTune {
 };
 int launch_gemm_tn(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int max_m, int max_n,
                    long cells, bool khatri_rao, int k0, int ksplit, long split_stride);
+// ... on a stream other than the context's own (the scan's side stream): plain products only -- the persistent Khatri-Rao
+// form counts on having the chip to itself, and Khatri-Rao launches are refused there
+int launch_gemm_tn(crm_ctx* ctx, hipStream_t st, const GemmProblem* probs_dev, int nz, int max_m, int max_n,
+                   long cells, bool khatri_rao, int k0, int ksplit, long split_stride);
 // number of slices along the cell axis for a launch that would otherwise have `blocks_without_split` workgroups
 int split_for(long cells_pad, long blocks_without_split);
 int contraction_tile_width(const crm_ctx* ctx, int mt, int max_n, int nz, int ksplit, bool khatri_rao);
@@ -130,6 +135,10 @@ int kr_split_for(const crm_ctx* ctx, long row_tiles, int max_n, int nz, long cel
 int launch_gemm_tn_glds(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int mt, int nt, long cells,
                         bool khatri_rao, int k0, int ksplit, long split_stride, bool transposed_out = false,
                         int bn = 128);
+int launch_gemm_tn_glds(crm_ctx* ctx, hipStream_t st, const GemmProblem* probs_dev, int nz, int mt, int nt, long cells,
+                        bool khatri_rao, int k0, int ksplit, long split_stride, bool transposed_out, int bn);
+// would a Khatri-Rao launch of this shape run as the persistent form (gemm_tn_glds_sync_kernel)?
+bool kr_launch_persistent(const crm_ctx* ctx, long tiles, long cells_per_slice, int bn);
 // Khatri-Rao contraction storing C' (N x M, leading dimension ldc): always the LDS-DMA kernel
 int launch_kr_transposed(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int max_m, int max_n, long cells,
                          int k0);

@@ -80,6 +80,13 @@ struct crm_ctx {
     hipStream_t upload_stream = nullptr;   // crm_panel_create copies on it, outside the context's lock: a panel can be
                                            // uploaded from one thread while another one runs the constructor
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // The side stream of the interaction scan (scan_side.hip): lowest priority, for the products of a
+    // block that depend on the block alone and so may run beside its null fits.  ev_fork: the main stream behind the batched
+    // rotation launch; ev_side: the side stream behind its last launch; ev_main: the main stream just before the join
+    // (form "side_stream" = 3); ev_fits: the main stream behind the copy of a block's fits (ScanPass::collect_fits).
+    // Outside a scan pass the side stream is idle.
+    hipStream_t side_stream = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_side = nullptr, ev_main = nullptr, ev_fits = nullptr;
     int block_variants = 0;  // 0 = automatic
     bool fast_T = true;    // T(rho) through the mixing matrices when the background offers them
     int kin_route = 1;          // H'(g o E0) donor by donor when the background knows its kinship structure: 0 never
@@ -120,6 +127,7 @@ struct crm_ctx {
     long rotation_tail_launches = 0;   // blocks whose rotations sent the last few columns of their spectra through it (crm_test_rotation_tail_launches)
     long rho0_position_blocks = 0;     // blocks whose null fits at rho = 0 read the position basis (crm_test_rho0_position_blocks)
     long wb_gram_fused_blocks = 0;     // blocks whose unrelated-donor Gram came straight from the pair products (crm_test_wb_gram_fused_blocks)
+    long side_stream_blocks = 0;       // blocks whose fit-independent products were enqueued on the side stream (crm_test_side_stream_blocks)
     long fused_blocks = 0;             // blocks read in place in the panel and prepared by the fused pass (crm_test_fused_blocks)
     long unrelated_donor_blocks = 0;   // blocks served by the unrelated-donor form (crm_test_unrelated_donor_blocks)
     long gram_dma_launches = 0;   // score-statistic Grams that went through a direct-to-LDS kernel (crm_test_gram_dma_launches)

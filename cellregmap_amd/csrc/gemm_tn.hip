@@ -367,8 +367,16 @@ int launch_kr_transposed(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int
 
 int launch_gemm_tn(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int max_m, int max_n,
                    long cells, bool khatri_rao, int k0, int ksplit, long split_stride) {
+    return launch_gemm_tn(ctx, ctx->stream, probs_dev, nz, max_m, max_n, cells, khatri_rao, k0, ksplit, split_stride);
+}
+
+int launch_gemm_tn(crm_ctx* ctx, hipStream_t st, const GemmProblem* probs_dev, int nz, int max_m, int max_n,
+                   long cells, bool khatri_rao, int k0, int ksplit, long split_stride) {
     if (nz <= 0 || max_m <= 0 || max_n <= 0) return CRM_OK;
-    hipStream_t st = ctx->stream;
+    if (khatri_rao && st != ctx->stream) {
+        set_error("contraction: Khatri-Rao launches run on the context's own stream");
+        return CRM_ERR_INTERNAL;
+    }
     if (ksplit < 1) ksplit = 1;
     // slices of ceil(stages / ksplit) stages; every slice must hold at least one (see split_for)
     const long total_stages = cells / GEMM_BK;
@@ -386,7 +394,7 @@ int launch_gemm_tn(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int max_m
     const int bn = contraction_tile_width(ctx, mt, max_n, nz, ksplit, khatri_rao);
     const int nt = (max_n + bn - 1) / bn;
     if (ctx->tune.glds && (bn == 128 || khatri_rao)) {
-        return launch_gemm_tn_glds(ctx, probs_dev, nz, mt, nt, cells, khatri_rao, k0, ksplit, split_stride, false, bn);
+        return launch_gemm_tn_glds(ctx, st, probs_dev, nz, mt, nt, cells, khatri_rao, k0, ksplit, split_stride, false, bn);
     }
     dim3 grid((unsigned)(mt * nt), (unsigned)ksplit, (unsigned)nz);
     size_t lds = (size_t)2 * GEMM_BK * (bn + 16) * sizeof(double);

@@ -453,7 +453,16 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_glds_sync_kernel(const GemmPro
     }
 }
 
+bool kr_launch_persistent(const crm_ctx* ctx, long tiles, long cells_per_slice, int bn) {
+    return ctx->tune.sync > 0 && bn == 128 && tiles > 1024 && cells_per_slice >= 1024;
+}
+
 int launch_gemm_tn_glds(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int mt, int nt, long cells,
+                        bool khatri_rao, int k0, int ksplit, long split_stride, bool transposed_out, int bn) {
+    return launch_gemm_tn_glds(ctx, ctx->stream, probs_dev, nz, mt, nt, cells, khatri_rao, k0, ksplit, split_stride, transposed_out, bn);
+}
+
+int launch_gemm_tn_glds(crm_ctx* ctx, hipStream_t st, const GemmProblem* probs_dev, int nz, int mt, int nt, long cells,
                         bool khatri_rao, int k0, int ksplit, long split_stride, bool transposed_out, int bn) {
     if (bn != 128 && !(bn == 64 && khatri_rao) && !(bn == 160 && khatri_rao && !transposed_out)) {
         set_error("contraction: %d-wide LDS-DMA tiles are not built for this form", bn);
@@ -463,7 +472,10 @@ int launch_gemm_tn_glds(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int 
         set_error("contraction: the transposed store is only built for the Khatri-Rao form");
         return CRM_ERR_UNSUPPORTED;
     }
-    hipStream_t st = ctx->stream;
+    if (khatri_rao && st != ctx->stream) {
+        set_error("contraction: Khatri-Rao launches run on the context's own stream");
+        return CRM_ERR_INTERNAL;
+    }
     dim3 grid((unsigned)(mt * nt), (unsigned)ksplit, (unsigned)nz);
     // waits of the previous persistent launch that ran out (read back asynchronously: a late value only delays the
     // fallback by a launch): the workgroups are not co-resident on this GPU right now -- one workgroup per tile from here
@@ -478,7 +490,7 @@ int launch_gemm_tn_glds(crm_ctx* ctx, const GemmProblem* probs_dev, int nz, int 
     // (long contractions only: a generation of short tiles -- the per-donor launches of the kinship-structure route, 13 stages --
     // does not pay for its re-alignment wait: 22 ms in this form against 17 ms with one workgroup per tile; nor does the plain
     // Mix(rho*)' product of that route, 231 against 228 ms per block)
-    const bool sync = sync_every > 0 && khatri_rao && bn == 128 && (long)mt * nt * ksplit * nz > 1024 && cells / ksplit >= 1024;
+    const bool sync = khatri_rao && kr_launch_persistent(ctx, (long)mt * nt * ksplit * nz, cells / ksplit, bn);
     unsigned* sync_counters = nullptr;
     if (sync) {
         CRM_TRY(ctx->sync_counters.ensure(64));

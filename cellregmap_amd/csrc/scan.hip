@@ -87,6 +87,10 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
     CRM_TRY(S.prepare_contexts());
     CRM_TRY(S.prepare_kinship());
     CRM_TRY(S.prepare_woodbury());
+    // The side stream (scan_side.hip): whatever way the pass ends -- the null-fit probe's early return, an error -- it ends
+    // with the side stream idle, so that the buffers its launches read and write can be reused or freed
+    S.side_form = S.side_serves() ? std::max(0, std::min(3, form("side_stream", 1))) : 0;
+    struct SideIdle { crm_ctx* c; bool on; ~SideIdle() { if (on) (void)hipStreamSynchronize(c->side_stream); } } side_idle{ctx, S.side_form != 0};
     for (long done = 0; done < count; done += P.BLK) {
         Block B;
         B.done = done;
@@ -111,8 +115,12 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
             Pairs Q;
             CRM_TRY(S.select_pairs(B, R, Q));
             CRM_TRY(S.form_A(B, R, Q));
-            CRM_TRY(S.side_contractions(B, R));
-            CRM_TRY(S.z1_products(B, R));
+            if (S.side_form != 0) {   // (Z2, Z3 and Z1 come from the side stream: the join before the assembly)
+                CRM_TRY(S.side_join(B));
+            } else {
+                CRM_TRY(S.side_contractions(B, R));
+                CRM_TRY(S.z1_products(B, R));
+            }
             for (int gi = 0; gi < S.ng; gi++) CRM_TRY(S.gene_results(B, R, gi));
             b0 += R.nb;
         }

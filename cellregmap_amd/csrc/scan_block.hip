@@ -267,7 +267,8 @@ int ScanPass::rotations(const Block& B) {
         all[i] = p;
     }
     const int n_list = plan_rotations(B, all);   // (probs[0, n_list), rot_tails, rho0_pos)
-    if (n_list == 0) return CRM_OK;
+    CRM_TRY(side_prepare(B));   // (the side stream's records, ahead of the launch it forks behind: scan_side.hip)
+    if (n_list == 0) return side_fork(B);
     int n_main = n_list;
     if (P.fastT) CRM_TRY(cut_rotations(B, n_list, n_main));
     CRM_TRY(upload(SLOT_RHO, probs.data(), n_main));
@@ -279,6 +280,7 @@ int ScanPass::rotations(const Block& B) {
         CRM_TRY(timer_close());
         for (int q = 0; q < n_main; q++) ctx->kr_flops += 2.0 * (double)P.kdim * (double)nb * (double)probs[q].N;
     }
+    CRM_TRY(side_fork(B));   // (behind timer_close: the timed pair still brackets the rotations alone)
     if (!rot_tails.empty()) {   // (records behind the batched launch's and the cut ones; rot_tails lives as long as the pass)
         CRM_TRY(upload(SLOT_RHO + n_list, rot_tails.data(), rot_tails.size()));
         CRM_TRY(launch_skinny_tn(st, d_probs + SLOT_RHO + n_list, (int)rot_tails.size(), nb, P.kdim));
@@ -447,7 +449,7 @@ int ScanPass::woodbury_phi(const Block& B) {
     p.X = ctx->ws_TH.as<double>() + (size_t)bg->kin_k1 * P.ldb; p.ldx = P.ldb; p.C = wb_g; p.ldc = P.ldwb; p.M = B.nb;
     woodbury_records(bg, p, (long)bg->kin_k2 * P.ldb, phi_recs.data());
     // (no with_records: the host is not to wait here, ahead of the step's largest launch -- phi_recs lives as long as
-    // the pass and is written again only in the next block, after collect_fits has synchronised the stream)
+    // the pass and is written again only in the next block, after gene_results has synchronised the stream)
     CRM_TRY(upload(SLOT_KIN, phi_recs.data(), phi_recs.size()));
     return launch_gemm_tn(ctx, d_probs + SLOT_KIN, (int)groups, B.nb, bg->kin_k2, bg->wb_k2pad, false, 0, 1, 0);
 }
@@ -458,7 +460,14 @@ int ScanPass::collect_fits(Block& B) {
     const int nb = B.nb, BLK = P.BLK;
     CRM_HIP(hipMemcpyAsync(h_fit.data(), d_fit, sizeof(NullFitOut) * (size_t)BLK * ng, hipMemcpyDeviceToHost, st));
     if (P.collapsed() && near_out) CRM_HIP(hipMemcpyAsync(h_near.data(), d_near, sizeof(int) * nb, hipMemcpyDeviceToHost, st));
-    CRM_HIP(hipStreamSynchronize(st));
+    if (early_pairs()) {
+        // (scan_side.hip: the pair products of the block behind the copy -- the host waits for the copy alone and the
+        // chip works while it reads the fits and enqueues the pair stage)
+        CRM_HIP(hipEventRecord(ctx->ev_fits, st));
+        CRM_TRY(launch_early_pairs(B));
+        CRM_HIP(hipEventSynchronize(ctx->ev_fits));
+    } else
+        CRM_HIP(hipStreamSynchronize(st));
     if (P.collapsed() && near_out)
         for (int b = 0; b < nb; b++)
             if (h_near[b]) near_out->push_back(B.done + b);

@@ -176,7 +176,8 @@ void ScanPass::a_records(const Pairs& Q, bool via_H, const bool* tail_of, AGroup
 // The kinship routes' operand columns in donor order (Gk): one phenotype takes them in the rho*-sorted pair order (Gs)
 // straight away, so that the result is the operand of the Mix products as it stands; several phenotypes share a
 // variant between pairs: block order, then the pair gather.  The unrelated-donor form has no Mix product: block order
-int ScanPass::donor_columns(const Block& B, const SubRange& R, const Pairs& Q, DonorCols& D) {
+// `on`: the stream of the gather; null: the columns' places alone (the gather is launched elsewhere, or was)
+int ScanPass::donor_columns(const Block& B, const SubRange& R, const Pairs& Q, DonorCols& D, hipStream_t on) {
     D.in_pair_order = ng == 1 && !P.wb_block;
     D.G = D.in_pair_order ? ctx->ws_Gs.as<double>() : B.Gt + R.b0;
     D.ldg = D.in_pair_order ? P.ldp : B.ldt;
@@ -187,8 +188,9 @@ int ScanPass::donor_columns(const Block& B, const SubRange& R, const Pairs& Q, D
         D.Gk = ctx->ws_Gkt.as<double>();
         return CRM_OK;
     }
+    if (!on) return CRM_OK;
     const int blk_cols = (int)(P.ldb - R.b0);   // (columns of the block buffers from the sub-range's first one on)
-    return launch_gather_rows(st, D.G, D.ldg, bg->kin_map.as<int>(), bg->kin_rows, D.in_pair_order ? (int)D.ldg : blk_cols,
+    return launch_gather_rows(on, D.G, D.ldg, bg->kin_map.as<int>(), bg->kin_rows, D.in_pair_order ? (int)D.ldg : blk_cols,
                               ctx->ws_Gk.as<double>(), D.ldk);
 }
 int ScanPass::gather_pairs(const double* src, long rows, const Pairs& Q) {   // (several phenotypes: the operand in pair order, XG)
@@ -203,10 +205,13 @@ int ScanPass::gather_pairs(const double* src, long rows, const Pairs& Q) {   // 
 // that its few output tiles fill the chip, summed, and copied into rows [0, k1).
 int ScanPass::folded_S(const Block& B, const SubRange& R, const Pairs& Q) {
     DonorCols D;
-    CRM_TRY(donor_columns(B, R, Q, D));
+    CRM_TRY(donor_columns(B, R, Q, D, early_pairs() ? nullptr : st));   // (launch_early_pairs has gathered them)
     double* S = ctx->ws_S.as<double>();
     const int k1 = bg->kin_k1, k2 = bg->kin_k2, ncol = D.ncol, npair = P.npair;
     const long groups = bg->kin_groups, ld_ah = P.ld_ah;
+    // (the pair products were launched from the block's side records, in collect_fits: this stage uploads no records, so
+    // the host does not wait here)
+    if (early_pairs()) return pair_stage(B, R, Q, D, nullptr, 0, GEMM_BK, 0);
     std::vector<GemmProblem> kp((size_t)groups + P.fold_split6);
     GemmProblem p{};
     p.X = D.Gk; p.ldx = D.ldk;
@@ -243,54 +248,61 @@ int ScanPass::folded_S(const Block& B, const SubRange& R, const Pairs& Q) {
         chunk_max = std::max(chunk_max, e.cells);
     }
     kp.resize((size_t)groups + std::max(slices, 1));
-    return with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) -> int {
-        double* AH = ctx->ws_AH.as<double>();
-        if (probed.donor_pairs) {
-            CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, npair, maxlen, false, 0, 1, 0));
-            // One phenotype, no second assembly from the rotated S (flags: flat_probes) and no replay: the Gram of the
-            // assembly straight from the pair products, the rotated S stays in LDS (wb_gram_fused.hip)
-            if (probed.wb_rotate && may_fuse_gram() && R.b0 == 0 && R.nb == B.nb) {
-                const AssembleArgs aa = assemble_args(R, 0);
-                const WbFusedArgs fa{ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, bg->wb_U.as<double>(), (long)bg->wb_k2pad * 128, 128,
-                                     AH, P.pd_slab, (int)groups, P.donor_pair_splits, bg->wb_k2pad};
-                if (wb_gram_fused_serves(aa, fa, nrho)) {
-                    CRM_TRY(launch_wb_gram_fused(st, aa, fa, nrho, ncol));
-                    gram_fused = true;
-                    ctx->wb_gram_fused_blocks++;
-                }
-            }
-            if (!gram_fused && P.wb()) CRM_TRY(ctx->ws_A.ensure(ws_A_bytes()));   // (workspaces() left it to the fused Gram)
-            if (gram_fused) {
-            } else if (probed.wb_rotate)   // (the rotated S straight from the pair products: the rows of S are not formed)
-                CRM_TRY(launch_donor_pairs_rotate(st, ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, (int)groups, ncol, k0,
-                                                  bg->wb_U.as<double>(), (long)bg->wb_k2pad * 128, 128, bg->wb_k2pad,
-                                                  ctx->ws_A.as<double>(), P.ldAw, AH, P.pd_slab, P.donor_pair_splits));
-            else
-                CRM_TRY(launch_donor_pairs_expand(st, ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, (int)groups, ncol, k0, k1, S, ld_ah,
-                                                  AH, P.pd_slab, P.donor_pair_splits));
-            CRM_TRY(launch_reduce_splits(st, AH, (long)ncol * P.ldPd, P.donor_pair_splits, P.pd_slab));
-            CRM_TRY(launch_pair_rows_sym(st, AH, P.ldPd, ncol, k0, S, ld_ah));
-            ctx->donor_pair_blocks++;
-        } else {
-            if (k2 == 1) CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, k0, maxlen, false, 0, 1, 0));
-            else CRM_TRY(launch_kr_transposed(ctx, d_kp, (int)groups, ncol * k0, k2, maxlen, k0));
-            if (P.e1_pairs) {
-                const long p_slab = (long)(std::max<long>(P.BLK, P.pair_cap) + 128) * P.ldP;
-                CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, 1, ncol, probed.e1_sym ? npair : k1 * k0, np, false, 0, P.fold_split6, p_slab));
-                CRM_TRY(launch_reduce_splits(st, AH, (long)ncol * P.ldP, P.fold_split6, p_slab));
-                if (probed.e1_sym) CRM_TRY(launch_pair_rows_sym(st, AH, P.ldP, ncol, k0, S, ld_ah));
-                else CRM_TRY(launch_pair_rows(st, AH, P.ldP, ncol, k1, k0, S, ld_ah));
-            } else {
-                CRM_TRY(launch_kr_transposed(ctx, d_kp + groups, slices, ncol * k0, k1, chunk_max, k0));
-                CRM_TRY(launch_reduce_splits(st, AH, e1_slab, slices, e1_slab));
-                CRM_HIP(hipMemcpyAsync(S, AH, sizeof(double) * (size_t)e1_slab, hipMemcpyDeviceToDevice, st));
+    return with_records(SLOT_KIN, kp, [&](GemmProblem* d_kp) -> int { return pair_stage(B, R, Q, D, d_kp, maxlen, chunk_max, slices); });
+}
+
+// ... its launches, from the records at d_kp (null: the pair products are in the stream's queue already, collect_fits)
+int ScanPass::pair_stage(const Block& B, const SubRange& R, const Pairs& Q, const DonorCols& D, GemmProblem* d_kp, long maxlen,
+                         long chunk_max, int slices) {
+    double* S = ctx->ws_S.as<double>();
+    const int k1 = bg->kin_k1, k2 = bg->kin_k2, ncol = D.ncol, npair = P.npair;
+    const long groups = bg->kin_groups, ld_ah = P.ld_ah, e1_slab = (long)k1 * ld_ah;
+    double* AH = ctx->ws_AH.as<double>();
+    if (probed.donor_pairs) {
+        if (d_kp) CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, npair, maxlen, false, 0, 1, 0));
+        // One phenotype, no second assembly from the rotated S (flags: flat_probes) and no replay: the Gram of the
+        // assembly straight from the pair products, the rotated S stays in LDS (wb_gram_fused.hip)
+        if (probed.wb_rotate && may_fuse_gram() && R.b0 == 0 && R.nb == B.nb) {
+            const AssembleArgs aa = assemble_args(R, 0);
+            const WbFusedArgs fa{ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, bg->wb_U.as<double>(), (long)bg->wb_k2pad * 128, 128,
+                                 AH, P.pd_slab, (int)groups, P.donor_pair_splits, bg->wb_k2pad};
+            if (wb_gram_fused_serves(aa, fa, nrho)) {
+                CRM_TRY(launch_wb_gram_fused(st, aa, fa, nrho, ncol));
+                gram_fused = true;
+                ctx->wb_gram_fused_blocks++;
             }
         }
-        // (2 kin_rows k2 k0 + 2 n k1 k0 flops per variant, outside the timed pair: the roofline figure is the MixK product's own;
-        // bench.py's whole_path counts them)
-        if (!D.in_pair_order && !P.wb()) CRM_TRY(gather_pairs(S, P.kdim, Q));
-        return CRM_OK;
-    });
+        if (!gram_fused && P.wb()) CRM_TRY(ctx->ws_A.ensure(ws_A_bytes()));   // (workspaces() left it to the fused Gram)
+        if (gram_fused) {
+        } else if (probed.wb_rotate)   // (the rotated S straight from the pair products: the rows of S are not formed)
+            CRM_TRY(launch_donor_pairs_rotate(st, ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, (int)groups, ncol, k0,
+                                              bg->wb_U.as<double>(), (long)bg->wb_k2pad * 128, 128, bg->wb_k2pad,
+                                              ctx->ws_A.as<double>(), P.ldAw, AH, P.pd_slab, P.donor_pair_splits));
+        else
+            CRM_TRY(launch_donor_pairs_expand(st, ctx->ws_Pd.as<double>(), P.pd_slab, P.ldPd, (int)groups, ncol, k0, k1, S, ld_ah,
+                                              AH, P.pd_slab, P.donor_pair_splits));
+        CRM_TRY(launch_reduce_splits(st, AH, (long)ncol * P.ldPd, P.donor_pair_splits, P.pd_slab));
+        CRM_TRY(launch_pair_rows_sym(st, AH, P.ldPd, ncol, k0, S, ld_ah));
+        ctx->donor_pair_blocks++;
+    } else {
+        if (k2 == 1) CRM_TRY(launch_gemm_tn(ctx, d_kp, (int)groups, ncol, k0, maxlen, false, 0, 1, 0));
+        else CRM_TRY(launch_kr_transposed(ctx, d_kp, (int)groups, ncol * k0, k2, maxlen, k0));
+        if (P.e1_pairs) {
+            const long p_slab = (long)(std::max<long>(P.BLK, P.pair_cap) + 128) * P.ldP;
+            CRM_TRY(launch_gemm_tn(ctx, d_kp + groups, 1, ncol, probed.e1_sym ? npair : k1 * k0, np, false, 0, P.fold_split6, p_slab));
+            CRM_TRY(launch_reduce_splits(st, AH, (long)ncol * P.ldP, P.fold_split6, p_slab));
+            if (probed.e1_sym) CRM_TRY(launch_pair_rows_sym(st, AH, P.ldP, ncol, k0, S, ld_ah));
+            else CRM_TRY(launch_pair_rows(st, AH, P.ldP, ncol, k1, k0, S, ld_ah));
+        } else {
+            CRM_TRY(launch_kr_transposed(ctx, d_kp + groups, slices, ncol * k0, k1, chunk_max, k0));
+            CRM_TRY(launch_reduce_splits(st, AH, e1_slab, slices, e1_slab));
+            CRM_HIP(hipMemcpyAsync(S, AH, sizeof(double) * (size_t)e1_slab, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    // (2 kin_rows k2 k0 + 2 n k1 k0 flops per variant, outside the timed pair: the roofline figure is the MixK product's own;
+    // bench.py's whole_path counts them)
+    if (!D.in_pair_order && !P.wb()) CRM_TRY(gather_pairs(S, P.kdim, Q));
+    return CRM_OK;
 }
 
 // AH = H'(g o E0) without an n-length contraction against the cols columns of H:
@@ -299,7 +311,7 @@ int ScanPass::folded_S(const Block& B, const SubRange& R, const Pairs& Q) {
 // donors with hKd, AH[(k1 + j m + d), .] = sum_d' hKd[d', d] S[(d' KK + j), .]; (d) the E1 rows: sums over d'
 int ScanPass::unfolded_AH(const Block& B, const SubRange& R, const Pairs& Q) {
     DonorCols D;
-    CRM_TRY(donor_columns(B, R, Q, D));
+    CRM_TRY(donor_columns(B, R, Q, D, st));
     double* S = ctx->ws_S.as<double>();
     double* AH = ctx->ws_AH.as<double>();
     const int k1 = bg->kin_k1, k2 = bg->kin_k2, ncol = D.ncol, npair = P.npair;
@@ -445,48 +457,62 @@ int ScanPass::form_A(const Block& B, const SubRange& R, const Pairs& Q) {
 
 // 7. elementwise products for the side contractions
 // 8. y-free side contractions: Z2 = (Gt o G)' E, Z3 = (Gt o Gt)' (E (x) E)
-int ScanPass::side_contractions(const Block& B, const SubRange& R) {
+// (the records -- Z2, Z3 -- and the launches apart: the side stream's are uploaded ahead of the fork, scan_side.hip)
+void ScanPass::side_records(const SubRange& R, GemmProblem* out) const {
+    double* G2 = ctx->ws_G2.as<double>();
+    double* GG = !P.collapsed() ? ctx->ws_GG.as<double>() : G2;   // (test direction) o (fixed-effect role)
+    GemmProblem p{};
+    p.ldx = P.ldb; p.M = R.nb;
+    p.X = GG; p.Y = P.collapsed() ? tab->Z2.as<double>() : d_Ep; p.ldy = g0->ld_ep; p.C = dZ2; p.ldc = P.ldZ2; p.N = k0;
+    out[0] = p;
+    p.X = G2; p.Y = P.collapsed() ? tab->Z3.as<double>() : d_EE; p.ldy = g0->ld_ee; p.C = dZ3; p.ldc = P.ldZ3; p.N = P.npair;
+    out[1] = p;
+}
+int ScanPass::side_launches(const Block& B, const SubRange& R, hipStream_t on, const GemmProblem* d_recs) {
     const long ldb = P.ldb;
     const int nb = R.nb;
-    double* const Gt = B.Gt + R.b0;
     double* G2 = ctx->ws_G2.as<double>();
-    double* GG = !P.collapsed() ? ctx->ws_GG.as<double>() : nullptr;   // (test direction) o (fixed-effect role)
+    double* GG = !P.collapsed() ? ctx->ws_GG.as<double>() : nullptr;
     // (a fused block: block_stats' pass has written both, from the same products)
-    if (!B.fused) CRM_TRY(launch_square_block(st, Gt, B.Gx + R.b0, ldb, ldb, P.xrows, (int)(ldb - R.b0), G2, GG, ldb));
-    if (!GG) GG = G2;
+    if (!B.fused) CRM_TRY(launch_square_block(on, B.Gt + R.b0, B.Gx + R.b0, ldb, ldb, P.xrows, (int)(ldb - R.b0), G2, GG, ldb));
     const int s2 = P.collapsed() ? 1 : P.ks2, s3 = P.collapsed() ? 1 : P.ks3;
-    GemmProblem p{};
-    p.ldx = ldb; p.M = nb;
-    p.X = GG; p.Y = P.collapsed() ? tab->Z2.as<double>() : d_Ep; p.ldy = g0->ld_ep; p.C = dZ2; p.ldc = P.ldZ2; p.N = k0;
-    probs[1] = p;
-    p.X = G2; p.Y = P.collapsed() ? tab->Z3.as<double>() : d_EE; p.ldy = g0->ld_ee; p.C = dZ3; p.ldc = P.ldZ3; p.N = P.npair;
-    probs[2] = p;
-    CRM_TRY(upload(SLOT_RHO, probs.data() + 1, 2));
     if (P.cross) {
-        CRM_TRY(launch_donor_cross(st, nb, B.Gb + R.b0, ldb, (int)panel->m, tab->Z2.as<double>(), P.ldZ2, k0, dZ2, P.ldZ2));
+        CRM_TRY(launch_donor_cross(on, nb, B.Gb + R.b0, ldb, (int)panel->m, tab->Z2.as<double>(), P.ldZ2, k0, dZ2, P.ldZ2));
     } else {
-        CRM_TRY(launch_gemm_tn(ctx, d_probs + SLOT_RHO, 1, nb, k0, P.xrows, false, 0, s2, z2_sz));
-        CRM_TRY(launch_reduce_splits(st, dZ2, z2_sz, s2, z2_sz));
+        CRM_TRY(launch_gemm_tn(ctx, on, d_recs, 1, nb, k0, P.xrows, false, 0, s2, z2_sz));
+        CRM_TRY(launch_reduce_splits(on, dZ2, z2_sz, s2, z2_sz));
     }
-    CRM_TRY(launch_gemm_tn(ctx, d_probs + SLOT_RHO + 1, 1, nb, P.npair, P.xrows, false, 0, s3, z3_sz));
-    return launch_reduce_splits(st, dZ3, z3_sz, s3, z3_sz);
+    CRM_TRY(launch_gemm_tn(ctx, on, d_recs + 1, 1, nb, P.npair, P.xrows, false, 0, s3, z3_sz));
+    return launch_reduce_splits(on, dZ3, z3_sz, s3, z3_sz);
+}
+int ScanPass::side_contractions(const Block& B, const SubRange& R) {
+    side_records(R, probs.data() + 1);
+    CRM_TRY(upload(SLOT_RHO, probs.data() + 1, 2));
+    return side_launches(B, R, st, d_probs + SLOT_RHO);
 }
 
 // 9. Z1 = Gt' [y o E, W o E] of every phenotype, one launch (ScanPlan::ks1)
-int ScanPass::z1_products(const Block& B, const SubRange& R) {
-    const int s1 = P.collapsed() ? 1 : P.ks1;
-    std::vector<GemmProblem> zp((size_t)ng);
+void ScanPass::z1_records(const Block& B, const SubRange& R, GemmProblem* out) const {
     for (int gi = 0; gi < ng; gi++) {
         crm_gene* g = genes[gi];
-        GemmProblem& p = zp[(size_t)gi];
+        GemmProblem p{};
         p.X = B.Gt + R.b0; p.ldx = B.ldt; p.Y = P.collapsed() ? g->dt_Z1.as<double>() : g->YE.as<double>(); p.ldy = g->ld_ye;
         p.C = dZ1 + (size_t)gi * z1_sz * P.ks1; p.ldc = P.ldZ1; p.M = R.nb; p.N = k0 * (1 + c);
+        out[gi] = p;
     }
-    CRM_TRY(upload(P.z1_slot(), zp.data(), zp.size()));
-    CRM_TRY(launch_gemm_tn(ctx, d_probs + P.z1_slot(), ng, R.nb, k0 * (1 + c), P.xrows, false, 0, s1, z1_sz));
+}
+int ScanPass::z1_launches(const SubRange& R, hipStream_t on, const GemmProblem* d_recs) {
+    const int s1 = P.collapsed() ? 1 : P.ks1;
+    CRM_TRY(launch_gemm_tn(ctx, on, d_recs, ng, R.nb, k0 * (1 + c), P.xrows, false, 0, s1, z1_sz));
     for (int gi = 0; gi < ng; gi++)
-        CRM_TRY(launch_reduce_splits(st, dZ1 + (size_t)gi * z1_sz * P.ks1, z1_sz, s1, z1_sz));
+        CRM_TRY(launch_reduce_splits(on, dZ1 + (size_t)gi * z1_sz * P.ks1, z1_sz, s1, z1_sz));
     return CRM_OK;
+}
+int ScanPass::z1_products(const Block& B, const SubRange& R) {
+    std::vector<GemmProblem> zp((size_t)ng);
+    z1_records(B, R, zp.data());
+    CRM_TRY(upload(P.z1_slot(), zp.data(), zp.size()));
+    return z1_launches(R, st, d_probs + P.z1_slot());
 }
 
 }  // namespace crm

@@ -69,7 +69,9 @@ enum class Route {
 // Slots of the pass's problem records (ctx->ws_probs): [0] a single product -- in step 6 the A~ groups, then their tails;
 // from 1 the rotations of step 3 (the side contractions at 1 and 2): the batched launch's problems, behind them the cut ones,
 // behind those the spectrum tails -- each a part of one of the nrho products, so at most 2 nrho records; from SLOT_KIN
-// the records of the kinship-structure routes (ScanPlan::kin_probs); after those, the Z1 problems
+// the records of the kinship-structure routes (ScanPlan::kin_probs); after those, the records of the side stream's launches
+// (ScanPlan::side_probs: the donors' pair products, Z2, Z3, Z1 -- read while the main stream writes the slots before them);
+// last, the Z1 problems
 constexpr int SLOT_ONE = 0, SLOT_RHO = 1, SLOT_KIN = 2 * CRM_MAX_RHO + 4;
 
 // What a pass does: sizes, leading dimensions, splits and the route, fixed before anything is launched (plan_scan).
@@ -87,7 +89,7 @@ struct ScanPlan {
          pd_slab = 0, ldwb = 0, ld_gW = 0, th_slab = 0, s_rows = 0;
     size_t s_bytes = 0;
     int ks1 = 1, ks2 = 1, ks3 = 1, ks_h = 1, fold_split6 = 1, fold_split3 = 1, donor_pair_splits = 1;
-    int npair = 0, KT = 0, KK = 0, kin_probs = 0;
+    int npair = 0, KT = 0, KK = 0, kin_probs = 0, side_probs = 0;
     // kdim: contraction length of the products with the mixing matrices; mp: groups of a grouped panel, padded; xrows:
     // contraction length of the block products -- cells, or on the collapsed path the groups
     long kdim = 0, mp = 0, xrows = 0;
@@ -96,7 +98,8 @@ struct ScanPlan {
     bool folded() const { return route == Route::kin_folded || route == Route::unrelated; }
     bool wb() const { return route == Route::unrelated; }
     bool through_H() const { return fastT && (ng > 1 || kin()); }   // (the operands of the routes through H exist)
-    int z1_slot() const { return SLOT_KIN + kin_probs; }
+    int side_slot() const { return SLOT_KIN + kin_probs; }
+    int z1_slot() const { return side_slot() + side_probs; }
 };
 
 // (scan_plan.hip)
@@ -180,6 +183,13 @@ struct ScanPass {
     std::vector<GemmProblem> rot_tails;     // the rotations' spectrum tails of the block (plan_rotations)
     std::vector<GemmProblem> phi_recs;      // the donors' records of Phi'gx of the block (woodbury_phi)
     bool gram_fused = false;                // the sub-range's wb_Gw came from the pair products (folded_S: launch_wb_gram_fused)
+    // The side stream (scan_side.hip).  side_form: form("side_stream") where the pass is served, else 0; side_recs: the host
+    // copy of the block's side records, alive as long as the pass (side_maxlen: the longest donor run of its pair products);
+    // side_enqueued: the block's side launches are in the side stream's queue
+    int side_form = 0;
+    bool side_enqueued = false;
+    long side_maxlen = 0;
+    std::vector<GemmProblem> side_recs;
 
     ScanPass(const std::vector<crm_gene*>& genes_, crm_panel* panel_, long first_, long count_, const int* idx_E_,
              const int* idx_G_, const std::vector<ScanOut>& outs_, bool allow_collapse, std::vector<long>* near_out_)
@@ -256,15 +266,29 @@ struct ScanPass {
     int select_pairs(const Block& B, const SubRange& R, Pairs& Q);
     int direct_splits(const Pairs& Q, AGroups& A, bool* tail_of);
     void a_records(const Pairs& Q, bool via_H, const bool* tail_of, AGroups& A);
-    int donor_columns(const Block& B, const SubRange& R, const Pairs& Q, DonorCols& D);
+    int donor_columns(const Block& B, const SubRange& R, const Pairs& Q, DonorCols& D, hipStream_t on);   // (null: no gather)
     int gather_pairs(const double* src, long rows, const Pairs& Q);
     int folded_S(const Block& B, const SubRange& R, const Pairs& Q);
+    int pair_stage(const Block& B, const SubRange& R, const Pairs& Q, const DonorCols& D, GemmProblem* d_kp, long maxlen, long chunk_max,
+                   int slices);
     int unfolded_AH(const Block& B, const SubRange& R, const Pairs& Q);
     int direct_AH(const Block& B, const SubRange& R, const Pairs& Q, AGroups& A);
     int woodbury_S(const SubRange& R, const Pairs& Q);
     int form_A(const Block& B, const SubRange& R, const Pairs& Q);
+    void side_records(const SubRange& R, GemmProblem* out) const;
+    int side_launches(const Block& B, const SubRange& R, hipStream_t on, const GemmProblem* d_recs);
     int side_contractions(const Block& B, const SubRange& R);
+    void z1_records(const Block& B, const SubRange& R, GemmProblem* out) const;
+    int z1_launches(const SubRange& R, hipStream_t on, const GemmProblem* d_recs);
     int z1_products(const Block& B, const SubRange& R);
+    // ---- scan_side.hip ----------------------------------------------------------------------------------------------
+    bool side_serves() const;
+    bool early_pairs() const { return side_form != 0 && probed.donor_pairs; }   // (the pair products leave the pair stage too)
+    int side_prepare(const Block& B);
+    int side_fork(const Block& B);
+    int side_enqueue(const Block& B);
+    int side_join(const Block& B);
+    int launch_early_pairs(const Block& B);
     // ---- scan_results.hip -------------------------------------------------------------------------------------------
     int flat_probes(const Block& B, const SubRange& R, int gi, const AssembleArgs& aa, double* slow_ws, std::vector<char>& flat,
                     std::vector<double>& probe_rec);

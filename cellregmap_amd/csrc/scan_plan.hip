@@ -193,6 +193,7 @@ ScanPlan plan_scan(const std::vector<crm_gene*>& genes, const crm_panel* panel, 
     }
     P.skip_pairs = form("pairs_without_kinship_term", 1) != 0;
     P.kin_probs = bg->kin ? bg->kin_groups * (bg->kin_wb ? 2 : 1) + bg->kin_k2 + 16 : 0;
+    P.side_probs = wb ? (int)bg->kin_groups + 3 : 0;   // (scan_side.hip: the donors' pair products, Z2, Z3, Z1)
     return P;
 }
 

@@ -40,6 +40,12 @@ extern "C" {
  *                         place and prepared by the fused pass (default 1; crm_test_fused_blocks)
  *   "wb_gram_fused" 0     unrelated-donor form: the rotated S goes through memory between the rotation launch and the Gram launch,
  *                         not from the pair products straight into the Gram (default 1; crm_test_wb_gram_fused_blocks)
+ *   "side_stream" 0 / 2 / 3   unrelated-donor form, one phenotype: the products of a block that do not depend on its fits 0: in
+ *                         the pair stage behind the fits, as before; 1 (default): Z2, Z3 and Z1 on a second, lowest-priority
+ *                         stream beside the spectrum tails and the null fits, the per-donor pair products on the main stream
+ *                         while the host reads the fits; 2: the main stream waits for the side stream right behind the fork;
+ *                         3: the side stream starts only when the main stream has reached the join -- the two extremes of
+ *                         the interleaving (crm_test_side_stream_blocks)
  *   "flat_kappa_milli" v  factor (in thousandths) on the noise bound of CRM_MODEL_FLAT_OPTIMUM / CRM_MODEL_RHO_TIE (study tool)
  * These replace the environment switches of earlier versions; the GPU suite flips every one of them. */
 int crm_test_set_form(const char* name, int value, int reset);
@@ -115,6 +121,10 @@ int crm_test_fused_blocks(const crm_ctx* ctx, long* blocks);
  * without model flags or permutation replay, the context count is even and the Gram has 65 to 128 rows.  *blocks: the count
  * so far. */
 int crm_test_wb_gram_fused_blocks(const crm_ctx* ctx, long* blocks);
+/* Blocks of this context's scans whose side contractions Z2 and Z3 and whose Z1 were enqueued on the context's side stream
+ * (scan_side.hip: one phenotype on the unrelated-donor form in block order, no permutation replay, no launch of the
+ * persistent contraction form in the pass; form "side_stream": 0 never).  *blocks: the count so far. */
+int crm_test_side_stream_blocks(const crm_ctx* ctx, long* blocks);
 /* Blocks of this context's scans on the unrelated-donor form whose null fits at rho = 0 read the position basis -- Phi'gx,
  * Phi'[y, W] and s_p(0), the assembly's own operands -- so that the rotation MixK(0)'(H'Gx) was not formed (scan_block.hip:
  * plan_rotations; taken where the kept positions are as many as the grid point's rank; form "rho0_positions" = 0: never).

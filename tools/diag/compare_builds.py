@@ -32,7 +32,7 @@ COUNTERS = ("crm_test_unrelated_donor_blocks", "crm_test_donor_pair_blocks", "cr
             "crm_test_tail_launches", "crm_test_spectrum_tail_launches", "crm_test_rotation_tail_launches",
             "crm_test_rho0_position_blocks", "crm_test_tests_without_pair", "crm_test_dense_repeats")
 # reported beside them, not compared: a form that one build has and the other lacks (how many blocks of the stream it served)
-REPORTED = ("crm_test_wb_gram_fused_blocks",)
+REPORTED = ("crm_test_wb_gram_fused_blocks", "crm_test_side_stream_blocks")
 # donors, cells per donor, contexts, variants (the last one: 67 Gram rows on the unrelated-donor route, the fused Gram's range)
 STRUCTURED = ((6, 120, 7, 37), (12, 90, 20, 130), (7, 60, 5, 37), (4, 70, 32, 10))
 

@@ -616,6 +616,26 @@ def _progress_default():
     return os.environ.get("CELLREGMAP_AMD_PROGRESS", "1").lower() not in ("0", "false", "no", "off")
 
 
+def _one_bar(progress, total):
+    """``progress`` of a scan that runs chunk by chunk: a tqdm bar becomes ONE bar over all chunks.  Returns the
+    callable (or False) to hand to every chunk's ``_progress`` and the bar to close."""
+    if progress is None:
+        progress = _progress_default()
+    if progress is not True:
+        return progress, None
+    try:
+        from tqdm import tqdm
+    except ImportError:  # pragma: no cover
+        return False, None
+    bar, seen = tqdm(total=total), {"done": 0}
+
+    def advance(done, _total):
+        bar.update(done - seen["done"])
+        seen["done"] = done
+
+    return advance, bar
+
+
 class _progress:
     """Context manager: installs a per-block progress callback on the device's context for one scan.
     ``progress``: None = the reference's behaviour (a tqdm bar, see ``_progress_default``), True = a tqdm bar,
@@ -932,25 +952,7 @@ class CellRegMap:
                     pass
             worker.join()
 
-    @staticmethod
-    def _one_bar(progress, total):
-        """``progress`` of a scan that runs chunk by chunk: a tqdm bar becomes ONE bar over all chunks.  Returns the
-        callable (or False) to hand to every chunk's ``_progress`` and the bar to close."""
-        if progress is None:
-            progress = _progress_default()
-        if progress is not True:
-            return progress, None
-        try:
-            from tqdm import tqdm
-        except ImportError:  # pragma: no cover
-            return False, None
-        bar, seen = tqdm(total=total), {"done": 0}
-
-        def advance(done, _total):
-            bar.update(done - seen["done"])
-            seen["done"] = done
-
-        return advance, bar
+    _one_bar = staticmethod(_one_bar)
 
     def _scan_streamed(self, lib, G, k0, idx_E, idx_G, return_stats, progress, groups="auto", exact=False):
         """A host matrix of many variants goes to the device in column chunks from a second thread while this one scans
@@ -1470,6 +1472,68 @@ def _cis_runs(cis_index, ngenes, p, dense_limit=1 << 26):
     return columns, runs
 
 
+def _shared_cohort(crms):
+    """``(list(crms), crms[0])`` of the phenotypes of one many-phenotype pass: at least one, on one background, with the same
+    covariates and contexts (the shared pass takes g'W, the context features and the donor tables from the first object)."""
+    crms = list(crms)
+    if not crms:
+        raise ValueError("no phenotypes given")
+    first = crms[0]
+    for c in crms[1:]:
+        if c._bg is not first._bg:
+            raise ValueError("all CellRegMap objects must share one background (pass background=...)")
+        if c._W.shape != first._W.shape or c._E0.shape != first._E0.shape:
+            raise ValueError("all CellRegMap objects must share W and E")
+        # (the shared pass takes g'W, the context features and the donor tables from the first object)
+        if not (c._W is first._W or np.array_equal(c._W, first._W)):
+            raise ValueError("all CellRegMap objects of one pass must hold the same covariates W")
+        if not (c._E0 is first._E0 or np.array_equal(c._E0, first._E0)):
+            raise ValueError("all CellRegMap objects of one pass must hold the same contexts E")
+    return crms, first
+
+
+def _walk_runs(keys, ng, p, k, cis_index, progress, scan):
+    """One pass of ``ng`` phenotypes over a panel of ``p`` variants, whole or along the runs of ``cis_index``.  ``keys``: the
+    outputs as (name, per variant and context?, dtype); ``scan(idx, a, count, out, offset, total, progress)`` fills ``out[name]`` --
+    (len(idx), count[, k]) arrays -- for the phenotypes ``idx`` on variants [a, a + count).  Returns {name: array} of shape
+    (ng, p[, k]), or with ``cis_index`` {name: list} whose entry i follows the columns of ``cis_index[i]`` (untested positions
+    are never selected: they hold NaN, or -1 in an integer output).  ``progress`` counts the variants that at least one
+    phenotype tests; ``True`` is one bar over the whole pass."""
+    def arrays(lead, count, fill=False):
+        out = {}
+        for name, each, dtype in keys:
+            shape = (*lead, count, k) if each else (*lead, count)
+            out[name] = np.full(shape, -1 if dtype is np.int32 else np.nan, dtype) if fill else np.empty(shape, dtype)
+        return out
+
+    if cis_index is None:
+        columns, runs = None, ([(0, p, np.arange(ng))] if p else [])
+    else:
+        columns, runs = _cis_runs(cis_index, ng, p)
+    tested = int(sum(count for _, count, _ in runs))
+    progress, bar = _one_bar(progress, tested)
+    try:
+        if columns is None:
+            out = arrays((ng,), p)
+            for a, count, active in runs:
+                scan(active, a, count, out, 0, p, progress)
+            return out
+        full = [arrays((), p, fill=True) if columns[i].size else None for i in range(ng)]
+        seen = 0
+        for a, count, active in runs:
+            out = arrays((len(active),), count)
+            scan(active, a, count, out, seen, tested, progress)
+            seen += count
+            for row, i in enumerate(active):
+                for name, _, _ in keys:
+                    full[i][name][a:a + count] = out[name][row]
+        empty = arrays((), 0)
+        return {name: [full[i][name][columns[i]] if columns[i].size else empty[name] for i in range(ng)] for name, _, _ in keys}
+    finally:
+        if bar is not None:
+            bar.close()
+
+
 def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progress=False, pvalue="reference"):
     """Interaction scans of several phenotypes against one genotype panel in a single pass.
 
@@ -1491,20 +1555,7 @@ def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progr
     ``pvalue_status`` of the same shape (lists with ``cis_index``)."""
     exact = _exact_pvalues(pvalue)
     lib = _lib.load()
-    crms = list(crms)
-    if not crms:
-        raise ValueError("no phenotypes given")
-    first = crms[0]
-    for c in crms[1:]:
-        if c._bg is not first._bg:
-            raise ValueError("all CellRegMap objects must share one background (pass background=...)")
-        if c._W.shape != first._W.shape or c._E0.shape != first._E0.shape:
-            raise ValueError("all CellRegMap objects must share W and E")
-        # (the shared pass takes g'W, the context features and the donor tables from the first object)
-        if not (c._W is first._W or np.array_equal(c._W, first._W)):
-            raise ValueError("all CellRegMap objects of one pass must hold the same covariates W")
-        if not (c._E0 is first._E0 or np.array_equal(c._E0, first._E0)):
-            raise ValueError("all CellRegMap objects of one pass must hold the same contexts E")
+    crms, first = _shared_cohort(crms)
     panel = first._panel(G)
     n, p = panel.shape
     # (the phenotypes share W and E -- checked above: the first one's copies on the device serve the others, and their
@@ -1532,55 +1583,44 @@ def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progr
         if contiguous and panel.n_groups is not None:
             res = {k: [] for k in keys}
             tested = int(sum(c.size for c in columns))
-            bar = None
-            if progress is True:
-                from tqdm import tqdm
-
-                bar = tqdm(total=tested)
+            progress, bar = _one_bar(progress, tested)
             seen = 0
-            for i, cols in enumerate(columns):
-                out = {k: np.empty(cols.size, dtypes.get(k, float)) for k in keys}
-                if cols.size:
-                    scan = lib.crm_scan_interaction_tail if exact else lib.crm_scan_interaction
-                    _lib.check(scan(genes[i], panel.handle, int(cols[0]), int(cols.size), _lib.ptr(iE), _lib.ptr(iG),
-                                    *[_lib.ptr(out[k]) for k in keys[:5]], None, None, None, None, None, None, *tail(out)))
-                seen += cols.size
+            try:
+                for i, cols in enumerate(columns):
+                    out = {k: np.empty(cols.size, dtypes.get(k, float)) for k in keys}
+                    if cols.size:
+                        scan = lib.crm_scan_interaction_tail if exact else lib.crm_scan_interaction
+                        _lib.check(scan(genes[i], panel.handle, int(cols[0]), int(cols.size), _lib.ptr(iE), _lib.ptr(iG),
+                                        *[_lib.ptr(out[k]) for k in keys[:5]], None, None, None, None, None, None, *tail(out)))
+                    seen += cols.size
+                    if callable(progress):
+                        progress(seen, tested)
+                    for k in keys:
+                        res[k].append(out[k])
+            finally:
                 if bar is not None:
-                    bar.update(cols.size)
-                elif callable(progress):
-                    progress(seen, tested)
-                for k in keys:
-                    res[k].append(out[k])
-            if bar is not None:
-                bar.close()
+                    bar.close()
             return res["pv"], {k: res[k] for k in keys[1:]}
         full = {k: [np.full(p, -1 if k == "pvalue_status" else np.nan, dtypes.get(k, float)) if columns[i].size else None
                     for i in range(ng)] for k in keys}
         tested = int(sum(count for _, count, _ in runs))
-        bar = None
-        if progress is True:   # one bar over all runs
-            from tqdm import tqdm
-
-            bar = tqdm(total=tested)
-            state = {"done": 0}
-
-            def progress(done, total, _bar=bar, _state=state):
-                _bar.update(done - _state["done"])
-                _state["done"] = done
+        progress, bar = _one_bar(progress, tested)   # one bar over all runs
         seen = 0
-        for a, count, active in runs:
-            handles = (ctypes.c_void_p * len(active))(*[genes[i].value for i in active])
-            out = {k: np.empty((len(active), count), dtypes.get(k, float)) for k in keys}
-            scan = lib.crm_scan_interaction_multi_tail if exact else lib.crm_scan_interaction_multi
-            with _progress(first._device, progress, count, offset=seen, grand_total=tested):
-                _lib.check(scan(handles, len(active), panel.handle, a, count, _lib.ptr(iE), _lib.ptr(iG),
-                                *[_lib.ptr(out[k]) for k in keys[:5]], None, *tail(out)))
-            seen += count
-            for row, i in enumerate(active):
-                for k in keys:
-                    full[k][i][a:a + count] = out[k][row]
-        if bar is not None:
-            bar.close()
+        try:
+            for a, count, active in runs:
+                handles = (ctypes.c_void_p * len(active))(*[genes[i].value for i in active])
+                out = {k: np.empty((len(active), count), dtypes.get(k, float)) for k in keys}
+                scan = lib.crm_scan_interaction_multi_tail if exact else lib.crm_scan_interaction_multi
+                with _progress(first._device, progress, count, offset=seen, grand_total=tested):
+                    _lib.check(scan(handles, len(active), panel.handle, a, count, _lib.ptr(iE), _lib.ptr(iG),
+                                    *[_lib.ptr(out[k]) for k in keys[:5]], None, *tail(out)))
+                seen += count
+                for row, i in enumerate(active):
+                    for k in keys:
+                        full[k][i][a:a + count] = out[k][row]
+        finally:
+            if bar is not None:
+                bar.close()
         res = {k: [full[k][i][columns[i]] if columns[i].size else np.empty(0, dtypes.get(k, float)) for i in range(ng)]
                for k in keys}
         return res["pv"], {k: res[k] for k in keys[1:]}
@@ -1614,19 +1654,7 @@ def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=Fals
         raise ValueError(f"return_stats={return_stats!r}: False, True or 'effects'")
     return_stats = bool(return_stats)
     lib = _lib.load()
-    crms = list(crms)
-    if not crms:
-        raise ValueError("no phenotypes given")
-    first = crms[0]
-    for c in crms[1:]:
-        if c._bg is not first._bg:
-            raise ValueError("all CellRegMap objects must share one background (pass background=...)")
-        if c._W.shape != first._W.shape or c._E0.shape != first._E0.shape:
-            raise ValueError("all CellRegMap objects must share W and E")
-        if not (c._W is first._W or np.array_equal(c._W, first._W)):
-            raise ValueError("all CellRegMap objects of one pass must hold the same covariates W")
-        if not (c._E0 is first._E0 or np.array_equal(c._E0, first._E0)):
-            raise ValueError("all CellRegMap objects of one pass must hold the same contexts E")
+    crms, first = _shared_cohort(crms)
     panel = first._panel(G)
     n, p = panel.shape
     first._bind_gene()
@@ -1642,73 +1670,24 @@ def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=Fals
         info["null_delta"] = null[:, 5].copy()
     fast = int(bool(fast))
 
-    def scan(idx, a, count, pv, alt, offset, total, eff=None):
+    # the outputs as _walk_runs takes them: (name, per variant and context?, dtype), in the order of the C-ABI's
+    keys = (("pv", False, float), ("alt_lml", False, float))
+    if effects:
+        keys += tuple((k, False, np.int32 if k == "effect_status" else float) for k in _EFFECT_KEYS)
+
+    def scan(idx, a, count, out, offset, total, progress):
         hs = (ctypes.c_void_p * len(idx))(*[genes[i].value for i in idx])
         rows = np.ascontiguousarray(null[idx])
+        entry = lib.crm_scan_association_multi_effects if effects else lib.crm_scan_association_multi
         with _progress(first._device, progress, count, offset=offset, grand_total=total):
-            if eff is None:
-                _lib.check(lib.crm_scan_association_multi(hs, len(idx), panel.handle, a, count, fast, _lib.ptr(rows),
-                                                          _lib.ptr(pv), _lib.ptr(alt)))
-            else:
-                _lib.check(lib.crm_scan_association_multi_effects(hs, len(idx), panel.handle, a, count, fast,
-                                                                  _lib.ptr(rows), _lib.ptr(pv), _lib.ptr(alt),
-                                                                  *[_lib.ptr(eff[k]) for k in _EFFECT_KEYS]))
+            _lib.check(entry(hs, len(idx), panel.handle, a, count, fast, _lib.ptr(rows), *[_lib.ptr(out[name]) for name, _, _ in keys]))
 
-    if cis_index is None:
-        columns, runs = None, ([(0, p, np.arange(ng))] if p else [])
-    else:
-        columns, runs = _cis_runs(cis_index, ng, p)
-    tested = int(sum(count for _, count, _ in runs))
-    bar = None
-    if progress is True:   # one bar over the whole pass
-        from tqdm import tqdm
-
-        bar = tqdm(total=tested)
-        state = {"done": 0}
-
-        def progress(done, total, _bar=bar, _state=state):
-            _bar.update(done - _state["done"])
-            _state["done"] = done
-    try:
-        if columns is None:
-            pv, alt = np.empty((ng, p)), np.empty((ng, p))
-            eff = _effect_arrays((ng, p)) if effects else None
-            if p:
-                scan(np.arange(ng), 0, p, pv, alt, 0, p, eff)
-            if return_stats:
-                info["alt_lml"] = alt
-            if effects:
-                info.update(eff)
-            return pv, info
-        full_pv = [np.full(p, np.nan) if columns[i].size else None for i in range(ng)]
-        full_alt = [np.full(p, np.nan) if columns[i].size else None for i in range(ng)]
-        full_eff = None
-        if effects:   # (untested positions: NaN, status -1 -- never selected, ``columns`` only names tested ones)
-            full_eff = {k: [np.full(p, -1 if k == "effect_status" else np.nan, np.int32 if k == "effect_status" else float)
-                            if columns[i].size else None for i in range(ng)] for k in _EFFECT_KEYS}
-        seen = 0
-        for a, count, active in runs:
-            pv, alt = np.empty((len(active), count)), np.empty((len(active), count))
-            eff = _effect_arrays((len(active), count)) if effects else None
-            scan(active, a, count, pv, alt, seen, tested, eff)
-            seen += count
-            for row, i in enumerate(active):
-                full_pv[i][a:a + count] = pv[row]
-                full_alt[i][a:a + count] = alt[row]
-                if effects:
-                    for k in _EFFECT_KEYS:
-                        full_eff[k][i][a:a + count] = eff[k][row]
-        pvs = [full_pv[i][columns[i]] if columns[i].size else np.empty(0) for i in range(ng)]
-        if return_stats:
-            info["alt_lml"] = [full_alt[i][columns[i]] if columns[i].size else np.empty(0) for i in range(ng)]
-        if effects:
-            for k in _EFFECT_KEYS:
-                info[k] = [full_eff[k][i][columns[i]] if columns[i].size
-                           else np.empty(0, np.int32 if k == "effect_status" else float) for i in range(ng)]
-        return pvs, info
-    finally:
-        if bar is not None:
-            bar.close()
+    out = _walk_runs(keys, ng, p, 0, cis_index, progress, scan)
+    pv, alt = out.pop("pv"), out.pop("alt_lml")
+    if return_stats:
+        info["alt_lml"] = alt
+    info.update(out)
+    return pv, info
 
 
 def _bind_context_genes(crms, C, own, batch=64):
@@ -1754,19 +1733,7 @@ _CONTEXT_MANY_KEYS = {
 def _scan_contexts_many(crms, G, cis_index, contexts, fast, return_stats, progress, joint):
     """The body of ``scan_interaction_contexts_many`` and ``scan_interaction_contexts_joint_many``."""
     lib = _lib.load()
-    crms = list(crms)
-    if not crms:
-        raise ValueError("no phenotypes given")
-    first = crms[0]
-    for c in crms[1:]:
-        if c._bg is not first._bg:
-            raise ValueError("all CellRegMap objects must share one background (pass background=...)")
-        if c._W.shape != first._W.shape or c._E0.shape != first._E0.shape:
-            raise ValueError("all CellRegMap objects must share W and E")
-        if not (c._W is first._W or np.array_equal(c._W, first._W)):
-            raise ValueError("all CellRegMap objects of one pass must hold the same covariates W")
-        if not (c._E0 is first._E0 or np.array_equal(c._E0, first._E0)):
-            raise ValueError("all CellRegMap objects of one pass must hold the same contexts E")
+    crms, first = _shared_cohort(crms)
     C = first._E0 if contexts is None else np.asarray(contexts, float)
     if C.ndim != 2 or C.shape[0] != first.n_samples or C.shape[1] < 1:
         raise ValueError(f"contexts must be {first.n_samples} x k, got {C.shape}")
@@ -1788,67 +1755,23 @@ def _scan_contexts_many(crms, G, cis_index, contexts, fast, return_stats, progre
     entry = lib.crm_scan_interaction_contexts_joint_multi if joint else lib.crm_scan_interaction_contexts_multi
     fast = int(bool(fast))
 
-    def arrays(lead, count, fill=False):
-        out = {}
-        for name, each, dtype in keys:
-            shape = (*lead, count, k) if each else (*lead, count)
-            out[name] = np.full(shape, -1 if dtype is np.int32 else np.nan, dtype) if fill else np.empty(shape, dtype)
-        return out
-
-    def scan(idx, a, count, out, offset, total):
+    def scan(idx, a, count, out, offset, total, progress):
         hs = (ctypes.c_void_p * len(idx))(*[genes[i].value for i in idx])
         rows = np.ascontiguousarray(null[idx])
         with _progress(first._device, progress, count, offset=offset, grand_total=total):
             _lib.check(entry(hs, len(idx), panel.handle, a, count, fast, _lib.ptr(rows),
                              *[_lib.ptr(out[name]) for name, _, _ in keys]))
 
-    def finish(out):
-        pv = out.pop("pv")
-        if joint:
-            out["dropped"] = [d.astype(bool) for d in out["dropped"]] if isinstance(out["dropped"], list) \
-                else out["dropped"].astype(bool)
-        stats = {name: out.pop(name) for name in ("null_lml", "null_delta", "alt_lml")}
-        info.update(out)
-        if return_stats:
-            info.update(stats, gene_null_lml=null[:, 4].copy(), gene_null_delta=null[:, 5].copy())
-        return pv, info
-
-    if cis_index is None:
-        columns, runs = None, ([(0, p, np.arange(ng))] if p else [])
-    else:
-        columns, runs = _cis_runs(cis_index, ng, p)
-    tested = int(sum(count for _, count, _ in runs))
-    bar = None
-    if progress is True:   # one bar over the whole pass
-        from tqdm import tqdm
-
-        bar = tqdm(total=tested)
-        state = {"done": 0}
-
-        def progress(done, total, _bar=bar, _state=state):
-            _bar.update(done - _state["done"])
-            _state["done"] = done
-    try:
-        if columns is None:
-            out = arrays((ng,), p)
-            if p:
-                scan(np.arange(ng), 0, p, out, 0, p)
-            return finish(out)
-        full = [arrays((), p, fill=True) if columns[i].size else None for i in range(ng)]
-        seen = 0
-        for a, count, active in runs:
-            out = arrays((len(active),), count)
-            scan(active, a, count, out, seen, tested)
-            seen += count
-            for row, i in enumerate(active):
-                for name, _, _ in keys:
-                    full[i][name][a:a + count] = out[name][row]
-        empty = arrays((), 0)
-        return finish({name: [full[i][name][columns[i]] if columns[i].size else empty[name] for i in range(ng)]
-                       for name, _, _ in keys})
-    finally:
-        if bar is not None:
-            bar.close()
+    out = _walk_runs(keys, ng, p, k, cis_index, progress, scan)
+    pv = out.pop("pv")
+    if joint:
+        out["dropped"] = [d.astype(bool) for d in out["dropped"]] if isinstance(out["dropped"], list) \
+            else out["dropped"].astype(bool)
+    stats = {name: out.pop(name) for name in ("null_lml", "null_delta", "alt_lml")}
+    info.update(out)
+    if return_stats:
+        info.update(stats, gene_null_lml=null[:, 4].copy(), gene_null_delta=null[:, 5].copy())
+    return pv, info
 
 
 def scan_interaction_contexts_many(crms, G, cis_index=None, contexts=None, fast=True, return_stats=False, progress=False):

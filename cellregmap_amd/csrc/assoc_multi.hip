@@ -23,7 +23,7 @@
 #include <algorithm>
 
 #include "delta_search.h"
-#include "objects.h"
+#include "lrt_scan.h"
 
 namespace crm {
 
@@ -79,20 +79,6 @@ __global__ __launch_bounds__(256) void multi_rhs_kernel(const MultiGene* __restr
         for (int u = 0; u < c; u++) b1[u] = in ? R.tW[(long)u * R.ldW + k] : 0.0;
         B2[(long)k * ld2 + R.col2] = in ? 1.0 : 0.0;
     }
-}
-
-// XY[i, dst[q]] = src[q][i * ld[q]] for the columns q of [W | y_1 .. y_g] (cells_pad rows: the sources are zero padded)
-struct ColumnSource {
-    const double* src;
-    long ld;
-    long dst;
-};
-__global__ __launch_bounds__(256) void multi_columns_kernel(const ColumnSource* __restrict__ cols, long rows, double* __restrict__ XY,
-                                                            long ldxy) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows) return;
-    const ColumnSource s = cols[blockIdx.y];
-    XY[i * ldxy + s.dst] = s.src[i * s.ld];
 }
 
 // T2 = T o T over [rpad x variants] of every group (blockIdx.z)
@@ -169,40 +155,6 @@ __global__ void multi_lrt_kernel(const double* __restrict__ alt_lml, const doubl
     pv[(long)a * ld + b] = p;
 }
 
-// The null model of crm_scan_association (ML, X = W, over the rho grid) with the same arguments, into *out.
-int association_null_fit(crm_gene* gene, double* d_zero, double* d_gg, double* d_gy, double* d_gW, long ld_gW,
-                         NullFitTrial* d_trial, NullFitOut* d_fit, double* xwide) {
-    NullFitArgs fa{};
-    nullfit_gene_args(fa, gene, 0);
-    for (int i = 0; i < fa.nrho; i++) { fa.rho[i].T = d_zero; fa.rho[i].ldT = 0; }
-    fa.gg = d_gg; fa.gy = d_gy; fa.gW = d_gW; fa.ld_gW = ld_gW;
-    fa.trial = d_trial; fa.out = d_fit;
-    fa.xwide = xwide;
-    return launch_nullfit(gene->ctx->stream, fa, 1);
-}
-
-int check_genes(crm_gene* const* genes, int ngenes, const char* what) {
-    if (!genes || ngenes <= 0) {
-        set_error("%s: no genes", what);
-        return CRM_ERR_ARG;
-    }
-    for (int i = 0; i < ngenes; i++)
-        if (!genes[i] || !genes[i]->bg) {
-            set_error("%s: gene %d is NULL", what, i);
-            return CRM_ERR_ARG;
-        }
-    const crm_gene* g0 = genes[0];
-    for (int i = 1; i < ngenes; i++) {
-        const crm_gene* g = genes[i];
-        // the shared pass takes g'W, T(rho)'W and the orthogonalisation from the first gene: the others must hold the same W
-        if (g->bg != g0->bg || g->ctx != g0->ctx || g->c != g0->c || g->w_key != g0->w_key) {
-            set_error("%s: genes of one call must share the background and W (gene %d differs from gene 0)", what, i);
-            return CRM_ERR_ARG;
-        }
-    }
-    return CRM_OK;
-}
-
 }  // namespace
 
 }  // namespace crm
@@ -211,235 +163,159 @@ using namespace crm;
 
 extern "C" int crm_association_null_multi(crm_gene* const* genes, int ngenes, double* out_null) {
     return crm::guarded_on("crm_association_null_multi", (genes && ngenes > 0 && genes[0]) ? genes[0]->ctx : nullptr, [&]() -> int {
-    CRM_TRY(check_genes(genes, ngenes, "association null multi"));
+    const char* what = "association null multi";
+    CRM_TRY(check_shared_genes(what, genes, ngenes, false));
     if (!out_null) {
-        set_error("association null multi: out_null is NULL");
+        set_error("%s: out_null is NULL", what);
         return CRM_ERR_ARG;
     }
     crm_background* bg = genes[0]->bg;
     crm_ctx* ctx = bg->ctx;
-    if (ctx->in_scan) {
-        set_error("association null multi: a scan is running on this context (started from a progress callback?)");
-        return CRM_ERR_UNSUPPORTED;
-    }
-    struct InScan { crm_ctx* c; explicit InScan(crm_ctx* c_) : c(c_) { c->in_scan = true; } ~InScan() { c->in_scan = false; } } in_scan(ctx);
+    InScan in_scan;
+    CRM_TRY(in_scan.enter(ctx, what));
     CRM_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
-    const long ldq = bg->ldq;
     const int nrho = bg->nrho, c = genes[0]->c;
-    const long ld_gW = round_up(c, 8);
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_zero = carve(sizeof(double) * ldq), o_gg = carve(sizeof(double)), o_gy = carve(sizeof(double)),
-                 o_gW = carve(sizeof(double) * ld_gW), o_trial = carve(sizeof(NullFitTrial) * nrho * nrho),
-                 o_fit = carve(sizeof(NullFitOut) * ngenes);
-    CRM_TRY(ctx->ws_small.ensure(off));
-    char* sm = ctx->ws_small.as<char>();
-    double* d_zero = (double*)(sm + o_zero);
-    NullFitOut* d_fit = (NullFitOut*)(sm + o_fit);
-    CRM_HIP(hipMemsetAsync(sm, 0, o_trial, st));   // zero T row, gg, gy, gW: the fit drops the zero "variant"
+    ZeroVariant zero;
+    zero.ld_gW = round_up(c, 8);
+    NullFitOut* d_fit = nullptr;
+    CRM_TRY(carve_workspace(ctx->ws_small, [&](auto& take) {
+        take(zero.zero, sizeof(double) * bg->ldq), take(zero.gg, sizeof(double)), take(zero.gy, sizeof(double));
+        take(zero.gW, sizeof(double) * zero.ld_gW), take(zero.trial, sizeof(NullFitTrial) * nrho * nrho);
+        take(d_fit, sizeof(NullFitOut) * ngenes);
+    }));
+    // zero T row, gg, gy, gW, which sit in this order in front of the trial records: the fit drops the zero "variant"
+    CRM_HIP(hipMemsetAsync(zero.zero, 0, (char*)zero.trial - (char*)zero.zero, st));
     double* xwide = nullptr;
     if (c > CRM_MAX_COV_WIDE) {
         CRM_TRY(ctx->ws_xwide.ensure(sizeof(double) * nullfit_xwide_scratch_doubles(1, nrho, c)));
         xwide = ctx->ws_xwide.as<double>();
     }
-    for (int i = 0; i < ngenes; i++)
-        CRM_TRY(association_null_fit(genes[i], d_zero, (double*)(sm + o_gg), (double*)(sm + o_gy), (double*)(sm + o_gW), ld_gW,
-                                     (NullFitTrial*)(sm + o_trial), d_fit + i, xwide));
+    NullFitArgs fa;
+    for (int i = 0; i < ngenes; i++) CRM_TRY(launch_gene_null(st, genes[i], zero, d_fit + i, xwide, fa));
     std::vector<NullFitOut> fits(ngenes);
     CRM_HIP(hipMemcpyAsync(fits.data(), d_fit, sizeof(NullFitOut) * ngenes, hipMemcpyDeviceToHost, st));
     CRM_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < ngenes; i++) {
-        const NullFitOut& f = fits[i];
-        if (f.rho_index < 0 || f.rho_index >= nrho) {
-            set_error("association null multi: the null model's fit of gene %d did not run (grid index %d)", i, f.rho_index);
-            return CRM_ERR_NUMERIC;
-        }
-        const double rho = bg->rho[f.rho_index];
-        double* o = out_null + 6 * (size_t)i;
-        o[0] = rho;
-        o[1] = f.v0 * rho;
-        o[2] = f.v0 * (1 - rho);
-        o[3] = f.v1;
-        o[4] = f.lml;
-        o[5] = f.delta;
-    }
+    for (int i = 0; i < ngenes; i++) CRM_TRY(gene_null_row(what, bg, i, fits[i], out_null + 6 * (size_t)i));
     return CRM_OK;
     });
 }
 
 namespace {
 
-// The scan behind crm_scan_association_multi (eff null: its launches and nothing else) and
-// crm_scan_association_multi_effects (assoc_effects.hip: fast, one more launch per block over every (variant, gene); full
-// refit, one per gene after its alt fits, whose trial records the next gene overwrites).
-int scan_association_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count, int fast,
-                           const double* null, double* out_pvalue, double* out_alt_lml, const AssocEffectsOut* eff) {
-    CRM_TRY(check_genes(genes, ngenes, "association multi"));
-    if (!panel || !null) {
-        set_error("association multi: %s is NULL", panel ? "null" : "panel");
-        return CRM_ERR_ARG;
-    }
-    crm_gene* g0 = genes[0];
-    crm_background* bg = g0->bg;
-    crm_ctx* ctx = bg->ctx;
-    if (panel->ctx != ctx || panel->n != bg->n) {
-        set_error("association multi: genes and panel do not match (context / cell count: %ld against %ld)", panel->n, bg->n);
-        return CRM_ERR_ARG;
-    }
-    if (first < 0 || count < 0 || first + count > panel->p) {
-        set_error("association multi: variants [%ld, %ld) outside the panel (p = %ld)", first, first + count, panel->p);
-        return CRM_ERR_ARG;
-    }
-    const int nrho = bg->nrho, c = g0->c;
-    std::vector<int> ri(ngenes);
-    for (int i = 0; i < ngenes; i++) {
-        const double* row = null + 6 * (size_t)i;
-        ri[i] = -1;
-        for (int k = 0; k < nrho; k++)
-            if (bg->rho[k] == row[0]) { ri[i] = k; break; }
-        if (ri[i] < 0) {
-            set_error("association multi: null row %d has rho1 = %.17g, not a point of the background's grid", i, row[0]);
-            return CRM_ERR_ARG;
-        }
-        if (!std::isfinite(row[4])) {
-            set_error("association multi: null row %d has a non-finite lml (the null model could not be fitted)", i);
-            return CRM_ERR_ARG;
-        }
-        if (fast && !(row[5] > 0.0 && row[5] <= 1.0)) {
-            set_error("association multi: null row %d has delta = %g outside (0, 1]", i, row[5]);
-            return CRM_ERR_ARG;
-        }
-    }
-    if (c > CMAX) {
-        set_error("association multi: %d covariate columns (supported up to %d)", c, CMAX);
-        return CRM_ERR_UNSUPPORTED;
-    }
-    if (count == 0) return CRM_OK;
-    if (ctx->in_scan) {
-        set_error("association multi: another scan is running on this context (started from a progress callback?)");
-        return CRM_ERR_UNSUPPORTED;
-    }
-    struct InScan { crm_ctx* c; explicit InScan(crm_ctx* c_) : c(c_) { c->in_scan = true; } ~InScan() { c->in_scan = false; } } in_scan(ctx);
-    CRM_HIP(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
-    const long n = bg->n, np = bg->n_pad, ldq = bg->ldq;
-    const int BLK = (int)std::min<long>(ctx->block_variants > 0 ? ctx->block_variants : CRM_DEFAULT_BLOCK,
-                                        round_up(std::max<long>(count, 1), 128));
-    const long ldb = BLK + 128;   // (column tiles of 128 over the variants stay inside every [.. x variants] buffer)
-    const long ld_gW = round_up(c, 8);
-    const long slab = (long)(1 + c) * ldq;
+// One call of crm_scan_association_multi (eff null: its launches and nothing else) or crm_scan_association_multi_effects
+// (assoc_effects.hip: fast, one more launch per block over every (variant, gene); full refit, one per gene after its alt
+// fits, whose trial records the next gene overwrites): what is fixed once the checks have passed, one function per stage.
+struct AssocMultiScan {
+    LrtBlock B;
+    crm_gene* const* genes; const int ngenes; const double* null;
+    const NullRows& R;
+    const AssocEffectsOut* eff;
+    crm_background* bg; crm_ctx* ctx; hipStream_t st;
+    const int BLK, c, ngrp;
+    const bool fast;
+    const long n, np, ldq, ldb, slab;
+    PhenotypeMatrix Y;
+    long rows_cy, ldcy, ldt, tslab, ld1 = 0, ld2 = 0;
+    int prep_d, rmax = 0;
+    size_t eff_rows;   // per output: [ngenes x BLK], five of doubles, then the status
+    std::vector<MultiGroup> groups;
+    std::vector<MultiGene> mg;
+    double *d_cy = nullptr, *d_alt = nullptr, *d_pv = nullptr, *d_nl = nullptr, *d_prep = nullptr, *d_wts = nullptr, *d_eff = nullptr;
+    AssocArgs* d_args = nullptr; MultiGene* d_mg = nullptr; MultiGroup* d_grp = nullptr;
+    NullFitTrial* d_trial = nullptr; NullFitOut* d_fit = nullptr; AssocEffectsGene* d_effg = nullptr;
+    GemmProblem* d_probs = nullptr; double* Tb = nullptr;
+    std::vector<double> null_lml;
+    std::vector<AssocArgs> aa;          // (host sources of asynchronous copies: alive until the last sync)
+    std::vector<AssocEffectsGene> eg;   // (host source of an asynchronous copy)
+    NullFitArgs alt{};
+    std::vector<GemmProblem> probs, pp;
 
-    // rho groups: the distinct grid indices of the genes' null models, in grid order
-    std::vector<int> grp_of_rho(nrho, -1), grp_rho;
-    for (int i = 0; i < ngenes; i++) grp_of_rho[ri[i]] = 0;
-    for (int k = 0; k < nrho; k++)
-        if (grp_of_rho[k] == 0) { grp_of_rho[k] = (int)grp_rho.size(); grp_rho.push_back(k); }
-    const int ngrp = (int)grp_rho.size();
-    for (int k : grp_rho) CRM_TRY(crm_background_require_q0(bg, k));
-
-    // [W | y_1 .. y_g] (cells x ldxy): W at columns 0 .. c-1, the phenotypes from column yoff
-    const long yoff = round_up(c, 16);
-    const long ldxy = round_up(yoff + ngenes, 128) + 128;   // (column tiles read from column 0 or from yoff stay inside a row)
-    CRM_TRY(ctx->ws_XG.ensure(sizeof(double) * (size_t)np * ldxy));
-    double* XY = ctx->ws_XG.as<double>();
-    CRM_HIP(hipMemsetAsync(XY, 0, sizeof(double) * (size_t)np * ldxy, st));
-    std::vector<ColumnSource> srcs;
-    for (int u = 0; u < c; u++) srcs.push_back({g0->yW.as<double>() + 1 + u, g0->ld_yw, u});
-    for (int i = 0; i < ngenes; i++) srcs.push_back({genes[i]->yW.as<double>(), genes[i]->ld_yw, yoff + i});
-    const long rows_cy = fast ? yoff + ngenes : ngenes;   // full refit: g'W of the orthogonalised block from launch_variant_stats
+    AssocMultiScan(crm_gene* const* genes_, int ngenes_, crm_panel* panel, long first, long count, int fast_, const double* null_,
+                   const NullRows& R_, const AssocEffectsOut* eff_)
+        : B(genes_[0], panel, first, count, fast_), genes(genes_), ngenes(ngenes_), null(null_), R(R_), eff(eff_), bg(B.bg),
+          ctx(B.ctx), st(B.st), BLK(B.BLK), c(B.c), ngrp(R_.ngrp()), fast(B.fast), n(B.n), np(B.np), ldq(B.ldq), ldb(B.ldb),
+          slab((long)(1 + B.c) * B.ldq), groups(ngrp), mg(ngenes_), null_lml(ngenes_) {
+        Y.plan(genes, ngenes);
+        rows_cy = fast ? Y.yoff + ngenes : ngenes;   // full refit: g'W of the orthogonalised block from launch_variant_stats
+        ldcy = ldb;
+        ldt = ldb;                                   // T_rho: [rpad x ldt] per group (full refit: [variants x ldq])
+        tslab = fast ? ldq * ldt : (long)BLK * ldq;
+        prep_d = (int)fastscan_prep_doubles();
+        eff_rows = (size_t)ngenes * BLK;
+        for (int i = 0; i < ngenes; i++) null_lml[i] = null[6 * (size_t)i + 4];
+        if (fast) layout();
+    }
 
     // column layout of the fast path's right-hand operands (per group: its own block, then its genes)
-    std::vector<MultiGroup> groups(ngrp);
-    std::vector<MultiGene> mg(ngenes);
-    long ld1 = 0, ld2 = 0;
-    if (fast) {
+    void layout() {
         long col1 = 0, col2 = 0;
         for (int q = 0; q < ngrp; q++) {
-            const int k = grp_rho[q];
-            MultiGroup& R = groups[q];
-            R.r = bg->r[k];
-            R.rpad = (int)std::max<long>(round_up(R.r, GEMM_BK), GEMM_BK);
-            R.ldW = ldq;
-            R.col1 = (int)col1; R.col2 = (int)col2;
-            int first_gene = -1;
-            for (int i = 0; i < ngenes; i++)
-                if (ri[i] == k && first_gene < 0) first_gene = i;
-            R.tW = genes[first_gene]->rot.as<double>() + (long)k * slab + ldq;
+            const int k = R.grp_rho[q];
+            MultiGroup& G = groups[q];
+            G.r = bg->r[k];
+            G.rpad = (int)std::max<long>(round_up(G.r, GEMM_BK), GEMM_BK);
+            G.ldW = ldq;
+            G.col1 = (int)col1; G.col2 = (int)col2;
+            G.tW = genes[R.members[q][0]]->rot.as<double>() + (long)k * slab + ldq;
             long a1 = col1 + c, a2 = col2 + 1;
-            for (int i = 0; i < ngenes; i++)
-                if (ri[i] == k) {
-                    mg[i].group = q;
-                    mg[i].col1 = (int)a1; a1 += c + 2;
-                    mg[i].col2 = (int)a2; a2 += 1;
-                }
+            for (int i : R.members[q]) {
+                mg[i].group = q;
+                mg[i].col1 = (int)a1; a1 += c + 2;
+                mg[i].col2 = (int)a2; a2 += 1;
+            }
             col1 = round_up(a1, 16);
             col2 = round_up(a2, 16);
+            rmax = std::max(rmax, G.rpad);
         }
         ld1 = col1 + 128;
         ld2 = col2 + 128;
     }
 
-    // device work buffers
-    const long ldt = ldb;                    // T_rho: [rpad x ldt] per group (full refit: [variants x ldq])
-    const long tslab = fast ? ldq * ldt : (long)BLK * ldq;
-    CRM_TRY(ctx->ws_T.ensure(sizeof(double) * (size_t)ngrp * tslab));
-    CRM_TRY(ctx->ws_Gb.ensure(sizeof(double) * (size_t)np * ldb));
-    if (!fast) CRM_TRY(ctx->ws_Gx.ensure(sizeof(double) * (size_t)np * ldb));
-    if (fast) {
-        CRM_TRY(ctx->ws_G2.ensure(sizeof(double) * (size_t)ngrp * tslab));
-        CRM_TRY(ctx->ws_A.ensure(sizeof(double) * (size_t)ldq * (ld1 + ld2)));
-        CRM_TRY(ctx->ws_F.ensure(sizeof(double) * (size_t)BLK * (ld1 + ld2)));
+    int workspaces() {
+        CRM_TRY(Y.ensure(ctx, np));
+        CRM_TRY(Y.clear(st, np));
+        CRM_TRY(ctx->ws_T.ensure(sizeof(double) * (size_t)ngrp * tslab));
+        CRM_TRY(B.ensure());
+        if (fast) {
+            CRM_TRY(ctx->ws_G2.ensure(sizeof(double) * (size_t)ngrp * tslab));
+            CRM_TRY(ctx->ws_A.ensure(sizeof(double) * (size_t)ldq * (ld1 + ld2)));
+            CRM_TRY(ctx->ws_F.ensure(sizeof(double) * (size_t)BLK * (ld1 + ld2)));
+        }
+        CRM_TRY(carve_workspace(ctx->ws_small, [&](auto& take) {
+            B.carve(take, !fast);
+            take(d_cy, sizeof(double) * rows_cy * ldcy);
+            take(d_alt, sizeof(double) * (size_t)ngenes * BLK), take(d_pv, sizeof(double) * (size_t)ngenes * BLK);
+            take(d_nl, sizeof(double) * ngenes);
+            take(d_prep, fast ? sizeof(double) * (size_t)ngenes * prep_d : 0), take(d_wts, fast ? sizeof(double) * (size_t)ngenes * ldq : 0);
+            take(d_args, fast ? sizeof(AssocArgs) * ngenes : 0), take(d_mg, fast ? sizeof(MultiGene) * ngenes : 0);
+            take(d_grp, fast ? sizeof(MultiGroup) * ngrp : 0);
+            take(d_trial, !fast ? sizeof(NullFitTrial) * BLK : 0), take(d_fit, !fast ? sizeof(NullFitOut) * BLK : 0);
+            take(Y.d_srcs, Y.srcs_bytes());
+            take(d_eff, eff ? (sizeof(double) * 5 + sizeof(int)) * eff_rows : 0), take(d_effg, eff ? sizeof(AssocEffectsGene) * ngenes : 0);
+        }));
+        CRM_TRY(ctx->ws_probs.ensure(sizeof(GemmProblem) * (size_t)(3 * ngrp + 2)));
+        d_probs = ctx->ws_probs.as<GemmProblem>();
+        Tb = ctx->ws_T.as<double>();
+        return CRM_OK;
     }
-    const long ldcy = ldb;
-    const int prep_d = (int)fastscan_prep_doubles();
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_cy = carve(sizeof(double) * rows_cy * ldcy), o_gg = carve(sizeof(double) * BLK),
-                 o_gy = carve(sizeof(double) * BLK), o_gW = carve(sizeof(double) * BLK * ld_gW),
-                 o_part = carve(variant_stats_workspace(BLK, std::min(c, CRM_MAX_COV))),
-                 o_alt = carve(sizeof(double) * (size_t)ngenes * BLK), o_pv = carve(sizeof(double) * (size_t)ngenes * BLK),
-                 o_nl = carve(sizeof(double) * ngenes),
-                 o_prep = fast ? carve(sizeof(double) * (size_t)ngenes * prep_d) : 0,
-                 o_wts = fast ? carve(sizeof(double) * (size_t)ngenes * ldq) : 0,
-                 o_args = fast ? carve(sizeof(AssocArgs) * ngenes) : 0,
-                 o_mg = fast ? carve(sizeof(MultiGene) * ngenes) : 0, o_grp = fast ? carve(sizeof(MultiGroup) * ngrp) : 0,
-                 o_trial = !fast ? carve(sizeof(NullFitTrial) * BLK) : 0, o_fit = !fast ? carve(sizeof(NullFitOut) * BLK) : 0,
-                 o_coef = !fast ? carve(sizeof(double) * (size_t)c * ldb) : 0, o_thr = !fast ? carve(sizeof(double) * BLK) : 0,
-                 o_drop = !fast ? carve(sizeof(int) * BLK) : 0, o_src = carve(sizeof(ColumnSource) * srcs.size());
-    const size_t eff_rows = (size_t)ngenes * BLK;   // per output: [ngenes x BLK], five of doubles, then the status
-    const size_t o_eff = eff ? carve((sizeof(double) * 5 + sizeof(int)) * eff_rows) : 0,
-                 o_effg = eff ? carve(sizeof(AssocEffectsGene) * ngenes) : 0;
-    CRM_TRY(ctx->ws_small.ensure(off));
-    char* sm = ctx->ws_small.as<char>();
-    double* d_cy = (double*)(sm + o_cy);
-    double* d_gg = (double*)(sm + o_gg);
-    double* d_gy = (double*)(sm + o_gy);
-    double* d_gW = (double*)(sm + o_gW);
-    double* d_part = (double*)(sm + o_part);
-    double* d_alt = (double*)(sm + o_alt);
-    double* d_pv = (double*)(sm + o_pv);
-    double* d_nl = (double*)(sm + o_nl);
-    CRM_TRY(ctx->ws_probs.ensure(sizeof(GemmProblem) * (size_t)(3 * ngrp + 2)));
-    GemmProblem* d_probs = ctx->ws_probs.as<GemmProblem>();
-    std::vector<double> null_lml(ngenes);
-    for (int i = 0; i < ngenes; i++) null_lml[i] = null[6 * (size_t)i + 4];
-    CRM_HIP(hipMemcpyAsync(d_nl, null_lml.data(), sizeof(double) * ngenes, hipMemcpyHostToDevice, st));
-    const double* d_W = g0->yW.as<double>() + 1;
-    double* Tb = ctx->ws_T.as<double>();
-    CRM_HIP(hipMemcpyAsync(sm + o_src, srcs.data(), sizeof(ColumnSource) * srcs.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(multi_columns_kernel, dim3((unsigned)((np + 255) / 256), (unsigned)srcs.size()), dim3(256), 0, st,
-                       (const ColumnSource*)(sm + o_src), np, XY, ldxy);
-    CRM_HIP(hipGetLastError());
 
-    // the per-gene records of the fast path and the right-hand operands (once per call)
-    std::vector<AssocArgs> aa(fast ? ngenes : 0);   // (host sources of asynchronous copies: alive until the last sync)
-    if (fast) {
-        double* d_prep = (double*)(sm + o_prep);
-        double* d_wts = (double*)(sm + o_wts);
+    // what does not depend on the block: the null lmls, the phenotype matrix, the fast path's records and right-hand
+    // operands, the shared arguments of the refits, the records of the effects launch
+    int operands() {
+        CRM_HIP(hipMemcpyAsync(d_nl, null_lml.data(), sizeof(double) * ngenes, hipMemcpyHostToDevice, st));
+        CRM_TRY(Y.fill(st, np));
+        if (fast) CRM_TRY(fast_operands());
+        else CRM_TRY(refit_operands());
+        if (eff) CRM_TRY(effects_operands());
+        return CRM_OK;
+    }
+
+    int fast_operands() {
+        aa.resize(ngenes);
         for (int i = 0; i < ngenes; i++) {
             crm_gene* g = genes[i];
-            const int k = ri[i];
+            const int k = R.ri[i];
             AssocArgs& A = aa[i];
             A.ty = g->rot.as<double>() + (long)k * slab;
             A.tW = A.ty + ldq; A.ldW = ldq; A.S0 = bg->S0[k].as<double>();
@@ -449,69 +325,68 @@ int scan_association_multi(crm_gene* const* genes, int ngenes, crm_panel* panel,
             M.ty = A.ty;
             M.wts = d_wts + (size_t)i * ldq;
             M.prep = d_prep + (size_t)i * prep_d;
-            M.row_y = (int)(yoff + i);
+            M.row_y = (int)(Y.yoff + i);
             M.inv_d = 1.0 / A.delta0;
             M.null_lml = null_lml[i];
         }
-        CRM_HIP(hipMemcpyAsync(sm + o_args, aa.data(), sizeof(AssocArgs) * ngenes, hipMemcpyHostToDevice, st));
-        CRM_HIP(hipMemcpyAsync(sm + o_mg, mg.data(), sizeof(MultiGene) * ngenes, hipMemcpyHostToDevice, st));
-        CRM_HIP(hipMemcpyAsync(sm + o_grp, groups.data(), sizeof(MultiGroup) * ngrp, hipMemcpyHostToDevice, st));
-        CRM_TRY(launch_fastscan_prep_batch(st, (const AssocArgs*)(sm + o_args), ngenes, c, d_prep, prep_d, d_wts, ldq));
+        CRM_HIP(hipMemcpyAsync(d_args, aa.data(), sizeof(AssocArgs) * ngenes, hipMemcpyHostToDevice, st));
+        CRM_HIP(hipMemcpyAsync(d_mg, mg.data(), sizeof(MultiGene) * ngenes, hipMemcpyHostToDevice, st));
+        CRM_HIP(hipMemcpyAsync(d_grp, groups.data(), sizeof(MultiGroup) * ngrp, hipMemcpyHostToDevice, st));
+        CRM_TRY(launch_fastscan_prep_batch(st, d_args, ngenes, c, d_prep, prep_d, d_wts, ldq));
         double* B1 = ctx->ws_A.as<double>();
         double* B2 = B1 + (size_t)ldq * ld1;
-        int rmax = 0;
-        for (const MultiGroup& R : groups) rmax = std::max(rmax, R.rpad);
         CRM_HIP(hipMemsetAsync(B1, 0, sizeof(double) * (size_t)ldq * (ld1 + ld2), st));
-        hipLaunchKernelGGL(multi_rhs_kernel, dim3((rmax + 255) / 256, ngenes + ngrp), dim3(256), 0, st,
-                           (const MultiGene*)(sm + o_mg), ngenes, (const MultiGroup*)(sm + o_grp), c, B1, ld1, B2, ld2);
+        hipLaunchKernelGGL(multi_rhs_kernel, dim3((rmax + 255) / 256, ngenes + ngrp), dim3(256), 0, st, (const MultiGene*)d_mg,
+                           ngenes, (const MultiGroup*)d_grp, c, B1, ld1, B2, ld2);
         CRM_HIP(hipGetLastError());
+        return CRM_OK;
     }
 
     // the shared full-refit arguments: the null's rho per gene, the block's shared quantities
-    NullFitArgs alt{};
-    if (!fast) {
+    int refit_operands() {
         alt.nrho = 1; alt.c = c; alt.restricted = 0;
         alt.polish = (ctx->polish && c <= CRM_MAX_COV) ? 1 : 0;
         alt.exact = (ctx->nullfit_exact || form("nullfit_exact", 0)) ? 1 : 0;
         alt.n = n;
-        alt.gg = d_gg; alt.gW = d_gW; alt.ld_gW = ld_gW;
-        alt.g_drop = (int*)(sm + o_drop);
-        alt.trial = (NullFitTrial*)(sm + o_trial); alt.out = (NullFitOut*)(sm + o_fit);
+        alt.gg = B.d_gg; alt.gW = B.d_gW; alt.ld_gW = B.ld_gW;
+        alt.g_drop = B.d_drop;
+        alt.trial = d_trial; alt.out = d_fit;
         if (c > CRM_MAX_COV_WIDE) {
-            CRM_TRY(ctx->ws_xwide.ensure(sizeof(double) * nullfit_xwide_scratch_doubles(BLK, nrho, c)));
+            CRM_TRY(ctx->ws_xwide.ensure(sizeof(double) * nullfit_xwide_scratch_doubles(BLK, B.nrho, c)));
             alt.xwide = ctx->ws_xwide.as<double>();
         }
+        return CRM_OK;
     }
 
     // the per-gene records of the effects launch; fast: in the order of the rho groups, so that the tests that read one
     // row of T are neighbours in the grid (record q writes the rows of gene eff_gene[q])
-    std::vector<AssocEffectsGene> eg(eff ? ngenes : 0);   // (host source of an asynchronous copy)
-    double* d_eff = eff ? (double*)(sm + o_eff) : nullptr;
-    const AssocEffectsGene* d_effg = eff ? (const AssocEffectsGene*)(sm + o_effg) : nullptr;
-    if (eff) {
+    int effects_operands() {
+        eg.resize(ngenes);
         std::vector<int> eff_gene(ngenes);
         for (int i = 0; i < ngenes; i++) eff_gene[i] = i;
-        if (fast) std::stable_sort(eff_gene.begin(), eff_gene.end(), [&](int x, int y) { return grp_of_rho[ri[x]] < grp_of_rho[ri[y]]; });
+        if (fast)
+            std::stable_sort(eff_gene.begin(), eff_gene.end(),
+                             [&](int x, int y) { return R.grp_of_rho[R.ri[x]] < R.grp_of_rho[R.ri[y]]; });
         for (int q = 0; q < ngenes; q++) {
-            const int i = eff_gene[q], k = ri[i];
+            const int i = eff_gene[q], k = R.ri[i];
             crm_gene* g = genes[i];
             AssocEffectsGene& E = eg[q];
-            E.T = Tb + (size_t)grp_of_rho[k] * tslab;
+            E.T = Tb + (size_t)R.grp_of_rho[k] * tslab;
             E.t_sb = fast ? 1 : ldq; E.t_sk = fast ? ldt : 1;
             E.ty = g->rot.as<double>() + (long)k * slab;
             E.tW = E.ty + ldq; E.ldW = ldq; E.S0 = bg->S0[k].as<double>();
             E.r = bg->r[k]; E.c = c; E.n = n;
             E.WW = g->WW.as<double>(); E.Wy = g->Wy.as<double>(); E.yy = g->yy;
-            E.gg = d_gg;
+            E.gg = B.d_gg;
             if (fast) {
-                E.gy = d_cy + (size_t)(yoff + i) * ldcy;
+                E.gy = d_cy + (size_t)(Y.yoff + i) * ldcy;
                 E.gW = d_cy; E.gW_sb = 1; E.gW_su = ldcy;
-                E.prep = (const double*)(sm + o_prep) + (size_t)i * prep_d;
-                E.wts = (const double*)(sm + o_wts) + (size_t)i * ldq;
+                E.prep = d_prep + (size_t)i * prep_d;
+                E.wts = d_wts + (size_t)i * ldq;
                 E.delta0 = null[6 * (size_t)i + 5];
             } else {
                 E.gy = d_cy + (size_t)i * ldcy;
-                E.gW = d_gW; E.gW_sb = ld_gW; E.gW_su = 1;
+                E.gW = B.d_gW; E.gW_sb = B.ld_gW; E.gW_su = 1;
                 E.trial = alt.trial;
             }
             E.alt_lml = d_alt + (size_t)i * BLK;
@@ -521,136 +396,146 @@ int scan_association_multi(crm_gene* const* genes, int ngenes, crm_panel* panel,
             E.out_logp = o + 4 * eff_rows;
             E.out_status = (int*)(d_eff + 5 * eff_rows) + (size_t)i * BLK;
         }
-        CRM_HIP(hipMemcpyAsync(sm + o_effg, eg.data(), sizeof(AssocEffectsGene) * ngenes, hipMemcpyHostToDevice, st));
+        CRM_HIP(hipMemcpyAsync(d_effg, eg.data(), sizeof(AssocEffectsGene) * ngenes, hipMemcpyHostToDevice, st));
+        return CRM_OK;
     }
 
-    std::vector<GemmProblem> probs, pp;
-    for (long done = 0; done < count; done += BLK) {
-        const int nb = (int)std::min<long>(BLK, count - done);
-        double* Gb = ctx->ws_Gb.as<double>();
-        if (panel->grouped)
-            CRM_TRY(launch_expand_block(st, panel->Gd.as<double>() + first + done, panel->ld, panel->group.as<int>(),
-                                        np, n, nullptr, nb, Gb, ldb, (int)ldb));
-        else
-            CRM_TRY(launch_gather_block(st, panel->G.as<double>() + first + done, panel->ld, np, n, nullptr, nullptr,
-                                        nb, Gb, ldb, (int)ldb));
+    // one batched launch: g'y_j (fast: g'W too) against the phenotype matrix, and T_rho of every rho group
+    int block_products(int nb) {
         probs.clear();
-        if (fast) {
-            // gg (the one column reduction); g'W and g'y_j from the product below
-            CRM_TRY(launch_variant_stats(st, Gb, ldb, np, nb, g0->yW.as<double>(), d_W, g0->ld_yw, 1, d_part, d_gg, d_gy,
-                                         d_gW, ld_gW));
-            GemmProblem p{};
-            p.X = XY; p.ldx = ldxy; p.Y = Gb; p.ldy = ldb; p.C = d_cy; p.ldc = ldcy; p.M = (int)rows_cy; p.N = nb;
+        GemmProblem p{};
+        if (fast) {   // (gg came from the one column reduction of the block's preparation)
+            p.X = Y.XY; p.ldx = Y.ldxy; p.Y = B.Gb; p.ldy = ldb; p.C = d_cy; p.ldc = ldcy; p.M = (int)rows_cy; p.N = nb;
             probs.push_back(p);
             for (int q = 0; q < ngrp; q++) {
                 GemmProblem t{};
-                t.X = bg->Q0[grp_rho[q]].as<double>(); t.ldx = ldq; t.Y = Gb; t.ldy = ldb;
+                t.X = bg->Q0[R.grp_rho[q]].as<double>(); t.ldx = ldq; t.Y = B.Gb; t.ldy = ldb;
                 t.C = Tb + (size_t)q * tslab; t.ldc = ldt; t.M = groups[q].rpad; t.N = nb;
                 probs.push_back(t);
             }
         } else {
-            double* Gx = ctx->ws_Gx.as<double>();
-            CRM_TRY(launch_variant_stats(st, Gb, ldb, np, nb, g0->yW.as<double>(), d_W, g0->ld_yw, c, d_part, d_gg, d_gy,
-                                         d_gW, ld_gW));
-            CRM_TRY(launch_ortho_block(st, Gb, ldb, np, nb, (int)ldb, d_W, g0->ld_yw, c, g0->Wproj.as<double>(), d_gW, ld_gW,
-                                       (double*)(sm + o_coef), ldb, (double*)(sm + o_thr), Gx, ldb));
-            CRM_TRY(launch_variant_stats(st, Gx, ldb, np, nb, g0->yW.as<double>(), d_W, g0->ld_yw, c, d_part, d_gg, d_gy,
-                                         d_gW, ld_gW));
-            CRM_TRY(launch_ortho_rank(st, d_gg, (double*)(sm + o_thr), nb, (int*)(sm + o_drop)));
-            Gb = Gx;
-            GemmProblem p{};
-            p.X = XY + yoff; p.ldx = ldxy; p.Y = Gb; p.ldy = ldb; p.C = d_cy; p.ldc = ldcy; p.M = ngenes; p.N = nb;
+            p.X = Y.XY + Y.yoff; p.ldx = Y.ldxy; p.Y = B.Gx; p.ldy = ldb; p.C = d_cy; p.ldc = ldcy; p.M = ngenes; p.N = nb;
             probs.push_back(p);
-            for (int q = 0; q < ngrp; q++) {
-                const int k = grp_rho[q];
-                GemmProblem t{};
-                t.X = Gb; t.ldx = ldb; t.Y = bg->Q0[k].as<double>(); t.ldy = ldq;
-                t.C = Tb + (size_t)q * tslab; t.ldc = ldq; t.M = nb; t.N = bg->r[k] > 0 ? bg->r[k] : 1;
-                probs.push_back(t);
-            }
+            for (int q = 0; q < ngrp; q++) probs.push_back(B.rotation(R.grp_rho[q], nb, Tb + (size_t)q * tslab, ldq));
         }
         int max_m = 0, max_n = 0;
-        for (const GemmProblem& p : probs) { max_m = std::max(max_m, p.M); max_n = std::max(max_n, p.N); }
+        for (const GemmProblem& q : probs) { max_m = std::max(max_m, q.M); max_n = std::max(max_n, q.N); }
         CRM_HIP(hipMemcpyAsync(d_probs, probs.data(), sizeof(GemmProblem) * probs.size(), hipMemcpyHostToDevice, st));
-        CRM_TRY(launch_gemm_tn(ctx, d_probs, (int)probs.size(), max_m, max_n, np, false, 0, 1, 0));
+        return launch_gemm_tn(ctx, d_probs, (int)probs.size(), max_m, max_n, np, false, 0, 1, 0);
+    }
 
-        if (fast) {
-            const MultiGroup* d_grp = (const MultiGroup*)(sm + o_grp);
-            double* T2 = ctx->ws_G2.as<double>();
-            int rmax = 0;
-            for (const MultiGroup& R : groups) rmax = std::max(rmax, R.rpad);
-            hipLaunchKernelGGL(multi_square_kernel, dim3((nb + 255) / 256, rmax, ngrp), dim3(256), 0, st, Tb, T2, tslab, ldt,
-                               d_grp, nb);
-            CRM_HIP(hipGetLastError());
-            double* B1 = ctx->ws_A.as<double>();
-            double* B2 = B1 + (size_t)ldq * ld1;
-            double* C1 = ctx->ws_F.as<double>();
-            double* C2 = C1 + (size_t)BLK * ld1;
-            pp.clear();
-            int mn = 0;
-            for (int q = 0; q < ngrp; q++) {
-                const MultiGroup& R = groups[q];
-                const int n1 = (q + 1 < ngrp ? groups[q + 1].col1 : (int)ld1 - 128) - R.col1;
-                const int n2 = (q + 1 < ngrp ? groups[q + 1].col2 : (int)ld2 - 128) - R.col2;
-                GemmProblem a{};
-                a.X = Tb + (size_t)q * tslab; a.ldx = ldt; a.Y = B1 + R.col1; a.ldy = ld1; a.C = C1 + R.col1; a.ldc = ld1;
-                a.M = nb; a.N = n1; a.cells = R.rpad;
-                GemmProblem b = a;
-                b.X = T2 + (size_t)q * tslab; b.Y = B2 + R.col2; b.ldy = ld2; b.C = C2 + R.col2; b.ldc = ld2; b.N = n2;
-                pp.push_back(a);
-                pp.push_back(b);
-                mn = std::max(mn, std::max(n1, n2));
-            }
-            GemmProblem* d_pp = d_probs + probs.size();
-            CRM_HIP(hipMemcpyAsync(d_pp, pp.data(), sizeof(GemmProblem) * pp.size(), hipMemcpyHostToDevice, st));
-            CRM_TRY(launch_gemm_tn(ctx, d_pp, (int)pp.size(), nb, mn, rmax, false, 0, 1, 0));
-            const dim3 grid((nb + 127) / 128, ngenes);
-            if (c <= 8)
-                hipLaunchKernelGGL(multi_finish_kernel<8>, grid, dim3(128), 0, st, (const MultiGene*)(sm + o_mg), d_grp, c, n, nb,
-                                   C1, ld1, C2, ld2, d_gg, d_cy, ldcy, d_alt, d_pv, (long)BLK);
-            else
-                hipLaunchKernelGGL(multi_finish_kernel<0>, grid, dim3(128), 0, st, (const MultiGene*)(sm + o_mg), d_grp, c, n, nb,
-                                   C1, ld1, C2, ld2, d_gg, d_cy, ldcy, d_alt, d_pv, (long)BLK);
-            CRM_HIP(hipGetLastError());
-            if (eff) CRM_TRY(launch_assoc_effects(st, d_effg, ngenes, nb, c, true));
-        } else {
-            for (int i = 0; i < ngenes; i++) {
-                crm_gene* g = genes[i];
-                const int k = ri[i];
-                NullFitRho& R = alt.rho[0];
-                R.T = Tb + (size_t)grp_of_rho[k] * tslab; R.ldT = ldq;
-                R.ty = g->rot.as<double>() + (long)k * slab;
-                R.tW = R.ty + ldq; R.ldW = ldq;
-                R.S0 = bg->S0[k].as<double>();
-                R.r = bg->r[k];
-                alt.WW = g->WW.as<double>(); alt.Wy = g->Wy.as<double>(); alt.yy = g->yy;
-                alt.gy = d_cy + (size_t)i * ldcy;
-                CRM_TRY(launch_nullfit(st, alt, nb));
-                CRM_TRY(launch_gather_trial_lml(st, alt.trial, nb, d_alt + (size_t)i * BLK));
-                if (eff) CRM_TRY(launch_assoc_effects(st, d_effg + i, 1, nb, c, false));
-            }
-            hipLaunchKernelGGL(multi_lrt_kernel, dim3((nb + 255) / 256, ngenes), dim3(256), 0, st, d_alt, d_nl, nb, (long)BLK,
-                               d_pv);
-            CRM_HIP(hipGetLastError());
+    // fast: T o T, the two weighted products per rho group, one thread per (gene, variant) to finish
+    int fast_tests(int nb) {
+        double* T2 = ctx->ws_G2.as<double>();
+        hipLaunchKernelGGL(multi_square_kernel, dim3((nb + 255) / 256, rmax, ngrp), dim3(256), 0, st, Tb, T2, tslab, ldt,
+                           (const MultiGroup*)d_grp, nb);
+        CRM_HIP(hipGetLastError());
+        double* B1 = ctx->ws_A.as<double>();
+        double* B2 = B1 + (size_t)ldq * ld1;
+        double* C1 = ctx->ws_F.as<double>();
+        double* C2 = C1 + (size_t)BLK * ld1;
+        pp.clear();
+        int mn = 0;
+        for (int q = 0; q < ngrp; q++) {
+            const MultiGroup& G = groups[q];
+            const int n1 = (q + 1 < ngrp ? groups[q + 1].col1 : (int)ld1 - 128) - G.col1;
+            const int n2 = (q + 1 < ngrp ? groups[q + 1].col2 : (int)ld2 - 128) - G.col2;
+            GemmProblem a{};
+            a.X = Tb + (size_t)q * tslab; a.ldx = ldt; a.Y = B1 + G.col1; a.ldy = ld1; a.C = C1 + G.col1; a.ldc = ld1;
+            a.M = nb; a.N = n1; a.cells = G.rpad;
+            GemmProblem b = a;
+            b.X = T2 + (size_t)q * tslab; b.Y = B2 + G.col2; b.ldy = ld2; b.C = C2 + G.col2; b.ldc = ld2; b.N = n2;
+            pp.push_back(a);
+            pp.push_back(b);
+            mn = std::max(mn, std::max(n1, n2));
         }
-        if (out_pvalue)
-            CRM_HIP(hipMemcpy2DAsync(out_pvalue + done, sizeof(double) * count, d_pv, sizeof(double) * BLK, sizeof(double) * nb,
-                                     ngenes, hipMemcpyDeviceToHost, st));
-        if (out_alt_lml)
-            CRM_HIP(hipMemcpy2DAsync(out_alt_lml + done, sizeof(double) * count, d_alt, sizeof(double) * BLK,
-                                     sizeof(double) * nb, ngenes, hipMemcpyDeviceToHost, st));
-        if (eff) {
-            double* const outs[5] = {eff->beta, eff->se, eff->delta, eff->scale, eff->logp};
-            for (int q = 0; q < 5; q++)
-                if (outs[q])
-                    CRM_HIP(hipMemcpy2DAsync(outs[q] + done, sizeof(double) * count, d_eff + q * eff_rows, sizeof(double) * BLK,
-                                             sizeof(double) * nb, ngenes, hipMemcpyDeviceToHost, st));
-            if (eff->status)
-                CRM_HIP(hipMemcpy2DAsync(eff->status + done, sizeof(int) * count, (const int*)(d_eff + 5 * eff_rows),
-                                         sizeof(int) * BLK, sizeof(int) * nb, ngenes, hipMemcpyDeviceToHost, st));
+        GemmProblem* d_pp = d_probs + probs.size();
+        CRM_HIP(hipMemcpyAsync(d_pp, pp.data(), sizeof(GemmProblem) * pp.size(), hipMemcpyHostToDevice, st));
+        CRM_TRY(launch_gemm_tn(ctx, d_pp, (int)pp.size(), nb, mn, rmax, false, 0, 1, 0));
+        const dim3 grid((nb + 127) / 128, ngenes);
+        if (c <= 8)
+            hipLaunchKernelGGL(multi_finish_kernel<8>, grid, dim3(128), 0, st, (const MultiGene*)d_mg, (const MultiGroup*)d_grp, c, n,
+                               nb, C1, ld1, C2, ld2, B.d_gg, d_cy, ldcy, d_alt, d_pv, (long)BLK);
+        else
+            hipLaunchKernelGGL(multi_finish_kernel<0>, grid, dim3(128), 0, st, (const MultiGene*)d_mg, (const MultiGroup*)d_grp, c, n,
+                               nb, C1, ld1, C2, ld2, B.d_gg, d_cy, ldcy, d_alt, d_pv, (long)BLK);
+        CRM_HIP(hipGetLastError());
+        if (eff) CRM_TRY(launch_assoc_effects(st, d_effg, ngenes, nb, c, true));
+        return CRM_OK;
+    }
+
+    // full refit: per gene the null-fit kernels over the block on the shared T(rho*), then the LRT of all genes
+    int refit_tests(int nb) {
+        for (int i = 0; i < ngenes; i++) {
+            crm_gene* g = genes[i];
+            const int k = R.ri[i];
+            NullFitRho& A = alt.rho[0];
+            A.T = Tb + (size_t)R.grp_of_rho[k] * tslab; A.ldT = ldq;
+            A.ty = g->rot.as<double>() + (long)k * slab;
+            A.tW = A.ty + ldq; A.ldW = ldq;
+            A.S0 = bg->S0[k].as<double>();
+            A.r = bg->r[k];
+            alt.WW = g->WW.as<double>(); alt.Wy = g->Wy.as<double>(); alt.yy = g->yy;
+            alt.gy = d_cy + (size_t)i * ldcy;
+            CRM_TRY(launch_nullfit(st, alt, nb));
+            CRM_TRY(launch_gather_trial_lml(st, alt.trial, nb, d_alt + (size_t)i * BLK));
+            if (eff) CRM_TRY(launch_assoc_effects(st, d_effg + i, 1, nb, c, false));
         }
-        CRM_HIP(hipStreamSynchronize(st));
-        ctx->report(done + nb, count);
+        hipLaunchKernelGGL(multi_lrt_kernel, dim3((nb + 255) / 256, ngenes), dim3(256), 0, st, d_alt, d_nl, nb, (long)BLK, d_pv);
+        CRM_HIP(hipGetLastError());
+        return CRM_OK;
+    }
+
+    // the block's rows, gene-major on the host: row i of [ngenes x count]
+    template <class T>
+    int copy_rows(T* out, long done, int nb, const T* d_rows) {
+        if (out)
+            CRM_HIP(hipMemcpy2DAsync(out + done, sizeof(T) * B.count, d_rows, sizeof(T) * BLK, sizeof(T) * nb, ngenes,
+                                     hipMemcpyDeviceToHost, st));
+        return CRM_OK;
+    }
+    int copy_out(long done, int nb, double* out_pvalue, double* out_alt_lml) {
+        CRM_TRY(copy_rows(out_pvalue, done, nb, d_pv));
+        CRM_TRY(copy_rows(out_alt_lml, done, nb, d_alt));
+        if (!eff) return CRM_OK;
+        double* const outs[5] = {eff->beta, eff->se, eff->delta, eff->scale, eff->logp};
+        for (int q = 0; q < 5; q++) CRM_TRY(copy_rows(outs[q], done, nb, d_eff + q * eff_rows));
+        return copy_rows(eff->status, done, nb, (const int*)(d_eff + 5 * eff_rows));
+    }
+};
+
+int scan_association_multi(crm_gene* const* genes, int ngenes, crm_panel* panel, long first, long count, int fast,
+                           const double* null, double* out_pvalue, double* out_alt_lml, const AssocEffectsOut* eff) {
+    const char* what = "association multi";
+    CRM_TRY(check_shared_genes(what, genes, ngenes, false));
+    if (!panel || !null) {
+        set_error("%s: %s is NULL", what, panel ? "null" : "panel");
+        return CRM_ERR_ARG;
+    }
+    crm_background* bg = genes[0]->bg;
+    CRM_TRY(check_panel_range(what, bg, panel, first, count));
+    NullRows R;
+    CRM_TRY(R.read(what, bg, null, ngenes, fast != 0));
+    if (genes[0]->c > CMAX) {
+        set_error("%s: %d covariate columns (supported up to %d)", what, genes[0]->c, CMAX);
+        return CRM_ERR_UNSUPPORTED;
+    }
+    if (count == 0) return CRM_OK;
+    InScan in_scan;
+    CRM_TRY(in_scan.enter(bg->ctx, what));
+    CRM_HIP(hipSetDevice(bg->ctx->device));
+    CRM_TRY(R.group(bg));
+    AssocMultiScan S(genes, ngenes, panel, first, count, fast, null, R, eff);
+    CRM_TRY(S.workspaces());
+    CRM_TRY(S.operands());
+    for (long done = 0; done < count; done += S.BLK) {
+        const int nb = S.B.nb_at(done);
+        CRM_TRY(S.B.prepare(done, nb, fast ? 1 : S.c));   // (fast: g'W and g'y_j come from the product below)
+        CRM_TRY(S.block_products(nb));
+        CRM_TRY(fast ? S.fast_tests(nb) : S.refit_tests(nb));
+        CRM_TRY(S.copy_out(done, nb, out_pvalue, out_alt_lml));
+        CRM_HIP(hipStreamSynchronize(S.st));
+        S.ctx->report(done + nb, count);
     }
     return CRM_OK;
 }

@@ -187,6 +187,43 @@ struct crm_ctx {
 };
 
 namespace crm {
+// crm_ctx::in_scan for the length of a scan: enter() refuses while another scan holds the context's work buffers (one
+// started from a progress callback), the destructor lets go of them.
+struct InScan {
+    crm_ctx* held = nullptr;
+    InScan() = default;
+    InScan(const InScan&) = delete;
+    InScan& operator=(const InScan&) = delete;
+    ~InScan() { if (held) held->in_scan = false; }
+    int enter(crm_ctx* ctx, const char* what) {
+        if (ctx->in_scan) {
+            set_error("%s: another scan is running on this context (started from a progress callback?); its work buffers are in use", what);
+            return CRM_ERR_UNSUPPORTED;
+        }
+        ctx->in_scan = true;
+        held = ctx;
+        return CRM_OK;
+    }
+};
+
+// The kernel timer (crm_ctx::timed): the event pair of the next timed launch, its start recorded now or by the caller;
+// the close records the end and counts the pair.
+inline int kernel_timer_open(crm_ctx* ctx, hipStream_t st, bool record_start) {
+    if (ctx->timed_used == ctx->timed.size()) {
+        hipEvent_t a, b;
+        CRM_HIP(hipEventCreate(&a));
+        CRM_HIP(hipEventCreate(&b));
+        ctx->timed.emplace_back(a, b);
+    }
+    if (record_start) CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].first, st));
+    return CRM_OK;
+}
+inline int kernel_timer_close(crm_ctx* ctx, hipStream_t st) {
+    CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].second, st));
+    ctx->timed_used++;
+    return CRM_OK;
+}
+
 // crm::guarded (no C++ exception across the C-ABI) with the context's lock held around the body; ctx may be null (the
 // body then reports the bad argument itself).
 template <class Body>

@@ -9,8 +9,7 @@
 //   crm_cov_solve  K^-1 rhs for one grid point of a background
 #include <algorithm>
 
-#include "nullfit.h"
-#include "objects.h"
+#include "lrt_scan.h"
 
 using namespace crm;
 
@@ -60,15 +59,15 @@ extern "C" int crm_lmm_fit(crm_gene* gene, int restricted, double* out_fit, doub
     const long ld_gW = round_up(std::max(c, 8), 8);
 
     DevBuf small;
+    double *d_zero = nullptr, *d_g3 = nullptr, *d_prep = nullptr, *d_wts = nullptr;
+    NullFitTrial* d_trial = nullptr;
+    NullFitOut* d_fit = nullptr;
     size_t off = 0;
-    auto carve = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_zero = carve(sizeof(double) * ldq), o_g3 = carve(sizeof(double) * (2 + ld_gW)),
-                 o_trial = carve(sizeof(NullFitTrial) * nrho), o_fit = carve(sizeof(NullFitOut)),
-                 o_prep = carve(sizeof(double) * fastscan_prep_doubles()), o_wts = carve(sizeof(double) * ldq);
-    CRM_TRY(small.ensure(off));
+    CRM_TRY(carve_workspace(small, [&](auto& take) {
+        take(d_zero, sizeof(double) * ldq), take(d_g3, sizeof(double) * (2 + ld_gW)), take(d_trial, sizeof(NullFitTrial) * nrho);
+        take(d_fit, sizeof(NullFitOut)), take(d_prep, sizeof(double) * fastscan_prep_doubles()), take(d_wts, sizeof(double) * ldq);
+    }, &off));
     char* sm = small.as<char>();
-    double* d_zero = (double*)(sm + o_zero);
-    double* d_g3 = (double*)(sm + o_g3);
     CRM_HIP(hipMemsetAsync(sm, 0, off, st));
 
     // a zero "variant" is dropped by the fit kernels (rank-deficient [M, 0]): exactly LMM(y, M)
@@ -76,8 +75,8 @@ extern "C" int crm_lmm_fit(crm_gene* gene, int restricted, double* out_fit, doub
     nullfit_gene_args(fa, gene, restricted ? 1 : 0);
     for (int i = 0; i < nrho; i++) { fa.rho[i].T = d_zero; fa.rho[i].ldT = 0; }
     fa.gg = d_g3; fa.gy = d_g3 + 1; fa.gW = d_g3 + 2; fa.ld_gW = ld_gW;
-    fa.trial = (NullFitTrial*)(sm + o_trial);
-    fa.out = (NullFitOut*)(sm + o_fit);
+    fa.trial = d_trial;
+    fa.out = d_fit;
     DevBuf xwide;
     if (c > CRM_MAX_COV_WIDE) {   // 63 .. 128 columns: the slower kernel with its scratch in global memory
         CRM_TRY(xwide.ensure(sizeof(double) * nullfit_xwide_scratch_doubles(1, nrho, c)));
@@ -106,8 +105,7 @@ extern "C" int crm_lmm_fit(crm_gene* gene, int restricted, double* out_fit, doub
     aa.ty = fa.rho[ri].ty; aa.tW = fa.rho[ri].tW; aa.ldW = ldq; aa.S0 = fa.rho[ri].S0;
     aa.r = bg->r[ri]; aa.c = c; aa.n = n; aa.delta0 = fit.delta;
     aa.WW = fa.WW; aa.Wy = fa.Wy; aa.yy = fa.yy;
-    double* d_prep = (double*)(sm + o_prep);
-    CRM_TRY(launch_fastscan_prep(st, aa, d_prep, (double*)(sm + o_wts)));
+    CRM_TRY(launch_fastscan_prep(st, aa, d_prep, d_wts));
     std::vector<double> prep(fastscan_prep_doubles());
     CRM_HIP(hipMemcpyAsync(prep.data(), d_prep, sizeof(double) * prep.size(), hipMemcpyDeviceToHost, st));
     CRM_HIP(hipStreamSynchronize(st));

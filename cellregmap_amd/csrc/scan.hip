@@ -52,11 +52,8 @@ static int scan_pass(const std::vector<crm_gene*>& genes, crm_panel* panel, long
         }
     }
     if (count == 0) return CRM_OK;
-    if (ctx->in_scan) {
-        set_error("scan: another scan is running on this context (started from a progress callback?); its work buffers are in use");
-        return CRM_ERR_UNSUPPORTED;
-    }
-    struct InScan { crm_ctx* c; explicit InScan(crm_ctx* c_) : c(c_) { c->in_scan = true; } ~InScan() { c->in_scan = false; } } in_scan(ctx);
+    InScan in_scan;
+    CRM_TRY(in_scan.enter(ctx, "scan"));
     // (the Gram kernel stages all k0 + c + 2 rows of a variant in LDS: refused here, before anything is launched, with
     // the limit named; past 144 rows / 128 contexts the scan runs through the slower forms of its per-variant kernels)
     if (g0->k0 + g0->c + 2 > CRM_MAX_GRAM_ROWS) {

@@ -274,10 +274,10 @@ int ScanPass::rotations(const Block& B) {
     CRM_TRY(upload(SLOT_RHO, probs.data(), n_main));
     // (unrelated-donor form: the kernel timer brackets this launch, the rotations MixK(rho)'(H'Gx) -- the step's largest)
     const bool timing_T = P.wb() && ctx->timing && ctx->timed_used < 65536;
-    if (timing_T) CRM_TRY(timer_open(true));
+    if (timing_T) CRM_TRY(kernel_timer_open(ctx, st, true));
     CRM_TRY(launch_gemm_tn(ctx, d_probs + SLOT_RHO, n_main, nb, (int)ldq, P.fastT ? P.kdim : P.xrows, false, 0, 1, 0));
     if (timing_T) {
-        CRM_TRY(timer_close());
+        CRM_TRY(kernel_timer_close(ctx, st));
         for (int q = 0; q < n_main; q++) ctx->kr_flops += 2.0 * (double)P.kdim * (double)nb * (double)probs[q].N;
     }
     CRM_TRY(side_fork(B));   // (behind timer_close: the timed pair still brackets the rotations alone)

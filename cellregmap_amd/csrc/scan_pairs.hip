@@ -411,7 +411,7 @@ int ScanPass::form_A(const Block& B, const SubRange& R, const Pairs& Q) {
     a_records(Q, via_H, tail_of, A);
     const bool timing = !P.wb() && ctx->timing && ctx->timed_used < 65536;  // bounded: a forgotten timer cannot grow for ever
     // (kinship-structure route: the pair brackets the dominant launch alone, the Mix(rho*)' product further down)
-    if (timing) CRM_TRY(timer_open(!P.kin()));
+    if (timing) CRM_TRY(kernel_timer_open(ctx, st, !P.kin()));
     if (P.folded()) CRM_TRY(folded_S(B, R, Q));
     else if (P.kin()) CRM_TRY(unfolded_AH(B, R, Q));
     else if (via_H) CRM_TRY(direct_AH(B, R, Q, A));
@@ -443,7 +443,7 @@ int ScanPass::form_A(const Block& B, const SubRange& R, const Pairs& Q) {
         }
     }
     if (timing) {
-        CRM_TRY(timer_close());
+        CRM_TRY(kernel_timer_close(ctx, st));
         ctx->kr_flops += A.kr_flops;
     }
     if (!A.spectrum_tails.empty()) {

@@ -212,22 +212,6 @@ struct ScanPass {
         CRM_HIP(hipStreamSynchronize(st));
         return CRM_OK;
     }
-    // the kernel timer (crm_ctx::timed): the event pair of the next timed launch, its start recorded now or by the caller
-    int timer_open(bool record_start) {
-        if (ctx->timed_used == ctx->timed.size()) {
-            hipEvent_t a, b;
-            CRM_HIP(hipEventCreate(&a));
-            CRM_HIP(hipEventCreate(&b));
-            ctx->timed.emplace_back(a, b);
-        }
-        if (record_start) CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].first, st));
-        return CRM_OK;
-    }
-    int timer_close() {
-        CRM_HIP(hipEventRecord(ctx->timed[ctx->timed_used].second, st));
-        ctx->timed_used++;
-        return CRM_OK;
-    }
     // A fit that ends with (practically) no kinship term -- delta at the upper clamp, v0 = 2.2e-16 scale: a phenotype without
     // a random effect, half of an eQTL run -- has K0 = v1 (I + (v0 / v1) Q0 S0 Q0'): where (v0 / v1) max S0 <= 1e-10 the
     // rotated test direction A~ enters Q and F with weights d_j <= 1e-10, below the tolerance of the test by four orders of

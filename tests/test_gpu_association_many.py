@@ -144,6 +144,40 @@ def test_cis_windows(fast):
     _check_against_single(sub, G, [pv[i] for i in nonempty], subinfo, fast, cols=[cols[i] for i in nonempty])
 
 
+@pytest.mark.parametrize("driver", ["association", "contexts"])
+def test_progress_true_is_one_bar_over_the_walk(driver, monkeypatch):
+    """``progress=True``: one tqdm bar over all runs of a cis walk, counted in the variants at least one phenotype tests."""
+    import sys
+    import types
+
+    import cellregmap_amd as crm
+
+    bars = []
+
+    class Bar:
+        def __init__(self, total=None):
+            self.total, self.n, self.closed = total, 0, False
+            bars.append(self)
+
+        def update(self, by):
+            self.n += by
+
+        def close(self):
+            self.closed = True
+
+    monkeypatch.setitem(sys.modules, "tqdm", types.SimpleNamespace(tqdm=Bar))
+    c = _cohort(10, 20, 3, 40, seed=33)
+    G = _genotypes(c, seed=8)[:, :40]
+    crms = _crms(c, _phenotypes(c, 3, seed=9), c.W, "B")
+    cis = [(0, 30), (10, 36), np.array([38, 5])]     # five runs; variants 36, 37 and 39 are nobody's
+    call = crm.scan_association_many if driver == "association" else crm.scan_interaction_contexts_many
+    silent = call(crms, G, cis_index=cis, fast=True)
+    shown = call(crms, G, cis_index=cis, fast=True, progress=True)
+    assert len(bars) == 1 and bars[0].total == 37 and bars[0].n == 37 and bars[0].closed
+    for a, b in zip(silent[0], shown[0]):
+        assert np.array_equal(a, b)
+
+
 @pytest.mark.parametrize("fast", [False, True])
 @pytest.mark.parametrize("k", [9, 62, 70])
 def test_run_association_many_wrapper(k, fast):

@@ -10,6 +10,11 @@ Last come the cohorts of tests/pinned_cases.py, which sit on the boundaries betw
 never leaves the first of: the whole trial table of crm_test_null_fit_probe(on = 2) -- lml, delta, scale, nfev and use_g
 of every (variant, grid point), and the selected index -- of every null-model cohort, once from the plain scan and once
 from the call that asks for model flags, and what estimate_betas_many returns on the pairs held of every effects cohort.
+After them the association LRTs and the fixed-effect context tests (lrt_tables): every output array of the single-gene and
+many-gene entries, with and without effect sizes, each and joint, fast and full refit, on the cohorts of
+tests/pinned_cases.py (ASSOCIATION), tests/context_block_cases.py (blocks of 128 and sub-ranges of 50 variants) and
+tests/context_many_cases.py (MIXED: several rho groups), on dense and donor-level panels, through a cis walk, from
+first > 0 and with count = 0.
 These are compared as 64-bit patterns.
 Exit status 0: every array and every counter identical.
     python tools/diag/compare_builds.py <other library> [count 150] [seed 2026] [--forms name=value[,name=value...]]
@@ -76,6 +81,7 @@ def child(lib_path, count, seed, out, forms):
         G = c.G + 0.05 * np.random.default_rng(k0).normal(size=c.G.shape)     # (general genotypes: the dense path)
         scan(CellRegMap(c.y, c.E, W=c.W, Ls=get_L_values(c.hK, c.E)), G, None)
     pinned = pinned_tables(lib, _engine._context(0))
+    pinned.update(lrt_tables(lib, _engine._context(0)))
     ctx, counters = _engine._context(0), {}
     for name in COUNTERS + REPORTED:
         if name not in _lib.SIGNATURES:
@@ -128,6 +134,128 @@ def pinned_tables(lib, ctx):
     return out
 
 
+def lrt_tables(lib, ctx):
+    """{"lrt <cohort>, <call>": float64 array} over the association and context scans' entries (ints go over exactly)."""
+    import context_block_cases as bc
+    import context_many_cases as mc
+    import pinned_cases as pc
+
+    import cellregmap_amd as crm
+    from cellregmap_amd import GenotypePanel, _engine, _lib
+
+    out = {}
+
+    def keep(tag, pv, info, st=None):
+        tables = {"pv": pv, **info, **(st or {})}
+        for key in sorted(tables):
+            parts = tables[key] if isinstance(tables[key], list) else [tables[key]]
+            if all(np.asarray(x).dtype.kind in "fiub" for x in parts):
+                out["lrt %s, %s" % (tag, key)] = np.concatenate([np.asarray(x, float).ravel() for x in parts] + [np.empty(0)])
+
+    def donors_of(cs):     # a donor-level copy of the cohort's panel: every cell carries its donor's first cell's genotypes
+        rows = np.array([np.flatnonzero(cs.donor_of_cell == d)[0] for d in range(cs.donors)])
+        return cs.G[rows][cs.donor_of_cell]
+
+    def windows(p, ng):    # phenotype 0: the whole panel; the others: stretches inside it (runs with a strict subset, first > 0)
+        return [(0, p)] + [(min(p - 1, 1 + 2 * i), max(min(p - 1, 1 + 2 * i) + 1, p - i)) for i in range(1, ng)]
+
+    def direct(tag, entry, head, spec, p):
+        """The C entry itself on a stretch inside the panel and on no variants: ``head(first, count)`` its leading arguments,
+        ``spec`` its outputs in order as (name, dtype, per variant?, values per row: 1, k or 6 for the null row)."""
+        rows = head(0, 0)[1] if isinstance(head(0, 0)[0], ctypes.Array) else 1
+        for first, count in ((1, p - 1), (p // 2, 0)):
+            bufs = [np.full((rows, count * width) if each else (rows, width), -7 if dtype is np.int32 else np.nan, dtype)
+                    for _, dtype, each, width in spec]
+            _lib.check(entry(*head(first, count), *[_lib.ptr(b) for b in bufs]))
+            for (what, _, _, _), b in zip(spec, bufs):
+                out["lrt %s, from %d, %d variants, %s" % (tag, first, count, what)] = b.astype(float).ravel()
+
+    F, I = float, np.int32
+    ASSOC = [("pv", F, True, 1), ("alt_lml", F, True, 1)]
+    EFFECTS = [(w, F, True, 1) for w in ("beta", "se", "delta", "scale", "logp")] + [("effect_status", I, True, 1)]
+
+    def context_spec(joint, k, single):
+        each = [("pv", F, True, k), ("alt_lml", F, True, k), ("beta", F, True, k), ("beta_se", F, True, k), ("logp", F, True, k),
+                ("status", I, True, k)]
+        jnt = [("pv", F, True, 1), ("logp", F, True, 1), ("alt_lml", F, True, 1), ("dof", I, True, 1), ("beta", F, True, k),
+               ("beta_se", F, True, k), ("dropped", I, True, k), ("status", I, True, 1)]
+        return (jnt if joint else each) + [("null_lml", F, True, 1), ("null_delta", F, True, 1)] + ([("null", F, False, 6)] if single else [])
+
+    for name in pc.ASSOCIATION:
+        cs = pc.AssociationCase(name, variants=7)
+        kw = {} if cs.hK is None else {"hK": cs.hK}
+        objs = [crm.CellRegMap(cs.y, cs.E, W=cs.W, E1=cs.E1, **kw)]
+        objs += [crm.CellRegMap(cs.y + 0.2 * i * cs.G[:, i], cs.E, W=cs.W, E1=cs.E1, background=objs[0]._bg, **kw) for i in (1, 2)]
+        for kind, G in (("dense", GenotypePanel(cs.G, groups=None)), ("donors", GenotypePanel(donors_of(cs), groups="auto"))):
+            for fast in (0, 1):
+                tag = "%s, %s, fast %d" % (name, kind, fast)
+                scan = objs[0].scan_association_fast if fast else objs[0].scan_association
+                keep(tag + ", single", *scan(G, return_stats=True, progress=False))
+                keep(tag + ", single effects", *scan(G, return_stats=True, progress=False, effects=True))
+                keep(tag + ", many", *crm.scan_association_many(objs, G, fast=bool(fast), return_stats=True))
+                keep(tag + ", many effects", *crm.scan_association_many(objs, G, fast=bool(fast), return_stats="effects"))
+                keep(tag + ", many effects cis", *crm.scan_association_many(objs, G, cis_index=windows(7, 3), fast=bool(fast),
+                                                                           return_stats="effects"))
+                gene = objs[0]._bind_gene()
+                hs = (ctypes.c_void_p * 3)(*[o._bind_gene(like=objs[0]).value for o in objs])
+                null = np.empty((3, 6))
+                _lib.check(lib.crm_association_null_multi(hs, 3, _lib.ptr(null)))
+                one = lambda first, count: (gene, G.handle, first, count, fast)
+                many = lambda first, count: (hs, 3, G.handle, first, count, fast, _lib.ptr(null))
+                direct(tag + ", single", lib.crm_scan_association, one, ASSOC + [("null", F, False, 6)], 7)
+                direct(tag + ", single effects", lib.crm_scan_association_effects, one, ASSOC + [("null", F, False, 6)] + EFFECTS, 7)
+                direct(tag + ", multi", lib.crm_scan_association_multi, many, ASSOC, 7)
+                direct(tag + ", multi effects", lib.crm_scan_association_multi_effects, many, ASSOC + EFFECTS, 7)
+
+    def cut(obj, cs, on):
+        ldq = -(-max(obj._bg.rank(i) for i in range(len(cs.grid))) // 128) * 128
+        _lib.check(lib.crm_set_block_variants(ctx, bc.BLOCK if on else 0))
+        _lib.check(lib.crm_test_set_context_budget(ctx, bc.SUB * 8 * cs.k * ldq + 8 if on else 0))
+
+    for name in bc.CASES:     # several blocks with a ragged tail, several sub-ranges per block; the joint cohorts: V in LDS and in global memory
+        cs = bc.case(name)
+        obj = crm.CellRegMap(cs.y, cs.C, W=cs.W, **cs.device_kw())
+        panels = [("dense", GenotypePanel(cs.G, groups=None))]
+        if name == bc.DOSAGES:
+            panels.append(("donors", GenotypePanel.from_dosages(cs.D, cs.donor_of_cell, standardize=False)))
+        cut(obj, cs, True)
+        try:
+            for kind, G in panels:
+                for fast in (False, True):
+                    for call in (("joint",) if bc.CASES[name][2] == "joint" else ("each", "joint")):
+                        scan = obj.scan_interaction_contexts_joint if call == "joint" else obj.scan_interaction_contexts
+                        keep("blocks %s, %s, %s, fast %d" % (name, kind, call, fast), *scan(G, fast=fast, return_stats=True))
+        finally:
+            cut(obj, cs, False)
+
+    for name in mc.MIXED + ("k 48, c 128, mode B",):     # three or more phenotypes on several rho groups; the WIDE joint cohort
+        base, views = mc.cohort(name)
+        first = crm.CellRegMap(views[0].y, views[0].C, W=views[0].W, **views[0].device_kw())
+        objs = [first] + [crm.CellRegMap(v.y, v.C, W=v.W, background=first._bg, **v.device_kw()) for v in views[1:]]
+        p = base.G.shape[1]
+        for kind, G in (("dense", GenotypePanel(base.G, groups=None)), ("donors", GenotypePanel(donors_of(base), groups="auto"))):
+            for fast in (False, True):
+                for joint in ((True,) if mc.is_joint(name) else (False, True)):
+                    many = crm.scan_interaction_contexts_joint_many if joint else crm.scan_interaction_contexts_many
+                    tag = "many %s, %s, joint %d, fast %d" % (name, kind, joint, fast)
+                    try:
+                        keep(tag, *many(objs, G, fast=fast, return_stats=True))
+                        keep(tag + ", cis", *many(objs, G, cis_index=windows(p, len(objs)), fast=fast, return_stats=True))
+                        genes = _engine._bind_context_genes(objs, base.C, True)
+                        hs = (ctypes.c_void_p * len(genes))(*[g.value for g in genes])
+                        null = np.empty((len(genes), 6))
+                        _lib.check(lib.crm_association_null_multi(hs, len(genes), _lib.ptr(null)))
+                        direct(tag + ", single", lib.crm_scan_interaction_contexts_joint if joint else lib.crm_scan_interaction_contexts,
+                               lambda first, count: (genes[0], G.handle, first, count, int(fast)), context_spec(joint, base.k, True), p)
+                        direct(tag + ", multi",
+                               lib.crm_scan_interaction_contexts_joint_multi if joint else lib.crm_scan_interaction_contexts_multi,
+                               lambda first, count: (hs, len(genes), G.handle, first, count, int(fast), _lib.ptr(null)),
+                               context_spec(joint, base.k, False), p)
+                    except _lib.CrmError as err:     # (a shape the joint test refuses: the refusal is the table)
+                        out["lrt %s, refused" % tag] = np.frombuffer(str(err).encode().ljust(256)[:256], np.float64).copy()
+    return out
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--child":
         return child(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), sys.argv[5], sys.argv[6])
@@ -154,10 +282,11 @@ def main():
         same = (a[k] == b[k]) | (np.isnan(a[k]) & np.isnan(b[k]))
         rep[k] = {"identical": int(same.sum()), "different": int((~same).sum()),
                   "worst_rel_difference": float(np.nanmax(np.abs(a[k] - b[k]) / np.maximum(np.abs(a[k]), 1e-300))) if (~same).any() else 0.0}
-    names = sorted(k for k in a.files if k.startswith("pinned "))
+    names = sorted(k for k in a.files if k.startswith(("pinned ", "lrt ")))
     same = {k: k in b.files and a[k].shape == b[k].shape and np.array_equal(a[k].view(np.uint64), b[k].view(np.uint64)) for k in names}
     rep["pinned"] = {"tables": len(names), "values": int(sum(a[k].size for k in names)), "identical_tables": int(sum(same.values())),
-                     "different": [k for k in names if not same[k]], "tables_match": names == sorted(k for k in b.files if k.startswith("pinned "))}
+                     "different": [k for k in names if not same[k]], "tables_match": names == sorted(k for k in b.files if k.startswith(("pinned ", "lrt "))),
+                     "lrt_tables": int(sum(k.startswith("lrt ") for k in names)), "lrt_values": int(sum(a[k].size for k in names if k.startswith("lrt ")))}
     rep["counters"] = {name[len("crm_test_"):]: {"other": na["counters"][name], "this": nb["counters"][name]} for name in COUNTERS}
     rep["reported"] = {name[len("crm_test_"):]: {"other": na["counters"].get(name), "this": nb["counters"].get(name)} for name in REPORTED}
     rep["counters_identical"] = all(v["other"] is not None and v["other"] == v["this"] for v in rep["counters"].values())

@@ -3,6 +3,7 @@
 // order the Khatri-Rao contraction consumes), elementwise products feeding the side
 // contractions.  All HBM-bound, coalesced along the variant / column axis.
 #include "nullfit.h"
+#include "wave_ops.h"
 
 namespace crm {
 
@@ -696,11 +697,8 @@ int launch_donor_pairs_expand(hipStream_t st, const double* P, long p_slab, long
 // A workgroup takes four variants and a range of donors and walks them in order, as donor_pairs_expand_kernel does (and forms
 // the same donor sums Psum, the E1 rows); wavefront w computes the rows i = 16 w .. 16 w + 15 of each variant, all columns j.
 constexpr int DR_LDU = 80;   // LDS row of Psi_d: 64 columns + 16, rows k and k + 1 on the two halves of the banks
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-// a barrier that waits for this wavefront's LDS operations alone: __syncthreads() also drains every global store in flight,
-// and each donor's 80 KB of rotated S would then be waited for before the next donor's loads are issued
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// (its barriers are lds_barrier(), wave_ops.h: __syncthreads() also drains every global store in flight, and each donor's
+// 80 KB of rotated S would then be waited for before the next donor's loads are issued)
 
 template <int DP_SLOTS>   // (a multiple of 8)
 __global__ __launch_bounds__(256, 2) void donor_pairs_rotate_kernel(const double* __restrict__ P, long p_slab, long ldp, int donors,

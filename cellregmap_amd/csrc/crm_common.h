@@ -36,6 +36,20 @@ const char* last_error_text();
         if (rc__ != CRM_OK) return rc__; \
     } while (0)
 
+// A launch with `lds` bytes of dynamic LDS.  raise_limit: set the kernel's hipFuncAttributeMaxDynamicSharedMemorySize to
+// `lds` first (required past the 64 KB every kernel may ask for; the caller decides when).  Returns the first error of the
+// two calls, for CRM_HIP.
+template <class... P, class... A>
+inline hipError_t launch_with_lds(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, bool raise_limit,
+                                  const A&... args) {
+    if (raise_limit) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(args)...);
+    return hipGetLastError();
+}
+
 inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 
 // Kernel forms that exist beside the default one (a slower or older variant kept because the default falls back to it, or

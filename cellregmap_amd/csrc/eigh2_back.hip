@@ -23,17 +23,14 @@
 #include <vector>
 
 #include "eigh.h"
+#include "wave_ops.h"
 
 namespace crm {
 namespace {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));
 constexpr int W = E2_W;            // 64
-
-// barrier of a workgroup for its LDS traffic only: global loads and stores in flight stay in flight
-__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // T of the group (sweep block S, chain position k): reflector j is v(S 64 + j, k) placed at rows j .. j + 63 of the
 // group's window of 127 rows.  S = V'V over the window (V kept in window coordinates in LDS: lanes run along a row), then

@@ -17,12 +17,12 @@
 #include <chrono>
 
 #include "eigh.h"
+#include "wave_ops.h"
 
 namespace crm {
 namespace {
 
 typedef unsigned long long u64;
-typedef double v4d __attribute__((ext_vector_type(4)));
 constexpr int W = E2_W;            // 64
 constexpr int CH_LD = 65;          // LDS row stride of the chase's blocks
 constexpr int PROG_DONE = 1 << 30;
@@ -43,8 +43,6 @@ __device__ inline v2d ld_sc1_x2(__amdgpu_buffer_rsrc_t rs, int byte_off) {
 __device__ inline void st_sc1_x2(__amdgpu_buffer_rsrc_t rs, int byte_off, double x, double y) {
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, (v2d){x, y}), rs, byte_off, 0, 16);
 }
-// barrier of a workgroup for its LDS traffic only: global loads in flight (prefetches) stay in flight
-__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 struct ChaseArgs {
     double* AB;  long ab_slab;      // [batch][dimp + 128][128]

@@ -16,10 +16,10 @@
 // with a row stride of 144 doubles (= 128 B mod 256 B) so that the four 16-lane groups of a
 // ds_read_b64 fragment read hit disjoint bank halves.
 #include "crm_internal.h"
+#include "wave_ops.h"
 
 namespace crm {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 typedef double v2d __attribute__((ext_vector_type(2)));
 
 constexpr int LDT = GEMM_BM + 16;  // LDS row stride of a plain operand tile (doubles)

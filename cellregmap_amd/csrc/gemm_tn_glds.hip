@@ -13,10 +13,10 @@
 #include <type_traits>
 
 #include "crm_internal.h"
+#include "wave_ops.h"
 
 namespace crm {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
 typedef const double __attribute__((address_space(1))) * gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
 typedef const double __attribute__((address_space(3))) * lcptr_t;

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "assemble.h"
 #include "nullfit.h"
 #include "objects.h"
 

@@ -1,8 +1,22 @@
-// Lane-to-lane primitives of a 64-wide wavefront shared by the kernels that reduce across lanes (nullfit.hip, davies.hip).
+// Primitives of a 64-wide wavefront shared by the kernels: the accumulator type of the FP64 MFMA, the workgroup barriers
+// that wait for less than __syncthreads() does, and the lane-to-lane sums of the kernels that reduce across lanes
+// (nullfit.hip, davies.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace crm {
+
+typedef double v4d __attribute__((ext_vector_type(4)));   // the accumulator of v_mfma_f64_16x16x4f64
+
+// A workgroup barrier for LDS traffic alone: it waits for this wavefront's LDS operations (lgkmcnt), not, as __syncthreads()
+// does, for its global loads and stores as well -- prefetches and stores in flight stay in flight across it.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// The barrier behind LDS-DMA: s_barrier does not wait for memory operations in flight, and the compiler adds the vmcnt wait
+// only for a DMA issued in the straight-line code before a __syncthreads(), not for one pending across a loop's back-edge.
+// Every barrier whose opening lets a wavefront read what a DMA wrote therefore waits explicitly, for this wavefront's loads
+// (vmcnt) and LDS operations (lgkmcnt); behind the barrier every wavefront's have landed.
+__device__ __forceinline__ void dma_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Sums over the 64 lanes, every lane ending with bitwise the same totals -- the xor butterfly
 //   for (off = 32, 16, 8, 4, 2, 1) v += shfl_xor(v, off)

@@ -1,5 +1,5 @@
 // Unrelated-donor form, one phenotype: the weighted Gram Gw of [rotated S ; W ; gx ; y ; E1] straight from the per-donor pair
-// products -- donor_pairs_rotate_kernel (blockops.hip) and gram_ext_dma_wide_kernel (assemble.hip) in one launch, so that the
+// products -- donor_pairs_rotate_kernel (blockops.hip) and gram_ext_dma_wide_kernel (gram_ext.hip) in one launch, so that the
 // rotated S (ws_A: variants x k0 rows x donors k2 positions) is neither written nor read back.
 //
 // One workgroup per variant of the block walks the donors.  A donor d owns the positions [k0 d, k0 d + k0) of the Gram's
@@ -20,33 +20,19 @@
 // does not write.  Columns that no chunk fills are zeros: written once for the rotated rows, and by every DMA for the
 // others (lanes off the chunk read a row of zeros, AssembleArgs::A_none).
 // Every buffer is single: a load is issued behind the barrier that frees its buffer and waited for (vmcnt(0), written out:
-// dma_barrier) before the next barrier, so it is in flight during the MFMAs of the phase between the two --
+// dma_barrier, wave_ops.h) before the next barrier, so it is in flight during the MFMAs of the phase between the two --
 //     rotation d | wait + barrier | issue P, Psi, S0 of d + 1 | Gram d | wait + barrier | issue the other rows of d + 1 | rotation d + 1 ...
 // (two of everything would not fit two workgroups per CU: 79 KB per workgroup at k0 = 50 as it is), and the second
 // workgroup of the CU fills what is left.  The loop holds no ordinary global load: each would be waited for together with
 // every LDS-DMA in flight.
 #include <type_traits>
 
-#include "nullfit.h"
-#include "tile_gram.h"
+#include "assemble.h"
+#include "gram_common.h"
 
 namespace crm {
 
 namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-typedef const double __attribute__((address_space(1))) * fused_gptr_t;
-typedef __attribute__((address_space(3))) void* fused_lptr_t;
-
-__device__ __forceinline__ void fused_dma16(const double* src, double* lds_wave_uniform) {
-    __builtin_amdgcn_global_load_lds((fused_gptr_t)src, (fused_lptr_t)lds_wave_uniform, 16, 0, 0);
-}
-
-// The barrier behind LDS-DMA: s_barrier does not wait for memory operations in flight, and the compiler adds the vmcnt wait
-// only for a DMA issued in the straight-line code before a __syncthreads(), not for one pending across the loop's back-edge.
-// Every barrier whose opening lets a wavefront read what a DMA wrote therefore waits explicitly, for this wavefront's loads
-// (vmcnt) and LDS operations (lgkmcnt); behind the barrier every wavefront's have landed.
-__device__ __forceinline__ void dma_barrier() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 constexpr int WF_MAXQ_P = 10, WF_MAXQ_O = 9, WF_PSUM = 6;   // DMA instructions per wavefront (P, Psi, S0 / other rows); sums per thread
 constexpr int WF_UW = 56;   // LDS row of Psi_d: a constant, so that the fragment reads carry their offsets as immediates (k0 <= 54)
@@ -96,21 +82,14 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lq = lane >> 4;
-    const int k0 = a.k0, c = a.c, RS = L.RS;
+    const int k0 = a.k0, RS = L.RS;
     constexpr int UW = WF_UW;
     const int npair = k0 * (k0 + 1) / 2, KS = (k0 + 3) / 4, JT = (k0 + 15) / 16;
     const int D = f.donors, Ptot = D * k0;
     const double* __restrict__ zeros = a.A_none;
 
     for (int e = tid; e < k0 * RS; e += 256) img[e] = 0.0;
-    for (int t = tid; t < L.rows_o; t += 256) {
-        const double* p;
-        if (t < c) p = R.tW + (long)t * R.ldW;
-        else if (t == c) p = R.T + (long)b * R.ldT;
-        else if (t == c + 1) p = R.ty;
-        else p = a.wb_R + (long)(t - c - 2) * a.wb_ldR;
-        rowp[t] = p;
-    }
+    for (int t = tid; t < L.rows_o; t += 256) rowp[t] = gram_other_row(a, R, b, t);
     // what each DMA instruction of this lane reads: instruction I = wave + 4 q carries the 16-byte units 64 I .. 64 I + 63 of
     // its LDS region.  P, Psi, S0: an element offset (P: into the variant's row; Psi: k ldu + column; S0: the column);
     // the other rows: (row << 8) | column, -1 off the rows
@@ -146,11 +125,11 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
 #pragma unroll
         for (int q = 0; q < WF_MAXQ_P; q++) {
             const int I = wave + 4 * q;
-            if (I < L.nP) fused_dma16(Pd + poff[q], Pl + 128 * I);
-            else if (I < L.nP + L.nU) fused_dma16(Ud + poff[q], Ul + 128 * (I - L.nP));
+            if (I < L.nP) gram_dma16(Pd + poff[q], Pl + 128 * I);
+            else if (I < L.nP + L.nU) gram_dma16(Ud + poff[q], Ul + 128 * (I - L.nP));
             else if (I < nPU) {
                 const int col = poff[q];
-                fused_dma16(col >= c0 && start - c0 + col < lim ? S0 + col : zeros, S0l);
+                gram_dma16(col >= c0 && start - c0 + col < lim ? S0 + col : zeros, S0l);
             }
         }
     };
@@ -166,7 +145,7 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
                 const bool in = code >= 0 && col >= c0 && shift + col < lim;
                 const double* src = zeros;
                 if (in) src = rowp[code >> 8] + (shift + col);
-                fused_dma16(src, img + k0 * RS + 128 * I);
+                gram_dma16(src, img + k0 * RS + 128 * I);
             }
         }
     };
@@ -178,24 +157,25 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
         const int k = 4 * ks + lq, lo = k < iw ? k : iw, hi = k < iw ? iw : k;
         pidx[ks] = k < k0 && iw < k0 ? lo * k0 - lo * (lo - 1) / 2 + (hi - lo) : 0;
     }
-    // tiles of this wavefront, as gram_ext_dma_wide_kernel deals them (rows past KT read row 0: never stored)
-    // (strips: `first` is the role of kStripDeal<NTL>; a tile row's fragments start at r_off[row])
-    const int first = (wave + b) & 3;
-    const int ntw = !STRIPS ? (NTILES - first + 3) / 4 : first == 0 ? kStripDeal<NTL>.n[0] : first == 1 ? kStripDeal<NTL>.n[1] : first == 2 ? kStripDeal<NTL>.n[2] : kStripDeal<NTL>.n[3];
+    // tiles of this wavefront, as gram_ext_dma_wide_kernel deals them (gram_common.h; rows past KT read row 0: never stored).
+    // Round-robin: listed here, for the fragment offsets; strips: a tile row's fragments start at r_off[row], and the list
+    // is made behind the loop, for the store alone
+    const int first = gram_wave_first(wave, b);
+    const int ntw = gram_wave_ntiles<NTL, STRIPS>(first);
     int t_i[MAXT], t_j[MAXT], t_ij[MAXT], r_off[NTL];
 #pragma unroll
     for (int i = 0; i < NTL; i++) {
         const int row = 16 * i + l15;
         r_off[i] = (row < KT ? row : 0) * RS + lq;
     }
+    if constexpr (!STRIPS) {
+        gram_wave_tiles<NTL, false>(first, t_ij);
 #pragma unroll
-    for (int t = 0; t < (STRIPS ? 0 : MAXT); t++) {
-        int ti = 0, rem = first + 4 * t < NTILES ? first + 4 * t : 0;
-        while (rem >= NTL - ti) { rem -= NTL - ti; ti++; }
-        t_ij[t] = ti | ((ti + rem) << 8);
-        const int ri = 16 * ti + l15, rj = 16 * (ti + rem) + l15;
-        t_i[t] = (ri < KT ? ri : 0) * RS + lq;
-        t_j[t] = (rj < KT ? rj : 0) * RS + lq;
+        for (int t = 0; t < MAXT; t++) {
+            const int ri = 16 * (t_ij[t] & 255) + l15, rj = 16 * (t_ij[t] >> 8) + l15;
+            t_i[t] = (ri < KT ? ri : 0) * RS + lq;
+            t_j[t] = (rj < KT ? rj : 0) * RS + lq;
+        }
     }
     v4d acc[MAXT];
 #pragma unroll
@@ -289,13 +269,7 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
         int start, end, c0, lim;
         chunk(d, start, end, c0, lim);
         // ---- rotation phase: weights, donor sums, A_d into the image (the other rows of chunk d are in flight) ----
-        if (tid < RS) {
-            // (the product rounded on its own, as the Gram launch rounds it: contracted into 1 + ratio S0 the weight would
-            // differ in its last bit)
-#pragma clang fp contract(off)
-            const double s = ratio * S0l[tid];     // (zeros off the chunk: d = 0)
-            dS[tid] = s / (1.0 + s);
-        }
+        if (tid < RS) dS[tid] = gram_weight(ratio, S0l[tid]);     // (zeros off the chunk: d = 0)
 #pragma unroll
         for (int q = 0; q < WF_PSUM; q++)
             if (tid + 256 * q < npair) psum[q] += Pl[tid + 256 * q];
@@ -379,28 +353,8 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
         double* __restrict__ out = f.Psum + (size_t)split * f.psum_slab + (long)b * f.ldp;
         for (int e = tid; e < npair; e += 256) out[e] = 0.0;
     }
-    double* __restrict__ out = a.wb_Gw + (long)b * KT * KT;
-    if constexpr (STRIPS) {
-        static_for<0, MAXT>([&](auto tc) {
-            constexpr int t = decltype(tc)::value;
-            constexpr int i0 = kStripDeal<NTL>.ti[0][t], i1 = kStripDeal<NTL>.ti[1][t], i2 = kStripDeal<NTL>.ti[2][t], i3 = kStripDeal<NTL>.ti[3][t];
-            constexpr int j0 = kStripDeal<NTL>.tj[0][t], j1 = kStripDeal<NTL>.tj[1][t], j2 = kStripDeal<NTL>.tj[2][t], j3 = kStripDeal<NTL>.tj[3][t];
-            t_ij[t] = (first == 0 ? i0 : first == 1 ? i1 : first == 2 ? i2 : i3) | ((first == 0 ? j0 : first == 1 ? j1 : first == 2 ? j2 : j3) << 8);
-        });
-    }
-#pragma unroll
-    for (int t = 0; t < MAXT; t++) {
-        if (t >= ntw) continue;
-        const int ri = (t_ij[t] & 255) * 16, cj = (t_ij[t] >> 8) * 16;
-#pragma unroll
-        for (int reg = 0; reg < 4; reg++) {
-            const int row = ri + lq + 4 * reg, col = cj + l15;
-            if (row < KT && col < KT) {
-                out[(long)row * KT + col] = acc[t][reg];
-                if (ri != cj) out[(long)col * KT + row] = acc[t][reg];
-            }
-        }
-    }
+    if constexpr (STRIPS) gram_wave_tiles<NTL, true>(first, t_ij);
+    gram_store_tiles(a.wb_Gw + (long)b * KT * KT, KT, t_ij, ntw, acc, lq, l15);
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -438,24 +392,16 @@ int launch_wb_gram_fused(hipStream_t st, const AssembleArgs& a, const WbFusedArg
     const WbFusedLayout L = wb_gram_fused_layout(a.k0, KT, f.ldp);
     const size_t lds = sizeof(double) * (size_t)L.total;
     const bool strips = form("gram_strips", 1) != 0;
-#define CRM_WB_FUSED_AS(NTL, STRIPS)                                                                                  \
-    do {                                                                                                              \
-        CRM_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&wb_gram_fused_kernel<NTL, STRIPS>),                \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-        hipLaunchKernelGGL((wb_gram_fused_kernel<NTL, STRIPS>), dim3(variants), dim3(256), lds, st, a, f, L, KT);     \
-    } while (0)
-#define CRM_WB_FUSED(NTL)                                                                                             \
-    do {                                                                                                              \
-        if (strips) CRM_WB_FUSED_AS(NTL, true);                                                                       \
-        else CRM_WB_FUSED_AS(NTL, false);                                                                             \
-    } while (0)
-    if (ts == 5) CRM_WB_FUSED(5);
-    else if (ts == 6) CRM_WB_FUSED(6);
-    else if (ts == 7) CRM_WB_FUSED(7);   // (config 3: 50 + 3 + 50 rows)
-    else CRM_WB_FUSED(8);
-#undef CRM_WB_FUSED_AS
-#undef CRM_WB_FUSED
-    CRM_HIP(hipGetLastError());
+    // (the limit is raised whatever the size: 79 KB at k0 = 50)
+    auto fused = [&](auto ntl) {
+        constexpr int NTL = decltype(ntl)::value;
+        return strips ? launch_with_lds(wb_gram_fused_kernel<NTL, true>, dim3(variants), dim3(256), lds, st, true, a, f, L, KT)
+                      : launch_with_lds(wb_gram_fused_kernel<NTL, false>, dim3(variants), dim3(256), lds, st, true, a, f, L, KT);
+    };
+    if (ts == 5) CRM_HIP(fused(std::integral_constant<int, 5>{}));
+    else if (ts == 6) CRM_HIP(fused(std::integral_constant<int, 6>{}));
+    else if (ts == 7) CRM_HIP(fused(std::integral_constant<int, 7>{}));   // (config 3: 50 + 3 + 50 rows)
+    else CRM_HIP(fused(std::integral_constant<int, 8>{}));
     return CRM_OK;
 }
 

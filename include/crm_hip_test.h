@@ -134,7 +134,7 @@ int crm_test_rho0_position_blocks(const crm_ctx* ctx, long* blocks);
  * routes) through the skinny one-pass kernel (scan_block.hip: plan_rotations; form "rotation_tails": 0 never, 1 where the
  * batched launch then takes fewer rounds, 2 wherever a problem is eligible).  *launches: the count so far. */
 int crm_test_rotation_tail_launches(const crm_ctx* ctx, long* launches);
-/* Score-statistic Grams of this context's scans that went through a direct-to-LDS kernel (assemble.hip: up to 144 rows
+/* Score-statistic Grams of this context's scans that went through a direct-to-LDS kernel (gram_ext.hip: up to 144 rows
  * with 16-byte-aligned operands, form "gram_staged" = 0) and not through the register-staged one.  *launches: the count so far. */
 int crm_test_gram_dma_launches(const crm_ctx* ctx, long* launches);
 /* (phenotype, variant) tests of this context's scans whose selected fit has no kinship term to speak of --

@@ -1,4 +1,4 @@
-"""The score-statistic Gram for 65 to 144 rows through direct-to-LDS loads (assemble.hip: gram_ext_dma_wide_kernel, 5 to 9
+"""The score-statistic Gram for 65 to 144 rows through direct-to-LDS loads (gram_ext.hip: gram_ext_dma_wide_kernel, 5 to 9
 rows of 16 x 16 tiles dealt to the four wavefronts) against the register-staged kernel (form ``gram_staged`` = 1), at the
 tolerances of test_gpu_edges.py::test_gram_kernel_forms_agree: Q within 1e-11 max(|Q|, tr F), F within 1e-11 max|F|, p
 within 1e-6 relative + 1e-13.  The null fits do not read the Gram: rho* and the other outputs are the same bits.  Every

@@ -5,7 +5,9 @@ the context's route counters after the last scan.  --forms switches kernel forms
 so that the routes the cost models leave to large cohorts are compared too (with CRM_KIN_ROUTE=2 in the environment the
 kinship-structure route is taken wherever a background knows its donors); the counters say whether they were reached.
 Behind the stream come a few cohorts whose kinship term carries the scan's own contexts, Ls = get_L_values(hK, E): the
-stream's mode C hands its Ls over as dense matrices, so nothing in it can reach the pair-product forms.
+stream's mode C hands its Ls over as dense matrices, so nothing in it can reach the pair-product forms.  Then the smallest
+cohorts that reach every instantiation of the score statistic's Gram (GRAM_COHORTS): the stream stops at 144 rows and 128
+contexts, so the staged kernel's grouped form is in nothing before them.
 Last come the cohorts of tests/pinned_cases.py, which sit on the boundaries between the null-fit kernels that the stream
 never leaves the first of: the whole trial table of crm_test_null_fit_probe(on = 2) -- lml, delta, scale, nfev and use_g
 of every (variant, grid point), and the selected index -- of every null-model cohort, once from the plain scan and once
@@ -40,6 +42,41 @@ COUNTERS = ("crm_test_unrelated_donor_blocks", "crm_test_donor_pair_blocks", "cr
 REPORTED = ("crm_test_wb_gram_fused_blocks", "crm_test_side_stream_blocks")
 # donors, cells per donor, contexts, variants (the last one: 67 Gram rows on the unrelated-donor route, the fused Gram's range)
 STRUCTURED = ((6, 120, 7, 37), (12, 90, 20, 130), (7, 60, 5, 37), (4, 70, 32, 10))
+# The Gram of the score statistic (gram_ext.hip, wb_gram_fused.hip) at every template instance, on the shapes of the tests that
+# hold its forms to each other: (mode, donors, cells per donor, contexts, covariates or None for the cohort's own, variants,
+# cohort seed).
+#   "B"  hK alone, tests/test_gpu_edges.py::test_gram_kernel_forms_agree: 1, 3 and 4 tile rows of 16 -- gram_ext_dma_kernel<2> and
+#        <4> (gram_staged=1: gram_ext_kernel<2> and <4>)
+#   "C"  ragged donors and Ls = get_L_values(hK, E), the first row of each tile-row count of tests/test_gpu_gram_wide.py: 2 k0 + c + 2
+#        rows, 5 to 9 tile rows, on the unrelated-donor route (CRM_KIN_ROUTE=2 with kin_fold=2, kin_diag=2, donor_pairs=2), and
+#        its rows of 96 and 99 rows, whose even context counts the fused Gram serves: gram_ext_dma_wide_kernel<5, 6, 7, 9> and
+#        wb_gram_fused_kernel<6, 7, 8> (<5>: the last cohort of STRUCTURED); wb_gram_fused=0: the wide kernel throughout;
+#        gram_strips=0: their round-robin instances; gram_staged=1: gram_ext_kernel<6>, <7>, <9>.  k0 + c + 2 rows on the other routes
+#   "A"  no kinship term, tests/test_gpu_edges.py::test_interaction_scan_with_many_contexts: 162, 232 and 253 rows --
+#        gram_ext_kernel<12, 2>, <15, 4> and <18, 4>
+GRAM_COHORTS = (("B", 8, 30, 5, None, 40, 17), ("B", 6, 40, 37, None, 24, 17), ("B", 10, 20, 60, None, 12, 17),
+                ("C", 5, 70, 31, 1, 13, 965), ("C", 5, 80, 39, 1, 11, 981), ("C", 4, 100, 47, 1, 10, 997), ("C", 4, 120, 54, 3, 9, 1013),
+                ("C", 4, 150, 63, 1, 7, 1029), ("C", 4, 100, 46, 2, 9, 996), ("C", 4, 100, 48, 1, 9, 999),
+                ("A", 8, 100, 100, 60, 5, 141), ("A", 8, 100, 160, 70, 5, 201), ("A", 8, 100, 250, 1, 5, 291))
+
+
+def gram_cohort(mode, donors, cells, k0, c, variants, seed):
+    """(y, E, W, G, keywords of CellRegMap) of one row of GRAM_COHORTS, built as its test builds it."""
+    from test_gpu_gram_wide import _covariates
+    from test_gpu_unrelated_donors import _ragged
+
+    from cellregmap_amd import get_L_values
+    from cellregmap_amd.synth import make_cohort
+
+    if mode == "C":
+        co, keep, G = _ragged(donors, cells, k0, variants, seed)
+        y, E, hK = co.y[keep], co.E[keep], co.hK[keep]
+        return y, E, _covariates(y.size, c, 2 * k0 + c + 2), G, {"Ls": get_L_values(hK, E)}
+    co = make_cohort(donors, cells, k0, variants, seed=seed)
+    if mode == "B":
+        return co.y, co.E, co.W, co.G, {"hK": co.hK}
+    W = np.concatenate([co.W, np.random.default_rng(k0 + c).normal(size=(co.y.size, c - 1))], axis=1) if c > 1 else co.W
+    return co.y, co.E, W, co.G, {}
 
 
 def parse_forms(text):
@@ -80,6 +117,9 @@ def child(lib_path, count, seed, out, forms):
         c = make_cohort(donors, cells, k0, variants, seed=300 + k0)
         G = c.G + 0.05 * np.random.default_rng(k0).normal(size=c.G.shape)     # (general genotypes: the dense path)
         scan(CellRegMap(c.y, c.E, W=c.W, Ls=get_L_values(c.hK, c.E)), G, None)
+    for row in GRAM_COHORTS:
+        y, E, W, G, kw = gram_cohort(*row)
+        scan(CellRegMap(y, E, W=W, **kw), G, None)
     pinned = pinned_tables(lib, _engine._context(0))
     pinned.update(lrt_tables(lib, _engine._context(0)))
     ctx, counters = _engine._context(0), {}
@@ -276,7 +316,7 @@ def main():
         outs.append(np.load(out))
     a, b = outs
     na, nb = json.loads(str(a["notes"])), json.loads(str(b["notes"]))
-    rep = {"other_library": args.other, "this_library": this or "cellregmap_amd/libcrm_hip.so", "problems": args.count, "seed": args.seed, "structured_cohorts": len(STRUCTURED),
+    rep = {"other_library": args.other, "this_library": this or "cellregmap_amd/libcrm_hip.so", "problems": args.count, "seed": args.seed, "structured_cohorts": len(STRUCTURED), "gram_cohorts": len(GRAM_COHORTS),
            "CRM_KIN_ROUTE": os.environ.get("CRM_KIN_ROUTE"), "forms": args.forms, "forms_applied": {"other": na["forms"], "this": nb["forms"]}, "variant_scans": int(a["pv"].size)}
     for k in ARRAYS:
         same = (a[k] == b[k]) | (np.isnan(a[k]) & np.isnan(b[k]))

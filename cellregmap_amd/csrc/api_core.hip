@@ -325,7 +325,7 @@ FormSlot g_forms[] = {{"gram_staged", 0, false}, {"kr_no_tail", 0, false}, {"nul
                       {"kin_diag", 0, false}, {"donor_pairs_rotate", 0, false}, {"rho0_positions", 0, false},
                       {"rotation_tails", 0, false}, {"woodbury_ytY", 0, false},
                       {"wb_block_order", 0, false}, {"block_fused", 0, false}, {"wb_gram_fused", 0, false},
-                      {"gram_strips", 0, false}, {"side_stream", 0, false}};
+                      {"gram_strips", 0, false}, {"side_stream", 0, false}, {"wb_gram_spread", 0, false}};
 std::mutex g_forms_mu;
 }  // namespace
 int form(const char* name, int otherwise) {

@@ -62,6 +62,7 @@ inline long round_up(long x, long m) { return (x + m - 1) / m * m; }
 //   "eigh_one_stage"    1: the constructor's eigen-solver tridiagonalises every grid point on its own (eigh_trd.hip)
 //   "nullfit_exact"     1: null-fit likelihood with IEEE division and one log per spectrum entry
 //   "gram_strips"       0: the 65-144-row direct-to-LDS Gram kernels deal their tiles round-robin (tile_gram.h: kStripDeal)
+//   "wb_gram_spread"    0: the fused unrelated-donor Gram issues a donor's LDS-DMA instructions in a bunch behind each barrier, not among the MFMAs
 //   "side_stream"       0: the fit-independent products of a block stay in the pair stage; 2 / 3: side first / side last (scan_side.hip)
 int form(const char* name, int otherwise);
 

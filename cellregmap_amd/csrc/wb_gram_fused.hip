@@ -23,8 +23,10 @@
 // dma_barrier, wave_ops.h) before the next barrier, so it is in flight during the MFMAs of the phase between the two --
 //     rotation d | wait + barrier | issue P, Psi, S0 of d + 1 | Gram d | wait + barrier | issue the other rows of d + 1 | rotation d + 1 ...
 // (two of everything would not fit two workgroups per CU: 79 KB per workgroup at k0 = 50 as it is), and the second
-// workgroup of the CU fills what is left.  The loop holds no ordinary global load: each would be waited for together with
-// every LDS-DMA in flight.
+// workgroup of the CU fills what is left.  With the form "wb_gram_spread" (the default) the issues do not stand in a bunch
+// behind the barrier but one by one among the MFMAs of the phase that follows it, behind the same barrier as before --
+//     rotation d, the other rows of d piece by piece | wait + barrier | Gram d, P, Psi, S0 of d + 1 piece by piece | wait + barrier | rotation d + 1 ...
+// The loop holds no ordinary global load: each would be waited for together with every LDS-DMA in flight.
 #include <type_traits>
 
 #include "assemble.h"
@@ -35,6 +37,8 @@ namespace crm {
 namespace {
 
 constexpr int WF_MAXQ_P = 10, WF_MAXQ_O = 9, WF_PSUM = 6;   // DMA instructions per wavefront (P, Psi, S0 / other rows); sums per thread
+// what may cross the marks around a spread piece (__builtin_amdgcn_sched_barrier): vector and scalar ALU, LDS -- not a load, not an MFMA
+constexpr int WF_PIN = 0x2 | 0x4 | 0x80 | 0x100 | 0x200;
 constexpr int WF_UW = 56;   // LDS row of Psi_d: a constant, so that the fragment reads carry their offsets as immediates (k0 <= 54)
 
 }  // namespace
@@ -63,8 +67,14 @@ namespace {
 // STRIPS (form "gram_strips", the default): the tiles are dealt in strips (tile_gram.h: kStripDeal) and the Gram phase is
 // written out per role and k-step; false: the round-robin deal, one k-loop for every role.  Every accumulator receives the
 // same operands in the same order either way.
-template <int NTL, bool STRIPS>
+// SPREAD (form "wb_gram_spread", the default; with STRIPS only): a donor's LDS-DMA instructions are issued one by one among
+// the MFMAs of the phase that they used to stand in front of -- P, Psi of d + 1 behind the first MFMA of the Gram's k-steps
+// 0, 1, ... of donor d, the other rows of d behind the MFMA pairs of the rotation's first k-steps of donor d; what is left
+// when the steps run out follows the last step.  Which barrier frees a piece's buffer and which one waits for it does not
+// change, and no accumulator sees another operand.  false: every piece in a bunch behind the barrier, the earlier order.
+template <int NTL, bool STRIPS, bool SPREAD>
 __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(AssembleArgs a, WbFusedArgs f, WbFusedLayout L, int KT) {
+    static_assert(STRIPS || !SPREAD, "the pieces are spread among the k-steps of the strip deal only");
     constexpr int NTILES = NTL * (NTL + 1) / 2, MAXT = (NTILES + 3) / 4;
     constexpr int MAXKS = 14;                      // k-steps of the longest chunk: (k0 + 2) / 4, k0 <= 54
     extern __shared__ __align__(16) double smem[];
@@ -107,7 +117,15 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
 #pragma unroll
     for (int q = 0; q < WF_MAXQ_O; q++) {
         const int u = 64 * (wave + 4 * q) + lane, t = u / (RS / 2), cu = u - t * (RS / 2);
-        ocode[q] = t < L.rows_o ? (t << 8) | (2 * cu) : -1;
+        ocode[q] = t < L.rows_o ? (t << 8) | (2 * cu) : (SPREAD ? 255 : -1);     // (SPREAD: row 0, a column off every chunk)
+    }
+    // SPREAD: P and Psi as unsigned byte offsets from the donor's wave-uniform P_d and Psi_d, so that a piece is its one
+    // instruction on a scalar base; P, Psi and S0 are one LDS region, instruction I at Pl + 128 I
+    const int nPsi = L.nP + L.nU;
+    unsigned pbyte[WF_MAXQ_P];
+    if constexpr (SPREAD) {
+#pragma unroll
+        for (int q = 0; q < WF_MAXQ_P; q++) pbyte[q] = 8u * (unsigned)poff[q];
     }
     // the chunk of donor d: positions [start, end) at columns c0 .., the columns [c0, c0 + lim - start) hold data
     auto chunk = [&](int d, int& start, int& end, int& c0, int& lim) __attribute__((always_inline)) {
@@ -147,6 +165,61 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
                 if (in) src = rowp[code >> 8] + (shift + col);
                 gram_dma16(src, img + k0 * RS + 128 * I);
             }
+        }
+    };
+    // SPREAD: the same pieces one at a time.  The donor that the Gram phase brings in: its P_d and Psi_d, and how many of
+    // the instructions 0 .. nPsi - 1 there are to issue (none behind the last donor)
+    const char* Pnext = nullptr;
+    const char* Unext = nullptr;
+    int n_next = 0;
+    auto set_next = [&](int d) __attribute__((always_inline)) {
+        Pnext = reinterpret_cast<const char*>(f.P + (size_t)d * f.p_slab + (long)b * f.ldp);
+        Unext = reinterpret_cast<const char*>(f.U + (size_t)d * f.u_slab);
+        n_next = d < D ? nPsi : 0;
+    };
+    auto pu_piece = [&](auto qc) __attribute__((always_inline)) {
+        constexpr int q = decltype(qc)::value;
+        if constexpr (q < WF_MAXQ_P) {
+            // (I and the offset pass through empty asm: what follows from them is a few scalar instructions beside the
+            // piece, not a table of flags and 64-bit offsets kept across the donor loop in registers that are not there)
+            int I = wave + 4 * q;
+            asm volatile("" : "+s"(I));
+            if (I < n_next) {
+                unsigned off = pbyte[q];
+                asm volatile("" : "+v"(off));
+                gram_dma16(reinterpret_cast<const double*>((I < L.nP ? Pnext : Unext) + off), Pl + 128 * I);
+            }
+        }
+    };
+    // S0 of chunk d (instruction nPsi, one wavefront's): its lanes choose between two sources, so it goes first in its phase
+    auto s0_piece = [&](int d) __attribute__((always_inline)) {
+        if (d < D && ((nPsi - wave) & 3) == 0) {
+            int start, end, c0, lim;
+            chunk(d, start, end, c0, lim);
+            const int col = 2 * lane;
+            gram_dma16(col >= c0 && start - c0 + col < lim ? R.S0 + (start - c0) + col : zeros, S0l);
+        }
+    };
+    // the other rows: the row's address is looked up (other_row) a step ahead of the piece that adds the chunk's shift
+    // (a lane is on the chunk when its column is one of the o_width from o_c0: one unsigned compare, both sources formed
+    // and one selected -- no branch among the MFMAs)
+    int n_other = 0, o_c0 = 0, o_shift = 0, o_width = 0;
+    auto set_others = [&](int d, bool on) __attribute__((always_inline)) {
+        int start, end, lim;
+        chunk(d, start, end, o_c0, lim);
+        o_shift = start - o_c0;
+        o_width = lim - start;
+        n_other = on ? L.nO : 0;
+    };
+    auto other_row = [&](int q) __attribute__((always_inline)) { return rowp[ocode[q] >> 8]; };
+    auto other_piece = [&](int q, const double* row) __attribute__((always_inline)) {     // (q: a constant once unrolled)
+        int I = wave + 4 * q;
+        asm volatile("" : "+s"(I));
+        if (I < n_other) {
+            const int col = ocode[q] & 255;
+            const double* src = row + (unsigned)(o_shift + col);
+            asm volatile("" : "+v"(src));
+            gram_dma16((unsigned)(col - o_c0) < (unsigned)o_width ? src : zeros, img + k0 * RS + 128 * I);
         }
     };
     // rotation fragments: lane (l15, lq) of k-step ks reads S_d[k = 4 ks + lq, i = 16 w + l15] (pair (0, 0) off the matrix)
@@ -237,7 +310,9 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
             }
         });
         double dk = Dw[0];
-        auto step = [&](int off) __attribute__((always_inline)) {
+        // (SPREAD: k-step ks carries piece ks of P and Psi of the next donor behind its first MFMA, held there against the
+        // scheduler: neither a load nor an MFMA crosses the two marks)
+        auto step = [&](int off, auto kc) __attribute__((always_inline)) {
             static_for<0, NTL>([&](auto jc) {
                 constexpr int j = decltype(jc)::value;
                 if constexpr (kStripDeal<NTL>.is_b(ROLE, j)) {
@@ -248,6 +323,11 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
             static_for<0, NT>([&](auto tc) {
                 constexpr int t = decltype(tc)::value;
                 acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(fr[kStripDeal<NTL>.ti[ROLE][t]], fw[kStripDeal<NTL>.tj[ROLE][t]], acc[t], 0, 0, 0);
+                if constexpr (SPREAD && t == 0) {
+                    __builtin_amdgcn_sched_barrier(WF_PIN);
+                    pu_piece(kc);
+                    __builtin_amdgcn_sched_barrier(WF_PIN);
+                }
                 static_for<0, NTL>([&](auto ic) {
                     constexpr int i = decltype(ic)::value;
                     if constexpr (kStripDeal<NTL>.last_a(ROLE, i) == t) fr[i] = rows[i][off + 4];
@@ -257,17 +337,28 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
         };
         static_for<0, MAXKS>([&](auto kc) {
             constexpr int ks = decltype(kc)::value;
-            if (ks < nks) step(4 * ks);
+            if (ks < nks) step(4 * ks, kc);
+            else if constexpr (SPREAD) pu_piece(kc);     // (more pieces than steps, nks = 0: the rest behind the last step)
         });
     };
 
     __syncthreads();   // (the row pointers are read by the first loads)
-    issue_pus(0);
-    issue_others(0);
+    if constexpr (!SPREAD) {
+        issue_pus(0);
+        issue_others(0);
+    } else {
+        set_next(0);
+        s0_piece(0);
+        static_for<0, WF_MAXQ_P>(pu_piece);
+        set_others(0, true);
+#pragma unroll
+        for (int q = 0; q < WF_MAXQ_O; q++) other_piece(q, other_row(q));
+    }
     dma_barrier();     // (P, Psi, S0 and the other rows of donor 0 have landed)
     for (int d = 0; d < D; d++) {
         int start, end, c0, lim;
         chunk(d, start, end, c0, lim);
+        if constexpr (SPREAD) set_others(d, d > 0);     // (this rotation phase issues the other rows of its own chunk)
         // ---- rotation phase: weights, donor sums, A_d into the image (the other rows of chunk d are in flight) ----
         if (tid < RS) dS[tid] = gram_weight(ratio, S0l[tid]);     // (zeros off the chunk: d = 0)
 #pragma unroll
@@ -306,12 +397,21 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
                     if (1 < KS) frag(1, 1);
 #pragma unroll
                     for (int ks = 0; ks < 16; ks++) {
+                        // (SPREAD: the first pass over the k-steps carries piece ks of the other rows behind the MFMAs of
+                        // step ks, its row looked up ahead of them; the steps that k0 does not have still issue theirs)
+                        const bool piece = SPREAD && th == 0 && ks < WF_MAXQ_O;
+                        const double* row = nullptr;
+                        if (piece) row = other_row(ks);
                         if (ks < KS) {
                             if (ks + 2 < KS) frag(ks + 2, (ks + 2) % 3);
 #pragma unroll
                             for (int t = 0; t < 2; t++)
                                 if (th + t < JT)
                                     cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[ks % 3], bf[ks % 3][t], cr[t], 0, 0, 0);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        if (piece) {
+                            other_piece(ks, row);
                             __builtin_amdgcn_sched_barrier(0);
                         }
                     }
@@ -328,14 +428,23 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
                     }
                 }
             }
+        } else if constexpr (SPREAD) {     // (no rotation of its own -- a variant without a kinship term, wave >= JT: in a bunch)
+#pragma unroll
+            for (int q = 0; q < WF_MAXQ_O; q++) other_piece(q, other_row(q));
         }
         dma_barrier();     // (A_d and the weights are written; P_d, Psi_d and S0 are free; the other rows of chunk d, issued
-                           // behind the previous barrier, are waited for here: nothing else of this wavefront is in flight)
-        if (d + 1 < D) issue_pus(d + 1);
+                           // behind the previous barrier -- SPREAD: in this phase --, are waited for here: nothing else of
+                           // this wavefront is in flight)
+        if constexpr (!SPREAD) {
+            if (d + 1 < D) issue_pus(d + 1);
+        } else {
+            set_next(d + 1);
+            s0_piece(d + 1);
+        }
         // ---- Gram phase ----
         const int nks = (end - start) / 4;
         if constexpr (STRIPS) {
-            if (nks > 0) {
+            if (SPREAD || nks > 0) {     // (SPREAD: a chunk without a step still issues the next donor's pieces)
                 if (first == 0) gram_strips(c0, nks, std::integral_constant<int, 0>{});
                 else if (first == 1) gram_strips(c0, nks, std::integral_constant<int, 1>{});
                 else if (first == 2) gram_strips(c0, nks, std::integral_constant<int, 2>{});
@@ -346,7 +455,9 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
             else gram(c0, nks, std::integral_constant<int, MAXT - 1>{});
         }
         dma_barrier();     // (the image is free; P, Psi and S0 of d + 1 are waited for)
-        if (d + 1 < D) issue_others(d + 1);
+        if constexpr (!SPREAD) {
+            if (d + 1 < D) issue_others(d + 1);
+        }
     }
     // ranges of donors that hold no donor (more splits than ranges): zeros, so that the sum over the splits is the sum
     for (; split < f.splits; split++) {
@@ -392,11 +503,13 @@ int launch_wb_gram_fused(hipStream_t st, const AssembleArgs& a, const WbFusedArg
     const WbFusedLayout L = wb_gram_fused_layout(a.k0, KT, f.ldp);
     const size_t lds = sizeof(double) * (size_t)L.total;
     const bool strips = form("gram_strips", 1) != 0;
+    const bool spread = strips && form("wb_gram_spread", 1) != 0;     // (the round-robin deal keeps its pieces in a bunch)
     // (the limit is raised whatever the size: 79 KB at k0 = 50)
     auto fused = [&](auto ntl) {
         constexpr int NTL = decltype(ntl)::value;
-        return strips ? launch_with_lds(wb_gram_fused_kernel<NTL, true>, dim3(variants), dim3(256), lds, st, true, a, f, L, KT)
-                      : launch_with_lds(wb_gram_fused_kernel<NTL, false>, dim3(variants), dim3(256), lds, st, true, a, f, L, KT);
+        if (spread) return launch_with_lds(wb_gram_fused_kernel<NTL, true, true>, dim3(variants), dim3(256), lds, st, true, a, f, L, KT);
+        return strips ? launch_with_lds(wb_gram_fused_kernel<NTL, true, false>, dim3(variants), dim3(256), lds, st, true, a, f, L, KT)
+                      : launch_with_lds(wb_gram_fused_kernel<NTL, false, false>, dim3(variants), dim3(256), lds, st, true, a, f, L, KT);
     };
     if (ts == 5) CRM_HIP(fused(std::integral_constant<int, 5>{}));
     else if (ts == 6) CRM_HIP(fused(std::integral_constant<int, 6>{}));

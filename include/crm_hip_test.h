@@ -40,6 +40,8 @@ extern "C" {
  *                         place and prepared by the fused pass (default 1; crm_test_fused_blocks)
  *   "wb_gram_fused" 0     unrelated-donor form: the rotated S goes through memory between the rotation launch and the Gram launch,
  *                         not from the pair products straight into the Gram (default 1; crm_test_wb_gram_fused_blocks)
+ *   "wb_gram_spread" 0    that fused launch issues a donor's LDS-DMA instructions in a bunch behind each barrier, not one by one
+ *                         among the MFMAs of the phase that follows (default 1; the same bits either way)
  *   "side_stream" 0 / 2 / 3   unrelated-donor form, one phenotype: the products of a block that do not depend on its fits 0: in
  *                         the pair stage behind the fits, as before; 1 (default): Z2, Z3 and Z1 on a second, lowest-priority
  *                         stream beside the spectrum tails and the null fits, the per-donor pair products on the main stream

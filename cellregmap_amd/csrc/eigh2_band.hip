@@ -357,7 +357,11 @@ bool eigh2_serves(long dim, int batch) {
 int eigh2_to_band(crm_ctx* ctx, EighWork& w) {
     hipStream_t st = ctx->stream;
     const long dim = w.dim, ld = w.ld, dimp = w.dimp;
-    if (dim <= E2_W + 2) return CRM_OK;
+    // (before any way out: the back-transformation reads slab 0 of Vt and tau whether a panel ran or not)
+    CRM_HIP(hipMemsetAsync(w.Vt.ptr, 0, sizeof(double) * w.slab, st));
+    CRM_HIP(hipMemsetAsync(w.tau.ptr, 0, sizeof(double) * ld, st));
+    // up to E2_W + 1 the matrix is a band already; at E2_W + 2 entry (E2_W + 1, 0) lies outside it: one panel, one reflector
+    if (dim <= E2_W + 1) return CRM_OK;
     const int npanels = (int)((dim - 2 - E2_W) / E2_W + 1);     // panels with at least two rows to reflect
     const int maxwg = (int)((dim - E2_W + QR_ROWS - 1) / QR_ROWS);
     const int maxch = (int)((dim - E2_W + CH_ROWS - 1) / CH_ROWS);
@@ -386,9 +390,7 @@ int eigh2_to_band(crm_ctx* ctx, EighWork& w) {
     CRM_HIP(hipMemsetAsync(abort_flag, 0, sizeof(int) * 16, st));
     CRM_HIP(hipMemsetAsync(bars, 0, sizeof(unsigned) * 2 * (size_t)npanels, st));
     CRM_HIP(hipMemsetAsync(base + oPX, 0, sizeof(double) * 2 * ((size_t)128 * ld + 256), st));
-    CRM_HIP(hipMemsetAsync(w.Vt.ptr, 0, sizeof(double) * w.slab, st));
     CRM_HIP(hipMemsetAsync(w.Vc.ptr, 0, sizeof(double) * w.slab, st));
-    CRM_HIP(hipMemsetAsync(w.tau.ptr, 0, sizeof(double) * ld, st));
     double* A = w.A.as<double>();
     double* Vc = w.Vc.as<double>();
     double* Wb = base + oW;

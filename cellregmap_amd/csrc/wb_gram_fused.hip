@@ -40,6 +40,7 @@ constexpr int WF_MAXQ_P = 10, WF_MAXQ_O = 9, WF_PSUM = 6;   // DMA instructions 
 // what may cross the marks around a spread piece (__builtin_amdgcn_sched_barrier): vector and scalar ALU, LDS -- not a load, not an MFMA
 constexpr int WF_PIN = 0x2 | 0x4 | 0x80 | 0x100 | 0x200;
 constexpr int WF_UW = 56;   // LDS row of Psi_d: a constant, so that the fragment reads carry their offsets as immediates (k0 <= 54)
+constexpr int WF_MAXKS = 14;   // k-steps of the rotation and of the longest chunk: (k0 + 2) / 4, k0 <= 54
 
 }  // namespace
 
@@ -76,7 +77,7 @@ template <int NTL, bool STRIPS, bool SPREAD>
 __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(AssembleArgs a, WbFusedArgs f, WbFusedLayout L, int KT) {
     static_assert(STRIPS || !SPREAD, "the pieces are spread among the k-steps of the strip deal only");
     constexpr int NTILES = NTL * (NTL + 1) / 2, MAXT = (NTILES + 3) / 4;
-    constexpr int MAXKS = 14;                      // k-steps of the longest chunk: (k0 + 2) / 4, k0 <= 54
+    constexpr int MAXKS = WF_MAXKS;
     extern __shared__ __align__(16) double smem[];
     double* const img = smem;                      // [KT][RS] (+ what the last DMA instruction overshoots)
     double* const Pl = smem + L.off_P;             // the donor's pair products of this variant
@@ -117,7 +118,10 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
 #pragma unroll
     for (int q = 0; q < WF_MAXQ_O; q++) {
         const int u = 64 * (wave + 4 * q) + lane, t = u / (RS / 2), cu = u - t * (RS / 2);
-        ocode[q] = t < L.rows_o ? (t << 8) | (2 * cu) : (SPREAD ? 255 : -1);     // (SPREAD: row 0, a column off every chunk)
+        // (SPREAD: not the row but the place of its pointer in LDS, in bytes from the start, other_row; off the rows: row 0, a
+        // column off every chunk)
+        if constexpr (SPREAD) ocode[q] = t < L.rows_o ? ((8 * (L.off_rp + t)) << 8) | (2 * cu) : ((8 * L.off_rp) << 8) | 255;
+        else ocode[q] = t < L.rows_o ? (t << 8) | (2 * cu) : -1;
     }
     // SPREAD: P and Psi as unsigned byte offsets from the donor's wave-uniform P_d and Psi_d, so that a piece is its one
     // instruction on a scalar base; P, Psi and S0 are one LDS region, instruction I at Pl + 128 I
@@ -211,7 +215,13 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
         o_width = lim - start;
         n_other = on ? L.nO : 0;
     };
-    auto other_row = [&](int q) __attribute__((always_inline)) { return rowp[ocode[q] >> 8]; };
+    // (the shift is written out: left to the compiler it is taken out of the donor loop, and the nine addresses that it
+    // yields are kept across the loop in vector registers that are not there)
+    auto other_row = [&](int q) __attribute__((always_inline)) {
+        unsigned at;
+        asm volatile("v_lshrrev_b32 %0, 8, %1" : "=v"(at) : "v"(ocode[q]));
+        return *reinterpret_cast<const double* const*>(reinterpret_cast<const char*>(smem) + at);
+    };
     auto other_piece = [&](int q, const double* row) __attribute__((always_inline)) {     // (q: a constant once unrolled)
         int I = wave + 4 * q;
         asm volatile("" : "+s"(I));
@@ -224,12 +234,13 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
     };
     // rotation fragments: lane (l15, lq) of k-step ks reads S_d[k = 4 ks + lq, i = 16 w + l15] (pair (0, 0) off the matrix)
     const int iw = 16 * wave + l15;
-    int pidx[16];
+    int pidx[MAXKS];
 #pragma unroll
-    for (int ks = 0; ks < 16; ks++) {
+    for (int ks = 0; ks < MAXKS; ks++) {
         const int k = 4 * ks + lq, lo = k < iw ? k : iw, hi = k < iw ? iw : k;
         pidx[ks] = k < k0 && iw < k0 ? lo * k0 - lo * (lo - 1) / 2 + (hi - lo) : 0;
     }
+    const unsigned st_base = 8u * (unsigned)((16 * wave + lq) * RS + l15 + 2);     // (the rotation's stores: byte offset of A_d[16 wave + lq, l15] in the image)
     // tiles of this wavefront, as gram_ext_dma_wide_kernel deals them (gram_common.h; rows past KT read row 0: never stored).
     // Round-robin: listed here, for the fragment offsets; strips: a tile row's fragments start at r_off[row], and the list
     // is made behind the loop, for the store alone
@@ -366,9 +377,13 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
             if (tid + 256 * q < npair) psum[q] += Pl[tid + 256 * q];
         if (d + 1 == D || d + 1 == (split + 1) * per) {
             double* __restrict__ out = f.Psum + (size_t)split * f.psum_slab + (long)b * f.ldp;
+            // (the thread's index through empty asm: the offsets and the masks of these stores, which a split runs once, are
+            // then formed here and not kept across the donor loop)
+            int at = tid;
+            asm volatile("" : "+v"(at));
 #pragma unroll
             for (int q = 0; q < WF_PSUM; q++)
-                if (tid + 256 * q < npair) { out[tid + 256 * q] = psum[q]; psum[q] = 0.0; }
+                if (at + 256 * q < npair) { out[at + 256 * q] = psum[q]; psum[q] = 0.0; }
             split++;
         }
         if (has_A && wave < JT) {
@@ -377,57 +392,88 @@ __global__ __launch_bounds__(256, NTL <= 7 ? 2 : 1) void wb_gram_fused_kernel(As
             const double* __restrict__ ub = Ul + uo;
             // column of A_d[., j]: j + 2, or -- past the chunk's end -- columns 0, 1 of the next chunk
             const int jcut = end - k0 * d;
-            // (two column tiles at a time: four would hold 32 more registers beside the Gram's accumulators)
+            // The counts that the passes compare with pass through empty asm in every donor's turn: a compare with a
+            // constant is then one scalar compare beside its branch.  Left loop-invariant, each of them (some forty: a k-step
+            // there is, a k-step two ahead, a column tile, a row or a column below k0) is formed once in front of the donor
+            // loop as a mask in two scalar registers and kept across it -- a hundred scalar registers more than there are,
+            // kept in the lanes of vector registers and read back lane by lane among the MFMAs.
+            // (the k-step count twice over, ksn for "this step exists" and ksf for "a fragment two steps ahead": of one count
+            // the compiler keeps the second compare of step ks as a mask for the first of step ks + 2, six scalar instructions
+            // a step where two compares and two branches do)
+            int ksn = KS, ksf = KS, jtn = JT, k0n = k0, rsn = RS;
+            asm volatile("" : "+s"(ksn), "+s"(ksf), "+s"(jtn), "+s"(k0n), "+s"(rsn));
+            // Where a pass stores: A_d[16 wave + lq + 4 reg, 16 tile + l15] at st + 32 RS reg + 128 tile bytes of the image, the
+            // two columns past jcut 8 (jcut + 2) bytes back.  One address from in front of the loop (through empty asm as
+            // well: the sixteen that follow from it were kept across the loop, in vector registers that are not there) and
+            // scalar offsets; a row or a column is below k0 when lq or l15 is below a scalar.
+            unsigned st = st_base;
+            asm volatile("" : "+v"(st));
+            const int rows_below = k0n - 16 * wave;
+            // One pass: NT (1 or 2) column tiles from tile TH on, every k-step (two tiles at a time: four would hold 32 more
+            // registers beside the Gram's accumulators).  NT is the pass's own, so no MFMA stands behind a branch of its own
+            // and an accumulator is one register tuple from its first MFMA (on zeros, an inline constant) to its store.
+            auto rotate = [&](auto th_tag, auto nt_tag) __attribute__((always_inline)) {
+                constexpr int TH = decltype(th_tag)::value, NT = decltype(nt_tag)::value;
+                v4d cr[NT];
 #pragma unroll
-            for (int th = 0; th < 4; th += 2) {
-                if (th < JT) {
-                    v4d cr[2];
+                for (int t = 0; t < NT; t++) cr[t] = (v4d){0.0, 0.0, 0.0, 0.0};
+                // the fragments of k-step ks + 2 are read before the MFMAs of ks are issued (two MFMAs a step: one step
+                // ahead would leave a read 128 cycles to land), and no further (the scheduler would pull every read up front)
+                double af[3], bf[3][NT];
+                auto frag = [&](int ks, int slot) __attribute__((always_inline)) {
+                    af[slot] = Pl[pidx[ks]];
 #pragma unroll
-                    for (int t = 0; t < 2; t++) cr[t] = (v4d){0.0, 0.0, 0.0, 0.0};
-                    // the fragments of k-step ks + 2 are read before the MFMAs of ks are issued (two MFMAs a step: one step
-                    // ahead would leave a read 128 cycles to land), and no further (the scheduler would pull every read up front)
-                    double af[3], bf[3][2];
-                    auto frag = [&](int ks, int slot) __attribute__((always_inline)) {
-                        af[slot] = Pl[pidx[ks]];
+                    for (int t = 0; t < NT; t++) bf[slot][t] = ub[4 * ks * UW + 16 * (TH + t)];
+                };
+                frag(0, 0);
+                if (1 < ksf) frag(1, 1);
 #pragma unroll
-                        for (int t = 0; t < 2; t++)
-                            if (th + t < JT) bf[slot][t] = ub[4 * ks * UW + 16 * (th + t)];
-                    };
-                    frag(0, 0);
-                    if (1 < KS) frag(1, 1);
+                for (int ks = 0; ks < MAXKS; ks++) {
+                    if (ks > 0 && ks >= ksn) break;     // (there is a first k-step: k0 >= 1)
+                    // (SPREAD: the first pass over the k-steps carries piece ks of the other rows behind the MFMAs of
+                    // step ks, its row looked up ahead of them)
+                    const bool piece = SPREAD && TH == 0 && ks < WF_MAXQ_O;
+                    const double* row = nullptr;
+                    if (piece) row = other_row(ks);
+                    if (ks + 2 < MAXKS && ks + 2 < ksf) frag(ks + 2, (ks + 2) % 3);
 #pragma unroll
-                    for (int ks = 0; ks < 16; ks++) {
-                        // (SPREAD: the first pass over the k-steps carries piece ks of the other rows behind the MFMAs of
-                        // step ks, its row looked up ahead of them; the steps that k0 does not have still issue theirs)
-                        const bool piece = SPREAD && th == 0 && ks < WF_MAXQ_O;
-                        const double* row = nullptr;
-                        if (piece) row = other_row(ks);
-                        if (ks < KS) {
-                            if (ks + 2 < KS) frag(ks + 2, (ks + 2) % 3);
-#pragma unroll
-                            for (int t = 0; t < 2; t++)
-                                if (th + t < JT)
-                                    cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[ks % 3], bf[ks % 3][t], cr[t], 0, 0, 0);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        if (piece) {
-                            other_piece(ks, row);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    }
-#pragma unroll
-                    for (int reg = 0; reg < 4; reg++) {
-                        const int r = 16 * wave + lq + 4 * reg;
-                        if (r < k0) {
-#pragma unroll
-                            for (int t = 0; t < 2; t++) {
-                                const int j = 16 * (th + t) + l15;
-                                if (th + t < JT && j < k0) img[r * RS + (j < jcut ? j + 2 : j - jcut)] = cr[t][reg];
-                            }
-                        }
+                    for (int t = 0; t < NT; t++)
+                        cr[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(af[ks % 3], bf[ks % 3][t], cr[t], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (piece) {
+                        other_piece(ks, row);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
                 }
-            }
+                if constexpr (SPREAD && TH == 0) {     // (the pieces of the k-steps that k0 does not have follow the last step)
+                    if (ksn < WF_MAXQ_O) {
+#pragma unroll
+                        for (int q = 1; q < WF_MAXQ_O; q++)
+                            if (q >= ksn) other_piece(q, other_row(q));
+                    }
+                }
+                bool below[NT];
+                unsigned back[NT];
+#pragma unroll
+                for (int t = 0; t < NT; t++) {
+                    below[t] = l15 < k0n - 16 * (TH + t);
+                    back[t] = l15 < jcut - 16 * (TH + t) ? 0u : 8u * (unsigned)(jcut + 2);
+                }
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    if (lq < rows_below - 4 * reg) {
+                        const unsigned at = st + (unsigned)(32 * reg) * (unsigned)rsn;
+#pragma unroll
+                        for (int t = 0; t < NT; t++)
+                            if (below[t])
+                                *reinterpret_cast<double*>(reinterpret_cast<char*>(smem) + (at - back[t] + 128u * (TH + t))) = cr[t][reg];
+                    }
+                }
+            };
+            if (jtn >= 2) rotate(std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
+            else rotate(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
+            if (jtn >= 4) rotate(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{});
+            else if (jtn == 3) rotate(std::integral_constant<int, 2>{}, std::integral_constant<int, 1>{});
         } else if constexpr (SPREAD) {     // (no rotation of its own -- a variant without a kinship term, wave >= JT: in a bunch)
 #pragma unroll
             for (int q = 0; q < WF_MAXQ_O; q++) other_piece(q, other_row(q));
@@ -489,7 +535,7 @@ bool wb_gram_fused_serves(const AssembleArgs& a, const WbFusedArgs& f, int nrho)
             return false;
     }
     const WbFusedLayout L = wb_gram_fused_layout(k0, KT, f.ldp);
-    return L.nP + L.nU + 1 <= 4 * WF_MAXQ_P && L.nO <= 4 * WF_MAXQ_O && L.RS <= 64 && k0 * (k0 + 1) / 2 <= 256 * WF_PSUM &&
+    return k0 + 2 <= 4 * WF_MAXKS && L.nP + L.nU + 1 <= 4 * WF_MAXQ_P && L.nO <= 4 * WF_MAXQ_O && L.RS <= 64 && k0 * (k0 + 1) / 2 <= 256 * WF_PSUM &&
            sizeof(double) * (size_t)L.total <= 160 * 1024;
 }
 

@@ -470,7 +470,7 @@ class GenotypePanel:
         assert G.ndim == 2
         # a block of columns of a row-major matrix (rows a fixed number of doubles apart) goes to the library as it lies --
         # the C-ABI takes the leading dimension -- so that a large host matrix can be uploaded in column chunks without
-        # a host copy of each (``CellRegMap._scan_streamed``); anything else is made contiguous first
+        # a host copy of each (``CellRegMap._panel_walk``); anything else is made contiguous first
         ldg = G.shape[1]
         if not G.flags.c_contiguous:
             if (G.shape[0] > 1 and G.shape[1] > 0 and G.strides[1] == G.itemsize and G.strides[0] % G.itemsize == 0
@@ -581,9 +581,44 @@ def _release_gene(lib, handle, _background_kept_alive):
     lib.crm_gene_destroy(handle)
 
 
+def _warn_if_saturated(crm):
+    """Say so when the background of the bound phenotype ``crm`` with its covariates and a variant spans all cells.  The
+    warning points at the first caller outside this module: the user's call, whichever driver and helpers did the binding."""
+    n, ncov = crm.n_samples, crm._ncov
+    rmax = max(crm._bg.rank(i) for i in range(len(crm._rho1)))
+    if rmax + ncov + 1 >= n:
+        import sys
+        import warnings
+
+        level, frame = 1, sys._getframe()
+        while frame.f_back is not None and frame.f_globals is globals():
+            level, frame = level + 1, frame.f_back
+        warnings.warn(f"saturated model: the background covariance has rank {rmax} and with the {ncov} covariate "
+                      f"column(s) and the variant it spans all {n} cells; the reference's likelihood then divides "
+                      "rounding noise by delta and its results (and these) are not reproducible to the usual "
+                      "tolerances (scan_interaction_info flags such variants)", RuntimeWarning, stacklevel=level)
+
+
+def _create_genes(like, ys, batch):
+    """Bind the phenotypes ``ys`` on the cohort of the bound gene ``like`` -- its background, covariates and contexts --
+    through ``crm_gene_create_batch``, ``batch`` at a time: yields every batch as (position of its first phenotype, handles)."""
+    lib = _lib.load()
+    for a in range(0, len(ys), batch):
+        part = ys[a:a + batch]
+        for y in part:
+            if not np.all(np.isfinite(y)):
+                raise ValueError("There are non-finite values in the outcome.")
+        Y = np.ascontiguousarray(np.stack(part, axis=1), dtype=np.float64)
+        handles = (ctypes.c_void_p * len(part))()
+        _lib.check(lib.crm_gene_create_batch(like, _lib.ptr(Y), Y.shape[1], len(part), handles))
+        yield a, [ctypes.c_void_p(h) for h in handles]
+
+
 _PROGRESS_CB = ctypes.CFUNCTYPE(None, ctypes.c_long, ctypes.c_long, ctypes.c_void_p)
 
 
+#: the variance components every scan reports: rho*, e2, g2 and eps2 of the reference's ``info`` (_cellregmap.py:439-440)
+_INFO_KEYS = ("rho1", "e2", "g2", "eps2")
 #: per-test outputs of the association scans' ``effects=True`` (crm_scan_association_effects), in the C-ABI's order
 _EFFECT_KEYS = ("beta", "beta_se", "alt_delta", "alt_scale", "log_pvalue", "effect_status")
 EFFECT_OK, EFFECT_G_IN_SPAN_W, EFFECT_NO_FIT, EFFECT_NON_FINITE = 0, 1, 2, 3   # include/crm_hip.h: CRM_EFFECT_*
@@ -594,8 +629,16 @@ def _effect_arrays(shape):
     return {k: np.empty(shape, np.int32 if k == "effect_status" else float) for k in _EFFECT_KEYS}
 
 
+def _null_info(null):
+    """The six numbers {rho1, e2, g2, eps2, lml, delta} of a fitted null model as the scans report them: ``(info, lml,
+    delta)``.  ``null``: one row (``info`` then holds arrays of one entry, lml and delta are scalars) or an (ng, 6) table of
+    one row per phenotype ((ng,) arrays throughout)."""
+    rows = null.T
+    return {key: np.array(rows[j], float, ndmin=1) for j, key in enumerate(_INFO_KEYS)}, rows[4].copy(), rows[5].copy()
+
+
 def _stream_chunk():
-    """Variants per chunk of the streamed scan of a host matrix (``CellRegMap._scan_streamed``): two blocks of the
+    """Variants per chunk of the streamed scan of a host matrix (``CellRegMap._panel_walk``): two blocks of the
     scan's largest block size; CELLREGMAP_AMD_STREAM_CHUNK overrides (0: never stream)."""
     import os
 
@@ -837,14 +880,7 @@ class CellRegMap:
             ncov = Wb.shape[1]
         self._gene = h
         self._ncov = ncov
-        n, rmax = self.n_samples, max(self._bg.rank(i) for i in range(len(self._rho1)))
-        if rmax + ncov + 1 >= n:
-            import warnings
-
-            warnings.warn(f"saturated model: the background covariance has rank {rmax} and with the {ncov} covariate "
-                          f"column(s) and the variant it spans all {n} cells; the reference's likelihood then divides "
-                          "rounding noise by delta and its results (and these) are not reproducible to the usual "
-                          "tolerances (scan_interaction_info flags such variants)", RuntimeWarning, stacklevel=3)
+        _warn_if_saturated(self)
         # (the background object rides along so that it outlives the gene whatever the collection order)
         self._gene_fin = weakref.finalize(self, _release_gene, lib, h, self._bg)
         return h
@@ -867,7 +903,7 @@ class CellRegMap:
         """Per-variant GxC score test.  ``G`` is n x p (array-like) or a ``GenotypePanel``; an array goes to the device as
         ``GenotypePanel(G, groups=groups)`` would take it (``"auto"``: donor-constant genotypes are found and scanned on
         the donor-collapsed path; ``None``: kept dense), in column chunks beside the scan when it has many variants
-        (``_scan_streamed``).
+        (``_panel_walk``).
         ``progress``: the reference always shows a tqdm bar over the variants (:340) and so does this method by
         default (it advances block by block); ``False`` silences it (or CELLREGMAP_AMD_PROGRESS=0 in the
         environment), a callable ``(done, total)`` replaces it.
@@ -885,29 +921,30 @@ class CellRegMap:
         exact = _exact_pvalues(pvalue)
         lib = _lib.load()
         k0 = self._E0.shape[1]
-        if not isinstance(G, GenotypePanel) and np.asarray(G).ndim == 2 and np.asarray(G).shape[1] == 0:
-            # no variants: the reference's loop body never runs (_cellregmap.py:340)
-            if np.asarray(G).shape[0] != self.n_samples:
-                raise ValueError(f"G must be {self.n_samples} x p, got {np.asarray(G).shape}")
-            empty = {key: np.empty(0) for key in ("rho1", "e2", "g2", "eps2")}
+        p, walk = self._panel_walk(G, groups)
+        out = {key: np.empty(p) for key in ("pv",) + _INFO_KEYS}
+        if exact:
+            out["log_pvalue"], out["pvalue_status"] = np.empty(p), np.empty(p, np.int32)
+        stats = {}
+        if return_stats:
+            stats = {"Q": np.empty(p), "lml": np.empty(p), "delta": np.empty(p), "scale": np.empty(p),
+                     "lambda": np.empty((p, k0)), "F": np.empty((p, k0, k0))}
+        if p:   # (no variants: the reference's loop body never runs (_cellregmap.py:340) -- nothing is bound, checked or called)
+            gene = self._bind_gene()
+            iE, iG = _permutation(idx_E, self.n_samples), _permutation(idx_G, self.n_samples)
+            entry = lib.crm_scan_interaction_tail if exact else lib.crm_scan_interaction
+            arrays = {**out, **stats}
+            order = ("pv",) + _INFO_KEYS + ("Q", "lml", "delta", "scale", "lambda", "F")    # (the C-ABI's order)
             if exact:
-                empty.update(log_pvalue=np.empty(0), pvalue_status=np.empty(0, np.int32))
-            if return_stats:
-                return np.empty(0), empty, {"Q": np.empty(0), "lml": np.empty(0), "delta": np.empty(0),
-                                            "scale": np.empty(0), "lambda": np.empty((0, k0)),
-                                            "F": np.empty((0, k0, k0))}
-            return np.empty(0), empty
-        if not isinstance(G, GenotypePanel):
-            G = np.asarray(G, float)
-            if G.ndim == 2 and G.shape[0] == self.n_samples and G.shape[1] >= 2 * _stream_chunk() > 0:
-                return self._scan_streamed(lib, G, k0, idx_E, idx_G, return_stats, progress, groups, exact)
-        panel = self._panel(G, groups)
-        n, p = panel.shape
-        gene = self._bind_gene()
+                order += ("log_pvalue", "pvalue_status")
 
-        iE, iG = _permutation(idx_E, n), _permutation(idx_G, n)
-        with _progress(self._device, progress, p):
-            return self._scan_interaction(lib, gene, panel, p, k0, iE, iG, return_stats, exact)
+            def scan(panel, count, j0):
+                _lib.check(entry(gene, panel.handle, 0, count, _lib.ptr(iE), _lib.ptr(iG),
+                                 *[_lib.ptr(arrays[key][j0:j0 + count]) if key in arrays else None for key in order]))
+
+            walk(progress, scan)
+        info = {key: out[key] for key in out if key != "pv"}
+        return (out["pv"], info, stats) if return_stats else (out["pv"], info)
 
     def _streamed_panels(self, G, groups="auto"):
         """Generator over ``(first, last, panel)``: the column chunks of a host matrix, uploaded one after the other by a
@@ -952,56 +989,56 @@ class CellRegMap:
                     pass
             worker.join()
 
-    _one_bar = staticmethod(_one_bar)
+    def _panel_walk(self, G, groups="auto", null_on_empty=False):
+        """The walk of a single-phenotype scan over its variants: ``(p, walk)`` with ``walk(progress, scan)`` making one
+        ``scan(panel, count, j0)`` -- one library call over the first ``count`` variants of ``panel`` into the slices
+        ``[j0:j0 + count]`` of the caller's outputs -- per panel it goes over.
 
-    def _scan_streamed(self, lib, G, k0, idx_E, idx_G, return_stats, progress, groups="auto", exact=False):
-        """A host matrix of many variants goes to the device in column chunks from a second thread while this one scans
-        the chunks that have arrived: PCIe beside the scan, and device memory for three chunks instead of the whole
-        matrix.  Every chunk is scanned as a panel of its own: where the chunk bounds fall on the block bounds of the
-        one-panel scan (the default 8192-variant chunks at the BASELINE configurations: blocks of 4096) the results are
-        identical bit for bit, otherwise -- other block sizes, donor structure found in some chunks only -- they agree
-        to the rounding of a different summation order."""
-        n, p = G.shape
-        iE, iG = _permutation(idx_E, n), _permutation(idx_G, n)
-        progress, bar = self._one_bar(progress, p)
-        panels = self._streamed_panels(G, groups)
-        parts = []
-        try:
-            gene = self._bind_gene()      # (beside the first chunk's upload)
-            for j0, j1, panel in panels:
-                with _progress(self._device, progress, j1 - j0, offset=j0, grand_total=p):
-                    parts.append(self._scan_interaction(lib, gene, panel, j1 - j0, k0, iE, iG, return_stats, exact))
-                panel = None      # (released before the next chunk is taken from the queue)
-        finally:
-            panels.close()
-            if bar is not None:
-                bar.close()
-        pv = np.concatenate([part[0] for part in parts])
-        info = {key: np.concatenate([part[1][key] for part in parts]) for key in parts[0][1]}
-        if return_stats:
-            return pv, info, {key: np.concatenate([part[2][key] for part in parts]) for key in parts[0][2]}
-        return pv, info
+        A ``GenotypePanel`` or a host matrix of few variants is one resident panel (``_panel``, built here) and one call.  A
+        host matrix of many variants goes to the device in column chunks from a second thread while this one scans the
+        chunks that have arrived (``_streamed_panels``): PCIe beside the scan, and device memory for three chunks instead of
+        the whole matrix, under ONE bar.  Every chunk is scanned as a panel of its own: where the chunk bounds fall on the
+        block bounds of the one-panel scan (the default 8192-variant chunks at the BASELINE configurations: blocks of 4096)
+        the results are identical bit for bit, otherwise -- other block sizes, donor structure found in some chunks only --
+        they agree to the rounding of a different summation order.  The uploading thread starts with the walk, so whatever
+        the caller binds between this call and ``walk`` is bound before any upload has begun.
 
-    def _scan_interaction(self, lib, gene, panel, p, k0, iE, iG, return_stats, exact=False):
-        out = {k: np.empty(p) for k in ("pv", "rho1", "e2", "g2", "eps2")}
-        extra = {}
-        if return_stats:
-            extra = {"Q": np.empty(p), "lml": np.empty(p), "delta": np.empty(p), "scale": np.empty(p),
-                     "lambda": np.empty((p, k0)), "F": np.empty((p, k0, k0))}
-        args = (gene, panel.handle, 0, p, _lib.ptr(iE), _lib.ptr(iG),
-                _lib.ptr(out["pv"]), _lib.ptr(out["rho1"]), _lib.ptr(out["e2"]), _lib.ptr(out["g2"]),
-                _lib.ptr(out["eps2"]), _lib.ptr(extra.get("Q")), _lib.ptr(extra.get("lml")),
-                _lib.ptr(extra.get("delta")), _lib.ptr(extra.get("scale")), _lib.ptr(extra.get("lambda")),
-                _lib.ptr(extra.get("F")))
-        if exact:
-            out["log_pvalue"], out["pvalue_status"] = np.empty(p), np.empty(p, np.int32)
-            _lib.check(lib.crm_scan_interaction_tail(*args, _lib.ptr(out["log_pvalue"]), _lib.ptr(out["pvalue_status"])))
-        else:
-            _lib.check(lib.crm_scan_interaction(*args))
-        info = {key: out[key] for key in ("rho1", "e2", "g2", "eps2", "log_pvalue", "pvalue_status") if key in out}
-        if return_stats:
-            return out["pv"], info, extra
-        return out["pv"], info
+        A host matrix without columns: p = 0, and ``walk`` is not to be called -- or, with ``null_on_empty``, makes one
+        call with ``count = 0`` on a one-column panel of zeros (the scans that fit and report a null model whatever p)."""
+        host, p = None, None
+        if not isinstance(G, GenotypePanel):
+            G = np.asarray(G, float)
+            if G.ndim == 2 and G.shape[1] == 0:
+                p = 0
+                if not null_on_empty:
+                    if G.shape[0] != self.n_samples:
+                        raise ValueError(f"G must be {self.n_samples} x p, got {G.shape}")
+                    return 0, None
+                G = np.zeros((G.shape[0], 1))
+            elif G.ndim == 2 and G.shape[0] == self.n_samples and G.shape[1] >= 2 * _stream_chunk() > 0:
+                host, p = G, G.shape[1]
+        if host is None:
+            panel = self._panel(G, groups)
+            p = panel.shape[1] if p is None else p
+
+        def walk(progress, scan):
+            if host is None:
+                with _progress(self._device, progress, p):
+                    scan(panel, p, 0)
+                return
+            progress, bar = _one_bar(progress, p)
+            chunks = self._streamed_panels(host, groups)
+            try:
+                for j0, j1, chunk in chunks:
+                    with _progress(self._device, progress, j1 - j0, offset=j0, grand_total=p):
+                        scan(chunk, j1 - j0, j0)
+                    chunk = None      # (released before the next chunk is taken from the queue)
+            finally:
+                chunks.close()
+                if bar is not None:
+                    bar.close()
+
+        return p, walk
 
     def scan_interaction_permutations(self, G, idx_E_list=None, idx_G_list=None, return_Q=False, pvalue="reference"):
         """``scan_interaction(G, idx_E=perm)`` for a whole list of permutations in one call -- the loop of the reference's
@@ -1034,7 +1071,7 @@ class CellRegMap:
         gene = self._bind_gene()
         pv = np.empty((nb, p))
         Q = np.empty((nb, p)) if return_Q else None
-        info = {k: np.empty(p) for k in ("rho1", "e2", "g2", "eps2")}
+        info = {k: np.empty(p) for k in _INFO_KEYS}
         if exact:
             info.update(log_pvalue=np.empty((nb, p)), pvalue_status=np.empty((nb, p), np.int32))
         if p > 0:
@@ -1081,15 +1118,14 @@ class CellRegMap:
     # -- association scans (_cellregmap.py:246-314) --------------------------------------------------
     def _scan_association(self, G, fast, return_stats=False, progress=None, effects=False):
         lib = _lib.load()
-        p_user = None
-        if not isinstance(G, GenotypePanel) and np.asarray(G).ndim == 2 and np.asarray(G).shape[1] == 0:
-            # no SNPs: the null model is still fitted and reported (_cellregmap.py:250-266)
-            p_user = 0
-            G = np.zeros((np.asarray(G).shape[0], 1))
-        null = np.empty(6)
+        # (no SNPs: the null model is still fitted and reported (_cellregmap.py:250-266); a host matrix of many SNPs is
+        # streamed, and every chunk's call fits the null model again -- the same eleven fits, the same numbers)
+        p, walk = self._panel_walk(G, null_on_empty=True)
+        gene = self._bind_gene()
+        pv, alt, null = np.empty(p), np.empty(p), np.empty(6)
+        eff = _effect_arrays((p,)) if effects else None
 
-        def scan(gene, panel, count, pv, alt, eff, j0=0):
-            # one library call over the first ``count`` variants of ``panel`` into the slices starting at ``j0``
+        def scan(panel, count, j0):
             j1 = j0 + count
             if eff is None:
                 _lib.check(lib.crm_scan_association(gene, panel.handle, 0, count, int(bool(fast)), _lib.ptr(pv[j0:j1]),
@@ -1099,47 +1135,10 @@ class CellRegMap:
                                                             _lib.ptr(pv[j0:j1]), _lib.ptr(alt[j0:j1]), _lib.ptr(null),
                                                             *[_lib.ptr(eff[k][j0:j1]) for k in _EFFECT_KEYS]))
 
-        if p_user is None and not isinstance(G, GenotypePanel):
-            G = np.asarray(G, float)
-            if G.ndim == 2 and G.shape[0] == self.n_samples and G.shape[1] >= 2 * _stream_chunk() > 0:
-                # a host matrix of many SNPs: column chunks uploaded beside the scan (``_streamed_panels``); every call
-                # fits the null model again -- the same eleven fits, the same numbers
-                p = G.shape[1]
-                pv, alt = np.empty(p), np.empty(p)
-                eff = _effect_arrays((p,)) if effects else None
-                progress, bar = self._one_bar(progress, p)
-                panels = self._streamed_panels(G)
-                try:
-                    gene = self._bind_gene()
-                    for j0, j1, panel in panels:
-                        with _progress(self._device, progress, j1 - j0, offset=j0, grand_total=p):
-                            scan(gene, panel, j1 - j0, pv, alt, eff, j0)
-                finally:
-                    panels.close()
-                    if bar is not None:
-                        bar.close()
-                return self._association_result(pv, alt, null, return_stats, eff)
-        panel = self._panel(G)
-        n, p = panel.shape
-        if p_user is not None:
-            p = p_user
-        gene = self._bind_gene()
-        pv = np.empty(p)
-        alt = np.empty(p)
-        eff = _effect_arrays((p,)) if effects else None
-        with _progress(self._device, progress, p):
-            scan(gene, panel, p, pv, alt, eff)
-        return self._association_result(pv, alt, null, return_stats, eff)
-
-    @staticmethod
-    def _association_result(pv, alt, null, return_stats, eff=None):
-        info = {"rho1": np.asarray([null[0]], float), "e2": np.asarray([null[1]], float),
-                "g2": np.asarray([null[2]], float), "eps2": np.asarray([null[3]], float)}
+        walk(progress, scan)
+        info, null_lml, null_delta = _null_info(null)
         if return_stats or eff is not None:
-            stats = {"alt_lml": alt, "null_lml": null[4], "null_delta": null[5]}
-            if eff is not None:
-                stats.update(eff)
-            return pv, info, stats
+            return pv, info, {"alt_lml": alt, "null_lml": null_lml, "null_delta": null_delta, **(eff or {})}
         return pv, info
 
     def scan_association(self, G, return_stats: bool = False, progress=None, effects: bool = False):
@@ -1200,20 +1199,12 @@ class CellRegMap:
         candidate lies in the span of ``[W, C, g]`` -- a constant context column -- or g in the span of ``[W, C]``:
         ``pv = 1 - eps``, beta and beta_se NaN; ``CONTEXT_NO_FIT``; ``CONTEXT_NON_FINITE``).  ``return_stats=True`` adds
         ``null_lml`` and ``null_delta`` (per variant), ``alt_lml`` (p x k), ``gene_null_lml`` and ``gene_null_delta``."""
-        out, null = self._scan_contexts(G, contexts, fast, progress, joint=False)
-        info = {"rho1": np.asarray([null[0]], float), "e2": np.asarray([null[1]], float),
-                "g2": np.asarray([null[2]], float), "eps2": np.asarray([null[3]], float),
-                "beta": out["beta"], "beta_se": out["beta_se"], "log_pvalue": out["log_pvalue"], "status": out["status"]}
-        if return_stats:
-            info.update(null_lml=out["null_lml"], null_delta=out["null_delta"], alt_lml=out["alt_lml"],
-                        gene_null_lml=null[4], gene_null_delta=null[5])
-        return out["pv"], info
+        return self._scan_contexts(G, contexts, fast, return_stats, progress, joint=False)
 
-    def _scan_contexts(self, G, contexts, fast, progress, joint):
+    def _scan_contexts(self, G, contexts, fast, return_stats, progress, joint):
         """The body of ``scan_interaction_contexts`` (``joint=False``: crm_scan_interaction_contexts, every result p x k)
         and ``scan_interaction_contexts_joint`` (crm_scan_interaction_contexts_joint: one test per variant): argument
-        checks, the kept gene binding, streaming of host matrices, the empty panel.  Returns (arrays by name, the six
-        numbers of the gene-level null)."""
+        checks, the kept gene binding, the outputs in the order of the C-ABI, ``(pv, info)``."""
         lib = _lib.load()
         C = self._E0 if contexts is None else np.asarray(contexts, float)
         if C.ndim != 2 or C.shape[0] != self.n_samples or C.shape[1] < 1:
@@ -1221,54 +1212,37 @@ class CellRegMap:
         if not (np.all(np.isfinite(C)) and np.all(np.isfinite(self._W)) and np.all(np.isfinite(self._y))):
             raise ValueError("There are non-finite values in the outcome, the covariates or the contexts.")
         k = C.shape[1]
-        p_user = None
-        if not isinstance(G, GenotypePanel) and np.asarray(G).ndim == 2 and np.asarray(G).shape[1] == 0:
-            p_user = 0   # no variants: the gene-level null is still fitted and reported
-            G = np.zeros((np.asarray(G).shape[0], 1))
-        chunks = None
-        if not isinstance(G, GenotypePanel):
-            G = np.asarray(G, float)
-            if p_user is None and G.ndim == 2 and G.shape[0] == self.n_samples and G.shape[1] >= 2 * _stream_chunk() > 0:
-                chunks, p = self._streamed_panels(G), G.shape[1]
-        if chunks is None:
-            panel = self._panel(G)
-            p = panel.shape[1] if p_user is None else p_user
+        p, walk = self._panel_walk(G, null_on_empty=True)   # (no variants: the gene-level null is still fitted and reported)
         if joint:
             out = {"pv": np.empty(p), "log_pvalue": np.empty(p), "alt_lml": np.empty(p), "dof": np.empty(p, np.int32),
                    "beta": np.empty((p, k)), "beta_se": np.empty((p, k)), "dropped": np.empty((p, k), np.int32),
                    "status": np.empty(p, np.int32)}
             order = ("pv", "log_pvalue", "alt_lml", "dof", "beta", "beta_se", "dropped", "status", "null_lml", "null_delta")
+            reported = ("dof", "log_pvalue", "beta", "beta_se", "dropped", "status")
             entry = lib.crm_scan_interaction_contexts_joint
         else:
             out = {key: np.empty((p, k)) for key in ("pv", "alt_lml", "beta", "beta_se", "log_pvalue")}
             out["status"] = np.empty((p, k), np.int32)
             order = ("pv", "alt_lml", "beta", "beta_se", "log_pvalue", "status", "null_lml", "null_delta")
+            reported = ("beta", "beta_se", "log_pvalue", "status")
             entry = lib.crm_scan_interaction_contexts
         out["null_lml"], out["null_delta"] = np.empty(p), np.empty(p)
         null = np.empty(6)
+        gene = self._bind_context_gene(C, contexts is None)
 
-        def scan(gene, panel, count, j0=0):
+        def scan(panel, count, j0):
             _lib.check(entry(gene, panel.handle, 0, count, int(bool(fast)),
                              *[_lib.ptr(out[key][j0:j0 + count]) for key in order], _lib.ptr(null)))
 
-        try:
-            gene = self._bind_context_gene(C, contexts is None)
-            if chunks is None:
-                with _progress(self._device, progress, p):
-                    scan(gene, panel, p)
-            else:
-                progress, bar = self._one_bar(progress, p)
-                try:
-                    for j0, j1, panel in chunks:
-                        with _progress(self._device, progress, j1 - j0, offset=j0, grand_total=p):
-                            scan(gene, panel, j1 - j0, j0)
-                finally:
-                    if bar is not None:
-                        bar.close()
-        finally:
-            if chunks is not None:
-                chunks.close()
-        return out, null
+        walk(progress, scan)
+        if joint:
+            out["dropped"] = out["dropped"].astype(bool)
+        info, gene_null_lml, gene_null_delta = _null_info(null)
+        info.update({key: out[key] for key in reported})
+        if return_stats:
+            info.update(null_lml=out["null_lml"], null_delta=out["null_delta"], alt_lml=out["alt_lml"],
+                        gene_null_lml=gene_null_lml, gene_null_delta=gene_null_delta)
+        return out["pv"], info
 
     def scan_interaction_contexts_joint(self, G, contexts=None, fast: bool = True, return_stats: bool = False, progress=False):
         """Is there any fixed-effect GxC at a variant?  Per variant g ONE likelihood-ratio test of all k columns
@@ -1292,15 +1266,7 @@ class CellRegMap:
         ``CONTEXT_NON_FINITE``), and p x k ``beta`` (the joint coefficient of ``g * C_j``), ``beta_se`` (both NaN for a
         dropped candidate) and ``dropped`` (bool).  ``return_stats=True`` adds ``null_lml``, ``null_delta`` and
         ``alt_lml`` (per variant), ``gene_null_lml`` and ``gene_null_delta``."""
-        out, null = self._scan_contexts(G, contexts, fast, progress, joint=True)
-        info = {"rho1": np.asarray([null[0]], float), "e2": np.asarray([null[1]], float),
-                "g2": np.asarray([null[2]], float), "eps2": np.asarray([null[3]], float),
-                "dof": out["dof"], "log_pvalue": out["log_pvalue"], "beta": out["beta"], "beta_se": out["beta_se"],
-                "dropped": out["dropped"].astype(bool), "status": out["status"]}
-        if return_stats:
-            info.update(null_lml=out["null_lml"], null_delta=out["null_delta"], alt_lml=out["alt_lml"],
-                        gene_null_lml=null[4], gene_null_delta=null[5])
-        return out["pv"], info
+        return self._scan_contexts(G, contexts, fast, return_stats, progress, joint=True)
 
     # -- effect sizes (_cellregmap.py:137-244) -----------------------------------------------------
     def _lmm_fit(self, bg, M):
@@ -1381,26 +1347,19 @@ class CellRegMap:
 def _bind_genes_like(first, others, batch=64):
     """Bind the phenotypes of ``others`` (same cohort as ``first``, which is bound) through ``crm_gene_create_batch``."""
     lib = _lib.load()
-    for a in range(0, len(others), batch):
-        part = others[a:a + batch]
-        for c in part:
-            if not np.all(np.isfinite(c._y)):
-                raise ValueError("There are non-finite values in the outcome.")
-        Y = np.ascontiguousarray(np.stack([c._y for c in part], axis=1), dtype=np.float64)
-        handles = (ctypes.c_void_p * len(part))()
-        _lib.check(lib.crm_gene_create_batch(first._gene, _lib.ptr(Y), Y.shape[1], len(part), handles))
-        n, rmax = first.n_samples, max(first._bg.rank(i) for i in range(len(first._rho1)))
-        for c, h in zip(part, handles):
-            c._gene = ctypes.c_void_p(h)
-            c._ncov = first._ncov
-            c._gene_fin = weakref.finalize(c, _release_gene, lib, c._gene, c._bg)
-        if rmax + first._ncov + 1 >= n:
-            import warnings
+    for a, handles in _create_genes(first._gene, [c._y for c in others], batch):
+        for c, h in zip(others[a:], handles):
+            c._gene, c._ncov = h, first._ncov
+            c._gene_fin = weakref.finalize(c, _release_gene, lib, h, c._bg)
+        _warn_if_saturated(first)
 
-            warnings.warn(f"saturated model: the background covariance has rank {rmax} and with the {first._ncov} covariate "
-                          f"column(s) and the variant it spans all {n} cells; the reference's likelihood then divides "
-                          "rounding noise by delta and its results (and these) are not reproducible to the usual "
-                          "tolerances (scan_interaction_info flags such variants)", RuntimeWarning, stacklevel=3)
+
+def _bind_cohort(crms, first):
+    """The gene handles of the phenotypes ``crms`` of one cohort (``_shared_cohort``).  They share W and E: the first one's
+    copies on the device serve the others, whose rotations are taken in batches."""
+    first._bind_gene()
+    _bind_genes_like(first, [c for c in crms[1:] if c._gene is None and c._bg is first._bg])
+    return [c._bind_gene(like=first) for c in crms]
 
 
 def _cis_runs(cis_index, ngenes, p, dense_limit=1 << 26):
@@ -1558,80 +1517,58 @@ def scan_interaction_many(crms, G, idx_E=None, idx_G=None, cis_index=None, progr
     crms, first = _shared_cohort(crms)
     panel = first._panel(G)
     n, p = panel.shape
-    # (the phenotypes share W and E -- checked above: the first one's copies on the device serve the others, and their
-    # rotations are taken in batches)
-    first._bind_gene()
-    _bind_genes_like(first, [c for c in crms[1:] if c._gene is None and c._bg is first._bg])
-    genes = [c._bind_gene(like=first) for c in crms]
+    genes = _bind_cohort(crms, first)
     ng = len(genes)
 
     iE, iG = _permutation(idx_E, n), _permutation(idx_G, n)
-    keys = ("pv", "rho1", "e2", "g2", "eps2") + (("log_pvalue", "pvalue_status") if exact else ())
-    dtypes = {"pvalue_status": np.int32}
+    # the outputs as _walk_runs takes them: (name, per variant and context?, dtype), in the order of the C-ABI's
+    keys = tuple((name, False, float) for name in ("pv",) + _INFO_KEYS)
+    if exact:
+        keys += (("log_pvalue", False, float), ("pvalue_status", False, np.int32))
 
-    def tail(out):   # the two extra outputs of the _tail entry points
-        return (_lib.ptr(out["log_pvalue"]), _lib.ptr(out["pvalue_status"])) if exact else ()
+    def outputs(out):   # (the Q .. F slots of the one-phenotype call, the Q slot of the many-phenotype call, stay empty)
+        return [_lib.ptr(out[name]) for name, _, _ in keys[:5]], [_lib.ptr(out[name]) for name, _, _ in keys[5:]]
 
-    if cis_index is not None:
-        columns, runs = _cis_runs(cis_index, ng, p)
+    if cis_index is not None and panel.n_groups is not None:
         # Donor-level panels (the collapsed path): what the phenotypes of a run share is small there, and a call per run of
         # constant phenotypes -- 128 short runs for 64 overlapping windows -- costs more than it saves.  Contiguous windows
         # are then scanned window by window on the resident panel, one call per phenotype (measured at BASELINE config 3,
         # 1024-variant windows: 206 000 against 147 000 variant-tests/s; general genotypes keep the runs, where the shared
         # rotations are what a block costs: 36 000 against 28 500).
-        contiguous = all(c.size == 0 or (c.size == int(c[-1] - c[0]) + 1 and np.all(np.diff(c) == 1)) for c in columns)
-        if contiguous and panel.n_groups is not None:
-            res = {k: [] for k in keys}
+        columns, _ = _cis_runs(cis_index, ng, p)
+        if all(c.size == 0 or (c.size == int(c[-1] - c[0]) + 1 and np.all(np.diff(c) == 1)) for c in columns):
+            res = {name: [] for name, _, _ in keys}
             tested = int(sum(c.size for c in columns))
             progress, bar = _one_bar(progress, tested)
             seen = 0
+            entry = lib.crm_scan_interaction_tail if exact else lib.crm_scan_interaction
             try:
                 for i, cols in enumerate(columns):
-                    out = {k: np.empty(cols.size, dtypes.get(k, float)) for k in keys}
+                    out = {name: np.empty(cols.size, dtype) for name, _, dtype in keys}
                     if cols.size:
-                        scan = lib.crm_scan_interaction_tail if exact else lib.crm_scan_interaction
-                        _lib.check(scan(genes[i], panel.handle, int(cols[0]), int(cols.size), _lib.ptr(iE), _lib.ptr(iG),
-                                        *[_lib.ptr(out[k]) for k in keys[:5]], None, None, None, None, None, None, *tail(out)))
+                        five, tail = outputs(out)
+                        _lib.check(entry(genes[i], panel.handle, int(cols[0]), int(cols.size), _lib.ptr(iE), _lib.ptr(iG),
+                                         *five, None, None, None, None, None, None, *tail))
                     seen += cols.size
                     if callable(progress):
                         progress(seen, tested)
-                    for k in keys:
-                        res[k].append(out[k])
+                    for name in res:
+                        res[name].append(out[name])
             finally:
                 if bar is not None:
                     bar.close()
-            return res["pv"], {k: res[k] for k in keys[1:]}
-        full = {k: [np.full(p, -1 if k == "pvalue_status" else np.nan, dtypes.get(k, float)) if columns[i].size else None
-                    for i in range(ng)] for k in keys}
-        tested = int(sum(count for _, count, _ in runs))
-        progress, bar = _one_bar(progress, tested)   # one bar over all runs
-        seen = 0
-        try:
-            for a, count, active in runs:
-                handles = (ctypes.c_void_p * len(active))(*[genes[i].value for i in active])
-                out = {k: np.empty((len(active), count), dtypes.get(k, float)) for k in keys}
-                scan = lib.crm_scan_interaction_multi_tail if exact else lib.crm_scan_interaction_multi
-                with _progress(first._device, progress, count, offset=seen, grand_total=tested):
-                    _lib.check(scan(handles, len(active), panel.handle, a, count, _lib.ptr(iE), _lib.ptr(iG),
-                                    *[_lib.ptr(out[k]) for k in keys[:5]], None, *tail(out)))
-                seen += count
-                for row, i in enumerate(active):
-                    for k in keys:
-                        full[k][i][a:a + count] = out[k][row]
-        finally:
-            if bar is not None:
-                bar.close()
-        res = {k: [full[k][i][columns[i]] if columns[i].size else np.empty(0, dtypes.get(k, float)) for i in range(ng)]
-               for k in keys}
-        return res["pv"], {k: res[k] for k in keys[1:]}
-    handles = (ctypes.c_void_p * ng)(*[g.value for g in genes])
-    out = {k: np.empty((ng, p), dtypes.get(k, float)) for k in keys}
-    scan = lib.crm_scan_interaction_multi_tail if exact else lib.crm_scan_interaction_multi
-    with _progress(first._device, progress, p):
-        _lib.check(scan(handles, ng, panel.handle, 0, p, _lib.ptr(iE), _lib.ptr(iG),
-                        _lib.ptr(out["pv"]), _lib.ptr(out["rho1"]), _lib.ptr(out["e2"]),
-                        _lib.ptr(out["g2"]), _lib.ptr(out["eps2"]), None, *tail(out)))
-    return out["pv"], {k: out[k] for k in keys[1:]}
+            return res.pop("pv"), res
+
+    entry = lib.crm_scan_interaction_multi_tail if exact else lib.crm_scan_interaction_multi
+
+    def scan(idx, a, count, out, offset, total, progress):
+        hs = (ctypes.c_void_p * len(idx))(*[genes[i].value for i in idx])
+        five, tail = outputs(out)
+        with _progress(first._device, progress, count, offset=offset, grand_total=total):
+            _lib.check(entry(hs, len(idx), panel.handle, a, count, _lib.ptr(iE), _lib.ptr(iG), *five, None, *tail))
+
+    out = _walk_runs(keys, ng, p, 0, cis_index, progress, scan)
+    return out.pop("pv"), out
 
 
 def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=False, progress=False):
@@ -1657,17 +1594,14 @@ def scan_association_many(crms, G, cis_index=None, fast=False, return_stats=Fals
     crms, first = _shared_cohort(crms)
     panel = first._panel(G)
     n, p = panel.shape
-    first._bind_gene()
-    _bind_genes_like(first, [c for c in crms[1:] if c._gene is None and c._bg is first._bg])
-    genes = [c._bind_gene(like=first) for c in crms]
+    genes = _bind_cohort(crms, first)
     ng = len(genes)
     handles = (ctypes.c_void_p * ng)(*[g.value for g in genes])
     null = np.empty((ng, 6))
     _lib.check(lib.crm_association_null_multi(handles, ng, _lib.ptr(null)))
-    info = {"rho1": null[:, 0].copy(), "e2": null[:, 1].copy(), "g2": null[:, 2].copy(), "eps2": null[:, 3].copy()}
+    info, null_lml, null_delta = _null_info(null)
     if return_stats:
-        info["null_lml"] = null[:, 4].copy()
-        info["null_delta"] = null[:, 5].copy()
+        info.update(null_lml=null_lml, null_delta=null_delta)
     fast = int(bool(fast))
 
     # the outputs as _walk_runs takes them: (name, per variant and context?, dtype), in the order of the C-ABI's
@@ -1702,16 +1636,9 @@ def _bind_context_genes(crms, C, own, batch=64):
     if like is None:
         like = have[0] = crms[0]._bind_context_gene(C, own)
     todo = [i for i, h in enumerate(have) if h is None]
-    for a in range(0, len(todo), batch):
-        part = todo[a:a + batch]
-        for i in part:
-            if not np.all(np.isfinite(crms[i]._y)):
-                raise ValueError("There are non-finite values in the outcome.")
-        Y = np.ascontiguousarray(np.stack([crms[i]._y for i in part], axis=1), dtype=np.float64)
-        handles = (ctypes.c_void_p * len(part))()
-        _lib.check(lib.crm_gene_create_batch(like, _lib.ptr(Y), Y.shape[1], len(part), handles))
-        for i, h in zip(part, handles):
-            c, h = crms[i], ctypes.c_void_p(h)
+    for a, handles in _create_genes(like, [crms[i]._y for i in todo], batch):
+        for i, h in zip(todo[a:], handles):
+            c = crms[i]
             kept = getattr(c, "_context_gene", None)
             if kept is not None:
                 kept[2]()       # (release the binding it replaces)
@@ -1750,7 +1677,7 @@ def _scan_contexts_many(crms, G, cis_index, contexts, fast, return_stats, progre
     handles = (ctypes.c_void_p * ng)(*[g.value for g in genes])
     null = np.empty((ng, 6))
     _lib.check(lib.crm_association_null_multi(handles, ng, _lib.ptr(null)))
-    info = {"rho1": null[:, 0].copy(), "e2": null[:, 1].copy(), "g2": null[:, 2].copy(), "eps2": null[:, 3].copy()}
+    info, gene_null_lml, gene_null_delta = _null_info(null)
     keys = _CONTEXT_MANY_KEYS[bool(joint)]
     entry = lib.crm_scan_interaction_contexts_joint_multi if joint else lib.crm_scan_interaction_contexts_multi
     fast = int(bool(fast))
@@ -1770,7 +1697,7 @@ def _scan_contexts_many(crms, G, cis_index, contexts, fast, return_stats, progre
     stats = {name: out.pop(name) for name in ("null_lml", "null_delta", "alt_lml")}
     info.update(out)
     if return_stats:
-        info.update(stats, gene_null_lml=null[:, 4].copy(), gene_null_delta=null[:, 5].copy())
+        info.update(stats, gene_null_lml=gene_null_lml, gene_null_delta=gene_null_delta)
     return pv, info
 
 
@@ -1802,17 +1729,22 @@ def scan_interaction_contexts_joint_many(crms, G, cis_index=None, contexts=None,
     return _scan_contexts_many(crms, G, cis_index, contexts, fast, return_stats, progress, joint=True)
 
 
-def _context_many_crms(Y, E, W, E1, E2, hK, device):
+def _model(y, E, W, E1, E2, hK, device, Ls=None, background=None):
+    """The model of ``run_interaction`` and the wrappers that share its defaults (_cellregmap.py:547-587): ``E1`` and ``E2``
+    default to ``E``, a kinship factor enters as ``get_L_values(hK, E2)`` -- unless ``Ls``, that list of a model of the same
+    cohort built before, is handed over."""
+    if Ls is None and hK is not None:
+        Ls = get_L_values(hK, E if E2 is None else E2)
+    return CellRegMap(y=y, E=E, W=W, E1=E if E1 is None else E1, Ls=Ls, device=device, background=background)
+
+
+def _models(Y, E, W, E1, E2, hK, device):
+    """``_model`` for the columns of ``Y`` (n x genes): one list ``Ls`` and one background, the first one's."""
     Y = np.asarray(Y, float)
     if Y.ndim != 2:
         raise ValueError("Y must be n x genes")
-    if E1 is None:
-        E1 = E
-    if E2 is None:
-        E2 = E
-    Ls = None if hK is None else get_L_values(hK, E2)
-    first = CellRegMap(y=Y[:, 0], E=E, W=W, E1=E1, Ls=Ls, device=device)
-    return [first] + [CellRegMap(y=Y[:, i], E=E, W=W, E1=E1, Ls=Ls, device=device, background=first._bg)
+    first = _model(Y[:, 0], E, W, E1, E2, hK, device)
+    return [first] + [_model(Y[:, i], E, W, E1, E2, hK, device, Ls=first._Ls, background=first._bg)
                       for i in range(1, Y.shape[1])]
 
 
@@ -1821,7 +1753,7 @@ def run_interaction_contexts_many(Y, E, G, W=None, E1=None, E2=None, hK=None, *,
     """``run_interaction_contexts`` for the columns of ``Y`` (n x genes) with one background decomposition, one genotype
     upload and shared per-variant work: ``scan_interaction_contexts_many`` -- ``(pv (genes, p, k), info)``, lists with
     ``cis_index``."""
-    crms = _context_many_crms(Y, E, W, E1, E2, hK, device)
+    crms = _models(Y, E, W, E1, E2, hK, device)
     return scan_interaction_contexts_many(crms, G, cis_index=cis_index, contexts=contexts, fast=fast)
 
 
@@ -1829,7 +1761,7 @@ def run_interaction_contexts_joint_many(Y, E, G, W=None, E1=None, E2=None, hK=No
                                         fast=True, device=0):
     """``run_interaction_contexts_joint`` for the columns of ``Y`` (n x genes): ``scan_interaction_contexts_joint_many`` --
     ``(pv (genes, p), info)``, lists with ``cis_index``."""
-    crms = _context_many_crms(Y, E, W, E1, E2, hK, device)
+    crms = _models(Y, E, W, E1, E2, hK, device)
     return scan_interaction_contexts_joint_many(crms, G, cis_index=cis_index, contexts=contexts, fast=fast)
 
 
@@ -1865,7 +1797,7 @@ def scan_interaction_resumable(crm, G, checkpoint, idx_E=None, idx_G=None, chunk
     G = np.asarray(G)
     n, p = G.shape
     chunk = max(1, int(chunk))
-    keys = ("pv", "rho1", "e2", "g2", "eps2")
+    keys = ("pv",) + _INFO_KEYS
     cols = sorted({0, p // 2, p - 1}) if p else []
     h = hashlib.blake2b(digest_size=16)      # (not _digest: the file must mean the same on a host without xxhash)
     for a in (crm._y, crm._E0, crm._W, [n, p, chunk], -1.0 if idx_E is None else idx_E, -1.0 if idx_G is None else idx_G,
@@ -1918,18 +1850,7 @@ def run_interaction_many(Y, E, G, W=None, E1=None, E2=None, hK=None, *, cis_inde
     ``cis_index`` (see ``scan_interaction_many``) lists of per-phenotype arrays over each phenotype's own
     variants.  ``pvalue``: as in ``CellRegMap.scan_interaction``."""
     _exact_pvalues(pvalue)
-    Y = np.asarray(Y, float)
-    if Y.ndim != 2:
-        raise ValueError("Y must be n x genes")
-    if E1 is None:
-        E1 = E
-    if E2 is None:
-        E2 = E
-    Ls = None if hK is None else get_L_values(hK, E2)
-    first = CellRegMap(y=Y[:, 0], E=E, W=W, E1=E1, Ls=Ls, device=device)
-    crms = [first] + [CellRegMap(y=Y[:, i], E=E, W=W, E1=E1, Ls=Ls, device=device, background=first._bg)
-                      for i in range(1, Y.shape[1])]
-    return scan_interaction_many(crms, G, cis_index=cis_index, pvalue=pvalue)
+    return scan_interaction_many(_models(Y, E, W, E1, E2, hK, device), G, cis_index=cis_index, pvalue=pvalue)
 
 
 def lrt_pvalues(null_lml, alt_lmls, dof=1):
@@ -1949,42 +1870,20 @@ def run_interaction(y, E, G, W=None, E1=None, E2=None, hK=None, idx_G=None, *, d
     As in the reference, ``idx_G`` is forwarded positionally and therefore lands in
     ``scan_interaction``'s ``idx_E`` slot (:586 vs :318): it permutes the rows of the
     contexts inside the test direction, not the genotypes."""
-    if E1 is None:
-        E1 = E
-    if E2 is None:
-        E2 = E
-    if hK is None:
-        Ls = None
-    else:
-        Ls = get_L_values(hK, E2)
     _exact_pvalues(pvalue)
-    crm = CellRegMap(y=y, E=E, W=W, E1=E1, Ls=Ls, device=device)
-    pv = crm.scan_interaction(G, idx_G, pvalue=pvalue)
-    return pv
+    return _model(y, E, W, E1, E2, hK, device).scan_interaction(G, idx_G, pvalue=pvalue)
 
 
 def run_interaction_contexts(y, E, G, W=None, E1=None, E2=None, hK=None, *, contexts=None, fast=True, device=0):
     """Per-context fixed-effect GxC tests with the model of ``run_interaction`` (same ``E1`` / ``E2`` / ``hK`` defaults):
     ``CellRegMap.scan_interaction_contexts(G, contexts=contexts, fast=fast)`` -- ``(pv (p x k), info)``."""
-    if E1 is None:
-        E1 = E
-    if E2 is None:
-        E2 = E
-    Ls = None if hK is None else get_L_values(hK, E2)
-    crm = CellRegMap(y=y, E=E, W=W, E1=E1, Ls=Ls, device=device)
-    return crm.scan_interaction_contexts(G, contexts=contexts, fast=fast)
+    return _model(y, E, W, E1, E2, hK, device).scan_interaction_contexts(G, contexts=contexts, fast=fast)
 
 
 def run_interaction_contexts_joint(y, E, G, W=None, E1=None, E2=None, hK=None, *, contexts=None, fast=True, device=0):
     """Joint fixed-effect GxC test with the model of ``run_interaction`` (same ``E1`` / ``E2`` / ``hK`` defaults):
     ``CellRegMap.scan_interaction_contexts_joint(G, contexts=contexts, fast=fast)`` -- ``(pv (p,), info)``."""
-    if E1 is None:
-        E1 = E
-    if E2 is None:
-        E2 = E
-    Ls = None if hK is None else get_L_values(hK, E2)
-    crm = CellRegMap(y=y, E=E, W=W, E1=E1, Ls=Ls, device=device)
-    return crm.scan_interaction_contexts_joint(G, contexts=contexts, fast=fast)
+    return _model(y, E, W, E1, E2, hK, device).scan_interaction_contexts_joint(G, contexts=contexts, fast=fast)
 
 
 def run_association(y, W, E, G, hK=None, *, device=0, effects=False):
@@ -1992,21 +1891,13 @@ def run_association(y, W, E, G, hK=None, *, device=0, effects=False):
     (:498) binds ``W`` to the contexts slot and ``E`` to the covariates slot; kept as is.
     ``effects=True``: ``(pv, info, stats)`` of ``CellRegMap.scan_association(G, effects=True)`` -- with that binding beta
     is the coefficient of g beside the columns of ``E``."""
-    crm = CellRegMap(y, W, E, hK=hK, device=device)
-    if effects:
-        return crm.scan_association(G, effects=True)
-    pv = crm.scan_association(G)
-    return pv
+    return CellRegMap(y, W, E, hK=hK, device=device).scan_association(G, effects=effects)
 
 
 def run_association_fast(y, W, E, G, hK=None, *, device=0, effects=False):
     """Fast association test (_cellregmap.py:502-531); same positional binding (:529).  ``effects`` as in
     ``run_association``."""
-    crm = CellRegMap(y, W, E, hK=hK, device=device)
-    if effects:
-        return crm.scan_association_fast(G, effects=True)
-    pv = crm.scan_association_fast(G)
-    return pv
+    return CellRegMap(y, W, E, hK=hK, device=device).scan_association_fast(G, effects=effects)
 
 
 def compute_maf(X):
@@ -2035,10 +1926,7 @@ def compute_maf(X):
 
 def estimate_betas(y, W, E, G, maf=None, E1=None, E2=None, hK=None, *, device=0):
     """Effect sizes (_cellregmap.py:640-682): persistent effects and cell-level GxC effects."""
-    E1 = E if E1 is None else E1
-    E2 = E if E2 is None else E2
-    Ls = None if hK is None else get_L_values(hK, E2)
-    crm = CellRegMap(y=y, E=E, W=W, E1=E1, Ls=Ls, device=device, background=_DEFERRED)
+    crm = _model(y, E, W, E1, E2, hK, device, background=_DEFERRED)
     if maf is None:
         maf = compute_maf(G)
     return crm.predict_interaction(G, maf)
@@ -2214,11 +2102,9 @@ def estimate_betas_many(Y, W, E, G, maf=None, E1=None, E2=None, hK=None, *, pair
     Y = np.asarray(Y, float)
     if Y.ndim != 2:
         raise ValueError("Y must be n x phenotypes")
-    E1 = E if E1 is None else E1
-    E2 = E if E2 is None else E2
-    Ls = None if hK is None else get_L_values(hK, E2)
-    crms = [CellRegMap(y=Y[:, i], E=E, W=W, E1=E1, Ls=Ls, device=device, background=_DEFERRED)
-            for i in range(Y.shape[1])]
+    crms = []
+    for i in range(Y.shape[1]):   # (one list Ls for all of them: predict_interaction_many tells by identity that they share it)
+        crms.append(_model(Y[:, i], E, W, E1, E2, hK, device, Ls=crms[0]._Ls if crms else None, background=_DEFERRED))
     if maf is None:
         maf = compute_maf(G)
     return predict_interaction_many(crms, G, maf, pairs=pairs, return_info=return_info)

@@ -887,7 +887,7 @@ def test_kinship_structure_route_equals_the_direct_route(hook, shape, monkeypatc
 @pytest.mark.parametrize("genotypes", ["general", "donor-constant"])
 def test_streamed_scan_of_a_host_matrix_equals_the_one_panel_scan(genotypes, monkeypatch):
     """A host matrix of many variants is uploaded in column chunks from a second thread while the chunks that have arrived
-    are scanned (``CellRegMap._scan_streamed``).  With the chunks whole blocks of the scan the results are those of the
+    are scanned (``CellRegMap._panel_walk``).  With the chunks whole blocks of the scan the results are those of the
     one-panel scan bit for bit -- p-values, info, statistics, with a permutation hook, for general and for donor-constant
     genotypes (every chunk finds the donor structure by itself) --, one progress report runs over all chunks, a
     non-finite entry in a late chunk raises the reference's ValueError, and a block of columns of a row-major matrix
